@@ -22,6 +22,12 @@ JSON line and exits with the child's code.  It refuses (non-zero exit, no JSON) 
 `--dry-collective gloo` rehearses exactly that launcher / rendezvous / sharding / arg-min record path on CPU ranks (no solve, no
 GPU; `value` is null and `dry` is true): the CPU test of the N > 1 path.
 
+A plain run sets up, warms up, times the K steps and prints its line.  Everything else it can measure is behind `--full`: the CPU
+baseline, two batches in flight, the tight stop levels, HBM traffic from rocprofv3 child passes, and on N > 1 ranks the per-rank rate
+without the collective (each of them can still be switched off one by one with its --no-* option).
+`--dump-outputs DIR` writes what the last timed step returned to its caller (x, u, cost, status, iters; on N > 1 ranks rank 0's shard
+and the arg-min) as DIR/<name>.npy, float32 or float64, at most 64 MB in all; the inputs depend on the arguments only.
+
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -92,14 +98,15 @@ def measured_traffic(N, B, dtype, variant=""):
 
 
 def traffic_child_args(argv, steps, warm):
-    """Command line of a PMC child pass: the parent's workload arguments, its own step counts, no side measurements, no nested passes."""
-    keep = [a for a in argv if a not in ("--no-cpu-baseline", "--no-two-in-flight", "--no-tight-stop", "--no-live-traffic")]
+    """Command line of a PMC child pass: the parent's workload arguments, its own step counts, no side measurements, no nested passes,
+    no output dump."""
+    keep = [a for a in argv if a not in ("--no-cpu-baseline", "--no-two-in-flight", "--no-tight-stop", "--no-live-traffic", "--full")]
     out = []
     i = 0
-    while i < len(keep):                                   # drop --steps / --warmup (and their values) of the parent
-        if keep[i] in ("--steps", "--warmup"):
+    while i < len(keep):                                   # drop --steps / --warmup / --dump-outputs (and their values) of the parent
+        if keep[i] in ("--steps", "--warmup", "--dump-outputs"):
             i += 2; continue
-        if keep[i].startswith(("--steps=", "--warmup=")):
+        if keep[i].startswith(("--steps=", "--warmup=", "--dump-outputs=")):
             i += 1; continue
         out.append(keep[i]); i += 1
     return out + ["--steps", str(steps), "--warmup", str(warm), "--no-cpu-baseline", "--no-two-in-flight", "--no-tight-stop", "--no-live-traffic"]
@@ -178,6 +185,29 @@ def cpu_baseline(cfg, scen, target_seconds=12.0):
                       % (reps, B, cfg.N, nthreads, 1.0 / t1)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, per_instance, extra=None):
+    """--dump-outputs: one DIR/<name>.npy per array.  `per_instance` arrays share their leading batch axis; if all of them together exceed
+    64 MB, the same fixed, seeded sample of instances is kept of each, and its indices are written as instance_index.npy.  Integer
+    arrays (status, iteration counts) are written as float64, which holds them exactly."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.asarray(a) for k, a in per_instance.items()}
+    out = {k: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)) for k, a in out.items()}
+    B = next(iter(out.values())).shape[0]
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        m = int((DUMP_LIMIT_BYTES - (1 << 20)) // (total / B + 8))
+        idx = np.sort(np.random.default_rng(20240601).choice(B, m, replace=False))
+        out = {k: a[idx] for k, a in out.items()}
+        out["instance_index"] = idx.astype(np.float64)
+    for k, a in (extra or {}).items():
+        out[k] = np.asarray(a, dtype=np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a))
+
+
 def spawn_ranks(n):
     """Start the N ranks of this very command as a child `python -m torch.distributed.run` (never an exec: nothing in this process
     has touched a GPU yet, and nothing will), relay the one JSON line of rank 0, return the child's exit code."""
@@ -229,37 +259,40 @@ def dry_collective(args, world, rank, launched):
             best = adist.global_argmin_records(adist.pack_pair(v, i), adist.pairs_min_host) if launched else adist.pack_pair(v, i)
     if launched: dist.barrier()
     elapsed = time.perf_counter() - t0
-    # the collective-free segment of the real run (per-rank rate by the rank's own clock, gathered): here the local arg-min loop stands in
-    tl = time.perf_counter()
-    for _ in range(max(K, 1)):
-        adist.local_argmin_torch(cost, index_offset=lo)
-    rl = torch.tensor([B * max(K, 1) / max(time.perf_counter() - tl, 1e-9)], dtype=torch.float64)
-    rates = [float(rl.item())]
     if launched:
         tt = torch.tensor([elapsed], dtype=torch.float64); dist.all_reduce(tt, op=dist.ReduceOp.MAX); elapsed = float(tt.item())
-        allr = [torch.empty_like(rl) for _ in range(world)]; dist.all_gather(allr, rl); rates = [float(t.item()) for t in allr]
+    rates = None
+    if args.full:
+        # the collective-free segment of the real run (per-rank rate by the rank's own clock, gathered): here the local arg-min loop stands in
+        tl = time.perf_counter()
+        for _ in range(K):
+            adist.local_argmin_torch(cost, index_offset=lo)
+        rl = torch.tensor([B * K / max(time.perf_counter() - tl, 1e-9)], dtype=torch.float64)
+        rates = [float(rl.item())]
+        if launched:
+            allr = [torch.empty_like(rl) for _ in range(world)]; dist.all_gather(allr, rl); rates = [float(t.item()) for t in allr]
     if rank == 0:
         traffic = measured_traffic(args.horizon, B, args.dtype, "")
-        cpu = None
-        if not args.no_cpu_baseline:
-            try:
-                cfg = default_config(N=args.horizon, Ts=0.05)
-                cpu = cpu_baseline(cfg, random_scenarios(64, N=args.horizon, Ts=0.05, seed=1234), target_seconds=0.5)
-            except Exception as e:
-                cpu = {"value": None, "unit": "solves/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (e,)}
         allc = torch.remainder((torch.arange(world * B, dtype=torch.float64) + 1.0) * 0.6180339887498949, 1.0) + 1.0
         bc, bidx = adist.unpack_pair(best)
-        print(json.dumps({"metric": "MPC solves/sec (N=%d, nx=7, nu=2, fp64)" % args.horizon, "value": None, "unit": "solves/s", "dry": True,
-                          "n_gpus": world, "ranks_seen": int(ones.item()), "steps": K, "warmup": Wm, "ms_per_step": elapsed / max(K, 1) * 1e3,
-                          "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-                          "config": {"workload": "DRY RUN of the N > 1 plumbing on CPU ranks (gloo): no solve", "batch_per_gpu": B,
-                                     "collective": "gloo all-gather arg-min (16 B/rank), reducer admpc_argmin_pairs_host",
-                                     "one_gpu_solves_per_s_at_this_batch": rates[0]},
-                          "per_rank_solves_per_s_no_collective": {"min": min(rates), "max": max(rates), "rank0": rates[0], "batch_per_gpu": B, "dry": True},
-                          "roofline": {"traffic": (traffic or {}).get("bytes"), "traffic_source": (traffic or {}).get("source")},
-                          "cpu_baseline": cpu,
-                          "argmin": {"cost": bc, "index": bidx},
-                          "argmin_single_process": {"cost": float(allc.min()), "index": int(torch.argmin(allc))}}), flush=True)
+        out = {"metric": "MPC solves/sec (N=%d, nx=7, nu=2, fp64)" % args.horizon, "value": None, "unit": "solves/s", "dry": True,
+               "n_gpus": world, "ranks_seen": int(ones.item()), "steps": K, "warmup": Wm, "ms_per_step": elapsed / K * 1e3,
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+               "config": {"workload": "DRY RUN of the N > 1 plumbing on CPU ranks (gloo): no solve", "batch_per_gpu": B,
+                          "collective": "gloo all-gather arg-min (16 B/rank), reducer admpc_argmin_pairs_host"},
+               "roofline": {"traffic": (traffic or {}).get("bytes"), "traffic_source": (traffic or {}).get("source")},
+               "argmin": {"cost": bc, "index": bidx},
+               "argmin_single_process": {"cost": float(allc.min()), "index": int(torch.argmin(allc))}}
+        if rates is not None:
+            out["config"]["one_gpu_solves_per_s_at_this_batch"] = rates[0]
+            out["per_rank_solves_per_s_no_collective"] = {"min": min(rates), "max": max(rates), "rank0": rates[0], "batch_per_gpu": B, "dry": True}
+        if args.full and not args.no_cpu_baseline:
+            try:
+                cfg = default_config(N=args.horizon, Ts=0.05)
+                out["cpu_baseline"] = cpu_baseline(cfg, random_scenarios(64, N=args.horizon, Ts=0.05, seed=1234), target_seconds=0.5)
+            except Exception as e:
+                out["cpu_baseline"] = {"value": None, "unit": "solves/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (e,)}
+        print(json.dumps(out), flush=True)
     if launched:
         dist.barrier(); dist.destroy_process_group()
 
@@ -284,7 +317,14 @@ def main():
                          "the committed PMC summary of the same workload is reported instead")
     ap.add_argument("--dry-collective", choices=("gloo",), default=None,
                     help="rehearse the N > 1 launcher / rendezvous / sharding / arg-min record path on CPU ranks (no solve, no GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (CPU baseline, two_in_flight, tight_stop, live roofline.traffic, per-rank rates "
+                         "without the collective); a plain run only times the K steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -397,7 +437,7 @@ def main():
     # denominator of a scaling efficiency that is measured in the same run, on the same per-GPU batch (the default batches of `--gpus 1`
     # and `--gpus N` differ: 4096 / 8192 per GPU, and the per-GPU rate depends on the batch -- VERDICT round 3, weak 6)
     local_rate = None
-    if launched:
+    if launched and args.full:
         for i in range(Wm):
             eng.solve(x0, yref, yref_e, p, xb[i].clone(), ub[i].clone(), cost, status, iters)
         xs = [xinit.clone() for _ in range(K)]; us = [uinit.clone() for _ in range(K)]
@@ -437,9 +477,15 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=eng.device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        last = Wm + K - 1
+        dump_outputs(args.dump_outputs,
+                     {"x": xb[last].cpu().numpy(), "u": ub[last].cpu().numpy(), "cost": (costs[last % NRING] if launched else cost).cpu().numpy(),
+                      "status": status.cpu().numpy(), "iters": iters.cpu().numpy()},
+                     {"argmin": adist.unpack_pair(best)} if best is not None else None)
 
     rates = None
-    if launched:
+    if local_rate is not None:
         rl = torch.tensor([local_rate], dtype=torch.float64, device=eng.device)
         allr = [torch.empty_like(rl) for _ in range(world)]
         dist.all_gather(allr, rl)
@@ -448,7 +494,7 @@ def main():
     it_host = iters.cpu().numpy(); st_host = status.cpu().numpy()
     two = None
     try:
-      if not args.no_two_in_flight and not launched:
+      if args.full and not args.no_two_in_flight and not launched:
           # two handles (each owns its workspace: one solve in flight per handle), two streams, steps alternate between them
           eng2 = BatchSolver(cfg, device=dev_index)
           engs = (eng, eng2); sts = (torch.cuda.Stream(), torch.cuda.Stream())
@@ -472,7 +518,7 @@ def main():
     # the same K steps at the tight stop levels of rounds 1-2 (every instance to within 1e-8 of the exact minimiser): a side measurement
     tight = None
     try:
-        if not args.no_tight_stop and not launched:
+        if args.full and not args.no_tight_stop and not launched:
             from ad_mpc_amd.config import tight_ipm
             engt = BatchSolver(tight_ipm(cfg.copy()), device=dev_index)
             itt = torch.empty_like(iters); stt = torch.empty_like(status)
@@ -500,7 +546,7 @@ def main():
         byts = algorithmic_bytes_per_solve(N, elem) * B
         traffic = None
         profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ)      # already under a profiler (scripts/profile*.sh): no nested passes
-        if not launched and not args.no_live_traffic and not profiled:
+        if args.full and not launched and not args.no_live_traffic and not profiled:
             traffic = live_traffic(sys.argv[1:])
         if traffic is None and not args.dynamic:
             traffic = measured_traffic(N, B, args.dtype, "gp" if args.gp else "")
@@ -559,7 +605,7 @@ def main():
         if best is not None:
             bc, bidx = adist.unpack_pair(best)
             out["argmin"] = {"cost": bc, "index": bidx}
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg, scen)
             except Exception as e:  # the baseline is a reported number, never a reason to lose the GPU line

@@ -10,6 +10,9 @@ text is copied.
       CasADi model code (c_generated_code/sim_car_model/sim_car_expl_ode_fun.c and
       sim_car_expl_vde_forw.c) driven as acados' ERK4 does (acados_solver_sim_car.c:655-665).
 
+  tests/golden/ref_model_points.npz
+      300 more random points (p = 0, 0.37, 1) -> xdot, phi, A, B of the same compiled model, float64 arrays.
+
   tests/golden/kat_sim_car_iterate.json
       Known-answer test for the solver, reconstructed from the converged acados iterate that the
       reference ships (src/ad_mpc/sim_car_iterate.json, N=40, kinematic mode p=0):
@@ -55,6 +58,24 @@ def shooting(ref):
                           A=A.tolist(), B=B.tolist()))
     return dict(source="reference CasADi C (sim_car_expl_ode_fun.c, sim_car_expl_vde_forw.c) via oracle/_ref",
                 cases=cases)
+
+
+def model_points(ref):
+    """300 further points over the ranges of shooting() (p in {0, 0.37, 1}, rng seed 123) -> xdot, phi, A, B of the reference's
+    compiled model: the fixture of tests/test_oracle_model.py::test_oracle_against_live_reference_model."""
+    rng = np.random.default_rng(123)
+    n = 300
+    out = dict(p=np.empty(n), x=np.empty((n, NX)), u=np.empty((n, NU)), xdot=np.empty((n, NX)), phi=np.empty((n, NX)),
+               A=np.empty((n, NX, NX)), B=np.empty((n, NX, NU)))
+    for i in range(n):
+        p = [0.0, 0.37, 1.0][i % 3]
+        x = np.array([rng.uniform(-50, 50), rng.uniform(-50, 50), rng.uniform(-np.pi, np.pi), rng.uniform(0.5, 20), rng.uniform(-1, 1),
+                      rng.uniform(-1, 1), rng.uniform(-0.5, 0.5)])
+        u = np.array([rng.uniform(-10, 5), rng.uniform(-3, 3)])
+        out["p"][i], out["x"][i], out["u"][i] = p, x, u
+        out["xdot"][i] = ref.ode(x, u, p)
+        out["phi"][i], out["A"][i], out["B"][i] = ref.rk4_sens(x, u, p, TS)
+    return out
 
 
 def kat(ref):
@@ -193,6 +214,7 @@ def main():
     os.makedirs(OUT, exist_ok=True)
     with open(os.path.join(OUT, "shooting.json"), "w") as f:
         json.dump(shooting(ref), f)
+    np.savez_compressed(os.path.join(OUT, "ref_model_points.npz"), **model_points(ref))
     k = kat(ref)
     with open(os.path.join(OUT, "kat_sim_car_iterate.json"), "w") as f:
         json.dump(k, f)

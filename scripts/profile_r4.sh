@@ -8,7 +8,7 @@ set -e
 tag=$1; N=$2; B=$3; DT=$4; shift 4
 out=gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
 ARGS="bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-two-in-flight --no-tight-stop --no-live-traffic --horizon $N --batch-per-gpu $B --dtype $DT $*"
-python3 bench.py --steps 20 --warmup 5 --horizon $N --batch-per-gpu $B --dtype $DT $* > $out/bench.json 2> $out/bench.err
+python3 bench.py --steps 20 --warmup 5 --full --horizon $N --batch-per-gpu $B --dtype $DT $* > $out/bench.json 2> $out/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python3 $ARGS > $out/kt.log 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAIT_INST_ANY SQ_WAIT_ANY --output-format csv -d $out/p1 -- python3 $ARGS > $out/p1.log 2>&1
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_WR SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $out/p2 -- python3 $ARGS > $out/p2.log 2>&1

@@ -5,7 +5,7 @@
 tag=$1; mode=$2; IFS=';' read -ra WL <<< "$3"; shift 3
 out=gpurun_out/$tag; mkdir -p $out
 if [ "$mode" = test ]; then timeout -k 10 600 python3 -m pytest tests -m gpu -q -x > $out/gputest.log 2>&1; tail -3 $out/gputest.log; fi
-F="--steps 40 --warmup 5 --no-cpu-baseline --no-live-traffic --no-tight-stop"
+F="--steps 40 --warmup 5 --full --no-cpu-baseline --no-live-traffic --no-tight-stop"
 for a in "${WL[@]}"; do
   for rep in 1 2; do
     for lib in "$@"; do

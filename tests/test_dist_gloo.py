@@ -114,7 +114,7 @@ def test_bench_starts_its_own_ranks_and_never_reports_fewer():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     bench = os.path.join(ROOT, "bench.py")
-    r = subprocess.run([sys.executable, bench, "--gpus", "2", "--dry-collective", "gloo", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, bench, "--gpus", "2", "--dry-collective", "gloo", "--steps", "3", "--warmup", "1", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=280)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
@@ -122,7 +122,7 @@ def test_bench_starts_its_own_ranks_and_never_reports_fewer():
     js = json.loads(lines[0])
     assert js["n_gpus"] == 2 and js["ranks_seen"] == 2 and js["dry"] is True and js["value"] is None and js["steps"] == 3
     assert js["argmin"] == js["argmin_single_process"] and js["argmin"]["index"] == 10945 >= 8192
-    # the inputs of a scaling curve: every N > 1 line carries a per-rank rate measured WITHOUT the collective in the
+    # the inputs of a scaling curve: every N > 1 line of --full carries a per-rank rate measured WITHOUT the collective in the
     # same run at the same per-GPU batch (min / max over ranks, rank 0's as the one-GPU value at this batch), the committed PMC traffic of
     # the 8192-instance shard (no live passes in a multi-rank run), and the CPU baseline of rank 0
     pr = js["per_rank_solves_per_s_no_collective"]
@@ -150,7 +150,38 @@ def test_bench_traffic_bookkeeping():
     bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
     got = bench.traffic_child_args(["--steps", "20", "--warmup=5", "--horizon", "40", "--gp", "--no-cpu-baseline", "--batch-per-gpu", "8192"], 3, 1)
     assert got == ["--horizon", "40", "--gp", "--batch-per-gpu", "8192", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-two-in-flight", "--no-tight-stop", "--no-live-traffic"]
+    # a --full parent's children run plain and never write the parent's output dump
+    assert bench.traffic_child_args(["--full", "--dump-outputs", "d", "--horizon", "40", "--dump-outputs=e"], 3, 1) == got[:2] + got[5:]
     plain, gp = bench.measured_traffic(20, 4096, "f64"), bench.measured_traffic(20, 4096, "f64", "gp")
     assert plain and gp and "gp" not in os.path.basename(plain["source"]) and os.path.basename(gp["source"]).startswith("gp")
     assert plain["bytes"] < 3 * 4096 * bench.algorithmic_bytes_per_solve(20) < gp["bytes"] * 3
     assert bench.measured_traffic(20, 4097, "f64") is None
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs (no GPU): float32 / float64 files only (integer outputs as exact float64), under 64 MB in all; an output
+    above the limit keeps the same seeded sample of instances in every array, and the sample's indices are written with it."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    rng = np.random.default_rng(0)
+    B = 4096
+    small = {"x": rng.standard_normal((B, 21, 7)), "u": rng.standard_normal((B, 20, 2)).astype(np.float32),
+             "status": rng.integers(0, 3, B, dtype=np.int32), "iters": rng.integers(0, 40, B, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), small, {"argmin": (1.5, 7)})
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sorted(got) == ["argmin", "iters", "status", "u", "x"]
+    assert got["x"].dtype == np.float64 and got["u"].dtype == np.float32 and got["status"].dtype == np.float64
+    assert np.array_equal(got["x"], small["x"]) and np.array_equal(got["iters"], small["iters"]) and list(got["argmin"]) == [1.5, 7.0]
+    B = 65536
+    big = {"x": np.arange(B * 81 * 7, dtype=np.float64).reshape(B, 81, 7), "cost": np.arange(B, dtype=np.float64)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(str(tmp_path / "b")))
+    assert files == ["cost.npy", "instance_index.npy", "x.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "b" / f)) for f in files) <= 64 << 20
+    idx = np.load(str(tmp_path / "b" / "instance_index.npy")).astype(np.int64)
+    assert len(idx) > B // 8 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "cost.npy")), big["cost"][idx])
+    assert np.array_equal(np.load(str(tmp_path / "b" / "x.npy")), big["x"][idx])
+    assert all(np.array_equal(np.load(str(tmp_path / "b" / f)), np.load(str(tmp_path / "c" / f))) for f in files)
