@@ -20,7 +20,21 @@
 #define NX ADMPC_QUAD_NX
 #define NU ADMPC_QUAD_NU
 #define NMAX (ADMPC_QUAD_MAX_N * ADMPC_QUAD_NU)
+#ifdef ORACLE_LONG_DOUBLE                 /* libquad_oracle_ld.so: every real in the x87 80-bit format, the rounding-error yardstick */
+typedef long double real;
+#define R_EXP expl
+#define R_SQRT sqrtl
+#define R_FABS fabsl
+#define R_FMAX fmaxl
+#define R_FMIN fminl
+#else
 typedef double real;
+#define R_EXP exp
+#define R_SQRT sqrt
+#define R_FABS fabs
+#define R_FMAX fmax
+#define R_FMIN fmin
+#endif
 typedef AdmpcQuadConfig Cfg;
 
 /* f(x, u) and its directional derivative df = Jx sx + Ju su (forward mode, by hand).
@@ -53,12 +67,12 @@ static void quad_f_tan(const Cfg* c, const real* x, const real* u, const real* s
         tx += c->max_thrust * u[i] * c->y_f[i]; ty -= c->max_thrust * u[i] * c->x_f[i]; tz += c->max_thrust * u[i] * c->z_l_tau[i];
         dtx += c->max_thrust * su[i] * c->y_f[i]; dty -= c->max_thrust * su[i] * c->x_f[i]; dtz += c->max_thrust * su[i] * c->z_l_tau[i];
     }
-    f[10] = (tx + (c->J[1] - c->J[2]) * r1 * r2) / c->J[0];
-    f[11] = (ty + (c->J[2] - c->J[0]) * r2 * r0) / c->J[1];
-    f[12] = (tz + (c->J[0] - c->J[1]) * r0 * r1) / c->J[2];
-    df[10] = (dtx + (c->J[1] - c->J[2]) * (t1 * r2 + r1 * t2)) / c->J[0];
-    df[11] = (dty + (c->J[2] - c->J[0]) * (t2 * r0 + r2 * t0)) / c->J[1];
-    df[12] = (dtz + (c->J[0] - c->J[1]) * (t0 * r1 + r0 * t1)) / c->J[2];
+    f[10] = (tx + ((real)c->J[1] - c->J[2]) * r1 * r2) / c->J[0];
+    f[11] = (ty + ((real)c->J[2] - c->J[0]) * r2 * r0) / c->J[1];
+    f[12] = (tz + ((real)c->J[0] - c->J[1]) * r0 * r1) / c->J[2];
+    df[10] = (dtx + ((real)c->J[1] - c->J[2]) * (t1 * r2 + r1 * t2)) / c->J[0];
+    df[11] = (dty + ((real)c->J[2] - c->J[0]) * (t2 * r0 + r2 * t0)) / c->J[1];
+    df[12] = (dtz + ((real)c->J[0] - c->J[1]) * (t0 * r1 + r0 * t1)) / c->J[2];
     const int drag = c->rdrv[0] != 0 || c->rdrv[1] != 0 || c->rdrv[2] != 0;
     if (drag) {
         /* linear rotor-drag compensation (quad_3d_optimizer.py:364-381, Faessler et al.): v' += R(q) D R(q)' v, D = diag(rdrv) */
@@ -108,7 +122,7 @@ static void quad_f_tan(const Cfg* c, const real* x, const real* u, const real* s
             for (int i = 0; i < gp->n_points; ++i) {
                 real e = 0, de = 0;
                 for (int k = 0; k < gp->n_feat; ++k) { const real dzk = z[gp->feat[k]] - gp->Z[k][i]; e += dzk * dzk * gp->inv_l2[k]; de += dzk * gp->inv_l2[k] * dz[gp->feat[k]]; }
-                const real ka = gp->sigma_f * exp(-0.5 * e) * gp->alpha[i];
+                const real ka = gp->sigma_f * R_EXP(-0.5 * e) * gp->alpha[i];
                 m += ka; dm -= ka * de;
             }
             mb[gp->out - 7] += m + gp->ymean; dmb[gp->out - 7] += dm;
@@ -124,7 +138,7 @@ static void quad_f_tan(const Cfg* c, const real* x, const real* u, const real* s
 /* classic RK4 (one step of length h) of the state and ONE sensitivity column: col < 13 -> d/dx_col, col >= 13 -> d/du_(col-13) */
 static void rk4_col(const Cfg* c, const real* x, const real* u, const real* gpx, real h, int col, real* phi, real* scol)
 {
-    static const real cs[4] = { 0, 0.5, 0.5, 1.0 }, ws[4] = { 1.0 / 6, 2.0 / 6, 2.0 / 6, 1.0 / 6 };
+    static const real cs[4] = { 0, 0.5, 0.5, 1.0 }, ws[4] = { (real)1 / 6, (real)2 / 6, (real)2 / 6, (real)1 / 6 };
     real kx[NX] = {0}, ks[NX] = {0}, ax[NX] = {0}, as[NX] = {0}, su[NU] = {0};
     if (col >= NX) su[col - NX] = 1;
     for (int s = 0; s < 4; ++s) {
@@ -136,21 +150,41 @@ static void rk4_col(const Cfg* c, const real* x, const real* u, const real* gpx,
     for (int i = 0; i < NX; ++i) { phi[i] = x[i] + h * ax[i]; scol[i] = (col == i ? 1.0 : 0.0) + h * as[i]; }
 }
 
-/* gpx: NULL, or the GP-state parameter of a first node (see quad_f_tan) */
-void quad_oracle_f(const Cfg* c, const double* x, const double* u, const double* gpx, double* f)
-{
-    real z13[NX] = {0}, z4[NU] = {0}, df[NX];
-    quad_f_tan(c, x, u, z13, z4, gpx, f, df);
-}
-
 /* phi [13], A [13][13], B [13][4] (row-major) */
-void quad_oracle_rk4_sens(const Cfg* c, const double* x, const double* u, const double* gpx, double h, double* phi, double* A, double* B)
+static void rk4_sens(const Cfg* c, const real* x, const real* u, const real* gpx, real h, real* phi, real* A, real* B)
 {
     real col[NX];
     for (int cc = 0; cc < NX + NU; ++cc) {
         rk4_col(c, x, u, gpx, h, cc, phi, col);
         for (int i = 0; i < NX; ++i) { if (cc < NX) A[i * NX + cc] = col[i]; else B[i * NU + (cc - NX)] = col[i]; }
     }
+}
+
+/* the exported entry points take double: inputs are copied into real buffers (NULL stays NULL), outputs rounded back to double */
+static const real* to_real(real* dst, const double* src, int n)
+{
+    if (!src) return 0;
+    for (int i = 0; i < n; ++i) dst[i] = src[i];
+    return dst;
+}
+static void to_double(double* dst, const real* src, int n)
+{
+    for (int i = 0; i < n; ++i) dst[i] = (double)src[i];
+}
+
+/* gpx: NULL, or the GP-state parameter of a first node (see quad_f_tan) */
+void quad_oracle_f(const Cfg* c, const double* x, const double* u, const double* gpx, double* f)
+{
+    real xr[NX], ur[NU], gr[NX], z13[NX] = {0}, z4[NU] = {0}, fr[NX], df[NX];
+    quad_f_tan(c, to_real(xr, x, NX), to_real(ur, u, NU), z13, z4, to_real(gr, gpx, NX), fr, df);
+    to_double(f, fr, NX);
+}
+
+void quad_oracle_rk4_sens(const Cfg* c, const double* x, const double* u, const double* gpx, double h, double* phi, double* A, double* B)
+{
+    real xr[NX], ur[NU], gr[NX], ph[NX], a[NX * NX], b[NX * NU];
+    rk4_sens(c, to_real(xr, x, NX), to_real(ur, u, NU), to_real(gr, gpx, NX), h, ph, a, b);
+    to_double(phi, ph, NX); to_double(A, a, NX * NX); to_double(B, b, NX * NU);
 }
 
 /* ------------------------------------------------------------------------------------------------------------------ */
@@ -164,7 +198,7 @@ static void condense(const Cfg* c, const real* x0, const real* yref, const real*
     real G[NX][NMAX], xh[NX];                     /* Gamma_k (13 x n), free response */
     memset(G, 0, sizeof G); memset(w->H, 0, sizeof w->H);
     for (int i = 0; i < NX; ++i) xh[i] = x0[i] - xbar[i];
-    for (int i = 0; i < n; ++i) w->g[i] = c->Ts * c->W[NX + i % NU] * (ubar[i] - yref[(i / NU) * ADMPC_QUAD_NY + NX + i % NU]);
+    for (int i = 0; i < n; ++i) w->g[i] = (real)c->Ts * c->W[NX + i % NU] * (ubar[i] - yref[(i / NU) * ADMPC_QUAD_NY + NX + i % NU]);
     for (int k = 0; k < N; ++k) {
         real Gn[NX][NMAX], xn[NX];
         for (int r = 0; r < NX; ++r) {
@@ -182,7 +216,7 @@ static void condense(const Cfg* c, const real* x0, const real* yref, const real*
         /* cost of stage k + 1: weight Ts W (stages < N) or W_e (terminal) on  xbar + xhat + Gamma du - ref */
         const real* ref = k + 1 < N ? yref + (k + 1) * ADMPC_QUAD_NY : yref_e;
         for (int cc = 0; cc < NX; ++cc) {
-            const real wq = k + 1 < N ? c->Ts * c->W[cc] : c->We[cc];
+            const real wq = k + 1 < N ? (real)c->Ts * c->W[cc] : c->We[cc];
             if (wq == 0) continue;
             const real e = xbar[(k + 1) * NX + cc] + xh[cc] - ref[cc];
             for (int i = 0; i < (k + 1) * NU; ++i) {
@@ -191,7 +225,7 @@ static void condense(const Cfg* c, const real* x0, const real* yref, const real*
             }
         }
     }
-    for (int i = 0; i < n; ++i) { w->H[i][i] += c->Ts * c->W[NX + i % NU]; for (int j = 0; j < i; ++j) w->H[j][i] = w->H[i][j]; }
+    for (int i = 0; i < n; ++i) { w->H[i][i] += (real)c->Ts * c->W[NX + i % NU]; for (int j = 0; j < i; ++j) w->H[j][i] = w->H[i][j]; }
 }
 
 /* in-place Cholesky M = L L' (strictly lower part of L in M, reciprocals of its diagonal in invd) and solve M x = rhs;
@@ -202,7 +236,7 @@ static int chol(int n, real M[NMAX][NMAX], real* invd)
         real d = M[j][j];
         for (int k = 0; k < j; ++k) d -= M[j][k] * M[j][k];
         if (!(d > 0)) return 0;
-        invd[j] = 1.0 / sqrt(d);
+        invd[j] = 1.0 / R_SQRT(d);
         for (int i = j + 1; i < n; ++i) {
             real s = M[i][j];
             for (int k = 0; k < j; ++k) s -= M[i][k] * M[j][k];
@@ -223,7 +257,7 @@ static int box_qp(const Cfg* c, int n, real H[NMAX][NMAX], const real* g, const 
     real tl[NMAX], tu[NMAX], ll[NMAX], lu[NMAX];
     for (int i = 0; i < n; ++i) {
         du[i] = 0;
-        tl[i] = fmax(du[i] - lo[i], c->ipm_thr0); tu[i] = fmax(hi[i] - du[i], c->ipm_thr0);
+        tl[i] = R_FMAX(du[i] - lo[i], c->ipm_thr0); tu[i] = R_FMAX(hi[i] - du[i], c->ipm_thr0);
         ll[i] = c->ipm_mu0 / tl[i]; lu[i] = c->ipm_mu0 / tu[i];
     }
     real alpha_prev = 1;
@@ -237,8 +271,8 @@ static int box_qp(const Cfg* c, int n, real H[NMAX][NMAX], const real* g, const 
             for (int j = 0; j < n; ++j) s += H[i][j] * du[j];
             rs[i] = s; rl[i] = du[i] - lo[i] - tl[i]; ru[i] = hi[i] - du[i] - tu[i];
             mu += tl[i] * ll[i] + tu[i] * lu[i];
-            cmax = fmax(cmax, fmax(tl[i] * ll[i], tu[i] * lu[i]));
-            rmax = fmax(rmax, fmax(fabs(rs[i]), fmax(fabs(rl[i]), fabs(ru[i]))));
+            cmax = R_FMAX(cmax, R_FMAX(tl[i] * ll[i], tu[i] * lu[i]));
+            rmax = R_FMAX(rmax, R_FMAX(R_FABS(rs[i]), R_FMAX(R_FABS(rl[i]), R_FABS(ru[i]))));
         }
         mu /= 2 * n;
         if (!(mu == mu) || !(rmax == rmax)) { *iters = it; return 4; }
@@ -247,7 +281,7 @@ static int box_qp(const Cfg* c, int n, real H[NMAX][NMAX], const real* g, const 
             cons = 1;
             for (int i = 0; i < n; ++i) {
                 du[i] = 0;
-                tl[i] = fmax(du[i] - lo[i], c->ipm_thr0); tu[i] = fmax(hi[i] - du[i], c->ipm_thr0);
+                tl[i] = R_FMAX(du[i] - lo[i], c->ipm_thr0); tu[i] = R_FMAX(hi[i] - du[i], c->ipm_thr0);
                 ll[i] = c->ipm_mu0 / tl[i]; lu[i] = c->ipm_mu0 / tu[i];
             }
             alpha_prev = 1;
@@ -268,10 +302,10 @@ static int box_qp(const Cfg* c, int n, real H[NMAX][NMAX], const real* g, const 
         for (int i = 0; i < n; ++i) {
             dtl[i] = da[i] + rl[i]; dtu[i] = -da[i] + ru[i];
             dll[i] = -ll[i] - Dl[i] * dtl[i]; dlu[i] = -lu[i] - Du[i] * dtu[i];
-            if (dtl[i] < 0) amax = fmin(amax, -tl[i] / dtl[i]);
-            if (dtu[i] < 0) amax = fmin(amax, -tu[i] / dtu[i]);
-            if (dll[i] < 0) amax = fmin(amax, -ll[i] / dll[i]);
-            if (dlu[i] < 0) amax = fmin(amax, -lu[i] / dlu[i]);
+            if (dtl[i] < 0) amax = R_FMIN(amax, -tl[i] / dtl[i]);
+            if (dtu[i] < 0) amax = R_FMIN(amax, -tu[i] / dtu[i]);
+            if (dll[i] < 0) amax = R_FMIN(amax, -ll[i] / dll[i]);
+            if (dlu[i] < 0) amax = R_FMIN(amax, -lu[i] / dlu[i]);
         }
         for (int i = 0; i < n; ++i) muaff += (tl[i] + amax * dtl[i]) * (ll[i] + amax * dll[i]) + (tu[i] + amax * dtu[i]) * (lu[i] + amax * dlu[i]);
         muaff /= 2 * n;
@@ -289,17 +323,17 @@ static int box_qp(const Cfg* c, int n, real H[NMAX][NMAX], const real* g, const 
         for (int i = 0; i < n; ++i) {
             dtl[i] = d[i] + rl[i]; dtu[i] = -d[i] + ru[i];
             dll[i] = cl[i] - ll[i] - Dl[i] * dtl[i]; dlu[i] = cu[i] - lu[i] - Du[i] * dtu[i];
-            if (dtl[i] < 0) amax = fmin(amax, -tl[i] / dtl[i]);
-            if (dtu[i] < 0) amax = fmin(amax, -tu[i] / dtu[i]);
-            if (dll[i] < 0) amax = fmin(amax, -ll[i] / dll[i]);
-            if (dlu[i] < 0) amax = fmin(amax, -lu[i] / dlu[i]);
+            if (dtl[i] < 0) amax = R_FMIN(amax, -tl[i] / dtl[i]);
+            if (dtu[i] < 0) amax = R_FMIN(amax, -tu[i] / dtu[i]);
+            if (dll[i] < 0) amax = R_FMIN(amax, -ll[i] / dll[i]);
+            if (dlu[i] < 0) amax = R_FMIN(amax, -lu[i] / dlu[i]);
         }
-        real tau = 1 - muaff; tau = fmax(tau, 0.995); tau = fmin(tau, 0.999999);
-        const real alpha = fmin(tau * amax, 1.0);
+        real tau = 1 - muaff; tau = R_FMAX(tau, 0.995); tau = R_FMIN(tau, 0.999999);
+        const real alpha = R_FMIN(tau * amax, 1.0);
         for (int i = 0; i < n; ++i) {
             du[i] += alpha * d[i];
-            tl[i] = fmax(tl[i] + alpha * dtl[i], 1e-40); tu[i] = fmax(tu[i] + alpha * dtu[i], 1e-40);
-            ll[i] = fmax(ll[i] + alpha * dll[i], 1e-40); lu[i] = fmax(lu[i] + alpha * dlu[i], 1e-40);
+            tl[i] = R_FMAX(tl[i] + alpha * dtl[i], 1e-40); tu[i] = R_FMAX(tu[i] + alpha * dtu[i], 1e-40);
+            ll[i] = R_FMAX(ll[i] + alpha * dll[i], 1e-40); lu[i] = R_FMAX(lu[i] + alpha * dlu[i], 1e-40);
         }
         alpha_prev = alpha;
     }
@@ -314,13 +348,13 @@ static int box_qp(const Cfg* c, int n, real H[NMAX][NMAX], const real* g, const 
  *   pi_{N-1} = We (x+_N - xref_N),   pi_{k-1} = Ts Q (x+_k - xref_k) + A_k' pi_k,   m_k = Ts R (u+_k - uref_k) + B_k' pi_k
  * (A_k, B_k of the linearisation the QP was built on; x+, u+ the iterate after the full step). */
 static int rti_step(const Cfg* c, const real* x0, const real* yref, const real* yref_e, const real* gp_state, real* xbar, real* ubar, real* cost, int* iters,
-                    real* H_out, real* g_out, real* pi_out, real* m_out)
+                    double* H_out, double* g_out, real* pi_out, real* m_out)
 {
     Work w;
     const int N = c->N, n = N * NU;
     for (int k = 0; k < N; ++k) {
         real phi[NX];
-        quad_oracle_rk4_sens(c, xbar + k * NX, ubar + k * NU, (k == 0 && c->n_gp > 0) ? (gp_state ? gp_state : x0) : 0, c->Ts, phi, &w.A[k][0][0], &w.B[k][0][0]);
+        rk4_sens(c, xbar + k * NX, ubar + k * NU, (k == 0 && c->n_gp > 0) ? (gp_state ? gp_state : x0) : 0, c->Ts, phi, &w.A[k][0][0], &w.B[k][0][0]);
         for (int i = 0; i < NX; ++i) w.b[k][i] = phi[i] - xbar[(k + 1) * NX + i];
     }
     condense(c, x0, yref, yref_e, xbar, ubar, &w);
@@ -341,13 +375,13 @@ static int rti_step(const Cfg* c, const real* x0, const real* yref, const real* 
             for (int m = 0; m < NU; ++m) a += w.B[k][r][m] * du[k * NU + m];
             dn[r] = a;
         }
-        for (int m = 0; m < NU; ++m) { un[k * NU + m] = ubar[k * NU + m] + du[k * NU + m]; if (!(fabs(un[k * NU + m]) <= 1e300)) bad = 1; }
-        for (int r = 0; r < NX; ++r) { dx[r] = dn[r]; xn[(k + 1) * NX + r] = xbar[(k + 1) * NX + r] + dn[r]; if (!(fabs(xn[(k + 1) * NX + r]) <= 1e300)) bad = 1; }
+        for (int m = 0; m < NU; ++m) { un[k * NU + m] = ubar[k * NU + m] + du[k * NU + m]; if (!(R_FABS(un[k * NU + m]) <= 1e300)) bad = 1; }
+        for (int r = 0; r < NX; ++r) { dx[r] = dn[r]; xn[(k + 1) * NX + r] = xbar[(k + 1) * NX + r] + dn[r]; if (!(R_FABS(xn[(k + 1) * NX + r]) <= 1e300)) bad = 1; }
     }
     if (bad) { *cost = INFINITY; return 4; }
     for (int k = 0; k < N; ++k) {
-        for (int cc = 0; cc < NX; ++cc) { const real e = xn[k * NX + cc] - yref[k * ADMPC_QUAD_NY + cc]; J += 0.5 * c->Ts * c->W[cc] * e * e; }
-        for (int m = 0; m < NU; ++m) { const real e = un[k * NU + m] - yref[k * ADMPC_QUAD_NY + NX + m]; J += 0.5 * c->Ts * c->W[NX + m] * e * e; }
+        for (int cc = 0; cc < NX; ++cc) { const real e = xn[k * NX + cc] - yref[k * ADMPC_QUAD_NY + cc]; J += 0.5 * (real)c->Ts * c->W[cc] * e * e; }
+        for (int m = 0; m < NU; ++m) { const real e = un[k * NU + m] - yref[k * ADMPC_QUAD_NY + NX + m]; J += 0.5 * (real)c->Ts * c->W[NX + m] * e * e; }
     }
     for (int cc = 0; cc < NX; ++cc) { const real e = xn[N * NX + cc] - yref_e[cc]; J += 0.5 * c->We[cc] * e * e; }
     memcpy(xbar, xn, sizeof(real) * (N + 1) * NX); memcpy(ubar, un, sizeof(real) * n);
@@ -358,14 +392,14 @@ static int rti_step(const Cfg* c, const real* x0, const real* yref, const real* 
         for (int k = N - 1; k >= 0; --k) {
             for (int i = 0; i < NX; ++i) pi_out[k * NX + i] = pk[i];
             for (int m = 0; m < NU; ++m) {
-                real a = c->Ts * c->W[NX + m] * (un[k * NU + m] - yref[k * ADMPC_QUAD_NY + NX + m]);
+                real a = (real)c->Ts * c->W[NX + m] * (un[k * NU + m] - yref[k * ADMPC_QUAD_NY + NX + m]);
                 for (int i = 0; i < NX; ++i) a += w.B[k][i][m] * pk[i];
                 m_out[k * NU + m] = a;
             }
             if (k >= 1) {
                 real pn[NX];
                 for (int j = 0; j < NX; ++j) {
-                    real a = c->Ts * c->W[j] * (xn[k * NX + j] - yref[k * ADMPC_QUAD_NY + j]);
+                    real a = (real)c->Ts * c->W[j] * (xn[k * NX + j] - yref[k * ADMPC_QUAD_NY + j]);
                     for (int i = 0; i < NX; ++i) a += w.A[k][i][j] * pk[i];
                     pn[j] = a;
                 }
@@ -384,15 +418,15 @@ static void quad_nlp_residuals(const Cfg* c, const real* x0, const real* yref, c
 {
     const int N = c->N;
     real rs = 0, re = 0, ri = 0, rc = 0;
-#define UPN(acc, v) do { real a_ = fabs(v); if (a_ > acc || !(a_ == a_)) acc = a_; } while (0)
+#define UPN(acc, v) do { real a_ = R_FABS(v); if (a_ > acc || !(a_ == a_)) acc = a_; } while (0)
     for (int i = 0; i < NX; ++i) UPN(re, xbar[i] - x0[i]);
     for (int k = 0; k < N; ++k) {
         real phi[NX], A[NX][NX], Bm[NX][NU];
-        quad_oracle_rk4_sens(c, xbar + k * NX, ubar + k * NU, (k == 0 && c->n_gp > 0) ? (gp_state ? gp_state : x0) : 0, c->Ts, phi, &A[0][0], &Bm[0][0]);
+        rk4_sens(c, xbar + k * NX, ubar + k * NU, (k == 0 && c->n_gp > 0) ? (gp_state ? gp_state : x0) : 0, c->Ts, phi, &A[0][0], &Bm[0][0]);
         for (int i = 0; i < NX; ++i) UPN(re, phi[i] - xbar[(k + 1) * NX + i]);
         for (int m = 0; m < NU; ++m) {
             const real u = ubar[k * NU + m];
-            real a = c->Ts * c->W[NX + m] * (u - yref[k * ADMPC_QUAD_NY + NX + m]) - mm[k * NU + m];
+            real a = (real)c->Ts * c->W[NX + m] * (u - yref[k * ADMPC_QUAD_NY + NX + m]) - mm[k * NU + m];
             for (int i = 0; i < NX; ++i) a += Bm[i][m] * pi[k * NX + i];
             UPN(rs, a);
             const real vl = c->lbu[m] - u, vu = u - c->ubu[m];
@@ -402,7 +436,7 @@ static void quad_nlp_residuals(const Cfg* c, const real* x0, const real* yref, c
         }
         if (k >= 1)
             for (int j = 0; j < NX; ++j) {
-                real a = c->Ts * c->W[j] * (xbar[k * NX + j] - yref[k * ADMPC_QUAD_NY + j]) - pi[(k - 1) * NX + j];
+                real a = (real)c->Ts * c->W[j] * (xbar[k * NX + j] - yref[k * ADMPC_QUAD_NY + j]) - pi[(k - 1) * NX + j];
                 for (int i = 0; i < NX; ++i) a += A[i][j] * pi[k * NX + i];
                 UPN(rs, a);
             }
@@ -412,11 +446,25 @@ static void quad_nlp_residuals(const Cfg* c, const real* x0, const real* yref, c
     res[0] = rs; res[1] = re; res[2] = ri; res[3] = rc;
 }
 
+/* one instance's arguments in real (see to_real) */
+typedef struct { real x0[NX], yref[ADMPC_QUAD_MAX_N * ADMPC_QUAD_NY], yref_e[NX], gs[NX], xbar[(ADMPC_QUAD_MAX_N + 1) * NX], ubar[NMAX]; const real* gp; } Inst;
+
+static void load_inst(const Cfg* c, Inst* r, const double* x0, const double* yref, const double* yref_e, const double* gp_state, const double* xbar, const double* ubar)
+{
+    const int N = c->N;
+    to_real(r->x0, x0, NX); to_real(r->yref, yref, N * ADMPC_QUAD_NY); to_real(r->yref_e, yref_e, NX);
+    r->gp = to_real(r->gs, gp_state, NX);
+    to_real(r->xbar, xbar, (N + 1) * NX); to_real(r->ubar, ubar, N * NU);
+}
+
 /* tests: the four residuals of an iterate with given multipliers */
 int quad_oracle_nlp_residuals(const Cfg* c, const double* x0, const double* yref, const double* yref_e, const double* gp_state,
                               const double* xbar, const double* ubar, const double* pi, const double* mm, double* res)
 {
-    quad_nlp_residuals(c, x0, yref, yref_e, gp_state, xbar, ubar, pi, mm, res);
+    Inst r; real pr[ADMPC_QUAD_MAX_N * NX], mr[NMAX], rr[4];
+    load_inst(c, &r, x0, yref, yref_e, gp_state, xbar, ubar);
+    quad_nlp_residuals(c, r.x0, r.yref, r.yref_e, r.gp, r.xbar, r.ubar, to_real(pr, pi, c->N * NX), to_real(mr, mm, c->N * NU), rr);
+    to_double(res, rr, 4);
     return 0;
 }
 
@@ -438,21 +486,22 @@ int quad_oracle_solve_batch(const Cfg* c, int B, const double* x0, const double*
         const int nsqp = c->sqp_iters > 1 ? c->sqp_iters : 1;
         const int tol_on = nsqp > 1 && c->sqp_tol > 0;
         real pi[ADMPC_QUAD_MAX_N * NX], mm[NMAX];
-        const real* gs = gp_state ? gp_state + (size_t)b * NX : 0;
+        Inst r;
+        double* xb = xbar + (size_t)b * (N + 1) * NX; double* ub = ubar + (size_t)b * N * NU;
+        load_inst(c, &r, x0 + (size_t)b * NX, yref + (size_t)b * N * ADMPC_QUAD_NY, yref_e + (size_t)b * NX, gp_state ? gp_state + (size_t)b * NX : 0, xb, ub);
         int st = 0;
         for (int sq = 0; sq < nsqp; ++sq) {
             if (tol_on && sq > 0) {
-                real r[4];
-                quad_nlp_residuals(c, x0 + (size_t)b * NX, yref + (size_t)b * N * ADMPC_QUAD_NY, yref_e + (size_t)b * NX, gs,
-                                   xbar + (size_t)b * (N + 1) * NX, ubar + (size_t)b * N * NU, pi, mm, r);
-                if (r[0] <= c->sqp_tol && r[1] <= c->sqp_tol && r[2] <= c->sqp_tol && r[3] <= c->sqp_tol) { st = -1; break; }
+                real res[4];
+                quad_nlp_residuals(c, r.x0, r.yref, r.yref_e, r.gp, r.xbar, r.ubar, pi, mm, res);
+                if (res[0] <= c->sqp_tol && res[1] <= c->sqp_tol && res[2] <= c->sqp_tol && res[3] <= c->sqp_tol) { st = -1; break; }
             }
-            st = rti_step(c, x0 + (size_t)b * NX, yref + (size_t)b * N * ADMPC_QUAD_NY, yref_e + (size_t)b * NX,
-                          gs, xbar + (size_t)b * (N + 1) * NX, ubar + (size_t)b * N * NU, &J, &it, 0, 0, pi, mm);
+            st = rti_step(c, r.x0, r.yref, r.yref_e, r.gp, r.xbar, r.ubar, &J, &it, 0, 0, pi, mm);
             if (st != 0) break;
         }
+        to_double(xb, r.xbar, (N + 1) * NX); to_double(ub, r.ubar, N * NU);
         if (tol_on) st = st == -1 ? 0 : (st == 0 ? 2 : st);
-        if (cost) cost[b] = J;
+        if (cost) cost[b] = (double)J;
         if (status) status[b] = st;
         if (iters) iters[b] = it;
         nbad += st != 0;
@@ -464,8 +513,10 @@ int quad_oracle_solve_batch(const Cfg* c, int B, const double* x0, const double*
 int quad_oracle_qp_debug(const Cfg* c, const double* x0, const double* yref, const double* yref_e, double* xbar, double* ubar,
                          double* H, double* g, int32_t* iters)
 {
-    int it = 0; real J;
-    const int st = rti_step(c, x0, yref, yref_e, 0, xbar, ubar, &J, &it, H, g, 0, 0);
+    int it = 0; real J; Inst r;
+    load_inst(c, &r, x0, yref, yref_e, 0, xbar, ubar);
+    const int st = rti_step(c, r.x0, r.yref, r.yref_e, 0, r.xbar, r.ubar, &J, &it, H, g, 0, 0);
+    to_double(xbar, r.xbar, (c->N + 1) * NX); to_double(ubar, r.ubar, c->N * NU);
     *iters = it;
     return st;
 }

@@ -18,9 +18,11 @@ def _ptr(a, ty=_dp):
 
 
 class QuadOracle:
-    def __init__(self):
-        subprocess.run(["make", "-C", _HERE, "libquad_oracle.so"], check=True, stdout=subprocess.DEVNULL)
-        self.lib = L = C.CDLL(os.path.join(_HERE, "libquad_oracle.so"))
+    def __init__(self, variant=None):
+        """variant "ld": the same file with every real in x87 80-bit arithmetic (libquad_oracle_ld.so), the rounding-error yardstick."""
+        target = "libquad_oracle_%s.so" % variant if variant else "libquad_oracle.so"
+        subprocess.run(["make", "-C", _HERE, target], check=True, stdout=subprocess.DEVNULL)
+        self.lib = L = C.CDLL(os.path.join(_HERE, target))
         cp = C.POINTER(AdmpcQuadConfig)
         L.quad_oracle_f.argtypes = [cp, _dp, _dp, _dp, _dp]
         L.quad_oracle_rk4_sens.argtypes = [cp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp]

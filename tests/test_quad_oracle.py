@@ -297,3 +297,30 @@ def test_sqp_mode_and_its_stopping_test(qoracle):
     xb, ub, _, stb, _ = qoracle.solve_batch(crti, s["x0"], s["yref"], s["yref_e"], s["xbar"], s["ubar"])
     assert (stb == 0).all() and np.abs(xa - xb).max() == 0.0 and np.abs(ua - ub).max() == 0.0
     np.testing.assert_array_equal(x3, xb)            # ... and the first three QPs of the SQP loop are exactly those
+
+
+@pytest.mark.parametrize("N,gp,tol", [(10, False, 2e-11), (10, True, 2e-11), (20, False, 4e-9), (20, True, 4e-9)])
+def test_fp64_quad_oracle_against_80_bit_arithmetic(qoracle, N, gp, tol):
+    """The fp64 quadrotor oracle against the same file with every real in x87 extended precision (libquad_oracle_ld.so, the yardstick of
+    tests/test_accuracy_80bit.py): same statuses, the same iteration count on >= 90 % of the instances, inputs and states within `tol`
+    (measured here, max |du| / max |dx|: N = 10 1.5e-12 / 2.6e-12 nominal, 1.7e-12 / 2.7e-12 GP; N = 20 3.5e-10 / 5.6e-10 nominal,
+    4.3e-10 / 6.1e-10 GP -- the condensed Hessian of the longer horizon is worse conditioned).  At least one instance must differ in its bits: a slip of the ORACLE_LONG_DOUBLE switch that
+    builds the fp64 arithmetic twice fails here."""
+    from oracle.quad_oracle import QuadOracle
+    from ad_mpc_amd.quad_config import set_quad_gp
+    ld = QuadOracle(variant="ld")
+    cfg = default_quad_config(N=N, t_horizon=0.1 * N)
+    if gp:
+        set_quad_gp(cfg, quad_gps())
+    s = random_quad_scenarios(128, cfg, seed=17 + N)
+    a = (cfg, s["x0"], s["yref"], s["yref_e"], s["xbar"], s["ubar"])
+    x8, u8, _, st8, it8 = ld.solve_batch(*a, nthreads=4)
+    x, u, _, st, it = qoracle.solve_batch(*a, nthreads=4)
+    np.testing.assert_array_equal(st8, st)
+    assert (st == 0).all()
+    same = it8 == it
+    assert same.mean() >= 0.9
+    du = np.abs(u8 - u)[same].max(); dx = np.abs(x8 - x)[same].max()
+    print("quad N=%d gp=%d  max|du| fp64 vs 80-bit = %.2e, max|dx| = %.2e  (same iteration count: %d of %d)" % (N, gp, du, dx, same.sum(), len(st)))
+    assert du <= tol and dx <= tol
+    assert (u8 != u).any(axis=(1, 2)).sum() >= 1
