@@ -6,7 +6,7 @@ surface raises.  The CPU oracle under ``oracle/`` is test infrastructure and is 
 import ctypes as C
 import os
 
-from .config import AdmpcConfig
+from .config import AdmpcConfig, AdmpcPath, AdmpcStepParams
 from .quad_config import AdmpcQuadConfig
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -14,7 +14,8 @@ LIB_PATH = os.path.join(_HERE, "libadmpc.so")
 
 EXPORTS = (
     "admpc_default_config", "admpc_create", "admpc_destroy", "admpc_reserve", "admpc_solve_batch", "admpc_solve_batch_ex", "admpc_nlp_residuals_batch", "admpc_solve_batch_f32", "admpc_shoot_batch",
-    "admpc_argmin", "admpc_argmin_pairs", "admpc_argmin_pairs_host", "admpc_argmin_global", "admpc_select_cluster_batch", "admpc_solve_batch_routed", "admpc_shift_batch", "admpc_epilogue_batch", "admpc_actuation_batch", "admpc_resample_vel_batch", "admpc_waypoints_batch", "admpc_last_error", "admpc_version",
+    "admpc_argmin", "admpc_argmin_pairs", "admpc_argmin_pairs_host", "admpc_argmin_global", "admpc_select_cluster_batch", "admpc_solve_batch_routed", "admpc_shift_batch", "admpc_epilogue_batch", "admpc_actuation_batch", "admpc_resample_vel_batch", "admpc_waypoints_batch",
+    "admpc_control_step_workspace", "admpc_control_step_batch", "admpc_last_error", "admpc_version",
 )
 QUAD_EXPORTS = ("admpc_quad_default_config", "admpc_quad_create", "admpc_quad_destroy", "admpc_quad_solve_batch", "admpc_quad_solve_batch_ex", "admpc_quad_select_cluster_batch",
                 "admpc_quad_solve_batch_routed", "admpc_quad_shoot_batch", "admpc_quad_shoot_batch_ex")   # include/admpc_quad.h
@@ -62,6 +63,9 @@ def load():
     L.admpc_resample_vel_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, C.c_double, C.c_double, dp, vp]; L.admpc_resample_vel_batch.restype = C.c_int
     L.admpc_waypoints_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_double, C.c_int] + [dp] * 13 + [vp]
     L.admpc_waypoints_batch.restype = C.c_int
+    L.admpc_control_step_workspace.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]; L.admpc_control_step_workspace.restype = C.c_int
+    L.admpc_control_step_batch.argtypes = [C.c_void_p, C.POINTER(AdmpcPath), C.POINTER(AdmpcStepParams), C.c_int] + [dp] * 7 + [dp] * 5 + [vp] + [dp] * 4 + [vp]
+    L.admpc_control_step_batch.restype = C.c_int
     qp = C.POINTER(AdmpcQuadConfig)
     L.admpc_quad_default_config.argtypes = [qp]; L.admpc_quad_default_config.restype = None
     L.admpc_quad_create.argtypes = [qp, C.c_int, C.POINTER(C.c_void_p)]; L.admpc_quad_create.restype = C.c_int

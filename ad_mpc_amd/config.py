@@ -68,6 +68,17 @@ class AdmpcConfig(C.Structure):
         return other
 
 
+class AdmpcPath(C.Structure):
+    """The global path of admpc_control_step_batch (include/admpc.h): device columns as admpc_waypoints_batch reads them."""
+    _fields_ = [("M", C.c_int32), ("H", C.c_int32), ("dt", C.c_double)] + \
+        [(k, C.c_void_p) for k in ("vel", "x", "y", "psi", "psi_unwrapped", "cdist", "curv")]
+
+
+class AdmpcStepParams(C.Structure):
+    _fields_ = [("blend_min", C.c_double), ("blend_max", C.c_double), ("acc_max", C.c_double), ("resample_dt", C.c_double),
+                ("resample", C.c_int32), ("threshold", C.c_int32)]
+
+
 # --- vehicle constants: src/ad_mpc/ad_3d.py:47-71 (the 3.14195 "pi" is part of the model) -----------
 VEH_MASS = 1500.0
 VEH_F_MASS = 900.0

@@ -878,7 +878,7 @@ __global__ __launch_bounds__(WAVE) void admpc_waypoints_kernel(int M, int H, dou
             const double ov = __shfl_xor(best, o, WAVE); const int oi = __shfl_xor(bi, o, WAVE);
             if (ov < best || (ov == best && oi < bi)) { best = ov; bi = oi; }
         }
-        const int ci = bi;
+        const int ci = bi < M ? bi : 0;                           // every distance NaN (a non-finite pose): numpy's argmin gives 0
         // (2) Frenet errors at the closest waypoint
         if (lane == 0) {
             const double pw = tpsi[ci];
@@ -1360,6 +1360,12 @@ const char* admpc_last_error(void) { return g_err.c_str(); }
 // for the other translation units of the library (admpc_quad.hip)
 __attribute__((visibility("hidden"))) int admpc_set_error(int code, const char* msg) { return fail(code, msg ? msg : ""); }
 const char* admpc_version(void) { return "admpc-mi355x 0.1 (gfx950)"; }
+// for the control step (admpc_step.hip): the problem a handle solves and the device it lives on
+__attribute__((visibility("hidden"))) const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device)
+{
+    if (device) *device = s->device;
+    return &s->cfg;
+}
 
 int admpc_default_config(AdmpcConfig* c, int N, double Ts)
 {

@@ -1,0 +1,107 @@
+"""The control step of a fleet: pose in, Ackermann command out, for B vehicles on one global path
+(include/admpc.h: admpc_control_step_batch; csrc/admpc_step.hip).
+
+``FleetController`` solves the problem of ``ROSGPMPC(point_reference=False)`` (create_ros_ad_mpc.py:41-101: SQP_RTI, Q_DIAG_ROS /
+R_DIAG_ROS) for every vehicle, and does per step what the reference node does per pose message (gp_ad_mpc_node.py:389-438 ->
+run_mpc :160-230): reference window, speed clamp, the padded references, the solve, the validity test, the fallback command of
+run_optimization, the Ackermann record and the node's gate.  Everything runs on the device as one chain of launches on the current
+stream; the per-vehicle state the node carries from call to call (the iterate, safe_count, the previous valid inputs) lives in device
+tensors of this object.
+
+One deliberate deviation: the node clamps the speed of the GLOBAL path once per waypoint message, at the speed the vehicle had then
+(:351-368).  Vehicles at different speeds cannot share that, so each step clamps each vehicle's local window at its current speed
+(admpc_resample_vel_batch); ``resample=False`` turns the clamp off.
+"""
+import ctypes as C
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import config as _c
+from .ad_3d import AD3D
+from .ad_3d_optimizer import ocp_config
+from .config import AdmpcPath, AdmpcStepParams, NX, NU
+from .engine import BatchSolver, _ptr
+from .ref_traj import RefTrajectory
+
+SAFE_COUNT_THRESHOLD = 10          # consecutive successes before the node issues an MPC command (gp_ad_mpc_node.py:62)
+
+
+class FleetStep(NamedTuple):
+    """Device tensors of one step; they are the controller's own buffers and are overwritten by the next step."""
+    ack: torch.Tensor          # float32 [B,4]: steering_angle, steering_angle_velocity, speed, acceleration
+    mode: torch.Tensor         # int32 [B]: 1 = MPC command, 0 = the auxiliary controller's brake record
+    status: torch.Tensor       # int32 [B]: acados status of the solve (0 success, 4 failure)
+    valid: torch.Tensor        # int32 [B]: is_valid_command of the prediction against the padded target
+    x_opt: torch.Tensor        # float64 [B,N+1,7]: the iterate (view of the controller's state)
+    w_opt: torch.Tensor        # float64 [B,N,2]
+
+
+class FleetController:
+    def __init__(self, t_horizon, n_mpc_nodes, opt_dt, B, device=0, resample=True, threshold=SAFE_COUNT_THRESHOLD):
+        N, B = int(n_mpc_nodes), int(B)
+        if B < 1:
+            raise ValueError("B must be positive")
+        self.ad = ad = AD3D(noisy=False, noisy_input=False)            # create_ros_ad_mpc.py:26-38
+        cfg = ocp_config(ad, t_horizon, N, np.array(_c.Q_DIAG_ROS), np.array(_c.R_DIAG_ROS), "SQP_RTI")
+        self._eng = eng = BatchSolver(cfg, device=device)
+        self.lib, self.device = eng.lib, eng.device
+        self.N, self.B, self.opt_dt = N, B, opt_dt
+        dt = float(t_horizon) / N                                         # traj_dt and the clamp's dt (gp_ad_mpc_node.py:55, :95)
+        self._ref = RefTrajectory(traj_horizon=N, traj_dt=dt, device=device)
+        self._path = AdmpcPath(M=0, H=N, dt=dt)
+        self._prm = AdmpcStepParams(blend_min=ad.blend_min, blend_max=ad.blend_max, acc_max=ad.acc_max, resample_dt=dt,
+                                    resample=1 if resample else 0, threshold=int(threshold))
+        _lib.check(self.lib.admpc_reserve(eng._h, B))                     # every later step is allocation-free (graph capture)
+        nbytes = C.c_size_t(0)
+        _lib.check(self.lib.admpc_control_step_workspace(eng._h, B, C.byref(nbytes)))
+        z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=self.device)
+        self._work = z(-(-nbytes.value // 8))
+        self.x_opt, self.w_opt = z(B, N + 1, NX), z(B, N, NU)            # the iterate: all zeros, as a fresh solver's
+        self.safe_count = z(B, dtype=torch.int32)
+        self.prev_u, self.has_valid = z(B, N, NU), z(B, dtype=torch.int32)
+        self.ack = z(B, 4, dtype=torch.float32)
+        self.mode, self.valid, self.status = z(B, dtype=torch.int32), z(B, dtype=torch.int32), z(B, dtype=torch.int32)
+
+    def close(self):
+        self._eng.close()
+
+    def set_traj(self, x_ref, y_ref, psi_ref, vel_ref):
+        """The global path every vehicle follows (RefTrajectory.set_traj, ref_traj.py:67-86)."""
+        self._ref.set_traj(x_ref, y_ref, psi_ref, vel_ref)
+        cols = self._ref._cols
+        p = self._path
+        p.M = int(self._ref.trajectory.shape[0])
+        p.vel, p.x, p.y, p.psi, p.psi_unwrapped, p.cdist, p.curv = [c.data_ptr() for c in cols]
+
+    def step(self, x, y, yaw, vx, vy, yaw_rate, steer):
+        """One control step for every vehicle: float64 [B] device tensors in.  Asynchronous on the current stream; returns FleetStep."""
+        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
+        for t in ins:
+            self._eng._chk(t, (self.B,))
+        _lib.check(self.lib.admpc_control_step_batch(
+            self._eng._h, C.byref(self._path), C.byref(self._prm), self.B, *[_ptr(t) for t in ins],
+            _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
+            _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), self._eng._stream()))
+        return FleetStep(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt)
+
+    def step_numpy(self, x, y, yaw, vx, vy, yaw_rate, steer):
+        """step() with host arrays in and host copies out (synchronises)."""
+        d = lambda a: torch.as_tensor(np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), (self.B,))), device=self.device)
+        r = self.step(*[d(a) for a in (x, y, yaw, vx, vy, yaw_rate, steer)])
+        torch.cuda.current_stream(self.device).synchronize()
+        return FleetStep(*[t.cpu().numpy() for t in r])
+
+    def reset(self, mask=None):
+        """Selected vehicles (bool [B], host or device; None: all) start over as a freshly created controller: zero iterate, no
+        previous valid inputs, safe_count 0 -- what re-creating the solver in reset_mpc_optimizer would give (gp_ad_mpc_node.py:154-158)."""
+        if mask is None:
+            m = slice(None)
+        else:
+            m = torch.as_tensor(np.asarray(mask) if not isinstance(mask, torch.Tensor) else mask, device=self.device).to(torch.bool)
+            if tuple(m.shape) != (self.B,):
+                raise ValueError("mask must have shape (%d,)" % self.B)
+        for t in (self.x_opt, self.w_opt, self.safe_count, self.prev_u, self.has_valid):
+            t[m] = 0

@@ -31,6 +31,7 @@
 #ifndef ADMPC_H
 #define ADMPC_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -326,6 +327,48 @@ int admpc_waypoints_batch(int device, int M, int H, double dt, int B,
                           const double* cdist, const double* curv,
                           const double* X_init, const double* Y_init, const double* psi_init,
                           double* out_ref, double* out_err, int32_t* out_stop, void* stream);
+
+/* The batched control step of a fleet (csrc/admpc_step.hip): what the reference node does for one pose message
+ * (gp_ad_mpc_node.py:389-438 -> run_mpc :160-230), for B vehicles on ONE global path, enqueued on `stream` as one chain:
+ *   admpc_waypoints_batch -> admpc_resample_vel_batch -> assembly (x0, the node's reference rows padded as host.pad_reference pads
+ *   them, host.yaw_fix, host.vel_switch) -> admpc_solve_batch -> command (is_valid_command against the padded target, the fallback
+ *   w[0:2] = prev[2:4] when a previous valid solution exists, the update of the previous valid inputs, the Ackermann fields, the
+ *   node's check_pred_trj against its N-row window, safe_count gate and steering command as in admpc_actuation_batch).
+ * Deliberate deviation from the node: it clamps the speed of the GLOBAL path once per waypoint message at the speed the vehicle had
+ * then (:351-368); vehicles at different speeds cannot share that, so the clamp runs on each vehicle's local window at its current
+ * speed (admpc_resample_vel_batch).  AdmpcStepParams.resample = 0 turns it off.
+ * No host synchronisation and no allocation once admpc_reserve(s, B) has run: the chain can be captured into a graph. */
+typedef struct AdmpcPath {
+    int32_t M;                 /* waypoints of the global path (>= 2); 0 = unset                                        */
+    int32_t H;                 /* local horizon (traj_horizon); must equal the solver's N (gp_ad_mpc_node.py:95)         */
+    double  dt;                /* traj_dt = t_horizon / N                                                               */
+    const double *vel, *x, *y, *psi, *psi_unwrapped, *cdist, *curv;   /* device columns [M] as for admpc_waypoints_batch */
+} AdmpcPath;
+
+typedef struct AdmpcStepParams {
+    double  blend_min, blend_max;  /* vel_switch (ad_3d.py)                                                              */
+    double  acc_max, resample_dt;  /* resample_vel: acc_max * dt * 0.8 per slot (node: dt = t_horizon / N)              */
+    int32_t resample;              /* != 0: clamp each vehicle's window of speeds                                        */
+    int32_t threshold;             /* consecutive successes before an MPC command is issued (node: 10)                   */
+} AdmpcStepParams;
+
+/* Device bytes of the step's workspace for batches of up to B vehicles (waypoint window, x0, yref, yref_e, p). */
+int admpc_control_step_workspace(const AdmpcSolver* s, int B, size_t* bytes);
+
+/* One control step for B vehicles.  Device arrays:
+ *   in        px, py, yaw, vx, vy, yaw_rate, steer [B]   pose, odometry, measured steering (x0 = this order, gp_ad_mpc_node.py:410)
+ *   state     xbar [B][N+1][7], ubar [B][N][2]           the iterate (warm start in, x_opt / w_opt out)
+ *   (in/out)  safe_count [B]                             consecutive successes (status > 0 resets it)
+ *             prev_u [B][N][2], has_valid [B]            the last valid input sequence and whether one exists
+ *   work      admpc_control_step_workspace bytes
+ *   out       ack [B][4] float32 {steering_angle, steering_angle_velocity, speed, acceleration}, mode [B] (1 = MPC, 0 = brake),
+ *             valid [B] (is_valid_command), status [B] (acados status of the solve)
+ * ADMPC_EINVAL: path H != N, N outside [3, 64] (the waypoint kernel's horizon), an unset path, a null array. */
+int admpc_control_step_batch(AdmpcSolver* s, const AdmpcPath* path, const AdmpcStepParams* prm, int B,
+                             const double* px, const double* py, const double* yaw, const double* vx, const double* vy,
+                             const double* yaw_rate, const double* steer,
+                             double* xbar, double* ubar, int32_t* safe_count, double* prev_u, int32_t* has_valid,
+                             void* work, float* ack, int32_t* mode, int32_t* valid, int32_t* status, void* stream);
 
 const char* admpc_last_error(void);
 const char* admpc_version(void);

@@ -1,0 +1,130 @@
+"""Vehicles per second of the fleet control step (ad_mpc_amd/fleet.py, admpc_control_step_batch) against the bare solve of the same
+batch (admpc_solve_batch on the same references) and against the per-vehicle loop through ROSGPMPC (get_waypoints, resample_vel,
+set_reference, optimize: what a host does for each vehicle without the fleet step).
+
+    python scripts/fleet_step.py [--batches 1,64,4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--loop-calls 200]
+
+One JSON line per (N, B) and one for the per-vehicle loop per N.  Times come from HIP events around `steps` back-to-back steps (fleet,
+bare solve) or wall time around `loop-calls` calls (the per-vehicle loop, which synchronises at every call by construction)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from ad_mpc_amd import host  # noqa: E402
+from ad_mpc_amd.create_ros_ad_mpc import ROSGPMPC  # noqa: E402
+from ad_mpc_amd.fleet import FleetController  # noqa: E402
+
+T_HORIZON, OPT_DT = 1.0, 0.01
+
+
+def path(M=400, ds=0.5):
+    s = np.arange(M) * ds
+    return s * np.cos(0.3), s * np.sin(0.3) + 2.0 * np.sin(s / 30.0), np.arctan2(np.sin(0.3) + 2.0 / 30.0 * np.cos(s / 30.0), np.cos(0.3) + 0 * s), \
+        7.0 + 1.5 * np.sin(s / 20.0)
+
+
+def poses(B, p, seed=0):
+    """Vehicles at the first waypoints of the path (the reference generator lays its window from the path's first waypoint on,
+    ref_traj.py:124-131), up to 1 m off it, speeds 5 .. 9 m/s."""
+    rng = np.random.default_rng(seed)
+    x, y, psi, _ = p
+    idx = rng.integers(0, 5, size=B)
+    e = rng.uniform(-1.0, 1.0, size=B)
+    px, py = x[idx] - e * np.sin(psi[idx]), y[idx] + e * np.cos(psi[idx])
+    yaw = psi[idx] + rng.uniform(-0.1, 0.1, size=B)
+    return [px, py, yaw, rng.uniform(5.0, 9.0, size=B), rng.uniform(-0.2, 0.2, size=B), rng.uniform(-0.1, 0.1, size=B),
+            rng.uniform(-0.05, 0.05, size=B)]
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) * 1e-3 / steps
+
+
+def fleet_and_bare(N, B, p, steps, warmup):
+    fc = FleetController(T_HORIZON, N, OPT_DT, B)
+    fc.set_traj(*p)
+    ins = [torch.as_tensor(a, dtype=torch.float64, device=fc.device) for a in poses(B, p)]
+    t_step = timed(lambda: fc.step(*ins), steps, warmup)
+    # the bare solve of the same batch: the references the step assembles, built here with the same host rules
+    ref, _, _ = fc._ref.get_waypoints_batch(ins[0], ins[1], ins[2])
+    fc._eng.resample_vel(ref[:, 3, :], ins[3], ins[4], fc.ad.acc_max, T_HORIZON / N)
+    r = ref.cpu().numpy()
+    yaw = ins[2].cpu().numpy()
+    yr = np.zeros((B, N, 9)); yr[:, :, 0], yr[:, :, 1], yr[:, :, 3] = r[:, 0], r[:, 1], r[:, 3]
+    yr[:, :, 2] = host.yaw_fix(yaw[:, None], r[:, 2])
+    ye = yr[:, N - 1, :7].copy()
+    x0 = np.stack([a.cpu().numpy() for a in ins], axis=1)
+    pp = host.vel_switch(x0[:, 3], fc.ad.blend_min, fc.ad.blend_max)
+    d = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=fc.device)
+    tx0, tyr, tye, tp = d(x0), d(yr), d(ye), d(pp)
+    xb, ub = torch.zeros_like(fc.x_opt), torch.zeros_like(fc.w_opt)
+    st = torch.empty(B, dtype=torch.int32, device=fc.device)
+    t_solve = timed(lambda: fc._eng.solve(tx0, tyr, tye, tp, xb, ub, None, st, None), steps, warmup)
+    modes = fc.mode.cpu().numpy()
+    fc.close()
+    return t_step, t_solve, float(modes.mean())
+
+
+def per_vehicle_loop(N, p, calls):
+    from ad_mpc_amd.ref_traj import RefTrajectory
+    mpc = ROSGPMPC(T_HORIZON, N, OPT_DT)
+    rt = RefTrajectory(traj_horizon=N, traj_dt=T_HORIZON / N)
+    rt.set_traj(*p)
+    ps = poses(calls, p, seed=1)
+
+    def one(i):
+        px, py, yaw, vx, vy, r, steer = (float(a[i]) for a in ps)
+        wd = rt.get_waypoints(px, py, yaw)
+        vel = host.resample_vel(wd["v_ref"], vx, vy, mpc.ad.acc_max, T_HORIZON / N)
+        ref = np.zeros([7, N]); ref[0], ref[1], ref[2], ref[3] = wd["x_ref"], wd["y_ref"], wd["psi_ref"], vel
+        mpc.set_state([px, py, yaw, vx, vy, r, steer])
+        mpc.set_reference(ref.T, np.zeros((N - 1, 2)), False)
+        mpc.optimize(0)
+    for i in range(min(20, calls)):
+        one(i)
+    t0 = time.perf_counter()
+    for i in range(calls):
+        one(i)
+    return (time.perf_counter() - t0) / calls
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,64,4096")
+    ap.add_argument("--horizons", default="20,40")
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--loop-calls", type=int, default=200)
+    a = ap.parse_args()
+    p = path()
+    gpu = torch.cuda.get_device_name(0)
+    for N in [int(v) for v in a.horizons.split(",")]:
+        t_loop = per_vehicle_loop(N, p, a.loop_calls)
+        print(json.dumps({"what": "per_vehicle_rosgpmpc_loop", "N": N, "vehicles_per_s": round(1.0 / t_loop, 1),
+                          "us_per_vehicle": round(t_loop * 1e6, 1), "gpu": gpu}), flush=True)
+        for B in [int(v) for v in a.batches.split(",")]:
+            t_step, t_solve, mode1 = fleet_and_bare(N, B, p, a.steps, a.warmup)
+            print(json.dumps({"what": "fleet_step", "N": N, "B": B, "vehicles_per_s": round(B / t_step, 1), "us_per_step": round(t_step * 1e6, 1),
+                              "bare_solve_vehicles_per_s": round(B / t_solve, 1), "us_per_bare_solve": round(t_solve * 1e6, 1),
+                              "step_over_solve": round(t_step / t_solve, 3), "vs_loop": round(t_loop * B / t_step, 1),
+                              "mpc_mode_share": round(mode1, 3), "gpu": gpu}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
