@@ -12,9 +12,33 @@
 //   C  H2-H4  Gauss-Newton cost, bounds, full condensing                ad_3d_optimizer.py:146-199; acados_solver_sim_car.c:145
 //   D  H5     unconstrained trial, Mehrotra predictor-corrector on the dense 40-input QP (reference: HPIPM, :688-692)
 //   E  H6     state expansion, full step, cost, status                  acados_solver_sim_car.c:647-648,677
-// The phase bodies descend from the four-kernel pipeline of rounds 1-2 (kernels A, C, D, E in admpc_kernels.hip, `make legacy` only;
-// DESIGN section 4); what changed is where the data lives and that no instance waits for a kernel boundary: the slowest instance
+// The phase bodies descend from the four-kernel pipeline of rounds 1-2 (kernels A, C, D, E; C, D, E removed, last
+// present at commit a808f29); what changed is where the data lives and that no instance waits for a kernel boundary: the slowest instance
 // of a batch starts at once instead of after everybody's linearisation and condensing.
+//
+// Alternatives that were built, measured and removed (compile-time switches, last present at commit a808f29):
+//   - H = sum_k Gamma_k' Q Gamma_k on the vector pipe (v_fmac_f64_dpp rows) instead of MFMA tiles: 13.4 against 10.1 us per instance
+//     in isolation (profiles/r3/mfma_condense_ab.txt).
+//   - the whole condensing -- recursion Gamma_{k+1} = A_k Gamma_k, free response, Hessian, reduced gradient -- in MFMA tiles: correct
+//     (106 GPU tests green) but 1 % SLOWER: a 16 x 16 x 4 tile carries 7 x 7 useful products in the recursion and the dependent chain
+//     of 42 of them is latency-bound (scripts/probes/mfma_condense_probe.hip, profiles/r3/mfma_condense_ab.txt).
+//   - the LDS reads of a condensing stage where hipcc puts them: 458 instead of 97 s_waitcnt in the phase (an instruction of any kind
+//     costs its wave an issue slot, and the single-wave time is what the end of a launch runs at).
+//   - the free response xhat_k propagated redundantly by all 64 lanes instead of riding in lane 40 as a 41st column of Gamma: 30 more
+//     multiply-adds per stage, the same bits.
+//   - the 30 entries of A_k by fifteen ds_read_b128 that hand all 64 lanes the same 16 bytes instead of two ds_read_b64 per stage and
+//     DPP row broadcasts: 15 KB of LDS return traffic per stage for 240 bytes of information, on an LDS pipe that was 76 % busy over
+//     the whole launch (SQ_ACTIVE_INST_LDS).  The same bits.
+//   - inputs and outputs loaded and stored non-temporally (to keep the slot buffers in the L2): no effect on traffic, 0.5 % slower.
+//   - the next ticket drawn between instances instead of under phase E: 3-4 us of a 36 us cheap instance in the drain.
+//   - deferred expansions: instances drawn by ticket pushed their expansion (phase A once more and phase E) into queues that the waves
+//     popped when the ticket queue was dry (jobs of 15 us instead of 54 at the end of a launch).  Bit-identical, and SLOWER: 19.2 M
+//     against 20.9 M solves/s at configs[1], 22.1 against 24.1 M at B = 8192, two batches in flight 20.6 against 23.1 M -- an expansion
+//     that changes waves pays ~6 us of dependent trips to the memory side (queue scan, pop, entry, du; the instance's inputs miss the
+//     other XCD's L2) on a 15 us job, more than the shorter ramp returns.  With ONE queue the counter line was the bottleneck
+//     (same-line atomics retire at ~10 ns: 35 % slower), and compare-and-swap pops took 35 ms per step.
+//   - wave-priority classes, a reversed ticket order for the second wave of a SIMD, a trap on the never-taken side of the per-stage
+//     block test, other rungs of the priority ladder (see phase D for the measured ones).
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
@@ -27,59 +51,6 @@
 #define WAVE 64
 #define IPM_FLOOR 1e-40
 #define GTS 42           // values per stage of the packed linearisation (see kernel A in admpc_kernels.hip)
-#ifndef F20_NT
-#define F20_NT 0
-#endif
-// 1 (shipped): the Hessian H = sum_k Gamma_k' Q Gamma_k is accumulated on the matrix pipe (v_mfma_f64_16x16x4_f64 tiles), the stage
-// recursion stays on the vector pipe; 0: everything by v_fmac_f64_dpp rows on the vector pipe; 2: the whole condensing -- recursion
-// Gamma_{k+1} = A_k Gamma_k, free response, Hessian, reduced gradient -- in MFMA tiles (correct, 106 GPU tests green, but 1 % SLOWER
-// than 1: a 16 x 16 x 4 tile carries 7 x 7 useful products in the recursion and the dependent chain of 42 of them is latency-bound) (A/B: scripts/probes/mfma_condense_probe.hip, profiles/r3/mfma_condense_ab.txt)
-#ifndef F20_MFMA
-#define F20_MFMA 1
-#endif
-// 1 (shipped): every LDS read of a condensing stage is issued in front of the stage (458 -> 97 s_waitcnt in the phase; an instruction of
-// any kind costs its wave an issue slot, and the single-wave time is what the end of a launch runs at); 0: where hipcc puts them
-#ifndef F20_CPREF
-#define F20_CPREF 1
-#endif
-// 1: the free response xhat_k of the condensing rides in lane 40 as a 41st column of Gamma (b_k enters it through a per-lane LDS
-// address, the other lanes read the components they need from the exchange buffer every lane writes anyway) instead of being propagated
-// redundantly by all 64 lanes: 30 multiply-adds per stage.  Needs F20_CPREF and F20_MFMA == 1.  The same bits.
-#ifndef F20_XHLANE
-#define F20_XHLANE 1
-#endif
-// 1: the 30 entries of A_k reach the propagation's multiply-adds through DPP row broadcasts -- every 16-lane row holds them in TWO registers
-// (lane e: entries e and 16 + e, two ds_read_b64 per stage) -- instead of fifteen ds_read_b128 that hand all 64 lanes the same 16 bytes:
-// 15 KB of LDS return traffic per stage for 240 bytes of information.  The LDS pipe of a CU is shared by its eight waves and was 76 % busy
-// over the whole launch (SQ_ACTIVE_INST_LDS).  Needs F20_XHLANE (no uniform operands left in the phase).  The same bits.
-#ifndef F20_ADPP
-#define F20_ADPP 1
-#endif
-#if F20_ADPP && !F20_XHLANE
-#error "F20_ADPP needs F20_XHLANE"
-#endif
-#if F20_XHLANE && !(F20_CPREF && F20_MFMA == 1)
-#error "F20_XHLANE needs F20_CPREF and F20_MFMA == 1"
-#endif
-#ifndef F20_TICKET_AHEAD
-#define F20_TICKET_AHEAD 1
-#endif
-// Deferred expansions (0, shipped: off; 1: the instances drawn by ticket push their expansion -- phase A once more and phase E -- into
-// queues that the waves pop when the ticket queue is dry: jobs of 15 us instead of 54 at the end of a launch).  Built, bit-identical
-// (scripts/defer_check.py), and measured SLOWER: 19.2 M against 20.9 M solves/s at configs[1], 22.1 against 24.1 M at B = 8192, two batches
-// in flight 20.6 against 23.1 M -- an expansion that changes waves pays ~6 us of dependent trips to the memory side (queue scan, pop,
-// entry, du; the instance's inputs miss the other XCD's L2) on a 15 us job, more than the shorter ramp returns.  With ONE queue the
-// counter line was the bottleneck (same-line atomics retire at ~10 ns: 35 % slower), as compare-and-swap pops 35 ms per step.  See
-// `expansion queue` in the kernel; kept as an A/B switch (make variant EXTRA=-DF20_DEFER=1).
-#ifndef F20_DEFER
-#define F20_DEFER 0
-#endif
-#if F20_DEFER && !F20_TICKET_AHEAD
-#error "F20_DEFER needs F20_TICKET_AHEAD"
-#endif
-#ifndef F20_TOKTRAP
-#define F20_TOKTRAP 0
-#endif
 
 namespace {
 
@@ -119,32 +90,6 @@ __device__ __forceinline__ unsigned long long f20_now() { unsigned long long t; 
 #include "dense40.h"
 #include "cond_common.h"
 
-// Inputs and outputs of an instance are touched once (xbar three times, minutes of L2 time apart): marked non-temporal so that
-// they do not push the waves' slot buffers out of the L2 (measured: no effect on traffic, 0.5 % slower: off)
-#if F20_NT
-#define LDG(p) __builtin_nontemporal_load(p)
-#define STG(p, v) __builtin_nontemporal_store(v, p)
-#else
-#define LDG(p) (*(p))
-#define STG(p, v) (*(p) = (v))
-#endif
-// stage_dq of cond_common.h with the loads above
-template <int NN>
-__device__ __forceinline__ void stage_dq_nt(double* __restrict__ dq, const double* __restrict__ xb, const double* __restrict__ yr,
-                                            const double* __restrict__ yre, const int lane) {
-    constexpr int CNT = (NN + 1) * NX, IT = (CNT + WAVE - 1) / WAVE;
-    double xv[IT], yv[IT];
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-        int i = lane + WAVE * it; i = i < CNT ? i : CNT - 1;
-        const int k = div7(i), c = i - 7 * k;
-        xv[it] = LDG(xb + i);
-        yv[it] = k < NN ? LDG(yr + k * 9 + c) : LDG(yre + c);
-    }
-#pragma unroll
-    for (int it = 0; it < IT; ++it) { int i = lane + WAVE * it; i = i < CNT ? i : CNT - 1; dq[i] = xv[it] - yv[it]; }
-}
-
 // LDS map of one instance (doubles): what the interior point needs and nothing else -- 18.2 KB, eight instances per CU (two waves per
 // SIMD).  The exchange buffers keep the relative layout dense40.h's col_head assumes (sb = cb + 128).  The other phases alias it:
 //   A   JT [0, 1960) Jacobian tables of the RK stages, bl [1960, 2100) defects; then GT [0, 840) (written when the tables are dead)
@@ -172,18 +117,6 @@ struct FusedLds {
 // is in the first round with it, and 1837 of the 1841 that need the interior point at all (correlation with the iteration count
 // 0.80).  A heuristic: it orders work and nothing else -- results do not depend on the draw order.
 //   sched: [0] ticket counter, [1] exit counter, [F20_BINS0 + q] instances in bin q, [F20_HDR + q * cap + j] j-th instance of bin q
-// wave priority by interior-point iteration (measured: 0/2/4 -> 0.250 ms per step, 1/3/6 0.254, 3/6 only 0.255, none 0.269)
-#ifndef F20_PRIO_IT1
-#define F20_PRIO_IT0 0
-#define F20_PRIO_IT1 2
-#define F20_PRIO_IT2 4
-#endif
-#ifndef F20_CLASS_PRIO
-#define F20_CLASS_PRIO 0
-#endif
-#ifndef F20_PAIR_REV
-#define F20_PAIR_REV 0
-#endif
 #include "work_order.h"
 
 static_assert(WAVE == 64, "one wavefront per workgroup: WSYNC is a wave-level fence in this build");
@@ -237,7 +170,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
 #define LAUNDER_CFG(c) int c##_z = 0; asm volatile("" : "+s"(c##_z)); const AdmpcConfig* __restrict__ c = cfg + c##_z
 
     // Factorisation of the Newton matrix M = H + diag(dbar) + (s_odd on the odd columns of the u1 rows) into L D L' (LDS: Lp, invd);
-    // text of kernel D (admpc_kernels.hip), see there and dense40.h for the look-ahead scheme.
+    // see dense40.h for the look-ahead scheme.
     auto factorise = [&](const double dbar_, const double sodd_, const int lz_) __attribute__((always_inline)) {
         const int trz_ = lz_ * (lz_ + 1) / 2;
         const bool uz_ = lz_ < n;
@@ -303,10 +236,9 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
     // Tickets.  Between two instances f20_next is three dependent trips to the L2 (the ticket counter, the bin counts, the bin's list) in
     // front of the instance's own loads -- 3-4 us of a 36 us cheap instance when the wave is alone on its SIMD (the drain).  The bin counts
     // do not change while the kernel runs: every wave scans them once into LDS.  The next ticket is drawn at the top of phase E and resolved
-    // behind its recursion, so both remaining trips run under the expansion (F20_TICKET_AHEAD=0: the plain f20_next between instances).
+    // behind its recursion, so both remaining trips run under the expansion.
     int* const sch_incl = reinterpret_cast<int*>(lds_raw + FusedLds::oSch);
     int* const sch_cnt = sch_incl + 64;
-#if F20_TICKET_AHEAD
     if (cap != 0) {
         LAUNDER_LANE(lane_s);
         const int c = sched[F20_BINS0 + F20_NB - 1 - lane_s];
@@ -323,102 +255,25 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
         const int base = __builtin_amdgcn_readlane(incl - c, l);
         return sched + F20_HDR + (size_t)(F20_NB - 1 - l) * cap + (t - base);
     };
-    int next_inst = -2, next_tk = 0;                                    // -2: not drawn yet; next_tk: the ticket of next_inst
-#endif
-    // ---- expansion queue.  What follows the interior point -- phase A once more and phase E, ~15 of the ~54 us of an instance the trial
-    // solves -- needs nothing of the instance but its step du (40 doubles): the linearisation is recomputed from the inputs anyway.  A wave
-    // that has finished phase D of an instance therefore PUSHES the expansion (du into the per-instance buffer, the instance index into the
-    // queue) and draws the next ticket at once; the expansions are popped by the waves that find the ticket queue dry.  The batch is then a
-    // list of jobs whose last and most numerous ones take 15 us instead of 54: the ramp at the end of the launch (two jobs per wave slot at
-    // B = 4096: a quarter of the run time with half of the slots idle) is filled with them.  Pops are fetch-adds (a compare-and-swap
-    // on the pop counter serialised 2000 waves: 35 ms per step); what makes that safe is at the pop.  Visibility across the XCDs' L2s
-    // without cache-wide write-backs: du and the queue entries are agent-scope relaxed atomic stores and loads (sc1: coherent per location
-    // across the XCDs; as read-modify-write atomics the 80 accesses per expansion cost 70 us per step), ordered by the wave's own
-    // s_waitcnt between them; the counters are fetch-adds like the ticket counter.
-    // One queue would be one cache line of counters: same-line atomics retire at ~10 ns each, and the 15 us jobs of 2048 waves ask for more
-    // pops than that (measured: the step 35 % SLOWER).  So F20_NQ sub-queues, a counter line each; ticket t pushes into queue (t - grid) mod
-    // F20_NQ, which makes every queue's entry count known; a wave pops from the first queue at or behind its home (block mod F20_NQ) whose
-    // pop counter -- one vector load over all queues -- is below its count.
-    //   qh[q][32]: pushes at +0, pops at +1 (zeroed by the order kernel); qitems[q][qcap] = instance (-1 until published, -2: none); dubuf[inst][40]
-    int* const qh = sched + F20_HDR + (size_t)F20_NB * cap;
-    int* const qitems = qh + F20_NQ * 32;
-    const int qcap = cap / F20_NQ + 1;
-    double* const dubuf = reinterpret_cast<double*>(qitems + cap + F20_NQ + (cap & 1));
-    const int nent = B - (int)gridDim.x;                                // entries of all queues: one per instance drawn by ticket
-    const bool can_defer = F20_DEFER && cap != 0 && !park_gt;           // (a parked linearisation lives in the slot of the wave that shot it)
-    (void)qcap; (void)dubuf; (void)nent; (void)can_defer;               // (unused with F20_DEFER == 0)
+    int next_inst = -2;                                                 // -2: not drawn yet
+    const int grid = (int)gridDim.x;
     for (;;) {
         LAUNDER_LANE(lane0);
-#if F20_TICKET_AHEAD
         int inst;
         if (cap == 0) inst = first_ticket ? (int)blockIdx.x : -1;
-        int cur_tk = next_tk;                                           // the ticket of this instance (its sub-queue)
-        if (cap == 0) { }
+        if (cap == 0) { }                                               // (kept apart from the test above: merging them changes the listing)
         else if (next_inst != -2) inst = next_inst;
         else {
             int t = (int)blockIdx.x;
-            if (!first_ticket) { int v = 0; if (lane0 == 0) v = atomicAdd(sched, 1); t = (int)gridDim.x + __builtin_amdgcn_readfirstlane(v); }
+            if (!first_ticket) { int v = 0; if (lane0 == 0) v = atomicAdd(sched, 1); t = grid + __builtin_amdgcn_readfirstlane(v); }
             const int* const e = ticket_entry_addr(t, lane0);
             inst = e ? __builtin_amdgcn_readfirstlane(*e) : -1;
-            cur_tk = t;
         }
         next_inst = -2;
-#else
-        int inst = f20_next(sched, cap, first_ticket, lane0);
-#endif
-        bool ejob = false;
-#if F20_DEFER
-        if (inst < 0 && can_defer) {
-            // the ticket queue is dry: pop an expansion.  Every instance drawn by ticket pushes exactly one entry (its expansion, or -2 when it
-            // has none: failed, or skipped by its status), so every queue's number of entries is known.  A pop beyond it sends the wave to
-            // the next queue (and out when all are spent); a pop in front of its push waits for it -- the pusher holds a ticket, so it is
-            // a RUNNING wave (the workgroups that have not started yet hold first tickets only, and those never push): the wait cannot
-            // depend on a workgroup that needs this wave's slot.
-            const int home = (int)blockIdx.x & (F20_NQ - 1);
-            for (;;) {
-                const int ql = (lane0 + home) & (F20_NQ - 1);           // lane l looks at queue home + l
-                const int tot = nent > ql ? (nent - ql + F20_NQ - 1) / F20_NQ : 0;
-                const int popped = __hip_atomic_load(qh + ql * 32 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const unsigned long long open = __ballot(popped < tot);
-                if (open == 0ull) break;                                // every queue is spent: the wave leaves
-                const int l = __ffsll((long long)open) - 1;
-                const int q = (l + home) & (F20_NQ - 1);
-                const int tq = __builtin_amdgcn_readlane(tot, l);
-                int pq = 0;
-                if (lane0 == 0) pq = atomicAdd(qh + q * 32 + 1, 1);
-                pq = __builtin_amdgcn_readfirstlane(pq);
-                if (pq >= tq) continue;                                 // somebody was faster: look again
-                int i = -1;
-                for (;;) {
-                    if (lane0 == 0) i = __hip_atomic_load(qitems + q * qcap + pq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    i = __builtin_amdgcn_readfirstlane(i);
-                    if (i != -1) break;
-                    __builtin_amdgcn_s_sleep(16);
-                }
-                if (i < 0) continue;                                    // an instance without an expansion
-                inst = i; ejob = true;
-                next_inst = -1;                                         // the ticket queue stays dry
-                break;
-            }
-        }
-#endif
-#if F20_CLASS_PRIO
-        const bool first_class = first_ticket && (int)blockIdx.x < (int)gridDim.x / 2;
-#endif
-        const bool by_ticket = !first_ticket; (void)by_ticket; (void)cur_tk;
         first_ticket = false;
         if (inst < 0) break;
         F20_TRACE_BEGIN();
-        auto push_none = [&]() __attribute__((always_inline)) {       // an instance drawn by ticket that has no expansion still owes the queue its entry
-#if F20_DEFER
-            if (can_defer && by_ticket && !ejob) {
-                LAUNDER_LANE(lq);
-                const int q = (cur_tk - (int)gridDim.x) & (F20_NQ - 1);
-                if (lq == 0) { const int qs = atomicAdd(qh + q * 32, 1); __hip_atomic_store(qitems + q * qcap + qs, -2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-            }
-#endif
-        };
-        if (!ejob && !first_pass && statusg[inst] != 0) { push_none(); continue; }    // failed / converged in an earlier SQP iteration of this call
+        if (!first_pass && statusg[inst] != 0) continue;    // failed / converged in an earlier SQP iteration of this call
         double* const xbg = xbarg + (size_t)inst * (N + 1) * NX;
         double* const ubg = ubarg + (size_t)inst * N * NU;
         const double* yrg = yrefg + (size_t)inst * N * NY;
@@ -432,16 +287,8 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
         int it = 0;
         // without a slot buffer phase A runs a second time in front of phase E: pass 1 of this loop (one copy of the code)
         int npass = park_gt ? 1 : 2; asm volatile("" : "+s"(npass));
-        bool deferred = false;
         int pass0 = 0;
-#if F20_DEFER
-        if (ejob) {                                                     // a popped expansion: its step, then pass 1 (phase A) and phase E
-            LAUNDER_LANE(lq);
-            du = lq < n ? __hip_atomic_load(dubuf + (size_t)inst * n + lq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
-            pass0 = 1;
-        }
-#endif
-        asm volatile("" : "+s"(pass0));
+        asm volatile("" : "+s"(pass0));                                 // an opaque first pass (a known 0 changes the listing)
 #pragma unroll 1
         for (int pass = pass0; pass < npass; ++pass) {
         {
@@ -457,8 +304,8 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                 const double pin = pg[inst];
                 double x[NX], u[NU], xn1[NX];
 #pragma unroll
-                for (int i = 0; i < NX; ++i) { x[i] = LDG(xbg + k * NX + i); xn1[i] = LDG(xbg + (k + 1) * NX + i); }
-                u[0] = LDG(ubg + k * NU); u[1] = LDG(ubg + k * NU + 1);
+                for (int i = 0; i < NX; ++i) { x[i] = *(xbg + k * NX + i); xn1[i] = *(xbg + (k + 1) * NX + i); }
+                u[0] = *(ubg + k * NU); u[1] = *(ubg + k * NU + 1);
                 double kx[NX], accx[NX];
 #pragma unroll
                 for (int i = 0; i < NX; ++i) { kx[i] = 0.0; accx[i] = 0.0; }
@@ -551,119 +398,11 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
         if (pass != 0) break;
 
         // =================================================================================================================
-        // phase C (H2-H4): condensing, lane i <-> input i = 2k + j (text of admpc_condense_kernel).  Leaves the packed
+        // phase C (H2-H4): condensing, lane i <-> input i = 2k + j.  Leaves the packed
         // Hessian rows in Hp and, in registers, g0 (reduced gradient at du = 0) and xhat6 of the lane's stage.
         // =================================================================================================================
         F20_STAMP(2);
         double g0, xh6_own = 0.0;
-#if F20_MFMA == 2
-        // ---- condensing on the matrix pipe.  Gamma_k (7 x 40) and the free response xhat_k (as a 41st column) live in three
-        // 16-column MFMA tiles in the C/D register layout (lane & 15 = column inside the block, (lane >> 4) + 4 v = row): register v of a
-        // tile IS the B operand of K-step v of the next product, so the stage recursion Gamma_{k+1} = A_k Gamma_k runs tile -> tile with
-        // no exchange at all, and the same registers are both operands of H += (W Gamma)' Gamma.  Column 40 carries xhat_k through the
-        // recursion (+ b_k) and, with the tracking error added, makes row 40 of the accumulated product the reduced gradient:
-        // g0_i = r_i + sum_k Gamma_k[:, i]' W (xhat_k + xbar_k - xref_k).  Per stage the vector pipe only fetches the operands (A_k, B_k,
-        // b_k, the error from LDS) and selects; 184 v_mfma_f64_16x16x4_f64 per instance replace ~3400 vector instructions.
-        {
-            LAUNDER_LANE(lane); LAUNDER_CFG(cf);
-            const int ji = lane & 1;
-            const bool uact = lane < n;
-            const int sc = uact ? lane : 0;
-            const int r16 = lane & 15, kq = lane >> 4;
-            const double Ts = cf->Ts, h = cf->Ts;
-            const double Rj = Ts * cf->W[NX + ji];
-            stage_dq_nt<N>(dqC, xbg, yrg, yrefeg + (size_t)inst * NX, lane);
-            const double ubar_i = ubg[sc];
-            const double r_i = Rj * (ubar_i - yrg[(sc >> 1) * 9 + 7 + (sc & 1)]);
-            // weights of the rows this lane holds: row kq (v = 0) and row 4 + kq (v = 1; row 7 does not exist)
-            const double wq0 = Ts * cf->W[kq], we0 = cf->We[kq];
-            const double wq1 = kq < 3 ? Ts * cf->W[4 + (kq < 3 ? kq : 0)] : 0.0, we1 = kq < 3 ? cf->We[4 + (kq < 3 ? kq : 0)] : 0.0;
-            const bool any_hi = (QMASK >> 4) != 0;                      // a tracking weight on v_y, psi_dot or delta: second K-step of H
-            const bool is40 = r16 == 8;                                 // (tile 2 only) the free-response column
-            const d4 z4 = {0.0, 0.0, 0.0, 0.0};
-            d4 G[3] = { z4, z4, z4 };
-            G[2][0] = is40 ? x0g[(size_t)inst * NX + kq] - xbg[kq] : 0.0;                                          // xhat_0 = x0 - xbar_0
-            G[2][1] = (is40 && kq < 3) ? x0g[(size_t)inst * NX + 4 + (kq < 3 ? kq : 0)] - xbg[4 + (kq < 3 ? kq : 0)] : 0.0;
-            d4 acc[3][3];
-#pragma unroll
-            for (int I = 0; I < 3; ++I)
-#pragma unroll
-                for (int J = 0; J < 3; ++J) acc[I][J] = z4;
-            WSYNC();
-            static_for<0, N + 1>([&](auto kc) __attribute__((always_inline)) {
-                constexpr int k = decltype(kc)::value;
-                constexpr int lim = 2 * k < n ? 2 * k : n;        // inputs of stages < k: the non-zero columns of Gamma_k
-                constexpr int nblk = (lim + 15) / 16;             // column blocks that hold them
-                int tok = B; asm volatile("" : "+s"(tok));         // one stage = one basic block (see the vector version)
-                if (tok > 0) {
-                if constexpr (k >= 1) {
-                    // ---- cost of stage k: H += (W Gamma_k)' Gamma_k, with the tracking error on the free-response column
-                    const double e0 = dqC[k * 7 + kq], e1 = dqC[k * 7 + 4 + (kq < 3 ? kq : 0)];
-                    d4 Gh2 = G[2];
-                    Gh2[0] += is40 ? e0 : 0.0;
-                    Gh2[1] += (is40 && kq < 3) ? e1 : 0.0;
-                    if constexpr (k < N) { const double x6 = rdlane(G[2][1], 40); if (lane == k) xh6_own = x6; }      // xhat_k[6]: row 6 = 2 + 4 * 1 of column 40
-                    const double wl0 = k < N ? wq0 : we0, wl1 = k < N ? wq1 : we1;
-                    static_for<0, nblk>([&](auto Jc) __attribute__((always_inline)) {
-                        constexpr int J = decltype(Jc)::value;
-                        static_for<J, 3>([&](auto Ic) __attribute__((always_inline)) {
-                            constexpr int I = decltype(Ic)::value;
-                            if constexpr (I < nblk || I == 2) {
-                                const d4& GI = I == 2 ? Gh2 : G[I];
-                                const d4& GJ = J == 2 ? Gh2 : G[J];
-                                acc[I][J] = __builtin_amdgcn_mfma_f64_16x16x4f64(wl0 * GI[0], GJ[0], acc[I][J], 0, 0, 0);
-                                if (any_hi) acc[I][J] = __builtin_amdgcn_mfma_f64_16x16x4f64(wl1 * GI[1], GJ[1], acc[I][J], 0, 0, 0);
-                            }
-                        });
-                    });
-                }
-                if constexpr (k < N) {
-                    // ---- propagate: Gamma_{k+1} = A_k Gamma_k, xhat_{k+1} = A_k xhat_k + b_k.  A operand of K-step s: A_k[lane & 15][4 s + (lane >> 4)]
-                    // (columns 0, 1 of A are unit vectors, row 6 is e6: not stored in the packed record)
-                    const double* Gk = GT + k * GTS;
-                    const int rr = r16 < 6 ? r16 : 0;
-                    const double a0l = Gk[(kq >= 2 ? kq - 2 : 0) * 6 + rr], a1l = Gk[((kq < 3 ? kq : 0) + 2) * 6 + rr];
-                    const double Aop0 = kq < 2 ? (r16 == kq ? 1.0 : 0.0) : (r16 < 6 ? a0l : 0.0);
-                    const double Aop1 = kq < 3 ? (r16 < 6 ? a1l : ((r16 == 6 && kq == 2) ? 1.0 : 0.0)) : 0.0;
-                    d4 Gn[3] = { z4, z4, z4 };
-                    static_for<0, 3>([&](auto Jc) __attribute__((always_inline)) {
-                        constexpr int J = decltype(Jc)::value;
-                        if constexpr (J < nblk || J == 2)
-                            Gn[J] = __builtin_amdgcn_mfma_f64_16x16x4f64(Aop0, G[J][0], __builtin_amdgcn_mfma_f64_16x16x4f64(Aop1, G[J][1], z4, 0, 0, 0), 0, 0, 0);
-                    });
-                    Gn[2][0] += is40 ? bl[k * 7 + kq] : 0.0;
-                    Gn[2][1] += (is40 && kq < 3) ? bl[k * 7 + 4 + (kq < 3 ? kq : 0)] : 0.0;
-                    // the two inputs of stage k enter with B_k: columns 2k, 2k + 1 of block (2k) / 16, rows 0..5 from the record, row 6 = (0, h)
-                    constexpr int Jn = (2 * k) / 16;
-                    const bool bsel = (r16 >> 1) == (k & 7);
-                    const int jc = r16 & 1;
-                    const double b0l = Gk[(5 + jc) * 6 + kq], b1l = Gk[(5 + jc) * 6 + 4 + (kq < 2 ? kq : 0)];
-                    const double b1v = kq < 2 ? b1l : (kq == 2 ? (jc ? h : 0.0) : 0.0);
-                    Gn[Jn][0] = bsel ? b0l : Gn[Jn][0];
-                    Gn[Jn][1] = bsel ? b1v : Gn[Jn][1];
-#pragma unroll
-                    for (int J = 0; J < 3; ++J) G[J] = Gn[J];
-                }
-                }
-            });
-            // the tiles into the packed lower-triangular rows: element (row = lane >> 4 + 4 v, column = lane & 15) of tile (I, J);
-            // row 40 (tile row block 2, element 8 = 0 + 4 * 2: lanes 0..15, v = 2) is the reduced gradient without its input part
-#pragma unroll
-            for (int I = 0; I < 3; ++I)
-#pragma unroll
-                for (int J = 0; J <= I; ++J)
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const int row = 16 * I + kq + 4 * v, col = 16 * J + r16;
-                        if (row < n && col <= row) Hp[row * (row + 1) / 2 + col] = acc[I][J][v];
-                    }
-            if (kq == 0) { gam[r16] = acc[2][0][2]; gam[16 + r16] = acc[2][1][2]; gam[32 + r16] = acc[2][2][2]; }
-            WSYNC();
-            g0 = r_i + gam[sc];
-            if (uact) Lp[(lane * (lane + 1)) / 2 + lane] = 0.0;         // diagonal slots of the packed factor (see the vector version)
-            WSYNC();
-        }
-#else
         {
             LAUNDER_LANE(lane); LAUNDER_CFG(cf);
             const int ki = lane >> 1, ji = lane & 1;
@@ -671,7 +410,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             const int sc = uact ? lane : 0;
             const double Ts = cf->Ts, h = cf->Ts;
             const double Rj = Ts * cf->W[NX + ji];
-            stage_dq_nt<N>(dqC, xbg, yrg, yrefeg + (size_t)inst * NX, lane);
+            stage_dq<N>(dqC, xbg, yrg, yrefeg + (size_t)inst * NX, lane);
             const double ubar_i = ubg[sc];
             const double r_i = Rj * (ubar_i - yrg[(sc >> 1) * 9 + 7 + (sc & 1)]);
             double Qd[NX], Qe[NX];
@@ -679,17 +418,16 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             for (int i = 0; i < NX; ++i) { Qd[i] = Ts * cf->W[i]; Qe[i] = cf->We[i]; }
             // the carried columns in two sets used alternately (stage k reads set k & 1 and writes the other one): with one set the
             // results of a stage were copied into it behind every stage (the stages are separate basic blocks: ten v_mov_b64 each)
-            double xh2[2][NX], g2[2][NX];
+            double xh0[NX], g2[2][NX];
 #pragma unroll
-            for (int c = 0; c < NX; ++c) { xh2[0][c] = x0g[(size_t)inst * NX + c] - xbg[c]; xh2[1][c] = 0.0; }      // uniform
+            for (int c = 0; c < NX; ++c) xh0[c] = x0g[(size_t)inst * NX + c] - xbg[c];      // uniform
             WSYNC();
 #pragma unroll
-            for (int c = 0; c < NX; ++c) { g2[0][c] = (F20_XHLANE && lane == n) ? xh2[0][c] : 0.0; g2[1][c] = 0.0; }      // lane 40: xhat_0 = x0 - xbar_0
-#if F20_MFMA
+            for (int c = 0; c < NX; ++c) { g2[0][c] = lane == n ? xh0[c] : 0.0; g2[1][c] = 0.0; }      // lane 40: xhat_0 = x0 - xbar_0
             // H on the matrix pipe: six 16 x 16 tiles (I >= J) of v_mfma_f64_16x16x4_f64.  One MFMA step takes K = 4 rows of the
             // 60 x 40 matrix G whose rows are the weighted components of Gamma_k: per stage the components of QMASK, four at a time
             // (QMASK 7: x, y, psi + a zero row).  Operand layout: lane = index + 16 * k  ->  lane >> 4 picks the component, lane & 15
-            // the column inside the block; operands come from the LDS exchange buffer the vector version broadcasts from.  The matrix
+            // the column inside the block; operands come from the LDS exchange buffer gam.  The matrix
             // pipe is otherwise idle and runs under the propagation FMAs: 1260 v_fmac_f64_dpp per instance leave the vector pipe
             // (measured in isolation: 13.4 -> 10.1 us per instance, profiles/r3/mfma_condense_ab.txt).
             constexpr int NCOMP = ((QMASK >> 0) & 1) + ((QMASK >> 1) & 1) + ((QMASK >> 2) & 1) + ((QMASK >> 3) & 1) + ((QMASK >> 4) & 1) + ((QMASK >> 5) & 1) + ((QMASK >> 6) & 1);
@@ -716,66 +454,37 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             for (int I = 0; I < 3; ++I)
 #pragma unroll
                 for (int J = 0; J < 3; ++J) acc[I][J] = d4{0.0, 0.0, 0.0, 0.0};
-#else
-            double hrow[n];
-#pragma unroll
-            for (int i = 0; i < n; ++i) hrow[i] = 0.0;
-#endif
             g0 = r_i;
             static_for<0, N + 1>([&](auto kc) __attribute__((always_inline)) {
                 constexpr int k = decltype(kc)::value;
                 constexpr int lim = 2 * k < n ? 2 * k : n;        // inputs of stages < k (even)
                 constexpr int nblk = (lim + 15) / 16;             // 16-lane blocks of Gamma that are non-zero at this stage
-                double (&g)[NX] = g2[k & 1]; double (&xh)[NX] = xh2[k & 1];
-                double (&gn)[NX] = g2[(k + 1) & 1]; double (&xn)[NX] = xh2[(k + 1) & 1];
+                double (&g)[NX] = g2[k & 1];
+                double (&gn)[NX] = g2[(k + 1) & 1];
                 // One stage = one basic block (an always-true test the compiler cannot see through): merged into one 21-stage block,
                 // hipcc hoists every LDS load of the whole instance and spills ~1600 registers.
                 int tok = B; asm volatile("" : "+s"(tok));
-#if F20_TOKTRAP
-                // the never-taken side of the test ends the program instead of joining the stage: no phi nodes behind the stage, i.e. no
-                // copies of the carried columns (g, xh: ten v_mov_b64 per stage) into the registers the skipped path would have kept
-                if (tok <= 0) __builtin_trap();
-                {
-#else
                 if (tok > 0) {
-#endif
                 double wg[NX];
-#if F20_MFMA
                 double blk[NSTEP][3];
-#else
-                double Rb[NX][3];
-#endif
-#if F20_CPREF
                 // Every LDS read of the stage's record is issued before anything else of the stage: left to itself hipcc keeps one or two
                 // ds_read_b128 in flight and the propagation (60 multiply-adds behind 21 reads) waits on each of them in turn.
-                double2 Av[15], Bv[3]; double blv[NX], Aq[2]; (void)Av; (void)Aq;
+                double2 Bv[3]; double blv[NX], Aq[2];
                 const bool mine_p = ki == k;
                 if constexpr (k < N) {
                     const double* Gk = GT + k * GTS;
                     // (indices into the one LDS array, not selected pointers: hipcc turns a select of two LDS pointers into flat pointers and
                     // converts every element address back with a null check -- five scalar instructions per load)
                     const int bidx = mine_p ? FusedLds::oGTC + k * GTS + 5 * 6 + 6 * ji : FusedLds::oGam + 7 * 64;
-#if F20_ADPP
                     { const int e16 = lane & 15; Aq[0] = Gk[e16]; Aq[1] = Gk[16 + (e16 < 14 ? e16 : 13)]; }
-#else
-#pragma unroll
-                    for (int q_ = 0; q_ < 15; ++q_) Av[q_] = *reinterpret_cast<const double2*>(Gk + 2 * q_);
-#endif
 #pragma unroll
                     for (int q_ = 0; q_ < 3; ++q_) Bv[q_] = *reinterpret_cast<const double2*>(lds_raw + bidx + 2 * q_);
-#if F20_XHLANE
                     const int lidx = lane == n ? FusedLds::oBlA + k * 7 : FusedLds::oGam + 7 * 64;      // b_k for the column of the free response, zeros for the others
 #pragma unroll
                     for (int r = 0; r < NX; ++r) blv[r] = lds_raw[lidx + r];
-#else
-#pragma unroll
-                    for (int r = 0; r < NX; ++r) blv[r] = bl[k * 7 + r];
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#endif
                 if constexpr (k >= 1) {
-#if F20_XHLANE
                     static_for<0, NX>([&](auto cc) __attribute__((always_inline)) {
                         constexpr int c = decltype(cc)::value;
                         if constexpr ((QMASK >> c) & 1) {
@@ -790,49 +499,22 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         if constexpr ((QMASK >> c) & 1) g0 += wg[c] * (gam[c * 64 + n] + dqC[k * 7 + c]);      // lane 40 has just published xhat_k[c]
                     });
                     { double x6 = gam[6 * 64 + n]; asm volatile("" : "+v"(x6)); xh6_own = lane == k ? x6 : xh6_own; }      // (an unconditional load)
-#else
-                    if (lane == k) xh6_own = xh[6];
-                    static_for<0, NX>([&](auto cc) __attribute__((always_inline)) {
-                        constexpr int c = decltype(cc)::value;
-                        if constexpr ((QMASK >> c) & 1) {
-                            const double w = k < N ? Qd[c] : Qe[c];
-                            wg[c] = w * g[c];
-                            g0 += wg[c] * (xh[c] + dqC[k * 7 + c]);
-                            gam[c * 64 + lane] = g[c];
-                        }
-                    });
-#endif
-#if F20_MFMA
 #pragma unroll
                     for (int st_ = 0; st_ < NSTEP; ++st_)
 #pragma unroll
                         for (int m = 0; m < nblk; ++m) blk[st_][m] = gam[crow[st_] * 64 + 16 * m + r16];
-#else
-                    static_for<0, NX>([&](auto cc) __attribute__((always_inline)) {
-                        constexpr int c = decltype(cc)::value;
-                        if constexpr ((QMASK >> c) & 1) {
-#pragma unroll
-                            for (int m = 0; m < nblk; ++m) Rb[c][m] = gam[c * 64 + 16 * m + (lane & 15)];
-                        }
-                    });
-#endif
                 }
                 if constexpr (k < N) {
-                    const double* Gk = GT + k * GTS; (void)Gk;
                     // The inputs of stage k enter with B_k: lanes 2k, 2k + 1 (whose column of Gamma is still zero) start the product from
                     // their column of B_k, every other lane from the zero row of gam -- one per-lane LDS address instead of 28 selects
                     // per stage (560 vector instructions per instance); 0 + A_k 0 = 0 exactly: the same bits as the selects gave.
                     const bool mine = ki == k;
-#if F20_CPREF
 #pragma unroll
                     for (int r = 0; r < 6; r += 2) { gn[r] = Bv[r / 2].x; gn[r + 1] = Bv[r / 2].y; }
                     gn[0] += g[0]; gn[1] += g[1];
                     gn[6] = mine ? (ji ? h : 0.0) : g[6];
-#if F20_XHLANE
 #pragma unroll
                     for (int r = 0; r < NX; ++r) gn[r] += blv[r];                  // b_k in lane 40, + 0.0 elsewhere
-                    (void)xn; (void)xh;
-#if F20_ADPP
                     static_for<0, 5>([&](auto cc) __attribute__((always_inline)) {
                         constexpr int c = decltype(cc)::value;
                         static_for<0, 6>([&](auto rc) __attribute__((always_inline)) {
@@ -840,54 +522,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                             fmac_rowbc_ld<q_ % 16>(gn[r], Aq[q_ / 16], g[c + 2]);      // gn[r] += A_k[r][c + 2] g[c + 2]
                         });
                     });
-#else
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) {
-#pragma unroll
-                        for (int r = 0; r < 6; r += 2) {
-                            const double2 a = Av[c * 3 + r / 2];
-                            gn[r] += a.x * g[c + 2];  gn[r + 1] += a.y * g[c + 2];
-                        }
-                    }
-#endif
-#else
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) xn[r] = r < 2 ? blv[r] + xh[r] : blv[r];
-                    xn[6] = blv[6] + xh[6];
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) {
-#pragma unroll
-                        for (int r = 0; r < 6; r += 2) {
-                            const double2 a = Av[c * 3 + r / 2];
-                            xn[r] += a.x * xh[c + 2]; xn[r + 1] += a.y * xh[c + 2];
-                            gn[r] += a.x * g[c + 2];  gn[r + 1] += a.y * g[c + 2];
-                        }
-                    }
-#endif
-#else
-                    const double* const bsrc = mine ? Gk + 5 * 6 + 6 * ji : gam + 7 * 64;
-#pragma unroll
-                    for (int r = 0; r < 6; r += 2) {
-                        const double2 v = *reinterpret_cast<const double2*>(bsrc + r);
-                        gn[r] = v.x; gn[r + 1] = v.y;
-                    }
-                    gn[0] += g[0]; gn[1] += g[1];
-                    gn[6] = mine ? (ji ? h : 0.0) : g[6];
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) xn[r] = r < 2 ? bl[k * 7 + r] + xh[r] : bl[k * 7 + r];
-                    xn[6] = bl[k * 7 + 6] + xh[6];
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) {
-#pragma unroll
-                        for (int r = 0; r < 6; r += 2) {
-                            const double2 a = *reinterpret_cast<const double2*>(Gk + c * 6 + r);
-                            xn[r] += a.x * xh[c + 2]; xn[r + 1] += a.y * xh[c + 2];
-                            gn[r] += a.x * g[c + 2];  gn[r + 1] += a.y * g[c + 2];
-                        }
-                    }
-#endif
                 }
-#if F20_MFMA
                 if constexpr (k >= 1) {
                     // H[I][J] += (W G_I)' G_J for the tiles whose columns are non-zero already (inputs of stages < k): I, J < nblk, I >= J
 #pragma unroll
@@ -903,26 +538,8 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         });
                     }
                 }
-#else
-                if constexpr (k >= 1) {
-                    static_for<0, NX>([&](auto cc) __attribute__((always_inline)) {
-                        constexpr int c = decltype(cc)::value;
-                        if constexpr ((QMASK >> c) & 1) {
-                            static_for<0, lim / 4>([&](auto q) __attribute__((always_inline)) {
-                                constexpr int i2 = 4 * decltype(q)::value;
-                                fmac_rowbc4_ld<i2 % 16>(hrow[i2], hrow[i2 + 1], hrow[i2 + 2], hrow[i2 + 3], Rb[c][i2 / 16], wg[c]);
-                            });
-                            if constexpr (lim % 4 == 2) {
-                                fmac_rowbc_ld<(lim - 2) % 16>(hrow[lim - 2], Rb[c][(lim - 2) / 16], wg[c]);
-                                fmac_rowbc_ld<(lim - 1) % 16>(hrow[lim - 1], Rb[c][(lim - 1) / 16], wg[c]);
-                            }
-                        }
-                    });
-                }
-#endif
                 }
             });
-#if F20_MFMA
             // the tiles into the packed lower-triangular rows: element (row = lane >> 4 + 4 v, column = lane & 15) of tile (I, J)
 #pragma unroll
             for (int I = 0; I < 3; ++I)
@@ -933,19 +550,15 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         const int row = 16 * I + kq + 4 * v, col = 16 * J + r16;
                         if (row < n && col <= row) Hp[row * (row + 1) / 2 + col] = acc[I][J][v];
                     }
-#else
-            store_row_40(hrow, lds_byte_addr(Hp + (uact ? (lane * (lane + 1)) / 2 : 0)));
-#endif
             // diagonal slots of the packed factor: 0.0 (the factorisation stores the strictly-lower part only; the substitution
             // assembly lets the source lane of a step take part with this multiplier).  Phase C used L's space: rewrite them.
             WSYNC();
             if (uact) Lp[(lane * (lane + 1)) / 2 + lane] = 0.0;
             WSYNC();
         }
-#endif
 
         // =================================================================================================================
-        // phase D (H5): unconstrained trial + interior point on the condensed QP (text of admpc_qp_dense_kernel)
+        // phase D (H5): unconstrained trial + interior point on the condensed QP
         // =================================================================================================================
         F20_STAMP(3);
         {
@@ -1032,19 +645,10 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             for (; it < itmax + (cons ? fbit : 0); ++it) {
                 // An instance that is still iterating is on its way to becoming the batch's straggler: give its wave the issue slots of the
                 // SIMD it shares (the partner is a fresh instance of the second round, which is not on anybody's critical path)
-#ifndef F20_NO_PRIO
-#if F20_CLASS_PRIO == 1        // experiment: the first-round first wave of a SIMD (predicted hardest 1024) one level above its partner
-                if (first_class) { if (it == 0) __builtin_amdgcn_s_setprio(2); if (it == 2) __builtin_amdgcn_s_setprio(3); }
-                else { if (it == 0) __builtin_amdgcn_s_setprio(1); if (it == 3) __builtin_amdgcn_s_setprio(2); if (it == 6) __builtin_amdgcn_s_setprio(3); }
-#elif F20_CLASS_PRIO == 2      // experiment: first class at 3 from its first iteration, the others capped at 2
-                if (first_class) { if (it == 0) __builtin_amdgcn_s_setprio(3); }
-                else { if (it == 0) __builtin_amdgcn_s_setprio(1); if (it == 3) __builtin_amdgcn_s_setprio(2); }
-#else
-                if (it == F20_PRIO_IT0) __builtin_amdgcn_s_setprio(1);
-                if (it == F20_PRIO_IT1) __builtin_amdgcn_s_setprio(2);
-                if (it == F20_PRIO_IT2) __builtin_amdgcn_s_setprio(3);
-#endif
-#endif
+                // (priority 1 / 2 / 3 from iteration 0 / 2 / 4; measured: 0/2/4 -> 0.250 ms per step, 1/3/6 0.254, 3/6 only 0.255, none 0.269)
+                if (it == 0) __builtin_amdgcn_s_setprio(1);
+                if (it == 2) __builtin_amdgcn_s_setprio(2);
+                if (it == 4) __builtin_amdgcn_s_setprio(3);
                 int lz = lane;                          // laundered lane id: per-lane addresses / predicates derived from it are recomputed in
                 asm volatile("" : "+v"(lz));            // place instead of being hoisted out of the loops
                 const int trz = lz * (lz + 1) / 2;
@@ -1096,9 +700,6 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     cmax = wave_reduce<OpMax0>(cmax);
                     rmax = wave_reduce<OpMaxNan0>(rmax);
                     step = wave_reduce<OpMax0>(stp_local);
-#ifdef F20_DEBUG
-                    if (lane == 0) printf("[f20] it %2d mu %.3e cmax %.3e rmax %.3e rmax_prev %.3e step %.3e alpha_prev %.6f\n", it, mu, cmax, rmax, rmax_prev, step, alpha_prev);
-#endif
                     if (!(mu == mu) || !(rmax == rmax)) { failed = true; break; }
                     if (cmax <= tol_comp && step <= tol_step &&
                         (rmax <= tol_res || (it > 0 && rmax > 0.1 * rmax_prev && rmax <= ADMPC_IPM_FLOOR_CAP * tol_res))) break;      // admpc.h: stopping test
@@ -1211,38 +812,18 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
         }
         F20_STAMP(5);
         if (failed) break;
-#if F20_DEFER
-        if (can_defer && by_ticket && !ejob) {
-            // push the expansion; the next ticket and the queue slot travel together with the stores of du
-            LAUNDER_LANE(lq);
-            int tk = 0, qs = 0;
-            if (lq == 0) tk = atomicAdd(sched, 1);
-            if (lq < n) __hip_atomic_store(dubuf + (size_t)inst * n + lq, du, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int q = (cur_tk - (int)gridDim.x) & (F20_NQ - 1);
-            if (lq == 0) qs = atomicAdd(qh + q * 32, 1);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // du is at the memory side before the entry can be seen
-            if (lq == 0) __hip_atomic_store(qitems + q * qcap + qs, inst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            next_tk = (int)gridDim.x + __builtin_amdgcn_readfirstlane(tk);
-            const int* const e = ticket_entry_addr(next_tk, lq);
-            next_inst = e ? __builtin_amdgcn_readfirstlane(*e) : -1;
-            deferred = true;
-            break;
-        }
-#endif
         }   // pass
-        if (!ejob) { LAUNDER_LANE(lw); if (lw == 0 && itersg) itersg[inst] = it; }
-        if (deferred) { __builtin_amdgcn_s_setprio(0); continue; }
+        { LAUNDER_LANE(lw); if (lw == 0 && itersg) itersg[inst] = it; }
         if (failed) {
             // non-finite QP data: acados returns before the update -- the iterate stays as it is, status 4, cost +inf
             { LAUNDER_LANE(lw); if (lw == 0) { statusg[inst] = ADMPC_STATUS_QP_FAILURE; if (costg) costg[inst] = INFINITY; } }
-            push_none();
             WSYNC();
             __builtin_amdgcn_s_setprio(0);
             continue;
         }
 
         // =================================================================================================================
-        // phase E (H6): expand the states through the linearised dynamics, full step, cost, status (text of admpc_expand_kernel)
+        // phase E (H6): expand the states through the linearised dynamics, full step, cost, status
         // =================================================================================================================
         {
             LAUNDER_LANE(lane); LAUNDER_CFG(cf);
@@ -1255,10 +836,8 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             const int r6 = lane < 6 ? lane : 0;                     // row of the packed linearisation this lane reads
             const int r7 = lane < NX ? lane : 0;
             const double wq = lane < NX ? Ts * cf->W[r7] : 0.0, wqe = lane < NX ? cf->We[r7] : 0.0;
-#if F20_TICKET_AHEAD
             int tk_v = 0;
-            if (cap != 0 && !ejob && lane == 0) tk_v = atomicAdd(sched, 1);       // the next ticket: its trip to the L2 runs under the expansion
-#endif
+            if (cap != 0 && lane == 0) tk_v = atomicAdd(sched, 1);       // the next ticket: its trip to the L2 runs under the expansion
             WSYNC();
             if (park_gt) {
                 // the slot buffer again: the wave's own stores of phase A have long retired, but the CU's vector L1 may still hold the
@@ -1269,7 +848,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                 stage_in<N * NX>(ble, slot + N * GTS, lane);
                 WSYNC();
             }
-            stage_dq_nt<N>(dqE, xbg, yrg, yrefeg + (size_t)inst * NX, lane);
+            stage_dq<N>(dqE, xbg, yrg, yrefeg + (size_t)inst * NX, lane);
             du = uact ? du : 0.0;
             dus[lane] = du;
             const double ubar_i = ubg[sc];
@@ -1302,14 +881,11 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     dx = lane < 6 ? acc : (lane == 6 ? acc6 : 0.0);
                 }
             });
-#if F20_TICKET_AHEAD
             int tk_e = -1;                                                // the list entry of the next ticket: loaded under the output stores
-            if (cap != 0 && !ejob) {
-                next_tk = (int)gridDim.x + __builtin_amdgcn_readfirstlane(tk_v);
-                const int* const e = ticket_entry_addr(next_tk, lane);
+            if (cap != 0) {
+                const int* const e = ticket_entry_addr(grid + __builtin_amdgcn_readfirstlane(tk_v), lane);
                 if (e) tk_e = *e;
             }
-#endif
             const double unew = ubar_i + du;
             if (uact && !(fabs(unew) <= 1e300)) bad = true;
             const int status = __any(bad) ? ADMPC_STATUS_QP_FAILURE : ADMPC_STATUS_SUCCESS;
@@ -1317,13 +893,13 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             WSYNC();
             if (status == 0) {
 #pragma unroll
-                for (int i0 = 0; i0 < (N + 1) * NX; i0 += WAVE) { const int i = i0 + lane; if (i < (N + 1) * NX) STG(xbg + i, LDG(xbg + i) + dqE[i]); }
+                for (int i0 = 0; i0 < (N + 1) * NX; i0 += WAVE) { const int i = i0 + lane; if (i < (N + 1) * NX) xbg[i] = xbg[i] + dqE[i]; }
                 if (uact) {
                     const double e = unew - uref_i;
                     Ju = 0.5 * Rj * e * e;
                     if (unew < cf->lbu[ji]) Ju += rho_l * (cf->lbu[ji] - unew);
                     if (unew > cf->ubu[ji]) Ju += rho_u * (unew - cf->ubu[ji]);
-                    STG(ubg + lane, unew);
+                    ubg[lane] = unew;
                 }
             }
             const double Jt = wave_reduce<OpSum>(J + Ju);
@@ -1332,9 +908,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                 statusg[inst] = status;
             }
             WSYNC();
-#if F20_TICKET_AHEAD
-            if (cap != 0 && !ejob) next_inst = __builtin_amdgcn_readfirstlane(tk_e);
-#endif
+            if (cap != 0) next_inst = __builtin_amdgcn_readfirstlane(tk_e);
             F20_STAMP(6);
             F20_TRACE_END(inst);
         }
@@ -1347,7 +921,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
         int gone = 0;
         if (lane0 == 0) gone = atomicAdd(sched + 1, 1);
         gone = __builtin_amdgcn_readfirstlane(gone);
-        if (gone == (int)gridDim.x - 1) { sched[lane0] = 0; sched[64 + lane0] = 0; __threadfence(); }
+        if (gone == grid - 1) { sched[lane0] = 0; sched[64 + lane0] = 0; __threadfence(); }
     }
 #undef PK_DL
 #undef PK_DUU
@@ -1366,9 +940,6 @@ __attribute__((visibility("hidden"))) int admpc_fused20_lds_bytes(void) { return
 __attribute__((visibility("hidden"))) size_t admpc_fused20_slot_doubles(int num_cu) { return (size_t)num_cu * 8 * FusedLds::SLOT; }
 
 // debug builds only: read and clear the phase counters (all zero in the shipped build)
-#ifdef F20_ORDER_HINT
-int admpc_debug_f20_order_hint(const int* d_hint) { return hipMemcpyToSymbol(HIP_SYMBOL(g_order_hint), &d_hint, sizeof(d_hint)) == hipSuccess ? 0 : -1; }
-#endif
 int admpc_debug_f20_ticks(unsigned long long* out16)
 {
 #ifdef ADMPC_PHASE_TIMERS
@@ -1404,15 +975,8 @@ __attribute__((visibility("hidden"))) void admpc_fused20_prepare(void)
 // sched ints of a handle that solves up to `cap` instances per call: TWO scheduler states used alternately (zeroed at allocation; the order kernel of a
 // launch zeroes the header of the next launch's state, the last workgroup to leave re-arms its own: no memset in front of a launch -- a hipMemsetAsync
 // there cost 2 us per step at configs[1] and 26 us at N = 40)
-// one state: header and the bins' lists; in a build with F20_DEFER also the expansion queues (F20_NQ counter lines, cap + F20_NQ entries, padded to an even
-// count) and the steps of the pushed expansions (cap x 40 doubles)
-__attribute__((visibility("hidden"))) size_t admpc_fused20_state_ints(int cap) {
-    size_t ints = (size_t)F20_HDR + (size_t)F20_NB * (size_t)cap;
-#if F20_DEFER
-    ints += (size_t)F20_NQ * 32 + (size_t)(cap + F20_NQ + (cap & 1)) + 2 * (size_t)40 * (size_t)cap;
-#endif
-    return ints;
-}
+// one state: header and the bins' lists
+__attribute__((visibility("hidden"))) size_t admpc_fused20_state_ints(int cap) { return (size_t)F20_HDR + (size_t)F20_NB * (size_t)cap; }
 __attribute__((visibility("hidden"))) size_t admpc_fused20_sched_ints(int cap) { return 2 * admpc_fused20_state_ints(cap); }      // two states (work_order.h)
 
 // grid: persistent, eight one-wave workgroups per CU (two waves per SIMD); slotbuf: admpc_fused20_slot_doubles(num_cu) doubles

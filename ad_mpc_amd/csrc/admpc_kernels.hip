@@ -6,8 +6,9 @@
 //   then the QP of the step (H2-H6), one of
 //   R  admpc_rowqp_kernel      (admpc_rowqp.hip) stage-wise Riccati interior point, one instance per 16-lane DPP row:
 //                              every horizon, fp64 and fp32
-//   C, D, E                    condensed pipeline for N = 20 fp64 (the reference's own QP strategy): condensing, dense
-//                              LDL' interior point, expansion
+//   F  admpc_fused20_kernel    (admpc_fused20.hip) N = 20 fp64, condensed (the reference's own QP strategy): shooting,
+//                              condensing, dense LDL' interior point and expansion in one persistent kernel, no kernel A
+//   S  admpc_seg_kernel        (admpc_seg.hip) N = 40 / 60 / 80 fp64, segmented condensed interior point, no kernel A
 //
 // Hot path restated (reference = data_driven_mpc/ros_gp_mpc/src/ad_mpc/...):
 //   H0/H1  model + ERK4 with forward sensitivities   ad_3d_optimizer.py:280-310, acados ERK
@@ -44,10 +45,7 @@ namespace {
 #define GTS 42           // values per stage of the packed linearisation
 #define LIN_BLOCK 64     // threads per block of the linearisation kernel: single waves balance best over the CUs (256 registers each)
 #define LIN_TASKS 63     // tasks per block (multiple of 3)
-// work scheduler of the condensed path (int array): [0] ticket counter, [64 + q] number of instances in effort bucket q,
-// [SCHED_HDR + q * cap + j] j-th instance of bucket q.  Zeroed by the linearisation kernel, filled by the condensing kernel,
-// drained (highest bucket first) by the persistent interior-point waves.  Kernel R uses [0] as its ticket counter.
-#define SCHED_NB 64
+// ticket header of kernel R (int array): [0] ticket counter, zeroed by the linearisation kernel
 #define SCHED_HDR 128
 
 template <class T>
@@ -58,7 +56,7 @@ __global__ __launch_bounds__(LIN_BLOCK) void admpc_linearize_kernel(const AdmpcC
 {
     const int N = cfg->N;
     const long total = (long)B * N * 3;
-    if (sched && blockIdx.x == 0) for (int i = threadIdx.x; i < SCHED_HDR; i += blockDim.x) sched[i] = 0;     // ticket counter + bucket counts of this step
+    if (sched && blockIdx.x == 0) for (int i = threadIdx.x; i < SCHED_HDR; i += blockDim.x) sched[i] = 0;     // ticket counter of this step
     // 63 tasks per 64-lane block: the three threads of a stage sit in adjacent lanes of one wave (gp_eval shares work among them)
     if (threadIdx.x >= LIN_TASKS) return;
     for (long tsk = (long)blockIdx.x * LIN_TASKS + threadIdx.x; tsk < total; tsk += (long)gridDim.x * LIN_TASKS) {
@@ -89,749 +87,7 @@ __global__ __launch_bounds__(LIN_BLOCK) void admpc_linearize_kernel(const AdmpcC
 // ---------------------------------------------------------------------------------------------
 // wave-level primitives
 // ---------------------------------------------------------------------------------------------
-#include "dense40.h"      // rdlane, WSYNC, lds_byte_addr, the 40 x 40 factorisation / substitution helpers, rcp_nr
-#include "cond_common.h"  // div7, lane scans, stage_in / stage_dq, DenseLds
-
-
-// ---------------------------------------------------------------------------------------------
-// kernel B' : condensed QP, dense Cholesky -- the reference's own QP strategy (FULL_CONDENSING_HPIPM,
-// acados_solver_sim_car.c:145) for horizons with 2N <= 64 inputs.  One instance per wavefront,
-// lane i <-> input i = 2k+j: it owns row i of the condensed Hessian / of its Cholesky factor (in
-// registers, statically indexed -> horizon is a template parameter) and the four inequalities of
-// that input.  The states are eliminated: dx_k = xhat_k + Gamma_k du, so the interior-point state
-// is (du, t, lam) only -- no dynamics multipliers, no state residuals.
-//   H   = sum_k Gamma_k' Q_k Gamma_k               (input weights R are added on the diagonal on the fly)
-//   g0  = r + sum_k Gamma_k' Q_k (xhat_k + xbar_k - xref_k)
-//   delta row of stage k:  dx6_k = xhat_k[6] + h * sum_{k'<k} du_{(k',1)}   (structural: delta' = u1)
-// ---------------------------------------------------------------------------------------------
-// next instance for a persistent wave (wave-uniform), -1 when the step is drained.  Instances were binned by predicted
-// interior-point effort; tickets walk the bins from the most expensive down (longest-processing-time-first), so the
-// stragglers start early instead of last.  Lane l looks at bin SCHED_NB-1-l.
-// The first ticket of a wave is its block index (no atomic: 2048 simultaneous draws on one word queue up for ~20 us),
-// later ones are gridDim.x + a global counter.
-// Placement (observed, scripts/probes/place_probe.hip + scripts/trace_d.py; nothing depends on it): the grid fills one wave
-// per SIMD first, block b + 4*CUs lands on the SIMD of block b, and the wave that arrived first keeps full speed
-// (11.1-11.9 us per iteration) while the second one gets 14-18 us as long as both are busy.  With first ticket = block index
-// the 1024 predicted-longest instances are exactly the ones that run at full speed.
-__device__ __forceinline__ int sched_next(int* __restrict__ sched, int cap, bool first) {
-    const int lane = threadIdx.x;
-    int t = blockIdx.x;
-    if (!first) {
-        int v = 0;
-        if (lane == 0) v = atomicAdd(sched, 1);
-        t = (int)gridDim.x + __builtin_amdgcn_readfirstlane(v);
-    }
-    const int c = sched[64 + SCHED_NB - 1 - lane];
-    const int incl = wave_scan_incl_int(c);
-    const unsigned long long m = __ballot(incl > t);
-    if (m == 0ull) return -1;
-    const int l = __ffsll((long long)m) - 1;
-    const int base = __builtin_amdgcn_readlane(incl - c, l);
-    return sched[SCHED_HDR + (size_t)(SCHED_NB - 1 - l) * cap + (t - base)];
-}
-
-// ---- optional in-kernel phase timers of the interior-point kernel (build with -DADMPC_PHASE_TIMERS; totals are printed by
-//      admpc_destroy).  s_memtime ticks, summed over all waves: 0 staging, 1 phase A, 2 factorisation, 3 phase C,
-//      4 substitutions, 5 expand/step, 6 final roll-out + outputs, 7 scheduler draw
-#ifdef ADMPC_PHASE_TIMERS
-__device__ unsigned long long g_phase_ticks[16];
-__device__ __forceinline__ unsigned long long phase_now() {
-    unsigned long long t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)); return t;
-}
-#define PHASE_DECL() unsigned long long ph_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long ph_last = phase_now()
-#define PHASE_STAMP(k) do { const unsigned long long t_ = phase_now(); ph_acc[k] += t_ - ph_last; ph_last = t_; } while (0)
-#define PHASE_FLUSH() do { if (threadIdx.x == 0) { for (int q_ = 0; q_ < 16; ++q_) atomicAdd(&g_phase_ticks[q_], ph_acc[q_]); } } while (0)
-#else
-#define PHASE_DECL() do { } while (0)
-#define PHASE_STAMP(k) do { } while (0)
-#define PHASE_FLUSH() do { } while (0)
-#endif
-
-// ---- The four-kernel N = 20 pipeline of rounds 1-2 (kernels C, D, E behind kernel A): superseded by the fused persistent kernel
-// (admpc_fused20.hip, whose phase bodies are these texts) and kept OUT of the product library -- `make legacy` builds
-// ../libadmpc_legacy.so with -DADMPC_LEGACY_N20 for A/B runs (ADMPC_N20=split selects the pipeline there).
-#ifdef ADMPC_LEGACY_N20
-// kernel C (N = 20 path): condensing.  One instance per wavefront, lane i <-> input i.  Writes, per instance, the packed
-// lower-triangular Hessian rows H[NTRI] and aux[128] = { g0[64] (reduced gradient at du = 0, per input), xhat6[64] (free
-// response of delta per stage) } for the interior-point kernel.  A kernel of its own so that its 40-double Hessian row and
-// the IPM state never compete for registers (and so that the IPM kernel's code stays small).
-// QMASK: state components that may carry a tracking weight (bit c <-> W[c] or We[c] non-zero); the host picks 0b0000111
-// (position + heading, the reference's weights) or the general 0b1111111 instantiation, which tests the weights at run time.
-template <int NT, int QMASK>
-__global__ __launch_bounds__(WAVE, 2) void admpc_condense_kernel(const AdmpcConfig* __restrict__ cfg, int B,
-                                                              const double* __restrict__ x0g, const double* __restrict__ yrefg,
-                                                              const double* __restrict__ yrefeg,
-                                                              const double* __restrict__ GTg, const double* __restrict__ blg,
-                                                              const double* __restrict__ xbarg, const double* __restrict__ ubarg,
-                                                              const int32_t* __restrict__ statusg, int first_pass,
-                                                              double* __restrict__ Hg, double* __restrict__ auxg,
-                                                              int* __restrict__ sched, int cap)
-{
-    constexpr int N = NT, n = 2 * NT, NTRI = DenseLds<NT>::NTRI;
-    extern __shared__ double lds_raw[];
-    double* const Hp = lds_raw;
-    double* const GT = Hp + NTRI + (NTRI & 1);
-    double* const bl = GT + N * GTS;
-    double* const dq = bl + DenseLds<NT>::BLS;
-    double* const gam = dq + DenseLds<NT>::DQS;    // [NX][64] Gamma components of the current stage, lane = input
-    const int lane = threadIdx.x;
-    const int ki = lane >> 1, ji = lane & 1;
-    const bool uact = lane < n;
-    const double Ts = cfg->Ts, h = cfg->Ts;
-    double Qd[NX], Qe[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) { Qd[i] = Ts * cfg->W[i]; Qe[i] = cfg->We[i]; }
-    const double Rj = Ts * cfg->W[NX + ji];
-    PHASE_DECL();
-    for (int inst = blockIdx.x; inst < B; inst += gridDim.x) {
-        if (!first_pass && statusg[inst] != 0) continue;
-        const double* xbg = xbarg + (size_t)inst * (N + 1) * NX;
-        const double* ubg = ubarg + (size_t)inst * N * NU;
-        const double* yrg = yrefg + (size_t)inst * N * NY;
-        const double* gtg = GTg + (size_t)inst * N * GTS;
-        PHASE_STAMP(13);
-        // ---------------- stage the instance ----------------
-        stage_in<N * GTS>(GT, gtg, lane);
-        stage_in<N * NX>(bl, blg + (size_t)inst * N * NX, lane);
-        stage_dq<N>(dq, xbg, yrg, yrefeg + (size_t)inst * NX, lane);
-        const int sc = uact ? lane : 0;
-        const double ubar_i = ubg[sc];
-        const double r_i = Rj * (ubar_i - yrg[(sc >> 1) * 9 + 7 + (sc & 1)]);
-        double xh[NX];
-#pragma unroll
-        for (int c = 0; c < NX; ++c) xh[c] = x0g[(size_t)inst * NX + c] - xbg[c];      // uniform
-        WSYNC();
-        PHASE_STAMP(10);
-        // ---------------- condensing ----------------
-        double g[NX], hrow[n];
-#pragma unroll
-        for (int c = 0; c < NX; ++c) g[c] = 0.0;
-#pragma unroll
-        for (int i = 0; i < n; ++i) hrow[i] = 0.0;
-        double g0 = r_i;
-        double xh6_own = 0.0;                   // xhat_k[6] of the stage whose delta box this lane owns
-        static_for<0, N + 1>([&](auto kc) __attribute__((always_inline)) {
-            constexpr int k = decltype(kc)::value;
-            constexpr int lim = 2 * k < n ? 2 * k : n;        // inputs of stages < k (even)
-            constexpr int nblk = (lim + 15) / 16;             // 16-lane blocks of Gamma that are non-zero at this stage
-            // One stage = one basic block: merged into a single 21-stage block, hipcc hoists every LDS load of the whole instance
-            // and spills ~1600 registers.  The test is always true (B >= 1) but opaque to the compiler.
-            int tok = B; asm volatile("" : "+s"(tok));
-            if (tok > 0) {
-            double wg[NX], Rb[NX][3];
-            if constexpr (k >= 1) {
-                // ---- cost of stage k, part 1: g0 += Gamma_k' Q (xhat + dq); publish the weighted components of this lane's Gamma
-                //      column in LDS and start reading them back as "block m of component c in every 16-lane row" (the DPP
-                //      sources of part 2).  The reads complete under the propagation below.
-                if (lane == k) xh6_own = xh[6];
-                static_for<0, NX>([&](auto cc) __attribute__((always_inline)) {
-                    constexpr int c = decltype(cc)::value;
-                    if constexpr ((QMASK >> c) & 1) {
-                        const double w = k < N ? Qd[c] : Qe[c];
-                        wg[c] = w * g[c];
-                        g0 += wg[c] * (xh[c] + dq[k * 7 + c]);
-                        gam[c * 64 + lane] = g[c];
-                    }
-                });
-                static_for<0, NX>([&](auto cc) __attribute__((always_inline)) {
-                    constexpr int c = decltype(cc)::value;
-                    if constexpr ((QMASK >> c) & 1) {
-#pragma unroll
-                        for (int m = 0; m < nblk; ++m) Rb[c][m] = gam[c * 64 + 16 * m + (lane & 15)];
-                    }
-                });
-            }
-            PHASE_STAMP(11);
-            double xn[NX], gn[NX];
-            if constexpr (k < N) {
-                // ---- propagate: xhat_{k+1} = A xhat + b ; Gamma_{k+1}[:,i] = A Gamma_k[:,i]  (or B[:,j] for the inputs of stage k)
-                const double* Gk = GT + k * GTS;
-#pragma unroll
-                for (int r = 0; r < 6; ++r) { xn[r] = bl[k * 7 + r] + (r < 2 ? xh[r] : 0.0); gn[r] = r < 2 ? g[r] : 0.0; }
-                xn[6] = bl[k * 7 + 6] + xh[6]; gn[6] = g[6];
-#pragma unroll
-                for (int c = 0; c < 5; ++c) {
-#pragma unroll
-                    for (int r = 0; r < 6; r += 2) {
-                        const double2 a = *reinterpret_cast<const double2*>(Gk + c * 6 + r);
-                        xn[r] += a.x * xh[c + 2]; xn[r + 1] += a.y * xh[c + 2];
-                        gn[r] += a.x * g[c + 2];  gn[r + 1] += a.y * g[c + 2];
-                    }
-                }
-                const bool mine = ki == k;
-                // B_k columns: loaded by every lane and pinned by an empty asm -- left alone, hipcc sinks each load into a divergent
-                // "if (mine)" block of its own (branch + ds_read + full wait, six times per stage)
-                double bb[12];
-#pragma unroll
-                for (int r = 0; r < 12; r += 2) {
-                    const double2 v = *reinterpret_cast<const double2*>(Gk + 5 * 6 + r);
-                    bb[r] = v.x; bb[r + 1] = v.y;
-                }
-#pragma unroll
-                for (int r = 0; r < 12; ++r) asm volatile("" : "+v"(bb[r]));
-#pragma unroll
-                for (int r = 0; r < 6; ++r) gn[r] = mine ? (ji ? bb[6 + r] : bb[r]) : gn[r];
-                gn[6] = mine ? (ji ? h : 0.0) : gn[6];
-            }
-            PHASE_STAMP(12);
-            if constexpr (k >= 1) {
-                // ---- cost of stage k, part 2: H += Gamma_k' Q Gamma_k over the inputs of stages < k
-                static_for<0, NX>([&](auto cc) __attribute__((always_inline)) {
-                    constexpr int c = decltype(cc)::value;
-                    if constexpr ((QMASK >> c) & 1) {
-                        static_for<0, lim / 4>([&](auto q) __attribute__((always_inline)) {
-                            constexpr int i2 = 4 * decltype(q)::value;
-                            fmac_rowbc4_ld<i2 % 16>(hrow[i2], hrow[i2 + 1], hrow[i2 + 2], hrow[i2 + 3], Rb[c][i2 / 16], wg[c]);
-                        });
-                        if constexpr (lim % 4 == 2) {
-                            fmac_rowbc_ld<(lim - 2) % 16>(hrow[lim - 2], Rb[c][(lim - 2) / 16], wg[c]);
-                            fmac_rowbc_ld<(lim - 1) % 16>(hrow[lim - 1], Rb[c][(lim - 1) / 16], wg[c]);
-                        }
-                    }
-                });
-            }
-            if constexpr (k < N) {
-#pragma unroll
-                for (int r = 0; r < NX; ++r) { g[r] = gn[r]; xh[r] = xn[r]; }
-            }
-            }
-            PHASE_STAMP(13);
-        });
-        // packed lower-triangular rows of H into LDS
-        static_assert(n == 40, "row store assembly is generated for n = 40");
-        store_row_40(hrow, lds_byte_addr(Hp + (uact ? (lane * (lane + 1)) / 2 : 0)));
-        WSYNC();
-        stage_in<NTRI>(Hg + (size_t)inst * NTRI, Hp, lane);
-        auxg[(size_t)inst * 128 + lane] = g0;
-        auxg[(size_t)inst * 128 + 64 + lane] = xh6_own;
-        // ---- effort bin for the scheduler: how far the diagonally scaled gradient step -g0_i / (H_ii + R_i) overshoots the input
-        //      box, relative to the box width (max over inputs).  0 = no bound in sight (4-5 interior-point iterations); the
-        //      iteration count grows with it (correlation 0.86 on the config-2 scenarios).  A heuristic: it orders work, nothing else.
-        {
-            const double hii = Hp[uact ? (lane * (lane + 1)) / 2 + lane : 0] + Rj;
-            const double sstep = -g0 / hii;
-            const double over = fmax(sstep - (cfg->ubu[ji] - ubar_i), (cfg->lbu[ji] - ubar_i) - sstep) / (cfg->ubu[ji] - cfg->lbu[ji]);
-            const double score = wave_reduce<OpMax>(uact ? fmax(over, 0.0) : 0.0);
-            const int q = (int)fmin(fmax(score * 32.0, 0.0), (double)(SCHED_NB - 1));
-            if (lane == 0) {
-                const int pos = atomicAdd(sched + 64 + q, 1);
-                sched[SCHED_HDR + (size_t)q * cap + pos] = inst;
-            }
-        }
-        WSYNC();
-    }
-    PHASE_FLUSH();
-}
-
-template <int NT>
-__global__ __launch_bounds__(WAVE, 2) void admpc_qp_dense_kernel(const AdmpcConfig* __restrict__ cfg, int B,
-                                                                 const double* __restrict__ xbarg, const double* __restrict__ ubarg,
-                                                                 double* __restrict__ costg, int32_t* __restrict__ statusg,
-                                                                 int32_t* __restrict__ itersg,
-                                                                 const double* __restrict__ Hg, double* auxg_out,
-                                                                 int* __restrict__ sched, int cap)
-{
-    const double* auxg = auxg_out;              // in: g0[64] | xhat6[64] per instance; out: du[64] over the g0 slot
-    constexpr int N = NT, n = 2 * NT, NTRI = DenseLds<NT>::NTRI;
-    extern __shared__ double lds_raw[];
-    double* const Hp = lds_raw;                 // packed lower-triangular rows of H
-    double* const Lp = Hp + NTRI + (NTRI & 1);  // packed strictly-lower rows of the unit factor L (M = L D L')
-    double* const park = Lp + NTRI + (NTRI & 1);   // [5][64] per-lane constants (registers are the scarce resource)
-    double* const cb = park + 5 * 64;           // [64] step broadcast buffer
-    double* const invd = cb + 64;               // [64] 1 / D_jj
-    double* const sb = invd + 64;               // [64] per-stage exchange
-    double* const sb2 = sb + 64;                // [64]
-#define PK_DL   park[0 * 64 + lane]
-#define PK_DUU  park[1 * 64 + lane]
-#define PK_G0   park[2 * 64 + lane]
-#define PK_DDL  park[3 * 64 + lane]
-#define PK_DDU  park[4 * 64 + lane]
-
-    const int lane = threadIdx.x;
-    const int ki = lane >> 1, ji = lane & 1;
-    const bool uact = lane < n;
-    const bool dact = lane >= 1 && lane < N;
-    const double Ts = cfg->Ts, h = cfg->Ts;
-    const double Rj = Ts * cfg->W[NX + ji];
-    const double rho_l = Ts * cfg->zl, rho_u = Ts * cfg->zu;
-    const double thr = cfg->ipm_thr0, mu0 = cfg->ipm_mu0;
-    const double tol_comp = cfg->ipm_tol_comp, tol_res = cfg->ipm_tol_res, tol_step = cfg->ipm_tol_step;
-    const int itmax = cfg->ipm_iter_max;
-    const bool try_unc = cfg->ipm_try_unconstrained != 0.0;
-    const double thw = cfg->ipm_warm_thr, wrest = cfg->ipm_warm_restart;
-    const int fbit = (int)cfg->ipm_fallback_iter;
-    const double inv_nineq = 1.0 / (double)(8 * N + 2 * (N - 1));
-    // Factorisation of the Newton matrix M = H + diag(dbar) + (s_odd on the odd columns of the u1 rows) into L D L' (LDS: Lp, invd).
-    // Used twice per instance at most: once without barrier terms (the unconstrained trial) and once per interior-point iteration.
-    auto factorise = [&](const double dbar_, const double sodd_, const int lz_) __attribute__((always_inline)) {
-        const int trz_ = lz_ * (lz_ + 1) / 2;
-        const bool uz_ = lz_ < n;
-        double a[n];
-        // a[c] = (c <= lane ? H[lane][c] : 0) + (c odd and this lane is a u1 input ? S_i : 0) + (c == lane ? Dbar : 0);
-        // idle lanes: unit rows (Dbar = 1 on a diagonal that never becomes a pivot, zeros elsewhere)
-        newton_row_40(a, lds_byte_addr(Hp + (uz_ ? trz_ : 0)), dbar_, sodd_);
-        // Square-root-free right-looking factorisation M = L D L' (unit lower L), row i in the registers of lane i.
-        // Column j (unscaled, w_i = a_i[j]) is published in LDS and read back as "block m in every 16-lane row", the DPP
-        // sources of the rank-1 update: a[jj] -= w_jj * (w_i / D_jj) is ONE v_fmac_f64_dpp per jj.  Look-ahead: the first
-        // update of column j makes column j+1 final; its pivot chain (v_readlane, v_rcp_f64 + Newton, scale, publish,
-        // read back) is started right there and completes under the remaining updates of column j.
-        // Entries on and above the diagonal of a row are never read (lane jj's w_jj is only picked up for jj > j), so the
-        // column is used unmasked; only the store of L is masked (EXEC).
-        const unsigned lrow = lds_byte_addr(Lp + (uz_ ? trz_ : 0));
-        const unsigned pub_wr = lds_byte_addr(cb + lane), pub_rd = lds_byte_addr(cb + (lane & 15));
-        // pivot chain of column j: reciprocal of the pivot, scaled column (the factor's entries), its masked store
-        auto chain = [&](auto jc, double& nln) __attribute__((always_inline)) {
-            constexpr int j = decltype(jc)::value;
-            const double dj = rdlane(a[j], j);
-            const double dinv = rcp_nr(dj);                             // 1 / D_jj
-            const double lu = a[j] * dinv;                              // L_ij for the lanes below the diagonal
-            invd[j] = dinv;                                             // uniform value, same address
-            if constexpr (j + 1 < n) {
-                asm volatile("s_bfm_b64 exec, %2, %3\n\tds_write_b64 %0, %1 offset:%4\n\ts_mov_b64 exec, -1"
-                             : : "v"(lrow), "v"(lu), "n"(n - 1 - j), "n"(j + 1), "n"(8 * j) : "memory");
-                nln = -lu;
-            }
-        };
-        // column 0: published by plain code (nothing to overlap with yet).  The block registers ping-pong between two sets so that
-        // no copy ever reads a register whose LDS load is still in flight.
-        double Rb[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, nlb[2] = {0.0, 0.0};
-        cb[lane] = a[0];
-#pragma unroll
-        for (int m = 0; m < 3; ++m) Rb[0][m] = cb[16 * m + (lane & 15)];
-        chain(std::integral_constant<int, 0>{}, nlb[0]);
-        static_for<0, n - 1>([&](auto jc) __attribute__((always_inline)) {
-            constexpr int j = decltype(jc)::value;
-            constexpr bool own = (j + 1) / 16 == 2;                     // column j: DPP sources are the lanes' own registers (VALU-written)
-            constexpr bool pub = j + 2 < n && (j + 2) / 16 < 2;         // column j + 1 still needs its blocks in other rows
-            double (&R)[3] = Rb[j & 1];
-            double (&Rn)[3] = Rb[(j + 1) & 1];
-            double& nl = nlb[j & 1];
-            double& nln = nlb[(j + 1) & 1];
-            col_head<j + 1, (j + 2) / 16, pub, own>(a[j + 1], R, nl, Rn, pub_wr, pub_rd);
-            if constexpr (!pub) Rn[2] = a[j + 1];                       // only lanes 32..39 are still involved: own row
-            chain(std::integral_constant<int, j + 1>{}, nln);
-            constexpr int j4 = ((j + 2 + 3) / 4) * 4 < n ? ((j + 2 + 3) / 4) * 4 : n;        // first 4-aligned column >= j + 2
-            static_for<j + 2, j4>([&](auto c) __attribute__((always_inline)) {
-                constexpr int jj = decltype(c)::value;
-                if constexpr (own) fmac_rowbc<jj % 16>(a[jj], R[jj / 16], nl);
-                else fmac_rowbc_ld<jj % 16>(a[jj], R[jj / 16], nl);
-            });
-            static_for<j4 / 4, n / 4>([&](auto c) __attribute__((always_inline)) {
-                constexpr int jj = 4 * decltype(c)::value;
-                if constexpr (own) fmac_rowbc4<jj % 16>(a[jj], a[jj + 1], a[jj + 2], a[jj + 3], R[jj / 16], nl);
-                else fmac_rowbc4_ld<jj % 16>(a[jj], a[jj + 1], a[jj + 2], a[jj + 3], R[jj / 16], nl);
-            });
-        });
-        WSYNC();
-    };
-    // M x = y through the factor: L z = y, z *= D^-1, L' x = z (assembly, see gen_subst_asm.py)
-    auto ldl_solve = [&](double y, const int lz_) __attribute__((always_inline)) -> double {
-        static_assert(n == 40, "the substitution assembly is generated for n = 40");
-        const bool uz_ = lz_ < n;
-        const unsigned pub = lds_byte_addr(cb + (lz_ & 15));                              // cb is free while a system is being solved
-        fwd_subst_40(y, lds_byte_addr(Lp + (uz_ ? lz_ * (lz_ + 1) / 2 : 0)), pub);      // idle lanes never take part (EXEC masks)
-        double x = y * invd[uz_ ? lz_ : 0];
-        bwd_subst_40(x, lds_byte_addr(Lp + (uz_ ? lz_ : 0)), pub);
-        return x;
-    };
-
-    // Instances need 4 .. 15+ interior-point iterations each: a static instance -> wave map leaves most of the chip idle while
-    // the unlucky waves finish.  The waves draw instances from the scheduler, predicted-expensive ones first.
-    // (Instances that failed in an earlier SQP iteration were not queued by the condensing kernel.)
-    // diagonal slots of the packed factor: 0.0, never overwritten (the factorisation stores the strictly-lower part only).  The
-    // substitution assembly lets the source lane of a step take part with this multiplier.
-    if (uact) Lp[(lane * (lane + 1)) / 2 + lane] = 0.0;
-    WSYNC();
-    PHASE_DECL();
-    for (int inst = sched_next(sched, cap, true); inst >= 0; inst = sched_next(sched, cap, false)) {
-        PHASE_STAMP(7);
-#ifdef ADMPC_TRACE_SCHED   // debug build (scripts/trace_d.py): start time, duration, block and iteration count of every instance, packed into `cost`
-        unsigned long long dbg_t0; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(dbg_t0));
-#endif
-        const double* xbg = xbarg + (size_t)inst * (N + 1) * NX;
-        const double* ubg = ubarg + (size_t)inst * N * NU;
-        // ---------------- stage: condensed Hessian (kernel C) and per-lane data ----------------
-        stage_in<NTRI>(Hp, Hg + (size_t)inst * NTRI, lane);
-        const int sc = uact ? lane : 0;
-        const double ubar_i = ubg[sc];
-        const double dl_i = cfg->lbu[ji] - ubar_i, duu_i = cfg->ubu[ji] - ubar_i;
-        const double g0 = auxg[(size_t)inst * 128 + lane];
-        const double xh6_own = auxg[(size_t)inst * 128 + 64 + lane];
-        // ---------------- interior point start ----------------
-        double t[4], lam[4], du = 0.0, sl = thr, su = thr;
-        {
-            const double r0[4] = { thr - dl_i, thr + duu_i, thr, thr };
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { t[i] = r0[i] > thr ? r0[i] : thr; lam[i] = mu0 * rcp_nr(t[i]); }
-        }
-        double Dt[2] = {1.0, 1.0}, Dlam[2] = {0.0, 0.0}, Ddl = 0.0, Ddu = 0.0, dx6 = 0.0;
-        if (dact) {
-            const double x6 = xbg[lane * 7 + 6];
-            Ddl = cfg->lbx_delta - x6; Ddu = cfg->ubx_delta - x6;
-            dx6 = xh6_own;
-            const double r0[2] = { dx6 - Ddl, Ddu - dx6 };
-#pragma unroll
-            for (int i = 0; i < 2; ++i) { Dt[i] = r0[i] > thr ? r0[i] : thr; Dlam[i] = mu0 * rcp_nr(Dt[i]); }
-        }
-        WSYNC();
-        PK_DL = dl_i; PK_DUU = duu_i; PK_G0 = g0; PK_DDL = Ddl; PK_DDU = Ddu;      // parked in LDS: registers are the scarce resource
-        WSYNC();
-
-        bool failed = false;
-        double rmax_prev = 0.0, step = 1e300, stp_local = 1e300, alpha_prev = 1.0;
-        int it = 0;
-        PHASE_STAMP(0);
-        // ---------------- trial: the QP without its inequalities ----------------
-        // (H + R) du = -g0 is one factorisation and one solve (about 0.6 of an interior-point iteration).  If that minimiser
-        // respects the input box and the steering box it is the solution of the full QP -- no bound is active, the slacks are
-        // zero -- and the interior point is skipped (iters = 0).  True for 55 % of the config-2 scenarios; the oracle does the same.
-        bool solved = false, warmed = false, cons = false;
-        if (try_unc) {
-            int lt = lane; asm volatile("" : "+v"(lt));
-            factorise(uact ? Rj : 1.0, 0.0, lt);
-            const double xt = ldl_solve(uact ? -g0 : 0.0, lt);
-            const double duc = uact ? xt : 0.0;
-            cb[lane] = duc;
-            WSYNC();
-            const double du1_stage = lane < N ? cb[2 * lane + 1] : 0.0;
-            const double pre = wave_scan_incl<OpSum>(du1_stage);
-            const double dx6c = xh6_own + h * (pre - du1_stage);
-            const bool ok = (!uact || (duc >= dl_i && duc <= duu_i)) && (!dact || (dx6c >= Ddl && dx6c <= Ddu));
-            WSYNC();
-            if (__all(ok)) { du = duc; solved = true; }
-            else if (thw > 0.0) {
-                // warm start (cfg.ipm_warm_thr): the interior point starts from that minimiser.  A violated input bound is absorbed
-                // by its slack (the input box is soft), a violated steering bound stays as a primal residual.
-                warmed = true;
-                du = duc;
-                sl = fmax(dl_i - duc, 0.0) + thw; su = fmax(duc - duu_i, 0.0) + thw;
-                const double r0[4] = { duc + sl - dl_i, su + duu_i - duc, sl, su };
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { t[i] = r0[i] > thw ? r0[i] : thw; lam[i] = mu0 * rcp_nr(t[i]); }
-                if (dact) {
-                    dx6 = dx6c;
-                    const double q0[2] = { dx6 - Ddl, Ddu - dx6 };
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) { Dt[i] = q0[i] > thw ? q0[i] : thw; Dlam[i] = mu0 * rcp_nr(Dt[i]); }
-                }
-            }
-        }
-        PHASE_STAMP(8);
-        // the cold start of the interior point, in place (wave-uniform callers): cfg.ipm_warm_restart and cfg.ipm_fallback_iter
-        auto cold_start = [&]() __attribute__((always_inline)) {
-            const double dlc = PK_DL, duc2 = PK_DUU;
-            du = 0.0; sl = thr; su = thr;
-            const double r0[4] = { thr - dlc, thr + duc2, thr, thr };
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { t[i] = r0[i] > thr ? r0[i] : thr; lam[i] = mu0 * rcp_nr(t[i]); }
-            dx6 = dact ? xh6_own : 0.0;
-            const double q0[2] = { dx6 - PK_DDL, PK_DDU - dx6 };
-#pragma unroll
-            for (int i = 0; i < 2; ++i) { Dt[i] = dact ? (q0[i] > thr ? q0[i] : thr) : 1.0; Dlam[i] = dact ? mu0 * rcp_nr(Dt[i]) : 0.0; }
-            alpha_prev = 1.0; stp_local = 1e300;
-        };
-        if (!solved)
-        for (; it < itmax + (cons ? fbit : 0); ++it) {
-            int lz = lane;                          // laundered lane id: per-lane addresses / predicates derived from it are recomputed in
-            asm volatile("" : "+v"(lz));            // place instead of being hoisted out of the loops (hipcc parked ~200 of them in scratch)
-            const int trz = lz * (lz + 1) / 2;
-            const bool uz = lz < n;
-            // ---- phase A: complementarity, reduced gradient, convergence test, Newton matrix, Cholesky.
-            // Everything derived from (t, lam) in this phase dies before the factorisation ends: the 40-double factor row
-            // and the interior-point state must not be live at the same time (256-register budget, two waves per SIMD).
-            double ru, mu, Dbar, S_i;
-            {
-                double musum = 0.0, cmax = 0.0, rmax = 0.0;
-                double G0, G1, G2, G3;
-                {
-                    const double i0 = rcp_nr(t[0]), i1 = rcp_nr(t[1]), i2_ = rcp_nr(t[2]), i3 = rcp_nr(t[3]);
-                    G0 = lam[0] * i0; G1 = lam[1] * i1; G2 = lam[2] * i2_; G3 = lam[3] * i3;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { const double rci = t[i] * lam[i]; musum += uact ? rci : 0.0; cmax = fmax(cmax, uact ? rci : 0.0); }
-#pragma unroll
-                for (int i = 0; i < 2; ++i) { const double rci = Dt[i] * Dlam[i]; musum += dact ? rci : 0.0; cmax = fmax(cmax, dact ? rci : 0.0); }
-                const double G56 = Dlam[0] * rcp_nr(Dt[0]) + Dlam[1] * rcp_nr(Dt[1]);
-                Dbar = uact ? Rj + G0 * G2 * rcp_nr(G0 + G2) + G1 * G3 * rcp_nr(G1 + G3) : 1.0;       // idle lanes: identity rows
-                // reduced gradient  ru = H du + R du + g0 - lam0 + lam1 + [u1 inputs] h * sum_{k>ki} (lam6_k - lam5_k)
-                cb[lane] = uact ? du : 0.0;
-                const double dlam_pref = wave_scan_incl<OpSum>(dact ? (Dlam[1] - Dlam[0]) : 0.0);     // lanes = stages
-                sb[lane] = rdlane(dlam_pref, 63) - dlam_pref;           // suffix over stages > lane
-                const double Ssuf_incl = wave_scan_incl<OpSum>(dact ? G56 : 0.0);
-                sb2[lane] = rdlane(Ssuf_incl, 63) - Ssuf_incl;          // lane = stage: sum over stages > lane
-                WSYNC();
-                // H du: the lane's full row of H by EXEC-masked loads (no address arithmetic), du[c] through DPP row broadcasts
-                double hdu = 0.0;
-                {
-                    double Rd3[3];
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) Rd3[m] = cb[16 * m + (lane & 15)];
-                    double hv[n];
-                    sym_row_40(hv, lds_byte_addr(Hp + (uz ? trz : 0)), lds_byte_addr(Hp + (uz ? lz : 0)));
-                    static_for<0, n>([&](auto cc) __attribute__((always_inline)) {
-                        constexpr int c = decltype(cc)::value;
-                        fmac_rowbc_ld<c % 16>(hdu, Rd3[c / 16], hv[c]);
-                    });
-                }
-                ru = hdu + Rj * du + PK_G0 - lam[0] + lam[1] + (ji ? h * sb[uact ? ki : 0] : 0.0);
-                S_i = h * h * sb2[uact ? ki : 0];                        // lane = input: S_{k_i}
-                {
-                    const double rd0 = du + sl - PK_DL - t[0], rd1 = -du + su + PK_DUU - t[1], rd2 = sl - t[2], rd3 = su - t[3];
-                    const double rsl = rho_l - lam[0] - lam[2], rsu = rho_u - lam[1] - lam[3];
-                    const double Drd0 = dx6 - PK_DDL - Dt[0], Drd1 = PK_DDU - dx6 - Dt[1];
-                    double ra = OpMaxNan::f(fabs(ru), fabs(rsl)); ra = OpMaxNan::f(ra, fabs(rsu));
-                    ra = OpMaxNan::f(ra, fabs(rd0)); ra = OpMaxNan::f(ra, fabs(rd1)); ra = OpMaxNan::f(ra, fabs(rd2)); ra = OpMaxNan::f(ra, fabs(rd3));
-                    const double rb = OpMaxNan::f(fabs(Drd0), fabs(Drd1));
-                    rmax = OpMaxNan::f(uact ? ra : 0.0, dact ? rb : 0.0);
-                }
-                mu = wave_reduce<OpSum>(musum) * inv_nineq;
-                cmax = wave_reduce<OpMax>(cmax);
-                rmax = wave_reduce<OpMaxNan>(rmax);
-                step = wave_reduce<OpMax>(stp_local);
-                if (!(mu == mu) || !(rmax == rmax)) { failed = true; break; }
-                if (cmax <= tol_comp && step <= tol_step &&
-                        (rmax <= tol_res || (it > 0 && rmax > 0.1 * rmax_prev && rmax <= ADMPC_IPM_FLOOR_CAP * tol_res))) break;      // admpc.h: stopping test
-                rmax_prev = rmax;
-            }
-            if (fbit > 0 && !cons && it >= fbit) {
-                // cfg.ipm_fallback_iter: still iterating, most likely in a limit cycle of the centring heuristic.  Start over and finish
-                // with plain predictor-centring steps (no second-order term) on a budget of its own; this pass is redone from the cold start.
-                cons = true; warmed = false;
-                cold_start();
-                rmax_prev = 0.0;
-                --it;
-                continue;
-            }
-            PHASE_STAMP(1);
-            // ---- Newton matrix row: M = H + diag(R + barrier) + h^2 S_{max(k,k')} on the u1 x u1 block, then its factorisation
-            factorise(Dbar, (uz && ji) ? S_i : 0.0, lz);
-            PHASE_STAMP(2);
-            // ---- phase C: re-derive the barrier quantities from (t, lam).  The asm statements make the compiler forget what
-            //      it computed in phase A so that nothing but the state itself stays live across the factorisation.
-#pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(t[i]), "+v"(lam[i]));
-#pragma unroll
-            for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(Dt[i]), "+v"(Dlam[i]));
-            double it_[4], il_[4], rc[4], Dit[2], Dil[2], Drc[2];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { it_[i] = rcp_nr(t[i]); il_[i] = rcp_nr(lam[i]); rc[i] = t[i] * lam[i]; }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) { Dit[i] = rcp_nr(Dt[i]); Dil[i] = rcp_nr(Dlam[i]); Drc[i] = Dt[i] * Dlam[i]; }
-            const double G0 = lam[0] * it_[0], G1 = lam[1] * it_[1], G2 = lam[2] * it_[2], G3 = lam[3] * it_[3];
-            const double iG02 = rcp_nr(G0 + G2), iG13 = rcp_nr(G1 + G3);
-            const double G5 = Dlam[0] * Dit[0], G6 = Dlam[1] * Dit[1];
-            const double rd0 = du + sl - PK_DL - t[0], rd1 = -du + su + PK_DUU - t[1], rd2 = sl - t[2], rd3 = su - t[3];
-            const double rsl = rho_l - lam[0] - lam[2], rsu = rho_u - lam[1] - lam[3];
-            const double Drd0 = dx6 - PK_DDL - Dt[0], Drd1 = PK_DDU - dx6 - Dt[1];
-
-            double mu_aff = 0.0, dsl = 0.0, dsu = 0.0, ddu = 0.0, dt[4], dlam[4], Ddt[2], Ddlam[2];
-#pragma unroll 1
-            for (int pass = 0; pass < 2; ++pass) {
-                // ---- right-hand side: eliminate slacks / multipliers
-                const double c0 = rc[0] * it_[0], c1 = rc[1] * it_[1], c2 = rc[2] * it_[2], c3 = rc[3] * it_[3];
-                const double e1 = rsl + c0 + c2 + G0 * rd0 + G2 * rd2;
-                const double e2 = rsu + c1 + c3 + G1 * rd1 + G3 * rd3;
-                const double etal = c0 + G0 * rd0 - G0 * e1 * iG02;
-                const double etau = -c1 - G1 * rd1 + G1 * e2 * iG13;
-                const double ek = dact ? (Drc[0] * Dit[0] + G5 * Drd0) - (Drc[1] * Dit[1] + G6 * Drd1) : 0.0;
-                const double epref = wave_scan_incl<OpSum>(ek);
-                sb[lane] = rdlane(epref, 63) - epref;
-                WSYNC();
-                double y = uact ? -(ru + etal + etau + (ji ? h * sb[ki] : 0.0)) : 0.0;
-                PHASE_STAMP(pass == 0 ? 3 : 5);
-                // ---- L z = y, z *= D^-1, L' x = z  (unit lower L packed by rows in LDS; assembly, see gen_subst_asm.py)
-                const double x = ldl_solve(y, lz);
-                PHASE_STAMP(4);
-                ddu = uact ? x : 0.0;
-                // ---- delta rows: ddx6_k = h * sum_{k'<k} ddu_{(k',1)}
-                cb[lane] = ddu;
-                WSYNC();
-                const double du1_stage = lane < N ? cb[2 * lane + 1] : 0.0;
-                const double pre = wave_scan_incl<OpSum>(du1_stage);
-                const double ddx6 = h * (pre - du1_stage);
-                // ---- expand
-                dsl = -(e1 + G0 * ddu) * iG02;
-                dsu = -(e2 - G1 * ddu) * iG13;
-                dt[0] = ddu + dsl + rd0; dt[1] = -ddu + dsu + rd1; dt[2] = dsl + rd2; dt[3] = dsu + rd3;
-                const double Gs[4] = { G0, G1, G2, G3 };
-                double rr = 0.0;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    dlam[i] = -rc[i] * it_[i] - Gs[i] * dt[i];
-                    rr = fmax(rr, uact ? fmax(-dt[i] * it_[i], -dlam[i] * il_[i]) : 0.0);
-                }
-                Ddt[0] = ddx6 + Drd0;  Ddlam[0] = -Drc[0] * Dit[0] - G5 * Ddt[0];
-                Ddt[1] = -ddx6 + Drd1; Ddlam[1] = -Drc[1] * Dit[1] - G6 * Ddt[1];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) rr = fmax(rr, dact ? fmax(-Ddt[i] * Dit[i], -Ddlam[i] * Dil[i]) : 0.0);
-                rr = wave_reduce<OpMax>(rr);
-                const double amax = rr > 1.0 ? rcp_nr(rr) : 1.0;
-                if (pass == 0) {
-                    double s_aff = 0.0;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) s_aff += uact ? (t[i] + amax * dt[i]) * (lam[i] + amax * dlam[i]) : 0.0;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) s_aff += dact ? (Dt[i] + amax * Ddt[i]) * (Dlam[i] + amax * Ddlam[i]) : 0.0;
-                    mu_aff = wave_reduce<OpSum>(s_aff) * inv_nineq;
-                    double sigma = mu_aff * rcp_nr(mu); sigma = sigma * sigma * sigma;
-                    if (alpha_prev < ADMPC_IPM_BLOCKED_STEP) sigma = 1.0;      // centring safeguard (admpc.h)
-                    const double smu = fmax(sigma * mu, ADMPC_IPM_MU_FLOOR * tol_comp);      // admpc.h: centring target floor
-                    if (!cons) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) rc[i] = t[i] * lam[i] + dt[i] * dlam[i] - smu;
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) Drc[i] = Dt[i] * Dlam[i] + Ddt[i] * Ddlam[i] - smu;
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) rc[i] = t[i] * lam[i] - smu;
-#pragma unroll
-                        for (int i = 0; i < 2; ++i) Drc[i] = Dt[i] * Dlam[i] - smu;
-                    }
-                } else {
-                    double tau = 1.0 - mu_aff; tau = fmax(tau, 0.995); tau = fmin(tau, 0.999999);
-                    const double alpha = fmin(tau * amax, 1.0);
-                    if (it == 0 && warmed && alpha < wrest) {
-                        // the first step from the warm start is blocked (cfg.ipm_warm_restart): start over from the cold start; the
-                        // iteration counts.  Wave-uniform (alpha is).
-                        warmed = false;
-                        cold_start();
-                    } else {
-                    alpha_prev = alpha;
-                    stp_local = uact ? fabs(alpha * ddu) : 0.0;
-                    // idle lanes carry harmless finite values (their steps are computed from finite data)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) { t[i] = fmax(t[i] + alpha * dt[i], IPM_FLOOR); lam[i] = fmax(lam[i] + alpha * dlam[i], IPM_FLOOR); }
-                    du += alpha * ddu; sl += alpha * dsl; su += alpha * dsu;
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {
-                        Dt[i] = dact ? fmax(Dt[i] + alpha * Ddt[i], IPM_FLOOR) : 1.0;
-                        Dlam[i] = dact ? fmax(Dlam[i] + alpha * Ddlam[i], IPM_FLOOR) : 1.0;
-                    }
-                    dx6 += dact ? alpha * ddx6 : 0.0;
-                    }
-                }
-                WSYNC();
-            }
-        }
-        PHASE_STAMP(5);
-        // ---------------- hand the step over to the expand kernel (H6): du per input, preliminary status, iteration count ----------------
-        auxg_out[(size_t)inst * 128 + lane] = uact ? du : 0.0;          // the g0 slot of this instance is dead by now
-        if (lane == 0) {
-            statusg[inst] = failed ? ADMPC_STATUS_QP_FAILURE : ADMPC_STATUS_SUCCESS;
-            if (failed && costg) costg[inst] = INFINITY;
-            if (itersg) itersg[inst] = it;
-#ifdef ADMPC_TRACE_SCHED
-            { unsigned long long dbg_t1; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(dbg_t1));
-              unsigned long long dur = dbg_t1 - dbg_t0; if (dur > 32767) dur = 32767;          // 100 MHz ticks
-              const unsigned long long pk = ((dbg_t0 & 0xfffffull) << 33) | (dur << 18) | ((unsigned long long)blockIdx.x << 6) | (unsigned long long)(it & 63);
-              if (costg) costg[inst] = (double)pk; }
-#endif
-        }
-        WSYNC();
-        PHASE_STAMP(6);
-    }
-    PHASE_FLUSH();
-}
-
-// ---------------------------------------------------------------------------------------------
-// kernel E (N = 20 path): H6 -- expand the states through the linearised dynamics, full step, cost, status.
-// One instance per wavefront.  Lane r < 7 owns state component r: dx_{k+1}[r] = b_k[r] + sum_c [A_k B_k][r][c] (dx_k, du_k)[c],
-// the dx_k[c] picked up inside the FMAs by DPP row broadcasts (v_fmac_f64_dpp row_newbcast:c) -- no cross-lane exchange, no
-// wait in the 20-stage chain; everything the chain needs from LDS is independent of it and prefetched by the compiler.
-// A kernel of its own: inside the interior-point kernel (256 registers, 2 waves/SIMD) the same work ran serialised on
-// single loads and took as long as six factorisations.
-// ---------------------------------------------------------------------------------------------
-template <int NT>
-__global__ __launch_bounds__(WAVE) void admpc_expand_kernel(const AdmpcConfig* __restrict__ cfg, int B,
-                                                            const double* __restrict__ x0g, const double* __restrict__ yrefg,
-                                                            const double* __restrict__ yrefeg,
-                                                            const double* __restrict__ GTg, const double* __restrict__ blg,
-                                                            double* __restrict__ xbarg, double* __restrict__ ubarg,
-                                                            double* __restrict__ costg, int32_t* __restrict__ statusg,
-                                                            const double* __restrict__ dug)
-{
-    constexpr int N = NT, n = 2 * NT;
-    extern __shared__ double lds_raw[];
-    double* const GT = lds_raw;                             // packed linearisation
-    double* const bl = GT + N * GTS;                        // defects b_k
-    double* const dq = bl + DenseLds<NT>::BLS;              // xbar_k - xref_k, k = 0..N (overwritten by dx_k)
-    double* const dus = dq + DenseLds<NT>::DQS;             // [64] du per input
-    const int lane = threadIdx.x;
-    const int ji = lane & 1;
-    const bool uact = lane < n;
-    const int r6 = lane < 6 ? lane : 0;                     // row of the packed linearisation this lane reads
-    const int r7 = lane < NX ? lane : 0;
-    const double Ts = cfg->Ts, h = cfg->Ts;
-    const double wq = lane < NX ? Ts * cfg->W[r7] : 0.0, wqe = lane < NX ? cfg->We[r7] : 0.0;
-    const double Rj = Ts * cfg->W[NX + ji];
-    const double rho_l = Ts * cfg->zl, rho_u = Ts * cfg->zu;
-    for (int inst = blockIdx.x; inst < B; inst += gridDim.x) {
-        if (statusg[inst] != 0) continue;                   // failed in the interior-point kernel (or failed / converged in an earlier SQP iteration)
-        const double* xbg = xbarg + (size_t)inst * (N + 1) * NX;
-        const double* ubg = ubarg + (size_t)inst * N * NU;
-        const double* yrg = yrefg + (size_t)inst * N * NY;
-        stage_in<N * GTS>(GT, GTg + (size_t)inst * N * GTS, lane);
-        stage_in<N * NX>(bl, blg + (size_t)inst * N * NX, lane);
-        stage_dq<N>(dq, xbg, yrg, yrefeg + (size_t)inst * NX, lane);
-        const double du = dug[(size_t)inst * 128 + lane];  // 0 on idle lanes
-        dus[lane] = du;
-        const int sc = uact ? lane : 0;
-        const double ubar_i = ubg[sc];
-        const double uref_i = yrg[(sc >> 1) * 9 + 7 + (sc & 1)];
-        double dx = lane < NX ? x0g[(size_t)inst * NX + r7] - xbg[r7] : 0.0;      // dx_0 (lanes 0..6)
-        WSYNC();
-        bool bad = false;
-        double J = 0.0;
-        static_for<0, N + 1>([&](auto kc) __attribute__((always_inline)) {
-            constexpr int k = decltype(kc)::value;
-            const double e = dx + dq[k * 7 + r7];
-            J += 0.5 * (k < N ? wq : wqe) * e * e;
-            if (!(fabs(dx) <= 1e300)) bad = true;
-            if (lane < NX) dq[k * 7 + lane] = dx;            // slot k now holds dx_k
-            if constexpr (k < N) {
-                const double* Gk = GT + k * GTS;
-                const double u0 = dus[2 * k], u1 = dus[2 * k + 1];
-                // rows 0..5: b + [e0 e1 A(:,2..6)] dx + B du ; row 6: delta' = delta + h u1
-                double acc = bl[k * 7 + r7] + (lane < 2 || lane == 6 ? dx : 0.0);
-                double g[5];
-#pragma unroll
-                for (int c = 0; c < 5; ++c) g[c] = lane < 6 ? Gk[c * 6 + r6] : 0.0;
-                const double b0 = lane < 6 ? Gk[5 * 6 + r6] : 0.0, b1 = lane < 6 ? Gk[6 * 6 + r6] : (lane == 6 ? h : 0.0);
-                acc += b0 * u0 + b1 * u1;
-                fmac_rowbc<2>(acc, dx, g[0]); fmac_rowbc<3>(acc, dx, g[1]); fmac_rowbc<4>(acc, dx, g[2]);
-                fmac_rowbc<5>(acc, dx, g[3]); fmac_rowbc<6>(acc, dx, g[4]);
-                dx = lane < NX ? acc : 0.0;
-            }
-        });
-        const double unew = ubar_i + du;
-        if (uact && !(fabs(unew) <= 1e300)) bad = true;
-        const int status = __any(bad) ? ADMPC_STATUS_QP_FAILURE : ADMPC_STATUS_SUCCESS;
-        double Ju = 0.0;
-        WSYNC();
-        if (status == 0) {
-            double* xo = xbarg + (size_t)inst * (N + 1) * NX;
-            double* uo = ubarg + (size_t)inst * N * NU;
-#pragma unroll
-            for (int i0 = 0; i0 < (N + 1) * NX; i0 += WAVE) { const int i = i0 + lane; if (i < (N + 1) * NX) xo[i] = xbg[i] + dq[i]; }
-            if (uact) {
-                const double e = unew - uref_i;
-                Ju = 0.5 * Rj * e * e;
-                if (unew < cfg->lbu[ji]) Ju += rho_l * (cfg->lbu[ji] - unew);
-                if (unew > cfg->ubu[ji]) Ju += rho_u * (unew - cfg->ubu[ji]);
-                uo[lane] = unew;
-            }
-        }
-        const double Jt = wave_reduce<OpSum>(J + Ju);
-        if (lane == 0) {
-#ifndef ADMPC_TRACE_SCHED
-            if (costg) costg[inst] = status == 0 ? Jt : INFINITY;
-#endif
-            statusg[inst] = status;
-        }
-        WSYNC();
-    }
-}
-#endif   // ADMPC_LEGACY_N20
+#include "dense40.h"      // wave_reduce
 
 // ---------------------------------------------------------------------------------------------
 // local reference generator: batched RefTrajectory.get_waypoints (src/ad_mpc/ref_traj.py:89-171).
@@ -1283,9 +539,7 @@ struct AdmpcSolver {
     AdmpcConfig* d_cfg;
     int device;
     int num_cu;
-    int use_dense;           // condensed dense-Cholesky QP kernel available for this horizon (N == 20) and not disabled
-    int dense_lds_bytes;
-    int n20_fused;           // N = 20 fp64 steps run the fused persistent kernel (admpc_fused20.hip); 0: the four-kernel pipeline (ADMPC_N20=split)
+    int use_dense;           // N = 20 fp64 steps run the fused condensed kernel (admpc_fused20.hip) unless ADMPC_QP=riccati
     int use_seg;             // N = 40 / 60 / 80 fp64 steps without GP models run the segmented condensed kernel (admpc_seg.hip; with GP models on ADMPC_QP=seg); ADMPC_QP=riccati: kernel R
     int* d_tick;             // 2 x [128 + 64 cap_fused] tickets, exit counter and work-order bins of the persistent kernels: two states used alternately (work_order.h)
     int tick_flip;           // which of the two the last launch used
@@ -1297,11 +551,7 @@ struct AdmpcSolver {
     int cap_lin;             // kernel A's output: every path but the fused one
     double* d_GT;            // [cap_lin][N][42]
     double* d_bl;            // [cap_lin][N][7]
-    int cap_dense;           // four-kernel N = 20 pipeline
-    double* d_H;             // [cap_dense][NTRI] condensed Hessians
-    double* d_aux;           // [cap_dense][128]
-    int* d_sched;            // [SCHED_HDR (+ SCHED_NB * cap_dense)] ticket counter of kernel R / work scheduler of the four-kernel pipeline
-    int sched_cap;           // instances the scheduler lists of d_sched were sized for (0: header only)
+    int* d_sched;            // [SCHED_HDR] ticket counter of kernel R
     int qmask;               // 7 when only x, y, psi carry tracking weights (specialised condensing kernel), else 127
     int cap_row;             // kernel R: every fp32 solve, fp64 for N != 20, every solve that asks for multipliers
     int row_elem;            // element width (8 / 4) the row workspace was sized for
@@ -1424,8 +674,8 @@ int admpc_create(const AdmpcConfig* cfg, int device, AdmpcSolver** out)
         int r_, st_, lb_, g_;
         if (admpc_rowqp_plan(cfg->N, 8, 1, s->num_cu, &r_, &st_, &lb_, &g_) != 0) { delete s; return fail(ADMPC_EINVAL, "horizon too long for the LDS-resident kernel"); }
     }
-    s->cap = s->cap_lin = s->cap_dense = s->cap_row = 0; s->row_elem = 8; s->sched_cap = 0; s->d_tick = nullptr; s->tick_flip = 0; s->d_slot = nullptr; s->cap_fused = 0;
-    s->d_GT = nullptr; s->d_bl = nullptr; s->d_status = nullptr; s->d_H = nullptr; s->d_aux = nullptr; s->d_ws = nullptr; s->d_pairs = nullptr; s->d_split = nullptr; s->d_dump = nullptr; s->d_mult = nullptr; s->cap_mult = 0; s->mult_elem = 0;
+    s->cap = s->cap_lin = s->cap_row = 0; s->row_elem = 8; s->d_tick = nullptr; s->tick_flip = 0; s->d_slot = nullptr; s->cap_fused = 0;
+    s->d_GT = nullptr; s->d_bl = nullptr; s->d_status = nullptr; s->d_ws = nullptr; s->d_pairs = nullptr; s->d_split = nullptr; s->d_dump = nullptr; s->d_mult = nullptr; s->cap_mult = 0; s->mult_elem = 0;
     {   // ADMPC_ROWQP_SPLIT=0 / 1: never / always run the row kernel in two phases (A/B tests); default: by batch size
         const char* e = getenv("ADMPC_ROWQP_SPLIT");
         s->split_mode = e && e[0] == '0' ? 0 : (e && e[0] == '1' ? 1 : -1);
@@ -1435,14 +685,6 @@ int admpc_create(const AdmpcConfig* cfg, int device, AdmpcSolver** out)
     {   // ADMPC_QP=riccati forces the stage-wise Riccati kernel (A/B tests); default: condensed kernel where instantiated
         const char* e = getenv("ADMPC_QP");
         s->use_dense = (cfg->N == 20) && !(e && strcmp(e, "riccati") == 0);
-        s->dense_lds_bytes = DenseLds<20>::total * (int)sizeof(double);
-        // ADMPC_N20=split keeps the four-kernel pipeline (linearise, condense, interior point, expand) for A/B runs and tests
-#ifdef ADMPC_LEGACY_N20
-        const char* m = getenv("ADMPC_N20");
-        s->n20_fused = !(m && strcmp(m, "split") == 0);
-#else
-        s->n20_fused = 1;                        // the product library carries the fused kernel only (`make legacy` for the older pipeline)
-#endif
         // default at N = 40 (the reference's shipped horizon: 6.2 M solves/s against kernel R's 3.4 M at B = 4096), 60 and 80 (2.7 / 2.0 M against
         // 1.7 / 1.2 M; scripts/cmp_seg_rowqp.sh); ADMPC_QP=riccati selects kernel R there
         // (nominal model only: with GP residuals in the dynamics the linearisation can have strongly unstable modes -- random regressors are
@@ -1459,9 +701,6 @@ int admpc_create(const AdmpcConfig* cfg, int device, AdmpcSolver** out)
     for (int c = 3; c < NX; ++c) if (cfg->W[c] != 0.0 || cfg->We[c] != 0.0) s->qmask = 127;
     // opt in to > 64 KB of dynamic LDS
     admpc_rowqp_prepare();
-#ifdef ADMPC_LEGACY_N20
-    (void)hipFuncSetAttribute((const void*)admpc_qp_dense_kernel<20>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#endif
     *out = s;
     return ADMPC_OK;
 }
@@ -1470,19 +709,6 @@ void admpc_destroy(AdmpcSolver* s)
 {
     if (!s) return;
     DeviceGuard guard(s->device);
-#ifdef ADMPC_PHASE_TIMERS
-    {
-        unsigned long long h[16] = {0};
-        (void)hipDeviceSynchronize();
-        if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase_ticks), sizeof h) == hipSuccess) {
-            static const char* nm[16] = {"ipm staging", "ipm phase A", "ipm factorisation", "ipm phase C", "ipm substitutions", "ipm expand/step", "ipm hand-over", "ipm scheduler draw", "ipm unconstrained trial", "-",
-                                         "cond staging", "cond H accumulate", "cond propagate", "cond store+bin", "-", "-"};
-            unsigned long long tot = 0; for (int i = 0; i < 10; ++i) tot += h[i];
-            unsigned long long totc = 0; for (int i = 10; i < 16; ++i) totc += h[i];
-            for (int i = 0; i < 14; ++i) if (i < 9 || i >= 10) fprintf(stderr, "[admpc phase] %-18s %14llu ticks %5.1f %%\n", nm[i], h[i], 100.0 * (double)h[i] / (double)((i < 10 ? tot : totc) ? (i < 10 ? tot : totc) : 1));
-        }
-    }
-#endif
     (void)hipFree(s->d_cfg);
     if (s->d_tick) (void)hipFree(s->d_tick);
     if (s->d_slot) (void)hipFree(s->d_slot);
@@ -1490,8 +716,6 @@ void admpc_destroy(AdmpcSolver* s)
     if (s->d_GT) (void)hipFree(s->d_GT);
     if (s->d_bl) (void)hipFree(s->d_bl);
     if (s->d_status) (void)hipFree(s->d_status);
-    if (s->d_H) (void)hipFree(s->d_H);
-    if (s->d_aux) (void)hipFree(s->d_aux);
     if (s->d_ws) (void)hipFree(s->d_ws);
     if (s->d_split) (void)hipFree(s->d_split);
     if (s->d_mult) (void)hipFree(s->d_mult);
@@ -1524,18 +748,16 @@ static int ensure_status(AdmpcSolver* s, int B)
     s->cap = B;
     return ADMPC_OK;
 }
-static int ensure_sched(AdmpcSolver* s, int lists_for)          // header (ticket counter, bucket counts) + optional scheduler lists
+static int ensure_sched(AdmpcSolver* s)                         // kernel R's ticket counter
 {
-    if (s->d_sched && lists_for <= s->sched_cap) return ADMPC_OK;
+    if (s->d_sched) return ADMPC_OK;
     HIPCHK(hipDeviceSynchronize());
-    s->sched_cap = 0;
-    GROW(s->d_sched, int, (size_t)SCHED_HDR + (size_t)SCHED_NB * (size_t)lists_for);
-    s->sched_cap = lists_for;
+    GROW(s->d_sched, int, SCHED_HDR);
     return ADMPC_OK;
 }
 static int ensure_lin(AdmpcSolver* s, int B)                    // kernel A's output
 {
-    int rc = ensure_sched(s, s->sched_cap); if (rc) return rc;
+    int rc = ensure_sched(s); if (rc) return rc;
     if (B <= s->cap_lin) return ADMPC_OK;
     HIPCHK(hipDeviceSynchronize());
     const size_t N = (size_t)s->cfg.N;
@@ -1545,25 +767,10 @@ static int ensure_lin(AdmpcSolver* s, int B)                    // kernel A's ou
     s->cap_lin = B;
     return ADMPC_OK;
 }
-static int ensure_dense(AdmpcSolver* s, int B)                  // four-kernel N = 20 pipeline
-{
-    int rc = ensure_lin(s, B); if (rc) return rc;
-    if (B <= s->cap_dense) return ADMPC_OK;
-    HIPCHK(hipDeviceSynchronize());
-    s->cap_dense = 0;
-    GROW(s->d_H, double, (size_t)B * DenseLds<20>::NTRI);
-    GROW(s->d_aux, double, (size_t)B * 128);
-    rc = ensure_sched(s, B); if (rc) return rc;
-    s->cap_dense = B;
-    return ADMPC_OK;
-}
 static int ensure_fused(AdmpcSolver* s, int B)                  // fused N = 20 step: one slot buffer per resident wave, the work-order lists
 {                                                                // (segmented kernel: the work-order lists only)
     // slot buffers only where parking the linearisation beats recomputing it: with GP residuals in the model (see admpc_fused20.hip)
-    // (ADMPC_F20_PARK=1 / 0 forces / forbids the slot buffers whatever the model: A/B runs)
-    const char* pk = getenv("ADMPC_F20_PARK");
-    const bool park = pk ? pk[0] == '1' : s->cfg.n_gp > 0;
-    if (!s->d_slot && park && !s->use_seg) HIPCHK(hipMalloc((void**)&s->d_slot, admpc_fused20_slot_doubles(s->num_cu) * sizeof(double)));
+    if (!s->d_slot && s->cfg.n_gp > 0 && !s->use_seg) HIPCHK(hipMalloc((void**)&s->d_slot, admpc_fused20_slot_doubles(s->num_cu) * sizeof(double)));
     // segmented kernel: one packed Hessian per resident wave (its LDS buffer doubles as the factor's)
     if (!s->d_slot && s->use_seg) HIPCHK(hipMalloc((void**)&s->d_slot, admpc_seg_slot_doubles(s->num_cu) * sizeof(double)));
     if (B <= s->cap_fused) return ADMPC_OK;
@@ -1614,9 +821,7 @@ int admpc_reserve(AdmpcSolver* s, int B)
     if (!guard.ok()) return fail(ADMPC_EHIP, "hipSetDevice failed");
     int rc = ensure_status(s, B); if (rc) return rc;
     const bool tol_on = s->cfg.sqp_iters > 1 && s->cfg.sqp_tol > 0.0;  // such solves run on the row kernel at every horizon (solve_impl)
-    if (s->use_dense && s->n20_fused && !tol_on) return ensure_fused(s, B);      // no per-instance workspace
-    if (s->use_seg && !tol_on) return ensure_fused(s, B);
-    if (s->use_dense && !tol_on) return ensure_dense(s, B);
+    if ((s->use_dense || s->use_seg) && !tol_on) return ensure_fused(s, B);      // no per-instance workspace
     const int chunk = rowqp_chunk(s, s->cfg.N, 8);
     rc = ensure_row(s, B < chunk ? B : chunk, 8); if (rc) return rc;
     return tol_on ? ensure_mult(s, B < chunk ? B : chunk, 8) : ADMPC_OK;
@@ -1705,11 +910,10 @@ static int solve_impl(AdmpcSolver* s, int B, const double* x0, const double* yre
     const int nsqp = s->cfg.sqp_iters > 0 ? s->cfg.sqp_iters : 1;
     // the condensed N = 20 kernels carry no multipliers: solves that return them, and SQP solves with a tolerance (whose stopping test
     // needs them between the passes), run on the row kernel at every horizon
-    const bool dense = s->use_dense && !snap && !(nsqp > 1 && s->cfg.sqp_tol > 0.0), fused = dense && s->n20_fused;
+    const bool dense = s->use_dense && !snap && !(nsqp > 1 && s->cfg.sqp_tol > 0.0);
     {   // workspaces of the path this call takes (no-ops once sized: admpc_reserve up front keeps the default path allocation-free)
         int rc = ensure_status(s, B); if (rc) return rc;
-        if (fused) { rc = ensure_fused(s, B); if (rc) return rc; }
-        else if (dense) { rc = ensure_dense(s, B); if (rc) return rc; }
+        if (dense) { rc = ensure_fused(s, B); if (rc) return rc; }
     }
     hipStream_t st = (hipStream_t)stream;
     int32_t* stat = status ? status : s->d_status;
@@ -1728,44 +932,9 @@ static int solve_impl(AdmpcSolver* s, int B, const double* x0, const double* yre
         HIPCHK(hipGetLastError());
         return ADMPC_OK;
     }
-    const long totalA = (long)B * N * 3;
-    int gridA = (int)((totalA + LIN_TASKS - 1) / LIN_TASKS);
-    if (gridA > s->num_cu * 64) gridA = s->num_cu * 64;
-    for (int sq = 0; sq < nsqp; ++sq) {
-        const int first = (sq == 0 && !routed) ? 1 : 0;
-        if (fused) {
-            // shooting, condensing, interior point and expansion of an instance in one persistent kernel: no workspace, no kernel boundary
-            admpc_fused20_launch(s->num_cu, st, s->d_cfg, B, s->qmask, x0, yref, yref_e, p, xbar, ubar, cost, stat, iters, first, s->d_tick, s->cap_fused, (s->tick_flip ^= 1), s->d_slot);
-            continue;
-        }
-#ifdef ADMPC_LEGACY_N20      // the four-kernel pipeline of rounds 1-2 (`make legacy`, ADMPC_N20=split)
-        hipLaunchKernelGGL(admpc_linearize_kernel<double>, dim3(gridA), dim3(LIN_BLOCK), 0, st, s->d_cfg, B, xbar, ubar, p,
-                           first ? (const int32_t*)nullptr : (const int32_t*)stat, s->d_GT, s->d_bl, s->d_sched);
-        {
-            constexpr int cond_lds = (DenseLds<20>::NTRI + (DenseLds<20>::NTRI & 1) + 20 * GTS + DenseLds<20>::BLS + DenseLds<20>::DQS + NX * 64) * (int)sizeof(double);
-            int gridC = s->num_cu * 8; if (gridC > B) gridC = B;
-            if (s->qmask == 7)
-                hipLaunchKernelGGL((admpc_condense_kernel<20, 7>), dim3(gridC), dim3(WAVE), cond_lds, st, s->d_cfg, B, x0, yref, yref_e,
-                                   (const double*)s->d_GT, (const double*)s->d_bl, (const double*)xbar, (const double*)ubar,
-                                   (const int32_t*)stat, first, s->d_H, s->d_aux, s->d_sched, s->sched_cap);
-            else
-                hipLaunchKernelGGL((admpc_condense_kernel<20, 127>), dim3(gridC), dim3(WAVE), cond_lds, st, s->d_cfg, B, x0, yref, yref_e,
-                                   (const double*)s->d_GT, (const double*)s->d_bl, (const double*)xbar, (const double*)ubar,
-                                   (const int32_t*)stat, first, s->d_H, s->d_aux, s->d_sched, s->sched_cap);
-            int gridD = s->num_cu * ((160 * 1024) / s->dense_lds_bytes < 8 ? (160 * 1024) / s->dense_lds_bytes : 8);   // two waves per SIMD
-            if (gridD > B) gridD = B;
-            hipLaunchKernelGGL((admpc_qp_dense_kernel<20>), dim3(gridD), dim3(WAVE), s->dense_lds_bytes, st, s->d_cfg, B,
-                               (const double*)xbar, (const double*)ubar, cost, stat, iters,
-                               (const double*)s->d_H, s->d_aux, s->d_sched, s->sched_cap);
-            constexpr int exp_lds = DenseLds<20>::expand_total * (int)sizeof(double);
-            int gridE = s->num_cu * 16; if (gridE > B) gridE = B;
-            hipLaunchKernelGGL((admpc_expand_kernel<20>), dim3(gridE), dim3(WAVE), exp_lds, st, s->d_cfg, B, x0, yref, yref_e,
-                               (const double*)s->d_GT, (const double*)s->d_bl, xbar, ubar, cost, stat, (const double*)s->d_aux);
-        }
-#else
-        (void)gridA;
-#endif
-    }
+    // shooting, condensing, interior point and expansion of an instance in one persistent kernel: no workspace, no kernel boundary
+    for (int sq = 0; sq < nsqp; ++sq)
+        admpc_fused20_launch(s->num_cu, st, s->d_cfg, B, s->qmask, x0, yref, yref_e, p, xbar, ubar, cost, stat, iters, (sq == 0 && !routed) ? 1 : 0, s->d_tick, s->cap_fused, (s->tick_flip ^= 1), s->d_slot);
     HIPCHK(hipGetLastError());
     return ADMPC_OK;
 }

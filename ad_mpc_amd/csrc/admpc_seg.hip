@@ -31,9 +31,6 @@
 #define IPM_FLOOR 1e-40
 #define GTS 42           // values per stage of the packed linearisation (see kernel A in admpc_kernels.hip)
 
-#ifndef SEG_CPREF
-#define SEG_CPREF 0
-#endif
 extern "C" size_t admpc_fused20_state_ints(int cap);      // admpc_fused20.hip: ints of one scheduler state
 namespace {
 
@@ -76,15 +73,6 @@ __device__ __forceinline__ void slot_fetch(double* lds_dst, const double* gsrc, 
 // Cross-WAVE exchange through LDS: inline-assembly LDS stores are invisible to the compiler's wait-count tracking, so the barrier
 // waits for everything this wave has in flight first.
 #define XSYNC() do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __syncthreads(); } while (0)
-
-// ---- bring-up dumps (build with -DSEG_DEBUG: `make variant`-style, scripts/seg_debug.py): instance SEG_DEBUG_INST leaves its LDS regions and
-//      a few per-lane values in a global buffer at two points (P1: behind the condensing, P2: behind the unconstrained trial)
-#ifdef SEG_DEBUG
-#define SEG_DBG_W 16384
-__device__ double g_seg_dbg[4 * 2 * SEG_DBG_W];
-__device__ int g_seg_dbg_inst = 0;
-__device__ __forceinline__ void seg_dbg_copy(double* dst, const double* src, int cnt, int lane) { for (int i = lane; i < cnt; i += 64) dst[i] = src[i]; }
-#endif
 
 // ---- optional per-phase wave-time accounting (-DADMPC_PHASE_TIMERS: `make timers`), s_memtime ticks (100 MHz) summed over all waves:
 //      0 ticket, 1 phase A, 2 phase C, 3 trial, 4 iteration top (residuals, exchange), 5 factorisation + Schur blocks, 6 forward substitution,
@@ -621,21 +609,6 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
                 const bool cost_k = k == 0 ? !first : (k == N ? last : true);
                 double wg[NX];
                 double blk[NSTEP][3];
-#if SEG_CPREF
-                // every LDS read of the stage's record is issued before anything else of the stage (see admpc_fused20.hip)
-                double2 Av[15], Bv[3]; double blv[NX];
-                if constexpr (k < N) {
-                    const double* Gk = GT + k * GTS;
-                    const double* const bsrc = ki == k ? Gk + 5 * 6 + 6 * ji : gam + 7 * 64;
-#pragma unroll
-                    for (int q_ = 0; q_ < 15; ++q_) Av[q_] = *reinterpret_cast<const double2*>(Gk + 2 * q_);
-#pragma unroll
-                    for (int q_ = 0; q_ < 3; ++q_) Bv[q_] = *reinterpret_cast<const double2*>(bsrc + 2 * q_);
-#pragma unroll
-                    for (int r = 0; r < NX; ++r) blv[r] = bl[k * 7 + r];
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#endif
                 if constexpr (k < N) { if (lane == k) xh6_own = xh[6]; }
                 if (cost_k) {
                     static_for<0, NX>([&](auto cc) __attribute__((always_inline)) {
@@ -661,10 +634,6 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
                     // their column of B_k, every other lane from the zero row of gam -- one per-lane LDS address instead of 28 selects
                     // per stage (560 vector instructions per instance); 0 + A_k 0 = 0 exactly: the same bits as the selects gave.
                     const bool mine = ki == k;
-#if SEG_CPREF
-#pragma unroll
-                    for (int r = 0; r < 6; r += 2) { gn[r] = Bv[r / 2].x; gn[r + 1] = Bv[r / 2].y; }
-#else
                     const double* const bsrc = mine ? Gk + 5 * 6 + 6 * ji : gam + 7 * 64;
 #pragma unroll
                     for (int r = 0; r < 6; r += 2) {
@@ -674,7 +643,6 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
                     double blv[NX];
 #pragma unroll
                     for (int r = 0; r < NX; ++r) blv[r] = bl[k * 7 + r];
-#endif
                     gn[0] += g[0]; gn[1] += g[1];
                     gn[6] = mine ? (ji ? h : 0.0) : g[6];
 #pragma unroll
@@ -684,11 +652,7 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
                     for (int c = 0; c < 5; ++c) {
 #pragma unroll
                         for (int r = 0; r < 6; r += 2) {
-#if SEG_CPREF
-                            const double2 a = Av[c * 3 + r / 2];
-#else
                             const double2 a = *reinterpret_cast<const double2*>(Gk + c * 6 + r);
-#endif
                             xn[r] += a.x * xh[c + 2]; xn[r + 1] += a.y * xh[c + 2];
                             gn[r] += a.x * g[c + 2];  gn[r + 1] += a.y * g[c + 2];
                         }
@@ -805,15 +769,6 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
         }
 
         SEG_STAMP(2);
-#ifdef SEG_DEBUG
-        if (inst == g_seg_dbg_inst) {
-            LAUNDER_LANE(ld_);
-            double* D = g_seg_dbg + (size_t)(wv_ * 2 + 0) * SEG_DBG_W;
-            seg_dbg_copy(D, lds_seg, LD::seg, ld_);
-            seg_dbg_copy(D + 4000, IFm, LD::IFS, ld_);
-            D[5000 + ld_] = g0; D[5064 + ld_] = xh6_own; D[5128 + ld_] = rsx;
-        }
-#endif
         // =================================================================================================================
         // phase D (H5): unconstrained trial + interior point, segments coupled through the cuts
         // =================================================================================================================
@@ -880,14 +835,6 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
                 const double xt = coupled_solve(uact ? -(g0 + zg) : (zact ? -(g0 + zg) : 0.0), lt);
                 slot_fetch<LD::NSLOT>(Hp, hsl, lt); hres = true;          // the trial's factor is dead
                 const double duc = uact ? xt : 0.0;
-#ifdef SEG_DEBUG
-                if (inst == g_seg_dbg_inst) {
-                    double* D = g_seg_dbg + (size_t)(wv_ * 2 + 1) * SEG_DBG_W;
-                    seg_dbg_copy(D, lds_seg, LD::seg, lane);
-                    seg_dbg_copy(D + 4000, IFm, LD::IFS, lane);
-                    D[5000 + lane] = duc; D[5064 + lane] = zg; D[5128 + lane] = g0;
-                }
-#endif
                 cb[lane] = duc;
                 WSYNC();
                 const double dz6 = first ? 0.0 : IFm[LD::IF_DZ + 6];
@@ -1327,7 +1274,7 @@ static void seg_launch(int num_cu, hipStream_t st, const AdmpcConfig* d_cfg, int
         prepared = true;
     }
     // two scheduler states, used alternately: the order kernel of this launch zeroes the header of the next (work_order.h)
-    const size_t one = admpc_fused20_state_ints(cap);      // the layout of a scheduler state is admpc_fused20.hip's (its order kernel also resets the expansion queue behind the lists)
+    const size_t one = admpc_fused20_state_ints(cap);      // the layout of a scheduler state is admpc_fused20.hip's
     int* const sched = sched2 + (flip ? one : 0);
     int* const sched_next = sched2 + (flip ? 0 : one);
     const int kcap = grid == B ? 0 : cap;      // the batch fits the grid: no work order (work_order.h: f20_next)
@@ -1369,21 +1316,6 @@ int admpc_debug_seg_trace(unsigned long long* out, int n_inst)
 #endif
 }
 
-// bring-up builds only: copy the dump buffer (4 waves x 2 points x 16384 doubles) to the host; 1 when the build carries none
-int admpc_debug_seg(double* out, int inst)
-{
-#ifdef SEG_DEBUG
-    if (out) {
-        if (hipDeviceSynchronize() != hipSuccess) return -1;
-        if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_seg_dbg), sizeof(double) * 4 * 2 * SEG_DBG_W) != hipSuccess) return -1;
-    } else if (hipMemcpyToSymbol(HIP_SYMBOL(g_seg_dbg_inst), &inst, sizeof(int)) != hipSuccess) return -1;
-    return 0;
-#else
-    (void)out; (void)inst;
-    return 1;
-#endif
-}
-
 // doubles of the slot buffer: one packed H per resident wave (at most 8 waves per CU)
 __attribute__((visibility("hidden"))) // (at most eight waves per CU; S > 2 parks its 14 constant border rows behind H: SegLds::NSLOT)
 size_t admpc_seg_slot_doubles(int num_cu) { return (size_t)num_cu * 8 * SegLds<4>::NSLOT; }
@@ -1406,17 +1338,9 @@ __attribute__((visibility("hidden"))) void admpc_seg_launch(int N, int num_cu, h
         double* cost, int32_t* stat, int32_t* iters, int first, int* sched2, int cap, int flip, double* hslot)
 {
     switch (N / 20) {
-#ifndef SEG_DEV_ONLY_S4
         case 2: seg_launch<2>(num_cu, st, d_cfg, B, qmask, x0, yref, yref_e, p, xbar, ubar, cost, stat, iters, first, sched2, cap, flip, hslot); break;
-#endif
-#if defined(SEG_DEV_ONLY_S4)
-        default: seg_launch<4>(num_cu, st, d_cfg, B, qmask, x0, yref, yref_e, p, xbar, ubar, cost, stat, iters, first, sched2, cap, flip, hslot); break;
-#elif !defined(SEG_DEV_ONLY_S2)      // development builds: one instantiation compiles in a third of the time
         case 3: seg_launch<3>(num_cu, st, d_cfg, B, qmask, x0, yref, yref_e, p, xbar, ubar, cost, stat, iters, first, sched2, cap, flip, hslot); break;
         default: seg_launch<4>(num_cu, st, d_cfg, B, qmask, x0, yref, yref_e, p, xbar, ubar, cost, stat, iters, first, sched2, cap, flip, hslot); break;
-#else
-        default: break;
-#endif
     }
 }
 

@@ -1,6 +1,6 @@
-// cond_common.h -- helpers shared by the condensed N = 20 pipeline (admpc_kernels.hip: kernels C, D, E) and its fused successor
-// (admpc_fused20.hip): lane-scan primitives, HBM <-> LDS staging of one instance, the LDS map.  Include inside the translation
-// unit's anonymous namespace after dense40.h (dpp_mov, WAVE) and after GTS / NX are defined.
+// cond_common.h -- helpers shared by the condensed kernels (admpc_fused20.hip, admpc_seg.hip): lane-scan primitives and
+// HBM <-> LDS staging of one instance.  Include inside the translation unit's anonymous namespace after dense40.h (dpp_mov,
+// WAVE) and after NX is defined.
 #pragma once
 
 // x / 7 for 0 <= x < 13107 as a 32-bit multiply-shift: hipcc 7.2 narrows small non-negative ints to 16 bits and its backend
@@ -17,16 +17,6 @@ __device__ __forceinline__ double wave_scan_incl(double v) {      // inclusive p
     v = Op::f(v, dpp_mov<0x142, 0xa>(Op::id(), v));
     v = Op::f(v, dpp_mov<0x143, 0xc>(Op::id(), v));
     return v;
-}
-
-// 1/sqrt(d) for well-scaled positive d: hardware estimate + two Newton steps (full double accuracy for the pivots seen here,
-// 1e-3 .. 1e15; ocml's rsqrt adds range scaling that the pivot chain does not need)
-__device__ __forceinline__ double rsqrt_nr(double d) {
-    double r = __builtin_amdgcn_rsq(d);
-    double e = fma(-d * r, r, 1.0);
-    r = fma(0.5 * r, e, r);
-    e = fma(-d * r, r, 1.0);
-    return fma(0.5 * r, e, r);
 }
 
 __device__ __forceinline__ int wave_scan_incl_int(int v) {        // inclusive prefix sum over lanes 0..lane
@@ -63,20 +53,10 @@ __device__ __forceinline__ void stage_dq(double* __restrict__ dq, const double* 
     for (int it = 0; it < IT; ++it) {
         int i = lane + WAVE * it; i = i < CNT ? i : CNT - 1;
         const int k = div7(i), c = i - 7 * k;
-        xv[it] = xb[i];
-        yv[it] = k < NN ? yr[k * 9 + c] : yre[c];
+        xv[it] = *(xb + i);
+        yv[it] = k < NN ? *(yr + k * 9 + c) : *(yre + c);
     }
 #pragma unroll
     for (int it = 0; it < IT; ++it) { int i = lane + WAVE * it; i = i < CNT ? i : CNT - 1; dq[i] = xv[it] - yv[it]; }
 }
-
-
-template <int NT>
-struct DenseLds {
-    static constexpr int N = NT, n = 2 * NT, NTRI = n * (n + 1) / 2;
-    static constexpr int LSZ = NTRI > N * GTS ? NTRI : N * GTS;
-    static constexpr int BLS = (N * 7 + 1) & ~1, DQS = ((N + 1) * 7 + 1) & ~1;     // keep every sub-array 16-byte aligned
-    static constexpr int total = 2 * (NTRI + (NTRI & 1)) + 5 * 64 + 4 * 64;     // interior-point kernel: H, L, parked constants, exchange buffers
-    static constexpr int expand_total = N * GTS + BLS + DQS + 64;                 // expand kernel: linearisation, defects, tracking error, du
-};
 
