@@ -1,10 +1,10 @@
 // admpc_fused20.hip -- the N = 20 fp64 SQP-RTI step (BASELINE configs[1..3]) as ONE persistent kernel for gfx950.
 //
 // One wavefront (= one workgroup of 64 lanes) owns one MPC instance from its inputs to its outputs and then draws the next one
-// from a ticket counter.  Nothing but the algorithmic inputs and outputs of SURVEY 8a crosses HBM: the condensed Hessian (6.6 KB),
-// its factor (6.6 KB) and every intermediate live in the wave's 18.2 KB of LDS or in registers -- eight instances per CU, two waves
-// per SIMD; the packed linearisation (7.8 KB) aliases that space and is recomputed in front of the expansion (or parked in a per-wave
-// slot of global memory when the model carries GP residuals).  Phases of an instance (reference = data_driven_mpc/ros_gp_mpc/src/ad_mpc/...):
+// from a ticket counter.  The packed linearisation (7.8 KB), the condensed Hessian H and its factor L (6.6 KB: one buffer, they are
+// never live together) and every intermediate live in the wave's 19.1 KB of LDS or in registers -- eight instances per CU, two waves
+// per SIMD; H waits in a per-wave slot of global memory (L2) while L occupies its buffer and comes back by LDS-DMA in front of every
+// interior-point iteration.  Phase A runs once per instance.  Phases of an instance (reference = data_driven_mpc/ros_gp_mpc/src/ad_mpc/...):
 //   A  H0/H1  ERK4 + forward sensitivities of all 20 stages           ad_3d_optimizer.py:280-310, acados ERK
 //             (A1: lanes (stage, third) integrate the state and table      (acados_solver_sim_car.c:655-665)
 //              the Jacobian entries of the four RK stages in LDS; A2: the same lanes integrate their 2-3 sensitivity columns
@@ -90,23 +90,35 @@ __device__ __forceinline__ unsigned long long f20_now() { unsigned long long t; 
 #include "dense40.h"
 #include "cond_common.h"
 
-// LDS map of one instance (doubles): what the interior point needs and nothing else -- 18.2 KB, eight instances per CU (two waves per
-// SIMD).  The exchange buffers keep the relative layout dense40.h's col_head assumes (sb = cb + 128).  The other phases alias it:
-//   A   JT [0, 1960) Jacobian tables of the RK stages, bl [1960, 2100) defects; then GT [0, 840) (written when the tables are dead)
-//   C   reads GT, bl; dq [860, 1008), gam [1008, 1456); leaves H in [0, 820) (row store after the last read of GT)
-//   E   GT, bl once more in the places of phase A (second run of phase A, or read back from the slot buffer); dq, du in C's places
-// The packed linearisation (GT, bl: 7.8 KB) is needed again behind the interior point, by the expansion, and LDS cannot keep it at this
-// occupancy: see `park_gt` in the kernel for the two ways across.
+// LDS map of one instance (doubles), 19.1 KB, eight instances per CU (two waves per SIMD):
+//   GT [0, 840)  packed linearisation, written at the end of phase A, read by phases C and E
+//   H/L [840, 1660)  H (from phase C's row store to the row build of a factorisation) and the factor L (from there to the last
+//        substitution of the iteration) in ONE buffer: H waits in the wave's slot of global memory and is fetched back (slot_fetch)
+//   park [1660, 1980), cb / invd / sb / sb2 [1980, 2236)  per-lane constants and exchange buffers of phase D (the relative layout
+//        dense40.h's col_head assumes: sb = cb + 128)
+//   bl [2236, 2376)  defects b_k, written by phase A, read by phases C and E;  scheduler table [2376, 2440)
+// The other phases alias it:
+//   A   JT [0, 1960) Jacobian tables of the RK stages (over GT, H/L, park; clear of bl and the scheduler table); GT is written when the
+//       tables are dead
+//   C   dq [860, 1008), gam [1008, 1520) in the H/L buffer (dead until the row store of H behind the last stage)
+//   E   dq -> dx [860, 1008), du [1008, 1072) in the H/L buffer (dead behind the interior point)
+// Banks: the tables keep stride 98; GT, dq, gam keep their offsets; H/L moves by 840 doubles as a whole (16-byte aligned: the
+// LDS-DMA destination), which keeps the triangular row starts' conflict-free pattern.
 struct FusedLds {
     static constexpr int N = 20, NTRI = 820;
-    static constexpr int oH = 0, oL = oH + NTRI, oPark = oL + NTRI, oCb = oPark + 5 * 64;
-    static constexpr int oSch = oCb + 4 * 64;                           // [2][64] ints: inclusive scan of the bin counts (most expensive bin first), the counts
-    static constexpr int total = oSch + 64;                             // 2280 doubles = 18 240 B
+    static constexpr int oGT = 0, oH = oGT + N * GTS, oL = oH, oPark = oH + NTRI, oCb = oPark + 5 * 64;
+    static constexpr int oBl = oCb + 4 * 64;
+    static constexpr int oSch = oBl + N * NX;                           // [2][64] ints: inclusive scan of the bin counts (most expensive bin first), the counts
+    static constexpr int total = oSch + 64;                             // 2440 doubles = 19 520 B
     static constexpr int JTS = 24, JTK = 4 * JTS + 2;                   // Jacobian entries per (stage, RK stage); doubles per stage: 98, not 96 --
                                                                         // 768 B apart the 20 stages of a table access all hit one bank group
-    static constexpr int oJT = 0, oBlA = N * JTK, oGTC = 0, oDqC = 860, oGam = oDqC + 148;
-    static constexpr int SLOT = N * GTS + N * NX;                       // doubles per wave in the slot buffer
-    static_assert(oBlA + N * NX <= total && oGTC + N * GTS <= oDqC && oGam + (NX + 1) * 64 <= oPark, "LDS aliases");
+    static constexpr int oJT = 0, oDqC = 860, oGam = oDqC + 148;
+    static_assert(oJT + N * JTK <= oBl, "LDS aliases: phase A's tables end before bl and the scheduler table");
+    static_assert(oGT + N * GTS <= oH, "LDS aliases: GT survives phases C, D, E (clear of H/L, park and the exchange buffers)");
+    static_assert(oDqC >= oH && oDqC + (N + 1) * NX <= oGam && oGam + (NX + 1) * 64 <= oH + NTRI, "LDS aliases: dq, gam (phase C), dx, du (phase E) inside H/L");
+    static_assert(oBl >= oCb + 4 * 64 && oBl + N * NX <= oSch && oSch + 64 <= total, "LDS aliases: bl, scheduler table");
+    static_assert(oH % 2 == 0 && oCb % 2 == 0, "16-byte alignment: LDS-DMA destination, double2 exchange");
+    static_assert(8 * total * 8 <= 160 * 1024, "eight instances per CU");
 };
 
 // ---- work order.  A wave owns an instance for 40 us (the trial solves it) up to 200 us (13 interior-point iterations), and a batch
@@ -132,29 +144,25 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
     constexpr int N = 20, n = 40;
     extern __shared__ double lds_raw[];
     double* const Hp = lds_raw + FusedLds::oH;          // packed lower-triangular rows of H
-    double* const Lp = lds_raw + FusedLds::oL;          // packed strictly-lower rows of the unit factor L (M = L D L')
+    double* const Lp = lds_raw + FusedLds::oL;          // packed strictly-lower rows of the unit factor L (M = L D L'): H's buffer
     double* const park = lds_raw + FusedLds::oPark;     // [5][64] per-lane constants (registers are the scarce resource)
     double* const cb = lds_raw + FusedLds::oCb;         // [64] step broadcast buffer
     double* const invd = cb + 64;                       // [64] 1 / D_jj
     double* const sb = invd + 64;                       // [64] per-stage exchange
     double* const sb2 = sb + 64;                        // [64]
     double* const JT = lds_raw + FusedLds::oJT;         // phase A: [N][4][24] Jacobian entries of the RK stages
-    double* const GT = lds_raw + FusedLds::oGTC;        // phases A (end), C: packed linearisation of the instance
-    double* const bl = lds_raw + FusedLds::oBlA;        // phases A, C: defects b_k
+    double* const GT = lds_raw + FusedLds::oGT;         // phases A (end), C, E: packed linearisation of the instance
+    double* const bl = lds_raw + FusedLds::oBl;         // phases A, C, E: defects b_k
     double* const dqC = lds_raw + FusedLds::oDqC;       // phase C: xbar_k - xref_k
     double* const gam = lds_raw + FusedLds::oGam;       // phase C: [NX][64] Gamma components of the current stage
-    double* const GTe = GT;                             // phase E: the linearisation again, in the same places (second run of phase A,
-    double* const ble = bl;                             //          or read back from the wave's slot buffer)
     double* const dqE = lds_raw + FusedLds::oDqC;       // phase E: xbar_k - xref_k, overwritten by dx_k
     double* const dus = lds_raw + FusedLds::oGam;       // phase E: [64] du per input
-    // How the linearisation gets across the interior point (LDS cannot keep it at eight instances per CU):
-    //   slotbuf == NULL  phase A runs a second time in front of phase E: nothing but the instance's inputs and outputs crosses HBM
-    //                    (24 MB per 4096-instance step, 1.3 x the algorithmic bytes; + 2 % time);
-    //   slotbuf != NULL  it is parked in a slot buffer that belongs to the WAVE (grid x 980 doubles, reused for every instance the wave
-    //                    draws, written behind phase A and read back in front of phase E: 71 MB per step).  The host chooses this when
-    //                    GP residuals are configured: their kernel sums make phase A several times as expensive.
-    const bool park_gt = slotbuf != nullptr;
-    double* const slot = slotbuf + (size_t)blockIdx.x * FusedLds::SLOT;
+    // H's slot: NTRI doubles of global memory that belong to the WAVE (grid x 820 doubles), rewritten for every instance the wave draws.
+    // Phase C stores H there behind its row store; the trial factorises in place; an instance that iterates fetches H back by LDS-DMA in
+    // front of iteration 0 and behind the corrector's last substitution of every iteration (the factor is dead there).  The lines stay in
+    // the L2 (no release fence: it would write them back to HBM; no acquire either: the fetches do not read through the L1).
+    double* const slot = slotbuf + (size_t)blockIdx.x * FusedLds::NTRI;
+    constexpr int slot_aux = 16;                    // cache policy of the fetches: sc1 (L2-served; see the first fetch in phase D)
 #define PK_DL   park[0 * 64 + lane]
 #define PK_DUU  park[1 * 64 + lane]
 #define PK_G0   park[2 * 64 + lane]
@@ -176,6 +184,9 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
         const bool uz_ = lz_ < n;
         double a[n];
         newton_row_40(a, lds_byte_addr(Hp + (uz_ ? trz_ : 0)), dbar_, sodd_);
+        // H's rows are in registers: its buffer becomes the factor's.  Diagonal slots of the packed factor: 0.0 (the factorisation stores the
+        // strictly-lower part only; the substitution assembly lets the source lane of a step take part with this multiplier)
+        if (uz_) Lp[trz_ + lz_] = 0.0;
         const unsigned lrow = lds_byte_addr(Lp + (uz_ ? trz_ : 0));
         const unsigned pub_wr = lds_byte_addr(cb + lz_), pub_rd = lds_byte_addr(cb + (lz_ & 15));
         auto chain = [&](auto jc, double& nln) __attribute__((always_inline)) {
@@ -285,12 +296,6 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
         double du = 0.0;
         bool failed = false;
         int it = 0;
-        // without a slot buffer phase A runs a second time in front of phase E: pass 1 of this loop (one copy of the code)
-        int npass = park_gt ? 1 : 2; asm volatile("" : "+s"(npass));
-        int pass0 = 0;
-        asm volatile("" : "+s"(pass0));                                 // an opaque first pass (a known 0 changes the listing)
-#pragma unroll 1
-        for (int pass = pass0; pass < npass; ++pass) {
         {
             LAUNDER_LANE(lane); LAUNDER_CFG(cf);
             const double h = cf->Ts;
@@ -376,7 +381,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                 // packed stage record: stored columns c = 0..6 <-> (A[:,2..6], B[:,0..1]), rows 0..5 of each
                 const int c0 = g == 0 ? 0 : (g == 1 ? 3 : 5);
                 const int nc = g == 0 ? 3 : 2;
-                WSYNC();                                   // REQUIRED: GT overlays the Jacobian tables (FusedLds: oGTC = oJT = 0) -- every lane has read its
+                WSYNC();                                   // REQUIRED: GT overlays the Jacobian tables (FusedLds: oGT = oJT = 0) -- every lane has read its
                                                            // tables before the first store.  With ADMPC_WSYNC_FENCE_ONLY this is a wave-level fence: the
                                                            // kernel must stay ONE wave per workgroup (launch bounds below)
                 double* Gk = GT + k * GTS;
@@ -390,12 +395,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         }
             }
             WSYNC();
-            if (park_gt) {      // park the linearisation in the wave's slot buffer (read back in front of phase E); the stores retire under phase C
-                stage_in<N * GTS>(slot, GT, lane);
-                stage_in<N * NX>(slot + N * GTS, bl, lane);
-            }
         }
-        if (pass != 0) break;
 
         // =================================================================================================================
         // phase C (H2-H4): condensing, lane i <-> input i = 2k + j.  Leaves the packed
@@ -475,11 +475,11 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     const double* Gk = GT + k * GTS;
                     // (indices into the one LDS array, not selected pointers: hipcc turns a select of two LDS pointers into flat pointers and
                     // converts every element address back with a null check -- five scalar instructions per load)
-                    const int bidx = mine_p ? FusedLds::oGTC + k * GTS + 5 * 6 + 6 * ji : FusedLds::oGam + 7 * 64;
+                    const int bidx = mine_p ? FusedLds::oGT + k * GTS + 5 * 6 + 6 * ji : FusedLds::oGam + 7 * 64;
                     { const int e16 = lane & 15; Aq[0] = Gk[e16]; Aq[1] = Gk[16 + (e16 < 14 ? e16 : 13)]; }
 #pragma unroll
                     for (int q_ = 0; q_ < 3; ++q_) Bv[q_] = *reinterpret_cast<const double2*>(lds_raw + bidx + 2 * q_);
-                    const int lidx = lane == n ? FusedLds::oBlA + k * 7 : FusedLds::oGam + 7 * 64;      // b_k for the column of the free response, zeros for the others
+                    const int lidx = lane == n ? FusedLds::oBl + k * 7 : FusedLds::oGam + 7 * 64;      // b_k for the column of the free response, zeros for the others
 #pragma unroll
                     for (int r = 0; r < NX; ++r) blv[r] = lds_raw[lidx + r];
                     __builtin_amdgcn_sched_barrier(0);
@@ -550,11 +550,10 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         const int row = 16 * I + kq + 4 * v, col = 16 * J + r16;
                         if (row < n && col <= row) Hp[row * (row + 1) / 2 + col] = acc[I][J][v];
                     }
-            // diagonal slots of the packed factor: 0.0 (the factorisation stores the strictly-lower part only; the substitution
-            // assembly lets the source lane of a step take part with this multiplier).  Phase C used L's space: rewrite them.
             WSYNC();
-            if (uact) Lp[(lane * (lane + 1)) / 2 + lane] = 0.0;
-            WSYNC();
+            // H to the wave's slot: the factor of the trial takes its buffer.  The stores retire under the trial; the first fetch (phase D)
+            // waits for them.
+            stage_in<FusedLds::NTRI>(slot, Hp, lane);
         }
 
         // =================================================================================================================
@@ -641,6 +640,15 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             };
         F20_STAMP(4);
             F20_TRACE_MID();
+            if (!solved && try_unc) {
+                // H back from the slot: the trial's factor is dead.  Phase C's slot stores have retired (under the trial): the L2 holds this
+                // instance's H.  The CU's vector L1 does not follow the wave's stores and may still hold the slot's lines that the PREVIOUS
+                // instance of this wave fetched -- so every fetch is an sc1 load (slot_aux), served by the L2 without consulting the L1.
+                // (Plain loads behind an agent-scope acquire, as kernel S reads its slot, measured 2 % slower at configs[1]: the L1 invalidate
+                // is waited for by every iterating instance and drops the lines of the CU's other seven waves.)
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                slot_fetch<FusedLds::NTRI, slot_aux>(Hp, slot, lane);
+            }
             if (!solved)
             for (; it < itmax + (cons ? fbit : 0); ++it) {
                 // An instance that is still iterating is on its way to becoming the batch's straggler: give its wave the issue slots of the
@@ -672,6 +680,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     sb[lane] = rdlane(dlam_pref, 63) - dlam_pref;           // suffix over stages > lane
                     const double Ssuf_incl = wave_scan_incl<OpSum>(dact ? G56 : 0.0);
                     sb2[lane] = rdlane(Ssuf_incl, 63) - Ssuf_incl;          // lane = stage: sum over stages > lane
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // H has landed (fetched in front of the loop or behind the last solve)
                     WSYNC();
                     double hdu = 0.0;
                     {
@@ -705,7 +714,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         (rmax <= tol_res || (it > 0 && rmax > 0.1 * rmax_prev && rmax <= ADMPC_IPM_FLOOR_CAP * tol_res))) break;      // admpc.h: stopping test
                     rmax_prev = rmax;
                 }
-                if (fbit > 0 && !cons && it >= fbit) {
+                if (fbit > 0 && !cons && it >= fbit) {            // (no factorisation behind the fetch yet: H stays in LDS for the restart)
                     cons = true; warmed = false;
                     cold_start();
                     rmax_prev = 0.0;
@@ -743,6 +752,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     WSYNC();
                     double y = uact ? -(ru + etal + etau + (ji ? h * sb[ki] : 0.0)) : 0.0;
                     const double x = ldl_solve(y, lz);
+                    if (pass == 1) slot_fetch<FusedLds::NTRI, slot_aux>(Hp, slot, lz);     // the factor is dead: next iteration's H under the step-length work
                     ddu = uact ? x : 0.0;
                     cb[lane] = ddu;
                     WSYNC();
@@ -789,7 +799,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     } else {
                         double tau = 1.0 - mu_aff; tau = fmax(tau, 0.995); tau = fmin(tau, 0.999999);
                         const double alpha = fmin(tau * amax, 1.0);
-                        if (it == 0 && warmed && alpha < wrest) {
+                        if (it == 0 && warmed && alpha < wrest) {      // (H is on its way from the slot, as for any next iteration)
                             warmed = false;
                             cold_start();
                         } else {
@@ -809,10 +819,9 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     WSYNC();
                 }
             }
-        }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // an iteration limit leaves the last fetch in flight: phase E (dx, du)
+        }                                                                   // and the next instance's phase A write into its destination
         F20_STAMP(5);
-        if (failed) break;
-        }   // pass
         { LAUNDER_LANE(lw); if (lw == 0 && itersg) itersg[inst] = it; }
         if (failed) {
             // non-finite QP data: acados returns before the update -- the iterate stays as it is, status 4, cost +inf
@@ -839,15 +848,6 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             int tk_v = 0;
             if (cap != 0 && lane == 0) tk_v = atomicAdd(sched, 1);       // the next ticket: its trip to the L2 runs under the expansion
             WSYNC();
-            if (park_gt) {
-                // the slot buffer again: the wave's own stores of phase A have long retired, but the CU's vector L1 may still hold the
-                // lines the PREVIOUS instance of this wave read here (the L1 does not follow the wave's stores): drop them
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                stage_in<N * GTS>(GTe, slot, lane);
-                stage_in<N * NX>(ble, slot + N * GTS, lane);
-                WSYNC();
-            }
             stage_dq<N>(dqE, xbg, yrg, yrefeg + (size_t)inst * NX, lane);
             du = uact ? du : 0.0;
             dus[lane] = du;
@@ -864,11 +864,11 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                 if (!(fabs(dx) <= 1e300)) bad = true;
                 if (lane < NX) dqE[k * 7 + lane] = dx;            // slot k now holds dx_k
                 if constexpr (k < N) {
-                    const double* Gk = GTe + k * GTS;
+                    const double* Gk = GT + k * GTS;
                     const double u0 = dus[2 * k], u1 = dus[2 * k + 1];
                     // rows 0..5 from the packed record; every lane loads (lanes >= 6 read row 0 and drop the result): seven loads under their
                     // own EXEC masks were 18 scalar instructions per stage.  Row 6 of [A B] is [e6, 0, h]: one multiply-add in lane 6.
-                    const double bk = ble[k * 7 + r7];
+                    const double bk = bl[k * 7 + r7];
                     double acc = bk + (lane < 2 ? dx : 0.0);
                     double gg[5];
 #pragma unroll
@@ -936,8 +936,8 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
 extern "C" {
 
 __attribute__((visibility("hidden"))) int admpc_fused20_lds_bytes(void) { return FusedLds::total * (int)sizeof(double); }
-// doubles of the per-wave slot buffers (only allocated and passed when the handle's model carries GP residuals)
-__attribute__((visibility("hidden"))) size_t admpc_fused20_slot_doubles(int num_cu) { return (size_t)num_cu * 8 * FusedLds::SLOT; }
+// doubles of the per-wave slot buffers: one packed H per workgroup of the persistent grid (at most num_cu * 8)
+__attribute__((visibility("hidden"))) size_t admpc_fused20_slot_doubles(int num_cu) { return (size_t)num_cu * 8 * FusedLds::NTRI; }
 
 // debug builds only: read and clear the phase counters (all zero in the shipped build)
 int admpc_debug_f20_ticks(unsigned long long* out16)
@@ -969,7 +969,7 @@ int admpc_debug_f20_trace(unsigned long long* out, int n_inst)
 
 __attribute__((visibility("hidden"))) void admpc_fused20_prepare(void)
 {
-    // 18.2 KB per workgroup: below the 64 KB default, no opt-in needed; kept for symmetry with the other units
+    // 19.1 KB per workgroup: below the 64 KB default, no opt-in needed; kept for symmetry with the other units
 }
 
 // sched ints of a handle that solves up to `cap` instances per call: TWO scheduler states used alternately (zeroed at allocation; the order kernel of a

@@ -544,7 +544,7 @@ struct AdmpcSolver {
     int* d_tick;             // 2 x [128 + 64 cap_fused] tickets, exit counter and work-order bins of the persistent kernels: two states used alternately (work_order.h)
     int tick_flip;           // which of the two the last launch used
     int cap_fused;
-    double* d_slot;          // per-wave slot buffers of the fused kernel (the linearisation across the interior point), allocated at its first launch
+    double* d_slot;          // per-wave slot buffers of the fused / segmented kernel (H while its factor holds the LDS buffer), allocated at the first launch
     // Workspaces, each grown on demand by the path that needs it (admpc_reserve sizes the handle's default path up front):
     int cap;                 // instances: d_status
     int32_t* d_status;       // [cap] used when the caller passes status == NULL
@@ -767,11 +767,10 @@ static int ensure_lin(AdmpcSolver* s, int B)                    // kernel A's ou
     s->cap_lin = B;
     return ADMPC_OK;
 }
-static int ensure_fused(AdmpcSolver* s, int B)                  // fused N = 20 step: one slot buffer per resident wave, the work-order lists
-{                                                                // (segmented kernel: the work-order lists only)
-    // slot buffers only where parking the linearisation beats recomputing it: with GP residuals in the model (see admpc_fused20.hip)
-    if (!s->d_slot && s->cfg.n_gp > 0 && !s->use_seg) HIPCHK(hipMalloc((void**)&s->d_slot, admpc_fused20_slot_doubles(s->num_cu) * sizeof(double)));
-    // segmented kernel: one packed Hessian per resident wave (its LDS buffer doubles as the factor's)
+static int ensure_fused(AdmpcSolver* s, int B)                  // fused N = 20 step and segmented kernel: one slot buffer per resident
+{                                                                // wave, the work-order lists
+    // one packed Hessian per resident wave (its LDS buffer doubles as the factor's): fused kernel and segmented kernel alike
+    if (!s->d_slot && !s->use_seg) HIPCHK(hipMalloc((void**)&s->d_slot, admpc_fused20_slot_doubles(s->num_cu) * sizeof(double)));
     if (!s->d_slot && s->use_seg) HIPCHK(hipMalloc((void**)&s->d_slot, admpc_seg_slot_doubles(s->num_cu) * sizeof(double)));
     if (B <= s->cap_fused) return ADMPC_OK;
     HIPCHK(hipDeviceSynchronize());

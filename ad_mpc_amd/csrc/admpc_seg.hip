@@ -51,25 +51,6 @@ __device__ __forceinline__ double uni(double v) {
     return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-// The wave's H (S = 4: and Hb behind it) from its slot in global memory (L2) straight into LDS: LDS-DMA (global_load_lds_dwordx4: destination =
-// wave-uniform base + lane * 16, no staging registers), issued as soon as the factor that occupies the buffer is dead -- behind the last back
-// substitution of an iteration -- so that the round trip hides under the step-length computations.  The caller waits vmcnt(0) before the first read.
-template <int CNT>
-__device__ __forceinline__ void slot_fetch(double* lds_dst, const double* gsrc, const int lane) {
-    constexpr int BYTES = CNT * 8, FULL = BYTES / 1024, REM = (BYTES % 1024) / 16;
-    static_assert(BYTES % 16 == 0, "slot_fetch copies 16 bytes per lane");
-    // 1 KiB pieces; four per base address (the instruction's 12-bit offset moves both the source and the LDS destination).  The base is laundered
-    // where the copy is issued: hipcc otherwise hoists one 64-bit address per piece out of the interior-point loop and spills them.
-    const char* g = reinterpret_cast<const char*>(gsrc) + lane * 16;
-    asm volatile("" : "+v"(g));
-    char* l = reinterpret_cast<char*>(lds_dst);
-    static_for<0, FULL + (REM > 0 ? 1 : 0)>([&](auto pc) __attribute__((always_inline)) {
-        constexpr int p = decltype(pc)::value, grp = p / 4, off = (p % 4) * 1024;
-        if (p < FULL || lane < REM)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + grp * 4096), (__attribute__((address_space(3))) void*)(l + grp * 4096), 16, off, 0);
-    });
-}
-
 // Cross-WAVE exchange through LDS: inline-assembly LDS stores are invisible to the compiler's wait-count tracking, so the barrier
 // waits for everything this wave has in flight first.
 #define XSYNC() do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __syncthreads(); } while (0)

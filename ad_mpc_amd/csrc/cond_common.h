@@ -1,6 +1,6 @@
-// cond_common.h -- helpers shared by the condensed kernels (admpc_fused20.hip, admpc_seg.hip): lane-scan primitives and
-// HBM <-> LDS staging of one instance.  Include inside the translation unit's anonymous namespace after dense40.h (dpp_mov,
-// WAVE) and after NX is defined.
+// cond_common.h -- helpers shared by the condensed kernels (admpc_fused20.hip, admpc_seg.hip): lane-scan primitives, HBM <-> LDS
+// staging of one instance and the LDS-DMA fetch of a wave's H from its slot.  Include inside the translation unit's anonymous namespace
+// after dense40.h (dpp_mov, static_for, WAVE) and after NX is defined.
 #pragma once
 
 // x / 7 for 0 <= x < 13107 as a 32-bit multiply-shift: hipcc 7.2 narrows small non-negative ints to 16 bits and its backend
@@ -42,6 +42,26 @@ __device__ __forceinline__ void stage_in(double* __restrict__ dst, const double*
     for (int it = 0; it < IT; ++it) { int i = lane + WAVE * it; i = i < C2 ? i : C2 - 1; tmp[it] = reinterpret_cast<const double2*>(src)[i]; }
 #pragma unroll
     for (int it = 0; it < IT; ++it) { int i = lane + WAVE * it; i = i < C2 ? i : C2 - 1; reinterpret_cast<double2*>(dst)[i] = tmp[it]; }
+}
+// A wave's H (kernel S at S = 4: and Hb behind it) from its slot in global memory (L2) straight into LDS: LDS-DMA (global_load_lds_dwordx4:
+// destination = wave-uniform base + lane * 16, no staging registers), issued as soon as the factor that occupies the buffer is dead -- behind the
+// last back substitution of an iteration -- so that the round trip hides under the step-length computations.  The caller waits vmcnt(0) before
+// the first read (and before any LDS store into the destination).  AUX: the loads' cache policy bits (16 = sc1: served by the L2,
+// never by a line the CU's vector L1 may still hold).
+template <int CNT, int AUX = 0>
+__device__ __forceinline__ void slot_fetch(double* lds_dst, const double* gsrc, const int lane) {
+    constexpr int BYTES = CNT * 8, FULL = BYTES / 1024, REM = (BYTES % 1024) / 16;
+    static_assert(BYTES % 16 == 0, "slot_fetch copies 16 bytes per lane");
+    // 1 KiB pieces; four per base address (the instruction's 12-bit offset moves both the source and the LDS destination).  The base is laundered
+    // where the copy is issued: hipcc otherwise hoists one 64-bit address per piece out of the interior-point loop and spills them.
+    const char* g = reinterpret_cast<const char*>(gsrc) + lane * 16;
+    asm volatile("" : "+v"(g));
+    char* l = reinterpret_cast<char*>(lds_dst);
+    static_for<0, FULL + (REM > 0 ? 1 : 0)>([&](auto pc) __attribute__((always_inline)) {
+        constexpr int p = decltype(pc)::value, grp = p / 4, off = (p % 4) * 1024;
+        if (p < FULL || lane < REM)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(g + grp * 4096), (__attribute__((address_space(3))) void*)(l + grp * 4096), 16, off, AUX);
+    });
 }
 // dq[k][c] = xbar[k][c] - (k < N ? yref[k][c] : yref_e[c]), k = 0..N: the same, for the tracking-error block
 template <int NN>
