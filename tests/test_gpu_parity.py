@@ -259,14 +259,33 @@ def _random_problem(rng, N):
     cfg.lbx_delta, cfg.ubx_delta = float(-rng.uniform(0.35, 0.5)), float(rng.uniform(0.35, 0.5))
     cfg.zl, cfg.zu = float(rng.uniform(5, 20)), float(rng.uniform(5, 20))
     cfg.mass *= float(rng.uniform(0.8, 1.2)); cfg.Iz *= float(rng.uniform(0.8, 1.2)); cfg.L_F *= float(rng.uniform(0.9, 1.1))
+    cfg.L_R *= float(rng.uniform(0.9, 1.1)); cfg.Cf *= float(rng.uniform(0.8, 1.2)); cfg.Cr *= float(rng.uniform(0.8, 1.2))
     return cfg
 
 
-@pytest.mark.parametrize("N", [13, 20, 40])
+def random_q7_problem(rng, N):
+    """Problem data away from the shipped values that keeps the shipped weight PATTERN: only x, y and psi carry weights (W[3..6] =
+    We[3..6] = 0), so admpc_create picks the qmask-7 instantiation of kernels F and S.  W[0], W[1], W[2] independent; Ts in [0.02, 0.1];
+    input weights; terminal scale in [1e-6, 1e-2]; asymmetric input, steering-rate and steering boxes; zl != zu; all six vehicle
+    parameters within 30 % of the shipped ones."""
+    q = (float(rng.uniform(2, 30)), float(rng.uniform(2, 30)), float(rng.uniform(20, 200)), 0.0, 0.0, 0.0, 0.0)
+    r = (float(rng.uniform(0.3, 3.0)), float(rng.uniform(20, 200)))
+    cfg = default_config(N=N, Ts=float(rng.uniform(0.02, 0.1)), q=q, r=r, terminal_scale=float(10 ** rng.uniform(-6, -2)))
+    cfg.lbu[0], cfg.ubu[0] = float(-rng.uniform(3, 10)), float(rng.uniform(1.5, 6))
+    cfg.lbu[1], cfg.ubu[1] = float(-rng.uniform(0.3, 1.0)), float(rng.uniform(0.3, 1.0))
+    cfg.lbx_delta, cfg.ubx_delta = float(-rng.uniform(0.25, 0.55)), float(rng.uniform(0.25, 0.55))
+    cfg.zl, cfg.zu = float(rng.uniform(3, 30)), float(rng.uniform(3, 30))
+    for f in ("mass", "L_F", "L_R", "Iz", "Cf", "Cr"):
+        setattr(cfg, f, getattr(cfg, f) * float(rng.uniform(0.7, 1.3)))
+    assert all(cfg.W[c] == 0.0 and cfg.We[c] == 0.0 for c in range(3, 7)) and cfg.W[0] != cfg.W[1]
+    return cfg
+
+
+@pytest.mark.parametrize("N", [13, 20, 40, 60, 80])
 def test_randomised_problem_data(gpu_engine_factory, oracle_omp, N):
     """Five random problem descriptions per horizon (weights, asymmetric bounds and slack penalties, sampling time, terminal scale,
-    vehicle parameters), 96 scenarios each, against the oracle: condensed pipeline (general-weight instantiation) at N = 20,
-    kernel R otherwise.  Same statuses and iteration counts, 1e-8 / 1e-7."""
+    vehicle parameters), 96 scenarios each, against the oracle: the general-weight instantiation of kernel F at N = 20 and of kernel S
+    at N = 40, 60 and 80, kernel R at N = 13.  Same statuses and iteration counts, 1e-8 / 1e-7."""
     rng = np.random.default_rng(100 + N)
     for trial in range(5):
         cfg = _random_problem(rng, N)

@@ -1,0 +1,212 @@
+"""The quadrotor's device paths on problem data away from the shipped values, and every horizon of the default path.
+
+The solve tests elsewhere run the shipped vehicle (J_x = J_y, 'x' rotor geometry, W_e = 0, W[3] = 0, box [0, 1]).  Here random problem
+descriptions (random_quad_problem: weights with W[3] != 0, terminal weights, an input box that is not [0, 1], mass, J with J_x != J_y,
+max_thrust, g, asymmetric rotor arms and yaw-torque coefficients or the reference's '+' geometry, sampling time, linear drag) run on
+every device path against the oracle and the device shooting against the oracle's ERK4; then the device's step at the tight stop levels
+is certified as THE minimiser of the box QP condensed in numpy from the device's own linearisation (no CPU solver involved).
+"""
+import math
+
+import numpy as np
+import pytest
+
+from ad_mpc_amd.quad_config import default_quad_config, set_quad_gp, tight_quad_ipm, QNX, QNU
+from ad_mpc_amd.quad_scenarios import random_quad_scenarios, hover_input
+
+pytestmark = pytest.mark.gpu
+
+B = 64
+
+
+@pytest.fixture(scope="module")
+def qoracle():
+    from oracle.quad_oracle import QuadOracle
+    return QuadOracle()
+
+
+@pytest.fixture(scope="module")
+def quad_engine():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from ad_mpc_amd.engine import QuadBatchSolver
+    return lambda cfg: QuadBatchSolver(cfg, device=0)
+
+
+# Longest horizon drawn (N Ts, seconds): the class default's 2 s.  Beyond it the condensed QP loses digits to the unstable attitude
+# dynamics in any fp64 evaluation order: at N = 24, Ts = 0.125 (3 s) the fp64 oracle is 1.1e-8 / 1.9e-8 (u / x) from the 80-bit one,
+# above the 1e-8 parity tolerance, with the device as far; at 2.3 - 2.7 s it is 3e-9 - 6e-9 / 5e-9 - 1.4e-8.
+T_MAX = 2.0
+
+
+def random_quad_problem(rng, N, plus=False, drag=False):
+    """An AdmpcQuadConfig that admpc_quad_create accepts (positive Ts, mass, J and input weights; lbu < ubu) with every model and cost
+    field drawn away from the shipped values; the box contains the hover input of the drawn vehicle (and the scenarios' iterate around
+    it).  plus: the reference's '+' rotor geometry (quad_3d.py:62-64); drag: a random rdrv."""
+    c = default_quad_config(N=N, t_horizon=float(rng.uniform(0.06, min(0.14, T_MAX / N))) * N)
+    w = np.r_[rng.uniform(5, 20, 3), rng.uniform(0.05, 0.5), rng.uniform(0.05, 0.3, 3), rng.uniform(0.02, 0.1, 6), rng.uniform(0.05, 0.2, 4)]
+    for i, v in enumerate(w):
+        c.W[i] = float(v)
+    for i in range(QNX):
+        c.We[i] = float(w[i] * rng.uniform(0.1, 1.0))
+    c.mass, c.max_thrust, c.g = float(rng.uniform(0.7, 1.5)), float(rng.uniform(14, 28)), float(rng.uniform(9.0, 10.5))
+    c.J[0], c.J[1], c.J[2] = float(rng.uniform(0.02, 0.05)), float(rng.uniform(0.02, 0.05)), float(rng.uniform(0.04, 0.09))
+    arm = 0.47 / 2 * float(rng.uniform(0.8, 1.2))
+    if plus:
+        xf, yf = (arm, 0.0, -arm, 0.0), (0.0, arm, 0.0, -arm)
+    else:
+        h = math.cos(math.pi / 4) * arm
+        xf = np.array([h, -h, -h, h]) * rng.uniform(0.8, 1.2, 4); yf = np.array([-h, -h, h, h]) * rng.uniform(0.8, 1.2, 4)
+    zt = np.array([-0.013, 0.013, -0.013, 0.013]) * rng.uniform(0.7, 1.3, 4)
+    for i in range(QNU):
+        c.x_f[i], c.y_f[i], c.z_l_tau[i] = float(xf[i]), float(yf[i]), float(zt[i])
+    hov = hover_input(c)
+    for m in range(QNU):
+        c.lbu[m], c.ubu[m] = float(rng.uniform(0.0, 0.4) * hov), float(rng.uniform(0.55, 0.95))
+    if drag:
+        for i in range(3):
+            c.rdrv[i] = float(-rng.uniform(0.05, 0.4))
+    assert c.J[0] != c.J[1] and c.W[3] > 0 and all(c.lbu[m] + 0.02 < hov < c.ubu[m] - 0.02 for m in range(QNU))
+    return c
+
+
+# path: (N, environment, GP model); the comment names the kernel admpc_quad.hip:quad_solve launches for it
+PATHS = {
+    "dense40_N10": (10, {}, False),                               # admpc_quad_solve_kernel<true>
+    "generic_N10": (10, {"ADMPC_QUAD_GENERIC": "1"}, False),      # admpc_quad_solve_kernel<false>
+    "generic_N5": (5, {}, False),
+    "generic_N16": (16, {}, False),
+    "wide_N17": (17, {}, False),                                  # admpc_quad_solve_wide_kernel
+    "wide_N24": (24, {}, False),
+    "wide_N20": (20, {"ADMPC_QUAD_WIDE": "1"}, False),
+    "seg_N20": (20, {}, False),                                   # admpc_quad_seg_kernel
+    "seg_N20_gp": (20, {}, True),
+}
+DRAWS = 3          # draw 1: the '+' geometry; draw 2: linear drag
+
+
+def _draw(path, d):
+    N, _, gp = PATHS[path]
+    cfg = random_quad_problem(np.random.default_rng([2026, N, d]), N, plus=d == 1, drag=d == 2)
+    if gp:
+        from test_quad_oracle import quad_gps
+        set_quad_gp(cfg, quad_gps())
+    return cfg, random_quad_scenarios(B, cfg, seed=700 + 10 * N + d)
+
+
+def _solve(quad_engine, monkeypatch, cfg, s, env):
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    eng = quad_engine(cfg)
+    for k in env:
+        monkeypatch.delenv(k)
+    g = eng.solve_numpy(s["x0"], s["yref"], s["yref_e"], s["xbar"], s["ubar"])
+    return eng, g
+
+
+def _assert_quad_parity(g, o, cfg, s):
+    """The assertions of test_quad_gpu.py:test_quad_solve_parity_with_oracle, with the config's box."""
+    np.testing.assert_array_equal(g[3], o[3]); assert (o[3] == 0).all()
+    np.testing.assert_array_equal(g[4], o[4])
+    du, dx = np.abs(g[1] - o[1]).max(), np.abs(g[0] - o[0]).max()
+    assert du <= 1e-8 and dx <= 1e-8, (du, dx)
+    np.testing.assert_allclose(g[2], o[2], rtol=1e-9)
+    lb, ub = np.array(cfg.lbu[:]), np.array(cfg.ubu[:])
+    assert (g[1] >= lb - 1e-9).all() and (g[1] <= ub + 1e-9).all() and ((g[1] <= lb + 1e-6) | (g[1] >= ub - 1e-6)).sum() > len(g[1]) // 4
+    np.testing.assert_array_equal(g[0][:, 0], s["x0"])
+    return du, dx
+
+
+@pytest.mark.parametrize("d", range(DRAWS))
+@pytest.mark.parametrize("path", list(PATHS))
+def test_quad_path_on_random_problem_data(quad_engine, qoracle, monkeypatch, path, d):
+    """One random problem description on one device path: shooting at 1e-11 relative against the oracle's ERK4, the solve with the
+    oracle's statuses and iteration counts, u / x within 1e-8, cost 1e-9 relative."""
+    import torch
+    N, env, _ = PATHS[path]
+    cfg, s = _draw(path, d)
+    eng, g = _solve(quad_engine, monkeypatch, cfg, s, env)
+    o = qoracle.solve_batch(cfg, s["x0"], s["yref"], s["yref_e"], s["xbar"], s["ubar"], nthreads=16)
+    du, dx = _assert_quad_parity(g, o, cfg, s)
+    dv = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")
+    phi, A, Bm = eng.shoot(dv(s["xbar"]), dv(s["ubar"]))
+    torch.cuda.synchronize()
+    phi, A, Bm = phi.cpu().numpy(), A.cpu().numpy(), Bm.cpu().numpy()
+    for b in range(0, B, 9):
+        for k in (0, N // 2, N - 1):
+            ref = qoracle.rk4_sens(cfg, s["xbar"][b, k], s["ubar"][b, k], cfg.Ts, gpx=s["xbar"][b, 0] if (k == 0 and cfg.n_gp) else None)
+            for got, want in zip((phi[b, k], A[b, k], Bm[b, k]), ref):
+                assert np.abs(got - want).max() <= 1e-11 * max(1.0, np.abs(want).max()), (b, k)
+    eng.close()
+    print("PDQ %-12s draw %d: Ts %.4f  max|du| %.1e max|dx| %.1e  tol 1e-08" % (path, d, cfg.Ts, du, dx))
+
+
+@pytest.mark.parametrize("N", range(2, 25))
+def test_quad_horizon_sweep(quad_engine, qoracle, N):
+    """Every horizon of the quadrotor at the shipped problem, on the kernel the handle picks by default."""
+    cfg = default_quad_config(N=N, t_horizon=0.1 * N)
+    s = random_quad_scenarios(B, cfg, seed=900 + N)
+    eng = quad_engine(cfg)
+    g = eng.solve_numpy(s["x0"], s["yref"], s["yref_e"], s["xbar"], s["ubar"])
+    eng.close()
+    o = qoracle.solve_batch(cfg, s["x0"], s["yref"], s["yref_e"], s["xbar"], s["ubar"], nthreads=16)
+    _assert_quad_parity(g, o, cfg, s)
+
+
+def _condense(cfg, x0, yref, yref_e, xbar, ubar, phi, A, Bm):
+    """Condensed QP in the input steps du (H, g) of the linearisation (phi, A, B) at (xbar, ubar): the matrix form of
+    test_quad_oracle.py:_numpy_condense, fed with the device's shooting instead of the oracle's."""
+    N, n = cfg.N, cfg.N * QNU
+    Qd = cfg.Ts * np.array(cfg.W[:QNX]); Rd = cfg.Ts * np.array(cfg.W[QNX:]); Qe = np.array(cfg.We[:])
+    G = np.zeros((QNX, n)); xh = x0 - xbar[0]
+    H = np.kron(np.eye(N), np.diag(Rd)); g = np.tile(Rd, N) * (ubar - yref[:, QNX:]).reshape(-1)
+    for k in range(N):
+        G = A[k] @ G; G[:, k * QNU:(k + 1) * QNU] = Bm[k]
+        xh = A[k] @ xh + (phi[k] - xbar[k + 1])
+        Q, ref = (Qd, yref[k + 1, :QNX]) if k + 1 < N else (Qe, yref_e)
+        H += G.T @ (Q[:, None] * G); g += G.T @ (Q * (xbar[k + 1] + xh - ref))
+    return H, g
+
+
+@pytest.mark.parametrize("N,d", [(10, 0), (20, 1)])
+def test_device_step_is_the_box_qp_minimiser(quad_engine, N, d):
+    """Tight stop levels on a random problem description: the device's du against the exact minimiser of the box QP condensed in numpy
+    from the device's own shooting.  The active set read off du (within 1e-6 of a bound, gradient pushing into it) fixes those inputs
+    at their bounds; the minimiser on that face solves H_FF du_F = -(g_F + H_FA du_A).  It is THE minimiser (H is positive definite)
+    when it is feasible and the gradient H du + g there is >= 0 at lower bounds and <= 0 at upper bounds.  The device's du must be
+    within 1e-5 of it and its objective within 1e-11 relative: the bounds of test_quad_oracle.py:test_condensed_qp_and_its_minimiser
+    (flat directions, cond(H) 2e5 .. 3e7 here; the oracle's du on these batches: 4.5e-7 / 2.0e-7)."""
+    import torch
+    cfg = tight_quad_ipm(random_quad_problem(np.random.default_rng([2027, N, d]), N, plus=d == 1))
+    s = random_quad_scenarios(32, cfg, seed=40 + N)
+    eng = quad_engine(cfg)
+    dv = lambda a: torch.as_tensor(np.ascontiguousarray(a), device="cuda")
+    phi, A, Bm = eng.shoot(dv(s["xbar"]), dv(s["ubar"]))
+    torch.cuda.synchronize()
+    phi, A, Bm = phi.cpu().numpy(), A.cpu().numpy(), Bm.cpu().numpy()
+    x, u, cost, st, it = eng.solve_numpy(s["x0"], s["yref"], s["yref_e"], s["xbar"], s["ubar"])
+    eng.close()
+    assert (st == 0).all()
+    nact, worst = 0, 0.0
+    for b in range(32):
+        H, g = _condense(cfg, s["x0"][b], s["yref"][b], s["yref_e"][b], s["xbar"][b], s["ubar"][b], phi[b], A[b], Bm[b])
+        np.linalg.cholesky(H)                                     # positive definite
+        du = (u[b] - s["ubar"][b]).reshape(-1)
+        lo = np.tile(np.array(cfg.lbu[:]), N) - s["ubar"][b].reshape(-1); hi = np.tile(np.array(cfg.ubu[:]), N) - s["ubar"][b].reshape(-1)
+        assert (du >= lo - 1e-9).all() and (du <= hi + 1e-9).all(), b
+        g0 = H @ du + g
+        atl, atu = (du - lo <= 1e-6) & (g0 > 0), (hi - du <= 1e-6) & (g0 < 0)
+        fr = ~atl & ~atu
+        star = np.where(atl, lo, np.where(atu, hi, 0.0))
+        star[fr] = np.linalg.solve(H[np.ix_(fr, fr)], -(g[fr] + H[np.ix_(fr, ~fr)] @ star[~fr]))
+        grad = H @ star + g
+        scale = np.abs(g).max()
+        assert (star >= lo - 1e-12).all() and (star <= hi + 1e-12).all(), b
+        assert (grad[atl] >= -1e-9 * scale).all() and (grad[atu] <= 1e-9 * scale).all(), b
+        f = lambda v: 0.5 * v @ H @ v + g @ v
+        assert np.abs(du - star).max() <= 1e-5 and f(du) - f(star) <= 1e-11 * abs(f(star)), (b, np.abs(du - star).max(), f(du) - f(star))
+        worst = max(worst, np.abs(du - star).max())
+        nact += int(atl.sum() + atu.sum())
+    print("PDQ box-QP minimiser N=%d: max|du - du*| %.1e (bound 1e-05), %d active bounds" % (N, worst, nact))
+    assert nact > 20                                              # the batch really has active input bounds
