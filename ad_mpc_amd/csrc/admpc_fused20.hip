@@ -10,11 +10,13 @@
 //              the Jacobian entries of the four RK stages in LDS; A2: the same lanes integrate their 2-3 sensitivity columns
 //              from the tables -- the split keeps the phase inside the 256-register budget of two waves per SIMD)
 //   C  H2-H4  Gauss-Newton cost, bounds, full condensing                ad_3d_optimizer.py:146-199; acados_solver_sim_car.c:145
-//   D  H5     unconstrained trial, Mehrotra predictor-corrector on the dense 40-input QP (reference: HPIPM, :688-692)
+//   D  H5     unconstrained trial, Mehrotra predictor-corrector on the dense 40-input QP (reference: HPIPM, :688-692);
+//             the 40 x 40 LDL' and its solve are dense40.h's dense40_factorise / dense40_solve (shared with admpc_quad.hip)
 //   E  H6     state expansion, full step, cost, status                  acados_solver_sim_car.c:647-648,677
 // The phase bodies descend from the four-kernel pipeline of rounds 1-2 (kernels A, C, D, E; C, D, E removed, last
 // present at commit a808f29); what changed is where the data lives and that no instance waits for a kernel boundary: the slowest instance
-// of a batch starts at once instead of after everybody's linearisation and condensing.
+// of a batch starts at once instead of after everybody's linearisation and condensing.  What this kernel shares with the segmented
+// kernel (admpc_seg.hip) -- dimensions, lane / config laundering, staging, slot fetch, the timers' clocks -- is cond_common.h.
 //
 // Alternatives that were built, measured and removed (compile-time switches, last present at commit a808f29):
 //   - H = sum_k Gamma_k' Q Gamma_k on the vector pipe (v_fmac_f64_dpp rows) instead of MFMA tiles: 13.4 against 10.1 us per instance
@@ -45,26 +47,20 @@
 #include <math.h>
 #include "../../include/admpc.h"
 
-#define NX ADMPC_NX
-#define NU ADMPC_NU
-#define NY ADMPC_NY
-#define WAVE 64
-#define IPM_FLOOR 1e-40
-#define GTS 42           // values per stage of the packed linearisation (see kernel A in admpc_kernels.hip)
-
 namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
+
+#include "cond_common.h"      // dimensions, model_dev.h, dense40.h, LAUNDER_LANE / LAUNDER_CFG, staging, slot fetch
 
 // ---- optional per-phase wave-time accounting (build with -DADMPC_PHASE_TIMERS: `make timers`): s_memtime ticks (100 MHz) summed
 //      over all waves: 0 ticket draw, 1 A1 (state RK4 + model), 2 A2 (sensitivity columns), 3 C (condensing), 4 D trial,
 //      5 D interior-point iterations, 6 E (expansion + outputs); [8] wave-time from kernel start to the wave's exit
 #if defined(ADMPC_PHASE_TIMERS) || defined(ADMPC_F20_TRACE)
 __device__ unsigned long long g_f20_trace[4 * 8192];      // per instance (first 8192): start, end (s_memrealtime, 100 MHz), block, IPM start
-__device__ __forceinline__ unsigned long long f20_real() { unsigned long long t; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)); return t; }
-#define F20_TRACE_BEGIN() const unsigned long long tr_t0 = f20_real(); unsigned long long tr_t1 = 0
-#define F20_TRACE_MID() tr_t1 = f20_real()
-#define F20_TRACE_END(inst) do { if (threadIdx.x == 0 && (inst) < 8192) { g_f20_trace[4 * (inst)] = tr_t0; g_f20_trace[4 * (inst) + 1] = f20_real(); g_f20_trace[4 * (inst) + 2] = blockIdx.x; g_f20_trace[4 * (inst) + 3] = tr_t1; } } while (0)
+#define F20_TRACE_BEGIN() const unsigned long long tr_t0 = clock_real(); unsigned long long tr_t1 = 0
+#define F20_TRACE_MID() tr_t1 = clock_real()
+#define F20_TRACE_END(inst) do { if (threadIdx.x == 0 && (inst) < 8192) { g_f20_trace[4 * (inst)] = tr_t0; g_f20_trace[4 * (inst) + 1] = clock_real(); g_f20_trace[4 * (inst) + 2] = blockIdx.x; g_f20_trace[4 * (inst) + 3] = tr_t1; } } while (0)
 #else
 #define F20_TRACE_BEGIN() do { } while (0)
 #define F20_TRACE_MID() do { } while (0)
@@ -72,10 +68,9 @@ __device__ __forceinline__ unsigned long long f20_real() { unsigned long long t;
 #endif
 #ifdef ADMPC_PHASE_TIMERS
 __device__ unsigned long long g_f20_ticks[16];
-__device__ __forceinline__ unsigned long long f20_now() { unsigned long long t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)); return t; }
-#define F20_DECL() unsigned long long ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long ph_t0 = f20_now(); unsigned long long ph_last = ph_t0
-#define F20_STAMP(k) do { const unsigned long long t_ = f20_now(); ph_acc[k] += t_ - ph_last; ph_last = t_; } while (0)
-#define F20_FLUSH() do { if (threadIdx.x == 0) { for (int q_ = 0; q_ < 8; ++q_) atomicAdd(&g_f20_ticks[q_], ph_acc[q_]); atomicAdd(&g_f20_ticks[8], f20_now() - ph_t0); atomicMax(&g_f20_ticks[9], f20_now() - ph_t0); } } while (0)
+#define F20_DECL() unsigned long long ph_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long ph_t0 = clock_ticks(); unsigned long long ph_last = ph_t0
+#define F20_STAMP(k) do { const unsigned long long t_ = clock_ticks(); ph_acc[k] += t_ - ph_last; ph_last = t_; } while (0)
+#define F20_FLUSH() do { if (threadIdx.x == 0) { for (int q_ = 0; q_ < 8; ++q_) atomicAdd(&g_f20_ticks[q_], ph_acc[q_]); atomicAdd(&g_f20_ticks[8], clock_ticks() - ph_t0); atomicMax(&g_f20_ticks[9], clock_ticks() - ph_t0); } } while (0)
 #elif defined(F20_MARKS)      // listing with phase markers for scripts/asm_phase_stats.py (hipcc -S -DF20_MARKS): the code after stamp k is phase k + 1
 #define F20_DECL() do { } while (0)
 #define F20_STAMP(k) asm volatile("; MARK_after" #k)
@@ -85,10 +80,6 @@ __device__ __forceinline__ unsigned long long f20_now() { unsigned long long t; 
 #define F20_STAMP(k) do { } while (0)
 #define F20_FLUSH() do { } while (0)
 #endif
-
-#include "model_dev.h"
-#include "dense40.h"
-#include "cond_common.h"
 
 // LDS map of one instance (doubles), 19.1 KB, eight instances per CU (two waves per SIMD):
 //   GT [0, 840)  packed linearisation, written at the end of phase A, read by phases C and E
@@ -169,76 +160,15 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
 #define PK_DDL  park[3 * 64 + lane]
 #define PK_DDU  park[4 * 64 + lane]
 
-    // Every phase derives its per-lane quantities from a freshly laundered lane id and reads its constants through a freshly
-    // laundered config pointer: what is loop-invariant across instances must be recomputed in place -- hoisted out of the persistent
-    // loop it was parked in scratch (257 SGPR lanes and 89 VGPRs in the first build) and reloaded inside the stage loops.
-// lane id from v_mbcnt (a workgroup is one wave), never from threadIdx.x: v0 would stay live (and be spilled) across the whole kernel
-#define LAUNDER_LANE(v) int v = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); asm volatile("" : "+v"(v))
-// an opaque zero offset, not an opaque pointer: the compiler keeps knowing that the config is uniform, read-only global memory (s_load)
-#define LAUNDER_CFG(c) int c##_z = 0; asm volatile("" : "+s"(c##_z)); const AdmpcConfig* __restrict__ c = cfg + c##_z
-
-    // Factorisation of the Newton matrix M = H + diag(dbar) + (s_odd on the odd columns of the u1 rows) into L D L' (LDS: Lp, invd);
-    // see dense40.h for the look-ahead scheme.
+    // Factorisation of the Newton matrix M = H + diag(dbar) + (s_odd on the odd columns of the u1 rows) into L D L' (LDS: Lp, invd) and
+    // the solve M x = y through the factor: dense40.h, the functions the quadrotor's kernel calls.
+    const Dense40Lds W{Hp, Lp, cb, invd};
     auto factorise = [&](const double dbar_, const double sodd_, const int lz_) __attribute__((always_inline)) {
-        const int trz_ = lz_ * (lz_ + 1) / 2;
-        const bool uz_ = lz_ < n;
-        double a[n];
-        newton_row_40(a, lds_byte_addr(Hp + (uz_ ? trz_ : 0)), dbar_, sodd_);
-        // H's rows are in registers: its buffer becomes the factor's.  Diagonal slots of the packed factor: 0.0 (the factorisation stores the
-        // strictly-lower part only; the substitution assembly lets the source lane of a step take part with this multiplier)
-        if (uz_) Lp[trz_ + lz_] = 0.0;
-        const unsigned lrow = lds_byte_addr(Lp + (uz_ ? trz_ : 0));
-        const unsigned pub_wr = lds_byte_addr(cb + lz_), pub_rd = lds_byte_addr(cb + (lz_ & 15));
-        auto chain = [&](auto jc, double& nln) __attribute__((always_inline)) {
-            constexpr int j = decltype(jc)::value;
-            const double dj = rdlane(a[j], j);
-            const double dinv = rcp_nr(dj);                             // 1 / D_jj
-            const double lu = a[j] * dinv;                              // L_ij for the lanes below the diagonal
-            invd[j] = dinv;                                             // uniform value, same address
-            if constexpr (j + 1 < n) {
-                asm volatile("s_bfm_b64 exec, %2, %3\n\tds_write_b64 %0, %1 offset:%4\n\ts_mov_b64 exec, -1"
-                             : : "v"(lrow), "v"(lu), "n"(n - 1 - j), "n"(j + 1), "n"(8 * j) : "memory");
-                nln = -lu;
-            }
-        };
-        double Rb[2][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, nlb[2] = {0.0, 0.0};
-        cb[lz_] = a[0];
-#pragma unroll
-        for (int m = 0; m < 3; ++m) Rb[0][m] = cb[16 * m + (lz_ & 15)];
-        chain(std::integral_constant<int, 0>{}, nlb[0]);
-        static_for<0, n - 1>([&](auto jc) __attribute__((always_inline)) {
-            constexpr int j = decltype(jc)::value;
-            constexpr bool own = (j + 1) / 16 == 2;                     // column j: DPP sources are the lanes' own registers (VALU-written)
-            constexpr bool pub = j + 2 < n && (j + 2) / 16 < 2;         // column j + 1 still needs its blocks in other rows
-            double (&R)[3] = Rb[j & 1];
-            double (&Rn)[3] = Rb[(j + 1) & 1];
-            double& nl = nlb[j & 1];
-            double& nln = nlb[(j + 1) & 1];
-            col_head<j + 1, (j + 2) / 16, pub, own>(a[j + 1], R, nl, Rn, pub_wr, pub_rd);
-            if constexpr (!pub) Rn[2] = a[j + 1];                       // only lanes 32..39 are still involved: own row
-            chain(std::integral_constant<int, j + 1>{}, nln);
-            constexpr int j4 = ((j + 2 + 3) / 4) * 4 < n ? ((j + 2 + 3) / 4) * 4 : n;        // first 4-aligned column >= j + 2
-            static_for<j + 2, j4>([&](auto c) __attribute__((always_inline)) {
-                constexpr int jj = decltype(c)::value;
-                if constexpr (own) fmac_rowbc<jj % 16>(a[jj], R[jj / 16], nl);
-                else fmac_rowbc_ld<jj % 16>(a[jj], R[jj / 16], nl);
-            });
-            static_for<j4 / 4, n / 4>([&](auto c) __attribute__((always_inline)) {
-                constexpr int jj = 4 * decltype(c)::value;
-                if constexpr (own) fmac_rowbc4<jj % 16>(a[jj], a[jj + 1], a[jj + 2], a[jj + 3], R[jj / 16], nl);
-                else fmac_rowbc4_ld<jj % 16>(a[jj], a[jj + 1], a[jj + 2], a[jj + 3], R[jj / 16], nl);
-            });
+        dense40_factorise(W, lz_, dbar_, sodd_, lz_, [&](double (&)[n]) __attribute__((always_inline)) {
+            // H's rows are in registers: its buffer becomes the factor's.  Diagonal slots of the packed factor: 0.0 (the factorisation stores the
+            // strictly-lower part only; the substitution assembly lets the source lane of a step take part with this multiplier)
+            if (lz_ < n) Lp[lz_ * (lz_ + 1) / 2 + lz_] = 0.0;
         });
-        WSYNC();
-    };
-    // M x = y through the factor: L z = y, z *= D^-1, L' x = z (assembly, see gen_subst_asm.py)
-    auto ldl_solve = [&](double y, const int lz_) __attribute__((always_inline)) -> double {
-        const bool uz_ = lz_ < n;
-        const unsigned pub = lds_byte_addr(cb + (lz_ & 15));                              // cb is free while a system is being solved
-        fwd_subst_40(y, lds_byte_addr(Lp + (uz_ ? lz_ * (lz_ + 1) / 2 : 0)), pub);      // idle lanes never take part (EXEC masks)
-        double x = y * invd[uz_ ? lz_ : 0];
-        bwd_subst_40(x, lds_byte_addr(Lp + (uz_ ? lz_ : 0)), pub);
-        return x;
     };
 
     // ---------------- persistent loop: first ticket = block index, later ones from one global counter ----------------
@@ -601,7 +531,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             if (try_unc) {
                 int lt = lane; asm volatile("" : "+v"(lt));
                 factorise(uact ? Rj : 1.0, 0.0, lt);
-                const double xt = ldl_solve(uact ? -g0 : 0.0, lt);
+                const double xt = dense40_solve(W, uact ? -g0 : 0.0, lt);
                 const double duc = uact ? xt : 0.0;
                 cb[lane] = duc;
                 WSYNC();
@@ -751,7 +681,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     sb[lane] = rdlane(epref, 63) - epref;
                     WSYNC();
                     double y = uact ? -(ru + etal + etau + (ji ? h * sb[ki] : 0.0)) : 0.0;
-                    const double x = ldl_solve(y, lz);
+                    const double x = dense40_solve(W, y, lz);
                     if (pass == 1) slot_fetch<FusedLds::NTRI, slot_aux>(Hp, slot, lz);     // the factor is dead: next iteration's H under the step-length work
                     ddu = uact ? x : 0.0;
                     cb[lane] = ddu;

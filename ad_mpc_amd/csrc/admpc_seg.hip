@@ -18,27 +18,19 @@
 // executable statement of the algebra is tests/seg_spec.py, checked against the oracle on the CPU (tests/test_seg_spec.py).
 //
 // Nothing but the algorithmic inputs and outputs crosses HBM (no workspace): the linearisation is recomputed in front of the expansion.
+// Dimensions, lane / config laundering (LAUNDER_LANE, LAUNDER_CFG), staging and the slot fetch come from cond_common.h, shared with kernel F.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include <stdint.h>
 #include <math.h>
 #include "../../include/admpc.h"
 
-#define NX ADMPC_NX
-#define NU ADMPC_NU
-#define NY ADMPC_NY
-#define WAVE 64
-#define IPM_FLOOR 1e-40
-#define GTS 42           // values per stage of the packed linearisation (see kernel A in admpc_kernels.hip)
-
 extern "C" size_t admpc_fused20_state_ints(int cap);      // admpc_fused20.hip: ints of one scheduler state
 namespace {
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-#include "model_dev.h"
-#include "dense40.h"
-#include "cond_common.h"
+#include "cond_common.h"      // dimensions, model_dev.h, dense40.h, LAUNDER_LANE / LAUNDER_CFG, staging, slot fetch
 #include "work_order.h"
 #include "seg_cut.h"          // bordered factorisation, Schur blocks, the operators of a single cut: shared with the quadrotor's segmented kernel
 
@@ -61,11 +53,9 @@ __device__ __forceinline__ double uni(double v) {
 //      13 (S = 2) wait for the Schur blocks + the cut's solution operators (wave 0)
 #ifdef ADMPC_PHASE_TIMERS
 __device__ unsigned long long g_seg_trace[4 * 16384];     // per instance (first 16384): start, end (s_memrealtime, 100 MHz), workgroup, interior-point start
-__device__ __forceinline__ unsigned long long seg_real() { unsigned long long t; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)); return t; }
 __device__ unsigned long long g_seg_ticks[16];
-__device__ __forceinline__ unsigned long long seg_now() { unsigned long long t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)); return t; }
-#define SEG_DECL() unsigned long long ph_acc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long ph_last = seg_now()
-#define SEG_STAMP(k) do { const unsigned long long t_ = seg_now(); ph_acc[k] += t_ - ph_last; ph_last = t_; } while (0)
+#define SEG_DECL() unsigned long long ph_acc[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long ph_last = clock_ticks()
+#define SEG_STAMP(k) do { const unsigned long long t_ = clock_ticks(); ph_acc[k] += t_ - ph_last; ph_last = t_; } while (0)
 #define SEG_FLUSH() do { if ((threadIdx.x & 63) == 0) { for (int q_ = 0; q_ < 14; ++q_) atomicAdd(&g_seg_ticks[q_], ph_acc[q_]); } } while (0)
 #elif defined(SEG_MARKS)      // listing with phase markers (hipcc -S -DSEG_MARKS): the code after stamp k belongs to the next phase
 #define SEG_DECL() do { } while (0)
@@ -326,8 +316,6 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
 #define PK_G0   park[2 * 64 + lane]
 #define PK_DDL  park[3 * 64 + (lane & 31)]           // the steering box: stages = lanes < 20 (the two bounds share one row)
 #define PK_DDU  park[3 * 64 + 32 + (lane & 31)]
-#define LAUNDER_LANE(v) int v = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); asm volatile("" : "+v"(v))
-#define LAUNDER_CFG(c) int c##_z = 0; asm volatile("" : "+s"(c##_z)); const AdmpcConfig* __restrict__ c = cfg + c##_z
     // partial reductions of the S waves: slot `ph` of every segment, combined in segment order by every wave (same bits everywhere)
 #define RED(s_, ph_, i_) ifb[(s_) * LD::IFS + LD::IF_RED + (ph_) * 8 + (i_)]
 
@@ -420,7 +408,7 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
 
         SEG_STAMP(0);
 #ifdef ADMPC_PHASE_TIMERS
-        const unsigned long long tr_t0 = seg_real(); unsigned long long tr_t1 = 0;
+        const unsigned long long tr_t0 = clock_real(); unsigned long long tr_t1 = 0;
 #endif
         double du = 0.0;
         bool failed = false;
@@ -435,7 +423,7 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
             LAUNDER_LANE(lane); LAUNDER_CFG(cf);
             const double h = cf->Ts;
             const int tsk = lane < 3 * N ? lane : 3 * N - 1;
-            const int k = (int)(((unsigned)tsk * 21846u) >> 16), g = tsk - 3 * k;
+            const int k = (int)(((unsigned)tsk * 21846u) >> 16), g = tsk - 3 * k;      // tsk / 3, tsk % 3 without a narrow udivrem
             const bool live = lane < 3 * N;
             {
                 const double pin = pg[inst];
@@ -850,7 +838,7 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
             }
             SEG_STAMP(3);
 #ifdef ADMPC_PHASE_TIMERS
-            tr_t1 = seg_real();
+            tr_t1 = clock_real();
 #endif
             auto cold_start = [&]() __attribute__((always_inline)) {
                 const double dlc = PK_DL, duc2 = PK_DUU;
@@ -1215,7 +1203,7 @@ __global__ __launch_bounds__(WAVE * S, 2) void admpc_seg_kernel(const AdmpcConfi
         __builtin_amdgcn_s_setprio(0);
         SEG_STAMP(12);
 #ifdef ADMPC_PHASE_TIMERS
-        if (threadIdx.x == 0 && inst < 16384) { g_seg_trace[4 * inst] = tr_t0; g_seg_trace[4 * inst + 1] = seg_real(); g_seg_trace[4 * inst + 2] = blockIdx.x; g_seg_trace[4 * inst + 3] = tr_t1; }
+        if (threadIdx.x == 0 && inst < 16384) { g_seg_trace[4 * inst] = tr_t0; g_seg_trace[4 * inst + 1] = clock_real(); g_seg_trace[4 * inst + 2] = blockIdx.x; g_seg_trace[4 * inst + 3] = tr_t1; }
 #endif
     }
     SEG_FLUSH();

@@ -1,7 +1,33 @@
-// cond_common.h -- helpers shared by the condensed kernels (admpc_fused20.hip, admpc_seg.hip): lane-scan primitives, HBM <-> LDS
-// staging of one instance and the LDS-DMA fetch of a wave's H from its slot.  Include inside the translation unit's anonymous namespace
-// after dense40.h (dpp_mov, static_for, WAVE) and after NX is defined.
+// cond_common.h -- what the condensed car kernels (kernel F in admpc_fused20.hip, kernel S in admpc_seg.hip) share: the problem's
+// dimensions, the model and the 40 x 40 linear algebra (model_dev.h, dense40.h), the laundering of lane id and config pointer,
+// lane-scan primitives, HBM <-> LDS staging of one instance and the LDS-DMA fetch of a wave's H from its slot.
+// Include inside the translation unit's anonymous namespace, after include/admpc.h.
 #pragma once
+
+#define NX ADMPC_NX
+#define NU ADMPC_NU
+#define NY ADMPC_NY
+#define WAVE 64
+#define IPM_FLOOR 1e-40
+#define GTS 42           // values per stage of the packed linearisation (see kernel A in admpc_kernels.hip)
+
+#include "model_dev.h"
+#include "dense40.h"
+
+// Every phase of a persistent kernel derives its per-lane quantities from a freshly laundered lane id and reads its constants through a
+// freshly laundered config pointer: what is loop-invariant across instances must be recomputed in place -- hoisted out of the persistent
+// loop it was parked in scratch (257 SGPR lanes and 89 VGPRs in the first build of kernel F) and reloaded inside the stage loops.
+// lane id from v_mbcnt (lane within the wave), never from threadIdx.x: v0 would stay live (and be spilled) across the whole kernel
+#define LAUNDER_LANE(v) int v = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); asm volatile("" : "+v"(v))
+// an opaque zero offset, not an opaque pointer: the compiler keeps knowing that the config is uniform, read-only global memory (s_load);
+// reads the kernel's parameter `cfg`
+#define LAUNDER_CFG(c) int c##_z = 0; asm volatile("" : "+s"(c##_z)); const AdmpcConfig* __restrict__ c = cfg + c##_z
+
+// the two clocks of the optional phase timers / instance traces (100 MHz): shader clock, constant-rate real-time clock
+#if defined(ADMPC_PHASE_TIMERS) || defined(ADMPC_F20_TRACE)
+__device__ __forceinline__ unsigned long long clock_ticks() { unsigned long long t; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)); return t; }
+__device__ __forceinline__ unsigned long long clock_real() { unsigned long long t; asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)); return t; }
+#endif
 
 // x / 7 for 0 <= x < 13107 as a 32-bit multiply-shift: hipcc 7.2 narrows small non-negative ints to 16 bits and its backend
 // cannot select the 16-bit udivrem by 7 at -Oz ("Cannot select: i16 udivrem"); there is no `/ 7` or `% 7` on the device.

@@ -175,10 +175,9 @@ template <int NR, int BS = 40>
 __device__ __forceinline__ unsigned dense40b_row_addr(double* tri_, double* brd, const int lz_) {
     return lds_byte_addr(lz_ < 40 ? tri_ + lz_ * (lz_ + 1) / 2 : (lz_ < NR ? brd + (lz_ - 40) * BS : tri_));
 }
-struct Dense40bNoFix { __device__ __forceinline__ void operator()(double (&)[40]) const {} };
 // fix(a): hook behind the row build (the rows are in registers, H's buffer is free): the car's kernel zeroes the factor's diagonal slots there
 // (H and L share one buffer) and adds the steering-box barrier to the z6 border row; s_odd: added to the odd columns of this lane's row
-template <int NR, int BS = 40, class Fix = Dense40bNoFix>
+template <int NR, int BS = 40, class Fix = Dense40NoFix>
 __device__ __forceinline__ void dense40b_factorise(const Dense40bLds& W, const double dbar_, const int lz_, const double sodd_ = 0.0, const Fix& fix = Fix())
 {
     constexpr int n = 40;
