@@ -273,40 +273,96 @@ __global__ __launch_bounds__(64) void admpc_quad_shoot_kernel(const Cfg* __restr
     }
 }
 
-// FAST (N nu = 40, the shipped horizon): the Newton systems go through dense40.h -- register-resident LDL' with DPP rank-1 updates and
-// the generated substitution assembly instead of the LDS-resident Cholesky below (3.9x less time per interior-point iteration).
-template <bool FAST>
-__global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restrict__ c, int B, const double* __restrict__ x0g, const double* __restrict__ yrefg,
+// ---- the dense solve kernel is one text; a path says how the block of an instance exchanges values, and nothing else:
+//   Dense40Path  64 threads   N nu = 40, the shipped horizon: the Newton systems go through dense40.h -- register-resident LDL' with DPP rank-1
+//                             updates and the generated substitution assembly (3.9x less time per interior-point iteration than the next)
+//   GenericPath  64 threads   every other horizon up to 16: Cholesky in LDS, row i on lane i, exchanges inside the wave
+//   WidePath    128 threads   horizons beyond 16 (N nu up to 96 inputs; the reference class defaults to n_nodes = 20, quad_3d_optimizer.py:29):
+//                             the same Cholesky with one THREAD per input; what one wave exchanges by v_readlane and DPP scans goes through
+//                             LDS slots and workgroup barriers -- about a thousand barriers per interior-point iteration: a compatibility path
+// All three keep the oracle's summation order in the factorisation and the substitutions.
+template <bool FAST_> struct WavePath {
+    static constexpr int NT = 64;
+    static constexpr bool FAST = FAST_;
+    const int tid;
+    __device__ __forceinline__ WavePath(double*, int, int tid_) : tid(tid_) {}
+    __device__ __forceinline__ double sum(double v) const { return wave_sum(v); }
+    __device__ __forceinline__ double max(double v) const { return wave_max(v); }
+    __device__ __forceinline__ double min(double v) const { return wave_min(v); }
+    __device__ __forceinline__ bool any(bool b) const { return __any(b) != 0; }
+    __device__ __forceinline__ double get(double v, int j) const { return bcast(v, j); }                 // v of thread j
+    __device__ __forceinline__ void order() const { }                                                    // LDS operations of one wave execute in order
+    // entry e of A_k for the propagation: a scalar operand (v_readlane) out of the three registers Ar the kernel has loaded
+    __device__ __forceinline__ double a(const double*, int, const double (&Ar)[3], int e) const { return bcast(Ar[e / 64], e % 64); }
+    // reciprocal pivots of the Cholesky factor: 1 / L_jj in a register of lane j
+    __device__ __forceinline__ void set_pivot(double& myinv, int j, double inv) const { if (tid == j) myinv = inv; }
+    __device__ __forceinline__ double pivot(double myinv, int j) const { return bcast(myinv, j); }
+    // next instance of this wave: from the work counter (many rounds) or by a static stride
+    __device__ __forceinline__ int next(int inst, int* ticket) const {
+        if (!ticket) return inst + (int)gridDim.x;
+        int tk = 0;
+        if (tid == 0) tk = atomicAdd(ticket, 1);
+        return (int)gridDim.x + __builtin_amdgcn_readfirstlane(tk);
+    }
+};
+typedef WavePath<true> Dense40Path;
+typedef WavePath<false> GenericPath;
+struct WidePath {
+    static constexpr int NT = 128;
+    static constexpr bool FAST = false;
+    const int tid;
+    double* const invs; double* const slot; double* const red;      // behind the Lds regions: [n] reciprocal pivots | [2] slot of get(), alternating | [2] the waves' partial results
+    __device__ __forceinline__ WidePath(double* p, int n, int tid_) : tid(tid_), invs(p), slot(p + n), red(p + n + 2) {}
+    template <class Op> __device__ __forceinline__ double reduce(double v) const {                        // wave 0's partial result first
+        v = wave_reduce<Op>(v); if ((tid & 63) == 0) red[tid >> 6] = v; __syncthreads(); const double r = Op::f(red[0], red[1]); __syncthreads(); return r;
+    }
+    __device__ __forceinline__ double sum(double v) const { return reduce<OpSum>(v); }
+    __device__ __forceinline__ double max(double v) const { return reduce<OpMaxNan>(v); }
+    __device__ __forceinline__ double min(double v) const { return reduce<OpMin>(v); }
+    __device__ __forceinline__ bool any(bool b) const { return max(b ? 1.0 : 0.0) > 0.0; }
+    // uniform: every thread reads the same slot.  Two get() in a row alternate between the slots (j and j +- 1); order() between any other two
+    __device__ __forceinline__ double get(double v, int j) const { if (tid == j) slot[j & 1] = v; __syncthreads(); return slot[j & 1]; }
+    __device__ __forceinline__ void order() const { __syncthreads(); }
+    __device__ __forceinline__ double a(const double* A, int k, const double (&)[3], int e) const { return A[k * QX * QX + e]; }
+    __device__ __forceinline__ void set_pivot(double&, int j, double inv) const { if (tid == j) invs[j] = inv; }
+    __device__ __forceinline__ double pivot(double, int j) const { return invs[j]; }
+    __device__ __forceinline__ int next(int inst, int* ticket) const {                                    // block-uniform: the draw of thread 0 through an LDS slot
+        if (!ticket) return inst + (int)gridDim.x;
+        if (tid == 0) red[0] = (double)atomicAdd(ticket, 1);
+        __syncthreads();
+        const int nx = (int)gridDim.x + (int)red[0];
+        __syncthreads();
+        return nx;
+    }
+};
+
+template <class P>
+__global__ __launch_bounds__(P::NT) void admpc_quad_solve_kernel(const Cfg* __restrict__ c, int B, const double* __restrict__ x0g, const double* __restrict__ yrefg,
                                                              const double* __restrict__ yrefeg, double* __restrict__ xbarg, double* __restrict__ ubarg,
                                                              double* __restrict__ costg, int32_t* __restrict__ statusg, int32_t* __restrict__ itersg,
                                                              int* __restrict__ ticket, const double* __restrict__ gpsg, const int32_t* __restrict__ routeg, int which)
 {
     extern __shared__ double lds_raw[];
-    const int N = c->N, n = N * QU, lane = threadIdx.x;
+    const int N = c->N, n = N * QU, tid = threadIdx.x;
     Lds L(lds_raw, N);
-    const bool act = lane < n;
-    const int li = act ? lane : 0, ji = li / QU, mi = li - ji * QU;
+    const P X(lds_raw + quad_lds_doubles(N), n, tid);
+    double* const dus = P::NT > 64 ? L.gam + QX : L.vec;            // du of all inputs: vec holds one wave's; a wider block parks them behind the dx slot of gam (free after condensing)
+    const bool act = tid < n;
+    const int li = act ? tid : 0, ji = li / QU, mi = li - ji * QU;
     const double Ts = c->Ts;
     // problem constants in registers / LDS: a read of *c inside a stage loop is a scalar load from global memory
-    if (lane < QX) { L.wts[lane] = Ts * c->W[lane]; L.wts[QX + lane] = c->We[lane]; }
+    if (tid < QX) { L.wts[tid] = Ts * c->W[tid]; L.wts[QX + tid] = c->We[tid]; }
     const double Rw = Ts * c->W[QX + mi], lbm = c->lbu[mi], ubm = c->ubu[mi];
     const double thr0 = c->ipm_thr0, mu0 = c->ipm_mu0, tolc = c->ipm_tol_comp, tolr = c->ipm_tol_res;
     const int itmax = c->ipm_iter_max;
     const Dense40Lds W{L.H, L.M, L.gam, L.gam + 64};                // FAST: factor in the M region, exchange buffer / pivots in gam (free after condensing)
-    if (FAST) { if (act) L.M[tri(li, li)] = 0.0; __syncthreads(); }     // diagonal slots of the packed unit factor: 0.0, never overwritten
+    if (P::FAST) { if (act) L.M[tri(li, li)] = 0.0; __syncthreads(); }     // diagonal slots of the packed unit factor: 0.0, never overwritten
     QDECL();
     // instances need 5 .. 18 interior-point iterations: with many rounds per wave the instances are drawn from a work counter (zeroed by
     // the host before the launch; + 5 % at B = 16384), with few a static stride is cheaper (no memset node, no atomics; + 5 % at B = 4096)
-    // next instance of this wave: from the work counter (many rounds) or by a static stride
-    auto next_inst = [&](int inst) -> int {
-        if (!ticket) return inst + (int)gridDim.x;
-        int tk = 0;
-        if (lane == 0) tk = atomicAdd(ticket, 1);
-        return (int)gridDim.x + __builtin_amdgcn_readfirstlane(tk);
-    };
     for (int inst = blockIdx.x; inst < B;) {
         // routed solve (admpc_quad_solve_batch_routed): this handle carries the model of cluster `which`; the others' instances are left alone
-        if (routeg && routeg[inst] != which) { inst = next_inst(inst); continue; }
+        if (routeg && routeg[inst] != which) { inst = X.next(inst, ticket); continue; }
         double* xb = xbarg + (size_t)inst * (N + 1) * QX;
         double* ub = ubarg + (size_t)inst * N * QU;
         const double* yr = yrefg + (size_t)inst * N * QY;
@@ -314,45 +370,48 @@ __global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restr
         const double* x0 = x0g + (size_t)inst * QX;
         const double* gq = gpsg ? gpsg + (size_t)inst * QX : x0;       // GP state of the first node: run_optimization's default is the initial state
         QSTART();
-        for (int i = lane; i < (N + 1) * QX; i += 64) L.xbs[i] = xb[i];
-        for (int i = lane; i < N * QY + QX; i += 64) L.yrs[i] = i < N * QY ? yr[i] : ye[i - N * QY];
+        for (int i = tid; i < (N + 1) * QX; i += P::NT) L.xbs[i] = xb[i];
+        for (int i = tid; i < N * QY + QX; i += P::NT) L.yrs[i] = i < N * QY ? yr[i] : ye[i - N * QY];
         // ---- 1. shooting
-        shoot_instance(c, xb, ub, gq, L, lane, nullptr);
+        shoot_instance(c, xb, ub, gq, L, tid, nullptr, P::NT);
         QSTAMP(0);
         // ---- 2. condensing (oracle: condense)
-        if constexpr (!FAST) { for (int j = 0; j <= li; ++j) if (act) L.H[tri(li, j)] = 0.0; }
-        double hrow[FAST ? 40 : 1];                                  // FAST: row li of H in registers, Gamma of the other inputs through DPP broadcasts
+        if constexpr (!P::FAST) { for (int j = 0; j <= li; ++j) if (act) L.H[tri(li, j)] = 0.0; }
+        double hrow[P::FAST ? 40 : 1];                                  // FAST: row li of H in registers, Gamma of the other inputs through DPP broadcasts
 #pragma unroll
-        for (int j = 0; j < (FAST ? 40 : 1); ++j) hrow[j] = 0.0;
+        for (int j = 0; j < (P::FAST ? 40 : 1); ++j) hrow[j] = 0.0;
         double g[QX];
 #pragma unroll
         for (int i = 0; i < QX; ++i) g[i] = 0.0;
-        if (lane < QX) L.xhs[lane] = x0[lane] - xb[lane];
+        if (tid < QX) L.xhs[tid] = x0[tid] - xb[tid];
         const double ubar_i = ub[li];
         double grad = Rw * (ubar_i - yr[ji * QY + QX + mi]);
         __syncthreads();
         for (int k = 0; k < N; ++k) {
             double gn[QX];
-            const int rr = lane < QX ? lane : 0;
-            double xn = L.b[k * QX + rr];                                    // free response: row `lane` of A xh + b on lanes 0..12
+            const int rr = tid < QX ? tid : 0;
+            double xn = L.b[k * QX + rr];                                    // free response: row `tid` of A xh + b on lanes 0..12
 #pragma unroll
             for (int cc = 0; cc < QX; ++cc) xn += L.A[(k * QX + rr) * QX + cc] * L.xhs[cc];
-            // A_k is the same for every lane: its 169 entries are fetched by three coalesced loads (entry e on lane e mod 64) and handed
-            // to the FMAs as scalar operands (v_readlane), instead of 169 broadcast reads of LDS per lane
+            // one wave: A_k is the same for every lane: its 169 entries are fetched by three coalesced loads (entry e on lane e mod 64) and
+            // handed to the FMAs as scalar operands (P::a), instead of 169 broadcast reads of LDS per lane, which is what a wider block does
             double Ar[3];
+            if constexpr (P::NT == 64) {
 #pragma unroll
-            for (int m = 0; m < 3; ++m) { const int e = lane + 64 * m; Ar[m] = L.A[k * QX * QX + (e < QX * QX ? e : QX * QX - 1)]; }
+                for (int m = 0; m < 3; ++m) { const int e = tid + 64 * m; Ar[m] = L.A[k * QX * QX + (e < QX * QX ? e : QX * QX - 1)]; }
+            }
 #pragma unroll
             for (int r = 0; r < QX; ++r) {
                 double s = 0.0;
 #pragma unroll
-                for (int cc = 0; cc < QX; ++cc) s += bcast(Ar[(r * QX + cc) / 64], (r * QX + cc) % 64) * g[cc];
+                for (int cc = 0; cc < QX; ++cc) s += X.a(L.A, k, Ar, r * QX + cc) * g[cc];
                 gn[r] = ji == k ? L.B[(k * QX + r) * QU + mi] : (ji < k ? s : 0.0);
             }
             QSTAMP(8);
+            X.order();                                                       // every read of xhs above is done
 #pragma unroll
-            for (int r = 0; r < QX; ++r) { g[r] = gn[r]; if (act) L.gam[r * n + lane] = gn[r]; }
-            if (lane < QX) L.xhs[lane] = xn;                                 // (LDS operations of one wave execute in order: every read above is done)
+            for (int r = 0; r < QX; ++r) { g[r] = gn[r]; if (act) L.gam[r * n + tid] = gn[r]; }
+            if (tid < QX) L.xhs[tid] = xn;
             __syncthreads();
             QSTAMP(9);
             const double* ref = L.yrs + (k + 1) * QY;                        // stage k + 1 (yrs[N * 17 ...] = terminal reference)
@@ -364,14 +423,14 @@ __global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restr
                 wg[cc] = g[cc] * wq;
                 if (wq != 0.0) grad += wg[cc] * (L.xbs[(k + 1) * QX + cc] + L.xhs[cc] - ref[cc]);
             }
-            if constexpr (FAST) {
-                // H[li][j] += sum_cc wg[cc] Gamma_j[cc] for every j at once: Gamma_j[cc] = lane j's value, picked up inside the FMAs
+            if constexpr (P::FAST) {
+                // H[li][j] += sum_cc wg[cc] Gamma_j[cc] for every j at once: Gamma_j[cc] = tid j's value, picked up inside the FMAs
                 // (columns of inputs of later stages are zero on both sides)
                 double Rb[QX][3];                                           // all 39 loads first: one LDS round trip per stage, not one per component
 #pragma unroll
                 for (int cc = 0; cc < QX; ++cc)
 #pragma unroll
-                    for (int m = 0; m < 3; ++m) Rb[cc][m] = L.gam[cc * n + 16 * m + (lane & 15)];
+                    for (int m = 0; m < 3; ++m) Rb[cc][m] = L.gam[cc * n + 16 * m + (tid & 15)];
                 static_for<0, 10>([&](auto qq) __attribute__((always_inline)) {
                     constexpr int i2 = 4 * decltype(qq)::value;
                     if (i2 < lim) {                                         // wave-uniform: the columns of later stages' inputs are still zero
@@ -393,7 +452,7 @@ __global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restr
             __syncthreads();
             QSTAMP(10);
         }
-        if constexpr (FAST) {
+        if constexpr (P::FAST) {
             store_row_40(hrow, lds_byte_addr(L.H + (act ? tri(li, 0) : 0)));
             __syncthreads();
         }
@@ -409,21 +468,21 @@ __global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restr
         int it = 0, st = 0;
         bool cons = false;                                           // fallback mode (admpc_quad.h): no second-order term
         for (;; ++it) {
-            int lz = lane;                                           // laundered lane id (dense40.h)
+            int lz = tid;                                           // laundered tid id (dense40.h)
             asm volatile("" : "+v"(lz));
             double rs = grad - ll + lu;
-            if constexpr (FAST) {
-                const double hdu = dense40_symv(W, lane, act ? du : 0.0, lz);
+            if constexpr (P::FAST) {
+                const double hdu = dense40_symv(W, tid, act ? du : 0.0, lz);
                 rs = act ? rs + hdu : 0.0;
             } else {
-                L.vec[lane] = du;
+                dus[tid] = du;
                 __syncthreads();
-                if (act) for (int j = 0; j < n; ++j) rs += L.H[sym(li, j)] * L.vec[j];
+                if (act) for (int j = 0; j < n; ++j) rs += L.H[sym(li, j)] * dus[j];
             }
             const double rl = du - lo - tl, ru = hi - du - tu;
-            const double mu = wave_sum(act ? tl * ll + tu * lu : 0.0) / (2.0 * n);
-            const double cmax = wave_max(act ? fmax(tl * ll, tu * lu) : 0.0);
-            const double rmax = wave_max(act ? fmax(fabs(rs), fmax(fabs(rl), fabs(ru))) : 0.0);
+            const double mu = X.sum(act ? tl * ll + tu * lu : 0.0) / (2.0 * n);
+            const double cmax = X.max(act ? fmax(tl * ll, tu * lu) : 0.0);
+            const double rmax = X.max(act ? fmax(fabs(rs), fmax(fabs(rl), fabs(ru))) : 0.0);
             __syncthreads();
             if (!(mu == mu) || !(rmax == rmax)) { st = 4; break; }
             if ((cmax <= tolc && rmax <= tolr) || it >= itmax + (cons ? ADMPC_QUAD_IPM_FALLBACK_ITER : 0)) break;
@@ -437,15 +496,15 @@ __global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restr
                 continue;                                              // this pass is redone from the cold start (the count is unchanged)
             }
             const double Dl = act ? ll / tl : 0.0, Du = act ? lu / tu : 0.0;
-            if constexpr (!FAST) {
+            if constexpr (!P::FAST) {
                 if (act) { for (int j = 0; j <= li; ++j) L.M[tri(li, j)] = L.H[tri(li, j)]; L.M[tri(li, li)] += Dl + Du; }
                 __syncthreads();
             }
             QSTAMP(2);
-            // Cholesky M = L L' (lower), row i on lane i, columns left to right (oracle: chol)
+            // Cholesky M = L L' (lower), row i on thread i, columns left to right (oracle: chol)
             bool posdef = true;
-            double myinv = 0.0;                                      // lane j: 1 / L_jj
-            if constexpr (FAST) dense40_factorise(W, lane, act ? Dl + Du : 1.0, 0.0, lz);
+            double myinv = 0.0;                                      // one wave: 1 / L_jj on lane j
+            if constexpr (P::FAST) dense40_factorise(W, tid, act ? Dl + Du : 1.0, 0.0, lz);
             else
             for (int j = 0; j < n; ++j) {
                 double s = 0.0;
@@ -463,11 +522,11 @@ __global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restr
                     }
                     for (; k2 < j; ++k2) s -= ri[k2] * rj[k2];
                 }
-                const double dj = bcast(s, j);
+                const double dj = X.get(s, j);
                 if (!(dj > 0.0)) { posdef = false; break; }
                 const double inv = 1.0 / sqrt(dj);
-                __syncthreads();
-                if (lane == j) myinv = inv;
+                if constexpr (P::NT == 64) __syncthreads();          // (a wider block has passed a barrier inside get())
+                X.set_pivot(myinv, j, inv);
                 if (act && li > j) L.M[tri(li, j)] = s * inv;
                 __syncthreads();
             }
@@ -475,18 +534,20 @@ __global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restr
             if (!posdef) { st = 4; break; }
             // two solves with the factor: forward by columns (same subtraction order as the oracle's rows), backward by columns
             auto solve = [&](double rhs) -> double {
-                if constexpr (FAST) { const double x = dense40_solve(W, rhs, lz); return act ? x : 0.0; }
+                if constexpr (P::FAST) { const double x = dense40_solve(W, rhs, lz); return act ? x : 0.0; }
                 double r = rhs;
                 for (int k2 = 0; k2 < n; ++k2) {
-                    const double xk = bcast(r, k2) * bcast(myinv, k2);
-                    if (lane == k2) r = xk;
+                    const double xk = X.get(r, k2) * X.pivot(myinv, k2);
+                    if (tid == k2) r = xk;
                     if (act && li > k2) r -= L.M[tri(li, k2)] * xk;
                 }
+                X.order();
                 for (int k2 = n - 1; k2 >= 0; --k2) {
-                    const double xk = bcast(r, k2) * bcast(myinv, k2);
-                    if (lane == k2) r = xk;
+                    const double xk = X.get(r, k2) * X.pivot(myinv, k2);
+                    if (tid == k2) r = xk;
                     if (act && li < k2) r -= L.M[tri(k2, li)] * xk;
                 }
+                X.order();
                 return r;
             };
             const double da = solve(act ? -rs + (-ll - Dl * rl) - (-lu - Du * ru) : 0.0);
@@ -500,10 +561,10 @@ __global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restr
                     if (dll < 0) a = fmin(a, -ll / dll);
                     if (dlu < 0) a = fmin(a, -lu / dlu);
                 }
-                return wave_min(a);
+                return X.min(a);
             };
             double amax = ratio();
-            const double muaff = wave_sum(act ? (tl + amax * dtl) * (ll + amax * dll) + (tu + amax * dtu) * (lu + amax * dlu) : 0.0) / (2.0 * n);
+            const double muaff = X.sum(act ? (tl + amax * dtl) * (ll + amax * dll) + (tu + amax * dtu) * (lu + amax * dlu) : 0.0) / (2.0 * n);
             double sigma = muaff / mu; sigma = sigma * sigma * sigma;
             if (alpha_prev < ADMPC_QUAD_IPM_BLOCKED_STEP) sigma = 1.0;
             const double smu = sigma * mu;
@@ -525,50 +586,50 @@ __global__ __launch_bounds__(64) void admpc_quad_solve_kernel(const Cfg* __restr
         }
         // ---- 4. expansion, full step, cost (oracle: rti_step)
         __syncthreads();
-        if (FAST) { if (act) L.M[tri(li, li)] = 0.0; }               // (the factor never writes its diagonal; kept for the next instance)
-        L.vec[lane] = act ? du : 0.0;
-        if (lane < QX) L.xnew[lane] = xb[lane] + (x0[lane] - xb[lane]);
+        if (P::FAST) { if (act) L.M[tri(li, li)] = 0.0; }               // (the factor never writes its diagonal; kept for the next instance)
+        dus[tid] = act ? du : 0.0;
+        if (tid < QX) L.xnew[tid] = xb[tid] + (x0[tid] - xb[tid]);
         __syncthreads();
         bool bad = st != 0;
         const double un = ubar_i + du;
         if (act && !(fabs(un) <= 1e300)) bad = true;
-        double dx = lane < QX ? x0[lane] - xb[lane] : 0.0;
+        double dx = tid < QX ? x0[tid] - xb[tid] : 0.0;
         double J = 0.0;
         if (act) { const double e = un - yr[ji * QY + QX + mi]; J += 0.5 * Rw * e * e; }
         for (int k = 0; k < N; ++k) {
-            if (lane < QX) L.gam[lane] = dx;                         // dx_k of all components
+            if (tid < QX) L.gam[tid] = dx;                         // dx_k of all components
             __syncthreads();
             double dn = 0.0;
-            if (lane < QX) {
-                dn = L.b[k * QX + lane];
-                for (int cc = 0; cc < QX; ++cc) dn += L.A[(k * QX + lane) * QX + cc] * L.gam[cc];
-                for (int m = 0; m < QU; ++m) dn += L.B[(k * QX + lane) * QU + m] * L.vec[k * QU + m];
-                const double xv = L.xbs[(k + 1) * QX + lane] + dn;
-                L.xnew[(k + 1) * QX + lane] = xv;
+            if (tid < QX) {
+                dn = L.b[k * QX + tid];
+                for (int cc = 0; cc < QX; ++cc) dn += L.A[(k * QX + tid) * QX + cc] * L.gam[cc];
+                for (int m = 0; m < QU; ++m) dn += L.B[(k * QX + tid) * QU + m] * dus[k * QU + m];
+                const double xv = L.xbs[(k + 1) * QX + tid] + dn;
+                L.xnew[(k + 1) * QX + tid] = xv;
                 if (!(fabs(xv) <= 1e300)) bad = true;
             }
             __syncthreads();
             dx = dn;
         }
-        for (int i = lane; i < (N + 1) * QX; i += 64) {
+        for (int i = tid; i < (N + 1) * QX; i += P::NT) {
             const int k = i / QX, cc = i - k * QX;
             const double e = L.xnew[i] - L.yrs[k * QY + cc];
             J += 0.5 * (k < N ? Ts * c->W[cc] : c->We[cc]) * e * e;        // (once per instance, parallel over lanes)
         }
-        bad = __any(bad) != 0;
-        J = wave_sum(J);
+        bad = X.any(bad);
+        J = X.sum(J);
         if (!bad) {
-            for (int i = lane; i < (N + 1) * QX; i += 64) xb[i] = L.xnew[i];
+            for (int i = tid; i < (N + 1) * QX; i += P::NT) xb[i] = L.xnew[i];
             if (act) ub[li] = un;
         }
         QSTAMP(5);
-        if (lane == 0) {
+        if (tid == 0) {
             if (costg) costg[inst] = bad ? INFINITY : J;
             if (statusg) statusg[inst] = bad ? 4 : 0;
             if (itersg) itersg[inst] = it;
         }
         __syncthreads();
-        inst = next_inst(inst);
+        inst = X.next(inst, ticket);
     }
     QFLUSH();
 }
@@ -1006,256 +1067,6 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef QRED
 }
 
-// ---- horizons beyond 16 (N nu up to 96 inputs; the reference class defaults to n_nodes = 20, quad_3d_optimizer.py:29): the same
-// algorithm with one THREAD per input in a workgroup of two wavefronts.  What the one-wave kernel exchanges inside the wave (v_readlane
-// broadcasts, DPP reductions) goes through LDS and workgroup barriers here -- about a thousand barriers per interior-point iteration:
-// a compatibility path (the shipped horizon N = 10 and everything up to 16 stay on the kernel above), with the oracle's summation
-// order in the factorisation and the substitutions, so that iteration counts and results follow the oracle as on the other paths.
-#define QW_NT 128
-struct WideRed { double* red; double* slot; };
-__device__ __forceinline__ double qw_sum(double v, const WideRed& R, int tid) {
-    v = wave_sum(v); if ((tid & 63) == 0) R.red[tid >> 6] = v; __syncthreads(); const double r = R.red[0] + R.red[1]; __syncthreads(); return r;
-}
-__device__ __forceinline__ double qw_max(double v, const WideRed& R, int tid) {
-    v = wave_max(v); if ((tid & 63) == 0) R.red[tid >> 6] = v; __syncthreads(); const double r = OpMaxNan::f(R.red[0], R.red[1]); __syncthreads(); return r;
-}
-__device__ __forceinline__ double qw_min(double v, const WideRed& R, int tid) {
-    v = wave_min(v); if ((tid & 63) == 0) R.red[tid >> 6] = v; __syncthreads(); const double r = fmin(R.red[0], R.red[1]); __syncthreads(); return r;
-}
-
-__global__ __launch_bounds__(QW_NT) void admpc_quad_solve_wide_kernel(const Cfg* __restrict__ c, int B, const double* __restrict__ x0g, const double* __restrict__ yrefg,
-                                                                      const double* __restrict__ yrefeg, double* __restrict__ xbarg, double* __restrict__ ubarg,
-                                                                      double* __restrict__ costg, int32_t* __restrict__ statusg, int32_t* __restrict__ itersg,
-                                                                      int* __restrict__ ticket, const double* __restrict__ gpsg, const int32_t* __restrict__ routeg, int which)
-{
-    extern __shared__ double lds_raw[];
-    const int N = c->N, n = N * QU, tid = threadIdx.x;
-    Lds L(lds_raw, N);
-    double* const invs = lds_raw + quad_lds_doubles(N);             // [n] reciprocal pivots, then [2] broadcast slots, [2] reduction slots
-    const WideRed R{ invs + n + 2, invs + n };
-    const bool act = tid < n;
-    const int li = act ? tid : 0, ji = li / QU, mi = li - ji * QU;
-    const double Ts = c->Ts;
-    if (tid < QX) { L.wts[tid] = Ts * c->W[tid]; L.wts[QX + tid] = c->We[tid]; }
-    const double Rw = Ts * c->W[QX + mi], lbm = c->lbu[mi], ubm = c->ubu[mi];
-    const double thr0 = c->ipm_thr0, mu0 = c->ipm_mu0, tolc = c->ipm_tol_comp, tolr = c->ipm_tol_res;
-    const int itmax = c->ipm_iter_max;
-    auto next_inst = [&](int inst) -> int {                          // block-uniform: the draw of thread 0 through an LDS slot
-        if (!ticket) return inst + (int)gridDim.x;
-        if (tid == 0) R.red[0] = (double)atomicAdd(ticket, 1);
-        __syncthreads();
-        const int nx = (int)gridDim.x + (int)R.red[0];
-        __syncthreads();
-        return nx;
-    };
-    for (int inst = blockIdx.x; inst < B;) {
-        if (routeg && routeg[inst] != which) { inst = next_inst(inst); continue; }      // routed solve: another cluster's instance
-        double* xb = xbarg + (size_t)inst * (N + 1) * QX;
-        double* ub = ubarg + (size_t)inst * N * QU;
-        const double* yr = yrefg + (size_t)inst * N * QY;
-        const double* ye = yrefeg + (size_t)inst * QX;
-        const double* x0 = x0g + (size_t)inst * QX;
-        const double* gq = gpsg ? gpsg + (size_t)inst * QX : x0;
-        for (int i = tid; i < (N + 1) * QX; i += QW_NT) L.xbs[i] = xb[i];
-        for (int i = tid; i < N * QY + QX; i += QW_NT) L.yrs[i] = i < N * QY ? yr[i] : ye[i - N * QY];
-        shoot_instance(c, xb, ub, gq, L, tid, nullptr, QW_NT);
-        // ---- condensing (oracle: condense)
-        for (int j = 0; j <= li; ++j) if (act) L.H[tri(li, j)] = 0.0;
-        double g[QX];
-#pragma unroll
-        for (int i = 0; i < QX; ++i) g[i] = 0.0;
-        if (tid < QX) L.xhs[tid] = x0[tid] - xb[tid];
-        const double ubar_i = ub[li];
-        double grad = Rw * (ubar_i - yr[ji * QY + QX + mi]);
-        __syncthreads();
-        for (int k = 0; k < N; ++k) {
-            double gn[QX];
-            const int rr = tid < QX ? tid : 0;
-            double xn = L.b[k * QX + rr];
-#pragma unroll
-            for (int cc = 0; cc < QX; ++cc) xn += L.A[(k * QX + rr) * QX + cc] * L.xhs[cc];
-#pragma unroll
-            for (int r = 0; r < QX; ++r) {
-                double s = 0.0;
-#pragma unroll
-                for (int cc = 0; cc < QX; ++cc) s += L.A[(k * QX + r) * QX + cc] * g[cc];
-                gn[r] = ji == k ? L.B[(k * QX + r) * QU + mi] : (ji < k ? s : 0.0);
-            }
-            __syncthreads();                                                     // every read of xhs above is done
-#pragma unroll
-            for (int r = 0; r < QX; ++r) { g[r] = gn[r]; if (act) L.gam[r * n + tid] = gn[r]; }
-            if (tid < QX) L.xhs[tid] = xn;
-            __syncthreads();
-            const double* ref = L.yrs + (k + 1) * QY;
-            const int lim = (k + 1) * QU;
-            double wg[QX];
-#pragma unroll
-            for (int cc = 0; cc < QX; ++cc) {
-                const double wq = L.wts[(k + 1 < N ? 0 : QX) + cc];
-                wg[cc] = g[cc] * wq;
-                if (wq != 0.0) grad += wg[cc] * (L.xbs[(k + 1) * QX + cc] + L.xhs[cc] - ref[cc]);
-            }
-            if (act && li < lim) {
-                for (int j = 0; j <= li; ++j) {
-                    double s = L.H[tri(li, j)];
-#pragma unroll
-                    for (int cc = 0; cc < QX; ++cc) s += wg[cc] * L.gam[cc * n + j];
-                    L.H[tri(li, j)] = s;
-                }
-            }
-            __syncthreads();
-        }
-        if (act) L.H[tri(li, li)] += Rw;
-        __syncthreads();
-        // ---- box QP (oracle: box_qp)
-        const double lo = lbm - ubar_i, hi = ubm - ubar_i;
-        double du = 0.0;
-        double tl = act ? fmax(du - lo, thr0) : 1.0, tu = act ? fmax(hi - du, thr0) : 1.0;
-        double ll = act ? mu0 / tl : 0.0, lu = act ? mu0 / tu : 0.0;
-        double alpha_prev = 1.0;
-        int it = 0, st = 0;
-        bool cons = false;
-        for (;; ++it) {
-            double rs = grad - ll + lu;
-            L.gam[tid] = du;                                                     // (gam is free after the condensing: n <= 96 values here)
-            __syncthreads();
-            if (act) for (int j = 0; j < n; ++j) rs += L.H[sym(li, j)] * L.gam[j];
-            const double rl = du - lo - tl, ru = hi - du - tu;
-            const double mu = qw_sum(act ? tl * ll + tu * lu : 0.0, R, tid) / (2.0 * n);
-            const double cmax = qw_max(act ? fmax(tl * ll, tu * lu) : 0.0, R, tid);
-            const double rmax = qw_max(act ? fmax(fabs(rs), fmax(fabs(rl), fabs(ru))) : 0.0, R, tid);
-            if (!(mu == mu) || !(rmax == rmax)) { st = 4; break; }
-            if ((cmax <= tolc && rmax <= tolr) || it >= itmax + (cons ? ADMPC_QUAD_IPM_FALLBACK_ITER : 0)) break;
-            if (!cons && it >= ADMPC_QUAD_IPM_FALLBACK_ITER) {
-                cons = true;
-                du = 0.0;
-                tl = act ? fmax(du - lo, thr0) : 1.0; tu = act ? fmax(hi - du, thr0) : 1.0;
-                ll = act ? mu0 / tl : 0.0; lu = act ? mu0 / tu : 0.0;
-                alpha_prev = 1.0;
-                --it;
-                continue;
-            }
-            const double Dl = act ? ll / tl : 0.0, Du = act ? lu / tu : 0.0;
-            if (act) { for (int j = 0; j <= li; ++j) L.M[tri(li, j)] = L.H[tri(li, j)]; L.M[tri(li, li)] += Dl + Du; }
-            __syncthreads();
-            // Cholesky M = L L' (lower), row i on thread i, columns left to right (oracle: chol)
-            bool posdef = true;
-            for (int j = 0; j < n; ++j) {
-                double s = 0.0;
-                if (act && li >= j) {
-                    const double* ri = L.M + tri(li, 0);
-                    const double* rj = L.M + tri(j, 0);
-                    s = ri[j];
-                    for (int k2 = 0; k2 < j; ++k2) s -= ri[k2] * rj[k2];
-                }
-                if (tid == j) R.slot[j & 1] = s;
-                __syncthreads();
-                const double dj = R.slot[j & 1];
-                if (!(dj > 0.0)) { posdef = false; break; }                       // uniform: every thread reads the same slot
-                const double inv = 1.0 / sqrt(dj);
-                if (tid == j) invs[j] = inv;
-                if (act && li > j) L.M[tri(li, j)] = s * inv;
-                __syncthreads();
-            }
-            if (!posdef) { st = 4; break; }
-            auto solve = [&](double rhs) -> double {
-                double r = rhs;
-                for (int k2 = 0; k2 < n; ++k2) {
-                    if (tid == k2) { r = r * invs[k2]; R.slot[k2 & 1] = r; }
-                    __syncthreads();
-                    const double xk = R.slot[k2 & 1];
-                    if (act && li > k2) r -= L.M[tri(li, k2)] * xk;
-                }
-                __syncthreads();
-                for (int k2 = n - 1; k2 >= 0; --k2) {
-                    if (tid == k2) { r = r * invs[k2]; R.slot[k2 & 1] = r; }
-                    __syncthreads();
-                    const double xk = R.slot[k2 & 1];
-                    if (act && li < k2) r -= L.M[tri(k2, li)] * xk;
-                }
-                __syncthreads();
-                return r;
-            };
-            const double da = solve(act ? -rs + (-ll - Dl * rl) - (-lu - Du * ru) : 0.0);
-            double dtl = da + rl, dtu = -da + ru;
-            double dll = -ll - Dl * dtl, dlu = -lu - Du * dtu;
-            auto ratio = [&]() -> double {
-                double a = 1.0;
-                if (act) {
-                    if (dtl < 0) a = fmin(a, -tl / dtl);
-                    if (dtu < 0) a = fmin(a, -tu / dtu);
-                    if (dll < 0) a = fmin(a, -ll / dll);
-                    if (dlu < 0) a = fmin(a, -lu / dlu);
-                }
-                return qw_min(a, R, tid);
-            };
-            double amax = ratio();
-            const double muaff = qw_sum(act ? (tl + amax * dtl) * (ll + amax * dll) + (tu + amax * dtu) * (lu + amax * dlu) : 0.0, R, tid) / (2.0 * n);
-            double sigma = muaff / mu; sigma = sigma * sigma * sigma;
-            if (alpha_prev < ADMPC_QUAD_IPM_BLOCKED_STEP) sigma = 1.0;
-            const double smu = sigma * mu;
-            const double cl = act ? (smu - (cons ? 0.0 : dtl * dll)) / tl : 0.0, cu = act ? (smu - (cons ? 0.0 : dtu * dlu)) / tu : 0.0;
-            const double d = solve(act ? -rs + (cl - ll - Dl * rl) - (cu - lu - Du * ru) : 0.0);
-            dtl = d + rl; dtu = -d + ru;
-            dll = cl - ll - Dl * dtl; dlu = cu - lu - Du * dtu;
-            amax = ratio();
-            double tau = 1.0 - muaff; tau = fmax(tau, 0.995); tau = fmin(tau, 0.999999);
-            const double alpha = fmin(tau * amax, 1.0);
-            if (act) {
-                du += alpha * d;
-                tl = fmax(tl + alpha * dtl, 1e-40); tu = fmax(tu + alpha * dtu, 1e-40);
-                ll = fmax(ll + alpha * dll, 1e-40); lu = fmax(lu + alpha * dlu, 1e-40);
-            }
-            alpha_prev = alpha;
-            __syncthreads();
-        }
-        // ---- expansion, full step, cost (oracle: rti_step)
-        __syncthreads();
-        L.gam[QX + tid] = act ? du : 0.0;                                        // du of all inputs behind the dx slot
-        if (tid < QX) L.xnew[tid] = xb[tid] + (x0[tid] - xb[tid]);
-        __syncthreads();
-        bool bad = st != 0;
-        const double un = ubar_i + du;
-        if (act && !(fabs(un) <= 1e300)) bad = true;
-        double dx = tid < QX ? x0[tid] - xb[tid] : 0.0;
-        double J = 0.0;
-        if (act) { const double e = un - yr[ji * QY + QX + mi]; J += 0.5 * Rw * e * e; }
-        for (int k = 0; k < N; ++k) {
-            if (tid < QX) L.gam[tid] = dx;
-            __syncthreads();
-            double dn = 0.0;
-            if (tid < QX) {
-                dn = L.b[k * QX + tid];
-                for (int cc = 0; cc < QX; ++cc) dn += L.A[(k * QX + tid) * QX + cc] * L.gam[cc];
-                for (int m = 0; m < QU; ++m) dn += L.B[(k * QX + tid) * QU + m] * L.gam[QX + k * QU + m];
-                const double xv = L.xbs[(k + 1) * QX + tid] + dn;
-                L.xnew[(k + 1) * QX + tid] = xv;
-                if (!(fabs(xv) <= 1e300)) bad = true;
-            }
-            __syncthreads();
-            dx = dn;
-        }
-        for (int i = tid; i < (N + 1) * QX; i += QW_NT) {
-            const int k = i / QX, cc = i - k * QX;
-            const double e = L.xnew[i] - L.yrs[k * QY + cc];
-            J += 0.5 * (k < N ? Ts * c->W[cc] : c->We[cc]) * e * e;
-        }
-        bad = qw_max(bad ? 1.0 : 0.0, R, tid) > 0.0;
-        J = qw_sum(J, R, tid);
-        if (!bad) {
-            for (int i = tid; i < (N + 1) * QX; i += QW_NT) xb[i] = L.xnew[i];
-            if (act) ub[li] = un;
-        }
-        if (tid == 0) {
-            if (costg) costg[inst] = bad ? INFINITY : J;
-            if (statusg) statusg[inst] = bad ? 4 : 0;
-            if (itersg) itersg[inst] = it;
-        }
-        __syncthreads();
-        inst = next_inst(inst);
-    }
-}
-
 // Cluster of an instance (the reference keeps one acados solver per GP cluster, quad_3d_optimizer.py:207, and picks one per solve from
 // the reference state: set_reference_state / set_reference_trajectory :446-452, :485-491 -> gp.py:738-770 select_gp): nearest centroid in
 // the selected features of z = [x with the velocity in the BODY frame; u], Euclidean distance, ties to the lower index (numpy.argmin).
@@ -1454,10 +1265,10 @@ int admpc_quad_create(const AdmpcQuadConfig* cfg, int device, AdmpcQuadSolver** 
         if (s->d_ticket) (void)hipFree(s->d_ticket);
         delete s; return admpc_set_error(ADMPC_EHIP, "device allocation failed");
     }
-    (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<GenericPath>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<Dense40Path>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)admpc_quad_shoot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)admpc_quad_solve_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<WidePath>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)admpc_quad_seg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     *out = s;
     return ADMPC_OK;
@@ -1493,11 +1304,11 @@ static int quad_solve(AdmpcQuadSolver* s, int B, const double* x0, const double*
         hipLaunchKernelGGL(admpc_quad_seg_kernel, dim3(grid), dim3(128), ldsb, st, s->d_cfg, B, x0, yref, yref_e, xbar, ubar, cost, status, iters, ticket, gp_state, route, which, s->d_slot);
     }
     else if (s->cfg.N * QU > 64)          // horizons beyond 16: one thread per input, two waves per instance
-        hipLaunchKernelGGL(admpc_quad_solve_wide_kernel, dim3(grid), dim3(QW_NT), s->lds_bytes, st, s->d_cfg, B, x0, yref, yref_e, xbar, ubar, cost, status, iters, ticket, gp_state, route, which);
+        hipLaunchKernelGGL(admpc_quad_solve_kernel<WidePath>, dim3(grid), dim3(WidePath::NT), s->lds_bytes, st, s->d_cfg, B, x0, yref, yref_e, xbar, ubar, cost, status, iters, ticket, gp_state, route, which);
     else if (s->cfg.N * QU == 40 && !s->generic)
-        hipLaunchKernelGGL(admpc_quad_solve_kernel<true>, dim3(grid), dim3(64), s->lds_bytes, st, s->d_cfg, B, x0, yref, yref_e, xbar, ubar, cost, status, iters, ticket, gp_state, route, which);
+        hipLaunchKernelGGL(admpc_quad_solve_kernel<Dense40Path>, dim3(grid), dim3(64), s->lds_bytes, st, s->d_cfg, B, x0, yref, yref_e, xbar, ubar, cost, status, iters, ticket, gp_state, route, which);
     else
-        hipLaunchKernelGGL(admpc_quad_solve_kernel<false>, dim3(grid), dim3(64), s->lds_bytes, st, s->d_cfg, B, x0, yref, yref_e, xbar, ubar, cost, status, iters, ticket, gp_state, route, which);
+        hipLaunchKernelGGL(admpc_quad_solve_kernel<GenericPath>, dim3(grid), dim3(64), s->lds_bytes, st, s->d_cfg, B, x0, yref, yref_e, xbar, ubar, cost, status, iters, ticket, gp_state, route, which);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "quad solve kernel launch failed");
     return ADMPC_OK;
 }

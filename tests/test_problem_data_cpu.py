@@ -175,8 +175,8 @@ def test_quad_dispatch_maps_each_tested_horizon_to_its_kernel():
     body = src[src.index("static int quad_solve("):]
     body = body[:body.index("\n}")]
     assert "const bool seg20 = s->cfg.N == 20 && !s->wide20;" in body
-    assert "else if (s->cfg.N * QU > 64)" in body and "admpc_quad_solve_wide_kernel" in body
-    assert "else if (s->cfg.N * QU == 40 && !s->generic)" in body and "admpc_quad_solve_kernel<true>" in body
+    assert "else if (s->cfg.N * QU > 64)" in body and "admpc_quad_solve_kernel<WidePath>" in body
+    assert "else if (s->cfg.N * QU == 40 && !s->generic)" in body and "admpc_quad_solve_kernel<Dense40Path>" in body
     assert 's->generic = e && e[0] == \'1\'' in src and 's->wide20 = e && e[0] == \'1\'' in src
     assert re.search(r'getenv\("ADMPC_QUAD_GENERIC"\)', src) and re.search(r'getenv\("ADMPC_QUAD_WIDE"\)', src)
 

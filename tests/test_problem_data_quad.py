@@ -73,11 +73,11 @@ def random_quad_problem(rng, N, plus=False, drag=False):
 
 # path: (N, environment, GP model); the comment names the kernel admpc_quad.hip:quad_solve launches for it
 PATHS = {
-    "dense40_N10": (10, {}, False),                               # admpc_quad_solve_kernel<true>
-    "generic_N10": (10, {"ADMPC_QUAD_GENERIC": "1"}, False),      # admpc_quad_solve_kernel<false>
+    "dense40_N10": (10, {}, False),                               # admpc_quad_solve_kernel<Dense40Path>
+    "generic_N10": (10, {"ADMPC_QUAD_GENERIC": "1"}, False),      # admpc_quad_solve_kernel<GenericPath>
     "generic_N5": (5, {}, False),
     "generic_N16": (16, {}, False),
-    "wide_N17": (17, {}, False),                                  # admpc_quad_solve_wide_kernel
+    "wide_N17": (17, {}, False),                                  # admpc_quad_solve_kernel<WidePath>
     "wide_N24": (24, {}, False),
     "wide_N20": (20, {"ADMPC_QUAD_WIDE": "1"}, False),
     "seg_N20": (20, {}, False),                                   # admpc_quad_seg_kernel
