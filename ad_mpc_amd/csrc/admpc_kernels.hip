@@ -212,11 +212,12 @@ __global__ __launch_bounds__(WAVE) void admpc_waypoints_kernel(int M, int H, dou
     }
 }
 
-// shooting only: phi, A, B to global memory (parity tests of H0/H1)
+// shooting only: phi, A, B to global memory (parity tests of H0/H1), T = double or float
+template <class T>
 __global__ __launch_bounds__(WAVE) void admpc_shoot_kernel(const AdmpcConfig* __restrict__ cfg, int B,
-                                                           const double* __restrict__ xbarg, const double* __restrict__ ubarg,
-                                                           const double* __restrict__ pg,
-                                                           double* __restrict__ phig, double* __restrict__ Ag, double* __restrict__ Bg)
+                                                           const T* __restrict__ xbarg, const T* __restrict__ ubarg,
+                                                           const T* __restrict__ pg,
+                                                           T* __restrict__ phig, T* __restrict__ Ag, T* __restrict__ Bg)
 {
     const int N = cfg->N;
     const long total = (long)B * N * 3;
@@ -224,15 +225,15 @@ __global__ __launch_bounds__(WAVE) void admpc_shoot_kernel(const AdmpcConfig* __
     for (long tsk = (long)blockIdx.x * LIN_TASKS + threadIdx.x; tsk < total; tsk += (long)gridDim.x * LIN_TASKS) {
         const long sk = tsk / 3; const int g = (int)(tsk % 3);
         const long inst = sk / N; const int k = (int)(sk % N);
-        double x[NX], u[NU], phi[NX], col[3][NX];
+        T x[NX], u[NU], phi[NX], col[3][NX];
         for (int i = 0; i < NX; ++i) x[i] = xbarg[(inst * (N + 1) + k) * NX + i];
         u[0] = ubarg[(inst * N + k) * NU]; u[1] = ubarg[(inst * N + k) * NU + 1];
-        rk4_group<double>(cfg, x, u, pg[inst], cfg->Ts, g, phi, col);
-        double* A = Ag + sk * NX * NX; double* Bm = Bg + sk * NX * NU;
+        rk4_group<T>(cfg, x, u, pg[inst], (T)cfg->Ts, g, phi, col);
+        T* A = Ag + sk * NX * NX; T* Bm = Bg + sk * NX * NU;
         if (g == 0) {
             for (int i = 0; i < NX; ++i) {
                 phig[sk * NX + i] = phi[i];
-                A[i * 7 + 0] = i == 0 ? 1.0 : 0.0; A[i * 7 + 1] = i == 1 ? 1.0 : 0.0;
+                A[i * 7 + 0] = i == 0 ? (T)1 : (T)0; A[i * 7 + 1] = i == 1 ? (T)1 : (T)0;
                 A[i * 7 + 2] = col[0][i]; A[i * 7 + 3] = col[1][i]; A[i * 7 + 4] = col[2][i];
             }
         } else if (g == 1) {
@@ -1037,6 +1038,9 @@ int admpc_solve_batch_f32(AdmpcSolver* s, int B, const float* x0, const float* y
     if (B < 0) return fail(ADMPC_EINVAL, "negative batch");
     if (B == 0) return ADMPC_OK;
     if (!x0 || !yref || !yref_e || !p || !xbar || !ubar) return fail(ADMPC_EINVAL, "null array argument");
+    // beyond this horizon the float recursion on GP-augmented dynamics returns status 0 on iterates without a correct digit (admpc.h)
+    if (s->cfg.n_gp > 0 && s->cfg.N > ADMPC_F32_GP_MAX_N)
+        return fail(ADMPC_EINVAL, "fp32 solve of a model with GP residuals: horizon beyond ADMPC_F32_GP_MAX_N (28), use the fp64 entry");
     DeviceGuard guard(s->device);
     if (!guard.ok()) return fail(ADMPC_EHIP, "hipSetDevice failed");
     { int rc = ensure_status(s, B); if (rc) return rc; }
@@ -1075,8 +1079,10 @@ int admpc_nlp_residuals_batch(AdmpcSolver* s, int B, const double* x0, const dou
     return ADMPC_OK;
 }
 
-int admpc_shoot_batch(AdmpcSolver* s, int B, const double* xbar, const double* ubar, const double* p,
-                      double* phi, double* A, double* Bm, void* stream)
+}  // extern "C"
+
+template <class T>
+static int shoot_impl(AdmpcSolver* s, int B, const T* xbar, const T* ubar, const T* p, T* phi, T* A, T* Bm, void* stream)
 {
     if (!s || B < 0) return fail(ADMPC_EINVAL, "bad argument");
     if (B == 0) return ADMPC_OK;
@@ -1085,9 +1091,23 @@ int admpc_shoot_batch(AdmpcSolver* s, int B, const double* xbar, const double* u
     if (!guard.ok()) return fail(ADMPC_EHIP, "hipSetDevice failed");
     long total = (long)B * s->cfg.N * 3;
     int grid = (int)((total + LIN_TASKS - 1) / LIN_TASKS); if (grid > s->num_cu * 32) grid = s->num_cu * 32;
-    hipLaunchKernelGGL(admpc_shoot_kernel, dim3(grid), dim3(WAVE), 0, (hipStream_t)stream, s->d_cfg, B, xbar, ubar, p, phi, A, Bm);
+    hipLaunchKernelGGL(admpc_shoot_kernel<T>, dim3(grid), dim3(WAVE), 0, (hipStream_t)stream, s->d_cfg, B, xbar, ubar, p, phi, A, Bm);
     HIPCHK(hipGetLastError());
     return ADMPC_OK;
+}
+
+extern "C" {
+
+int admpc_shoot_batch(AdmpcSolver* s, int B, const double* xbar, const double* ubar, const double* p,
+                      double* phi, double* A, double* Bm, void* stream)
+{
+    return shoot_impl<double>(s, B, xbar, ubar, p, phi, A, Bm, stream);
+}
+
+int admpc_shoot_batch_f32(AdmpcSolver* s, int B, const float* xbar, const float* ubar, const float* p,
+                          float* phi, float* A, float* Bm, void* stream)
+{
+    return shoot_impl<float>(s, B, xbar, ubar, p, phi, A, Bm, stream);
 }
 
 int admpc_argmin(AdmpcSolver* s, const double* cost, int B, int64_t index_offset, double* val, int64_t* idx, void* stream)

@@ -155,14 +155,19 @@ class BatchSolver:
         return tx.cpu().numpy(), tu.cpu().numpy(), cost.cpu().numpy(), status.cpu().numpy(), iters.cpu().numpy()
 
     def shoot(self, xbar, ubar, p):
-        """H1 only: phi [B,N,7], A [B,N,7,7], B [B,N,7,2] (device tensors)."""
+        """H1 only: phi [B,N,7], A [B,N,7,7], B [B,N,7,2] (device tensors).  The dtype of xbar selects the instantiation: float64
+        (admpc_shoot_batch) or float32 (admpc_shoot_batch_f32)."""
         N = self.N
         B = xbar.shape[0]
-        self._chk(xbar, (B, N + 1, NX)); self._chk(ubar, (B, N, NU)); self._chk(p, (B,))
-        phi = torch.empty((B, N, NX), dtype=torch.float64, device=self.device)
-        A = torch.empty((B, N, NX, NX), dtype=torch.float64, device=self.device)
-        Bm = torch.empty((B, N, NX, NU), dtype=torch.float64, device=self.device)
-        _lib.check(self.lib.admpc_shoot_batch(self._h, B, _ptr(xbar), _ptr(ubar), _ptr(p), _ptr(phi), _ptr(A), _ptr(Bm), self._stream()))
+        dt = xbar.dtype
+        if dt not in (torch.float64, torch.float32):
+            raise ValueError("xbar must be float64 or float32")
+        self._chk(xbar, (B, N + 1, NX), dt); self._chk(ubar, (B, N, NU), dt); self._chk(p, (B,), dt)
+        phi = torch.empty((B, N, NX), dtype=dt, device=self.device)
+        A = torch.empty((B, N, NX, NX), dtype=dt, device=self.device)
+        Bm = torch.empty((B, N, NX, NU), dtype=dt, device=self.device)
+        fn = self.lib.admpc_shoot_batch if dt == torch.float64 else self.lib.admpc_shoot_batch_f32
+        _lib.check(fn(self._h, B, _ptr(xbar), _ptr(ubar), _ptr(p), _ptr(phi), _ptr(A), _ptr(Bm), self._stream()))
         return phi, A, Bm
 
     def shift(self, xbar, ubar, p=None, rollout=True):

@@ -223,7 +223,15 @@ int admpc_nlp_residuals_batch(AdmpcSolver* s, int B,
  * tighter values in cfg are clipped to these) -- the result is the fp64 minimiser to about 1e-3 of the input range.
  * The model's "+1e-99" denominators (ad_3d_optimizer.py:290,296-297) vanish in fp32: with p == 0 the dynamic branch is dropped
  * instead of multiplied by 0 (it would be inf * 0 at v_x = 0); 0 < p <= 1 reproduces the blend.
- * Every horizon runs the row kernel here (the condensed N = 20 pipeline is fp64 only). */
+ * Every horizon runs the row kernel here (the condensed N = 20 pipeline is fp64 only).
+ * Models with GP residuals are refused beyond N = ADMPC_F32_GP_MAX_N (ADMPC_EINVAL): the GP-augmented dynamics can carry an unstable
+ * lateral mode through which the float Riccati recursion loses every digit at longer horizons, and it would return status 0 with an
+ * iterate far outside the bound above (CPU census of the float algorithm against the fp64 oracle, scripts/census_f32_gp.py: no
+ * instance of 2048 per horizon past 2.5e-3 in u up to N = 28, 1 at N = 29, 128 at N = 40).  Use the fp64 entry there.
+ * The margin at the bound is thin and is an emulator figure: the worst census instance at N = 28 is 2.2e-3, about 10 % inside 2.5e-3,
+ * and single worst instances move between the emulator and the device (one 512-instance batch: 1.2e-3 / 1.7e-3), so an instance past
+ * 2.5e-3 at N = 27 or 28 on other data is possible.  The states of such a model are further off than its inputs. */
+#define ADMPC_F32_GP_MAX_N 28
 int admpc_solve_batch_f32(AdmpcSolver* s, int B,
                           const float* x0, const float* yref, const float* yref_e, const float* p,
                           float* xbar, float* ubar,
@@ -236,6 +244,12 @@ int admpc_solve_batch_f32(AdmpcSolver* s, int B,
 int admpc_shoot_batch(AdmpcSolver* s, int B,
                       const double* xbar, const double* ubar, const double* p,
                       double* phi, double* A, double* Bm, void* stream);
+
+/* The same test hook for the fp32 instantiation of the model (the shooting admpc_solve_batch_f32 linearises with): float arrays,
+ * float arithmetic, the p == 0 rule stated above. */
+int admpc_shoot_batch_f32(AdmpcSolver* s, int B,
+                          const float* xbar, const float* ubar, const float* p,
+                          float* phi, float* A, float* Bm, void* stream);
 
 /* Local arg-min over cost[0..B): writes the smallest cost and its index (+index_offset) into
  * the device scalars val/idx; ties -> lowest index; +inf / NaN costs never win unless all are.

@@ -39,12 +39,32 @@ typedef long double real;
 #define R_COS cosl
 #define R_EXP expl
 #define R_FABS fabsl
+#elif defined(ORACLE_FLOAT)
+/* liboracle_f32.so: the yardstick of the device's fp32 MODEL (oracle_f, oracle_jac, oracle_rk4_sens: tests/test_fp32_path.py).  Inputs are
+ * rounded to float on entry and every operation is a float operation.  The solver side compiles but is not a reference for anything:
+ * its stop levels and floors are those of the fp64 build. */
+typedef float real;
+#define R_SIN sinf
+#define R_COS cosf
+#define R_EXP expf
+#define R_FABS fabsf
 #else
 typedef double real;
 #define R_SIN sin
 #define R_COS cos
 #define R_EXP exp
 #define R_FABS fabs
+#endif
+
+/* The slip-angle denominators v_x + 1e-99 (ad_3d_optimizer.py:290,296-297).  In float 1e-99 is 0, and at v_x = 0 the dynamic branch
+ * would be inf * 0 = NaN even with the blend p = 0 switching it off: the float build follows the device's float rule (model_dev.h,
+ * model_eval) and takes 1 / v as 0 when p == 0, which drops the dynamic terms from f and from the Jacobians. */
+#ifdef ORACLE_FLOAT
+#define SLIP_DIV(num, v, p) ((p) == 0 ? (real)0 : (num) / (v))
+#define SLIP_EPS ((real)0)
+#else
+#define SLIP_DIV(num, v, p) ((num) / (v))
+#define SLIP_EPS ((real)1e-99)
 #endif
 
 #define NX ADMPC_NX
@@ -83,9 +103,9 @@ static void model_f(const AdmpcConfig* c, const real* x, const real* u, real p, 
     f[0] = vx * cp - vy * sp;                                   /* ad_3d_optimizer.py:281 */
     f[1] = vx * sp + vy * cp;                                   /* :284 */
     f[2] = r;                                                   /* :287 */
-    const real v = vx + (real)1e-99;
-    const real Ffy = 2 * Cf * (dl - (vy + LF * r) / v);         /* :290 */
-    const real Fry = 2 * Cr * (LR * r - vy) / v;                /* :296 */
+    const real v = vx + SLIP_EPS;
+    const real Ffy = 2 * Cf * (dl - SLIP_DIV(vy + LF * r, v, p));   /* :290 */
+    const real Fry = 2 * Cr * SLIP_DIV(LR * r - vy, v, p);          /* :296 */
     const real dyn3 = u[0] - (1 / m) * Ffy * R_SIN(dl) + vy * r;            /* :291 */
     const real kin3 = u[0];                                                  /* :292 */
     const real dyn4 = (1 / m) * (Fry + Ffy * R_COS(dl)) - vx * r;           /* :298 */
@@ -116,12 +136,12 @@ static void model_jac(const AdmpcConfig* c, const real* x, const real* u, real p
     Jx[0][2] = -vx * sp - vy * cp; Jx[0][3] = cp; Jx[0][4] = -sp;
     Jx[1][2] = vx * cp - vy * sp;  Jx[1][3] = sp; Jx[1][4] = cp;
     Jx[2][5] = 1;
-    const real v = vx + (real)1e-99;
-    const real Ffy = 2 * Cf * (dl - (vy + LF * r) / v);
-    const real Fry = 2 * Cr * (LR * r - vy) / v;
+    const real v = vx + SLIP_EPS;
+    const real Ffy = 2 * Cf * (dl - SLIP_DIV(vy + LF * r, v, p));
+    const real Fry = 2 * Cr * SLIP_DIV(LR * r - vy, v, p);
     /* gradients w.r.t. (vx, vy, r, delta) */
-    const real gF[4] = { 2 * Cf * (vy + LF * r) / (v * v), -2 * Cf / v, -2 * Cf * LF / v, 2 * Cf };
-    const real gR[4] = { -Fry / v, -2 * Cr / v, 2 * Cr * LR / v, 0 };
+    const real gF[4] = { SLIP_DIV(2 * Cf * (vy + LF * r), v * v, p), SLIP_DIV(-2 * Cf, v, p), SLIP_DIV(-2 * Cf * LF, v, p), 2 * Cf };
+    const real gR[4] = { SLIP_DIV(-Fry, v, p), SLIP_DIV(-2 * Cr, v, p), SLIP_DIV(2 * Cr * LR, v, p), 0 };
     real d3[4], d4[4], d5[4];
     for (int i = 0; i < 4; ++i) {
         d3[i] = -gF[i] * sd / m;

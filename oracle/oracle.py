@@ -17,7 +17,7 @@ _ip = C.POINTER(C.c_int32)
 
 
 def _target(omp=False, variant=None):
-    if variant:                                 # "asan" (sanitizers) or "ld" (80-bit arithmetic): tests/test_oracle_hygiene.py
+    if variant:                                 # "asan" (sanitizers), "ld" (80-bit arithmetic), "f32" (float model: f, jac, rk4_sens only)
         return "liboracle_%s.so" % variant
     return "liboracle_omp.so" if omp else "liboracle.so"
 

@@ -26,6 +26,18 @@ LAUNCH_LINES = (
     ("admpc_kernels.hip", "solve_rows", "hipLaunchKernelGGL(admpc_nlp_res_kernel<T>, dim3(nb < s->num_cu * 32 ? nb : s->num_cu * 32)"),
     ("admpc_kernels.hip", "admpc_nlp_residuals_batch", "hipLaunchKernelGGL(admpc_nlp_res_kernel<double>, dim3(B < s->num_cu * 32 ? B : s->num_cu * 32)"),
     ("admpc_kernels.hip", "admpc_waypoints_batch", "int grid = B < 4096 ? B : 4096;"),
+    ("admpc_rowqp.hip", "rowqp_inst_stride", "int s = RQ_HDR + N * RQ_RS;"),
+    ("admpc_rowqp.hip", "rowqp_inst_stride", "s += s & 1;"),
+    ("admpc_rowqp.hip", "rowqp_inst_stride", "while (s % (2 * half) != half) s += 2;"),
+    ("rowqp_core.h", "", "#define RQ_HDR 16"),
+    ("rowqp_core.h", "", "#define RQ_RS 31"),
+    ("admpc_rowqp.hip", "admpc_rowqp_plan", "const int cap = 160 * 1024;"),
+    ("admpc_rowqp.hip", "admpc_rowqp_plan", "int r = 4;"),
+    ("admpc_rowqp.hip", "admpc_rowqp_plan", "while (r > 1 && r * stride * elem > cap) r >>= 1;"),
+    ("admpc_rowqp.hip", "admpc_rowqp_plan", "int per_cu = cap / (r * stride * elem);"),
+    ("admpc_rowqp.hip", "admpc_rowqp_plan", "while (r > 1 && (B + r - 1) / r < num_cu * 4 && (B + r / 2 - 1) / (r / 2) <= num_cu * 4) r >>= 1;"),
+    ("admpc_rowqp.hip", "admpc_rowqp_plan", "if (per_cu > 4) per_cu = 4;"),
+    ("admpc_kernels.hip", "rowqp_split", "return (s->split_mode == 1 || nquads > grid) ? s->d_split : nullptr;"),
 )
 
 
@@ -110,3 +122,47 @@ def nlp_res_past(nc):
 
 
 WAYPOINTS_PAST = 2 * 4096 + 901
+
+
+# ---- kernel R (admpc_rowqp_plan, rowqp_split).  rowqp_rows / rowqp_splits assume a horizon whose LDS footprint allows four instances per
+# wave and four waves per CU; rowqp_lds_rows / rowqp_per_cu state that footprint, and the tests assert it for the horizon they use
+RQ_HDR, RQ_RS = 16, 31
+
+
+def rowqp_inst_stride(N):
+    """Values of T per instance in LDS (rowqp_inst_stride: the records, padded to an odd multiple of 16 values)."""
+    s = RQ_HDR + N * RQ_RS
+    s += s & 1
+    while s % 32 != 16:
+        s += 2
+    return s
+
+
+def rowqp_lds_rows(N, elem):
+    """Instances per wave the LDS allows (the first loop of admpc_rowqp_plan); 0: the horizon does not fit."""
+    r = 4
+    while r > 1 and r * rowqp_inst_stride(N) * elem > LDS_BYTES:
+        r >>= 1
+    return r if r * rowqp_inst_stride(N) * elem <= LDS_BYTES else 0
+
+
+def rowqp_per_cu(N, elem, rows):
+    return min(4, LDS_BYTES // (rows * rowqp_inst_stride(N) * elem))
+
+
+def rowqp_rows(nc, B):
+    """Instances per wave: 4, halved while the batch would not fill one wave per SIMD (4 per CU) with the smaller count either."""
+    r = 4
+    while r > 1 and (B + r - 1) // r < nc * 4 and (B + r // 2 - 1) // (r // 2) <= nc * 4:
+        r >>= 1
+    return r
+
+
+def rowqp_splits(nc, B, rows):
+    """Two phases (trial for all, interior point for the deferred) when the batch is more than one round of waves."""
+    return (B + rows - 1) // rows > nc * 4
+
+
+def rowqp_sizes(nc):
+    """One batch per regime: 1, 2, 4 instances per wave in one round, and 4 per wave past one round (split)."""
+    return {"rows1": nc * 4, "rows2": nc * 4 + nc // 2 + 37, "rows4": nc * 8 + nc // 2 + 37, "split": nc * 16 + nc // 2 + 37}

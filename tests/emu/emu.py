@@ -19,17 +19,28 @@ def build():
     return _SO
 
 
-def pack_linearisation(oracle, cfg, xbar, ubar, p):
-    """GT [B][N][7][6] (stored columns A[:,2..6], B[:,0..1], rows 0..5) and the defects b [B][N][7], as kernel A writes them."""
+def pack_linearisation(oracle, cfg, xbar, ubar, p, dtype=np.float64):
+    """GT [B][N][7][6] (stored columns A[:,2..6], B[:,0..1], rows 0..5) and the defects b [B][N][7], as kernel A writes them.
+    dtype=np.float32 with the float oracle (Oracle(variant="f32")): float arrays whose defect is the float subtraction of kernel A."""
     B, N = xbar.shape[0], cfg.N
-    GT = np.zeros((B, N, 7, 6)); bl = np.zeros((B, N, 7))
+    xbar = np.asarray(xbar, dtype=dtype)
+    GT = np.zeros((B, N, 7, 6), dtype=dtype); bl = np.zeros((B, N, 7), dtype=dtype)
     for b in range(B):
         for k in range(N):
             phi, A, Bm = oracle.rk4_sens(cfg, xbar[b, k], ubar[b, k], p[b], cfg.Ts)
             GT[b, k, :5] = A[:6, 2:].T
             GT[b, k, 5:] = Bm[:6, :].T
-            bl[b, k] = phi - xbar[b, k + 1]
+            bl[b, k] = phi.astype(dtype) - xbar[b, k + 1]
     return GT, bl
+
+
+def pack_shooting(phi, A, Bm, xbar):
+    """The same packing from shooting arrays phi [B][N][7], A [B][N][7][7], B [B][N][7][2] (the device's shooting hook) in their own
+    dtype: no value passes through another number format."""
+    dt = phi.dtype
+    assert A.dtype == dt and Bm.dtype == dt
+    GT = np.concatenate([np.swapaxes(A[:, :, :6, 2:], 2, 3), np.swapaxes(Bm[:, :, :6, :], 2, 3)], axis=2)
+    return np.ascontiguousarray(GT), phi - np.asarray(xbar, dtype=dt)[:, 1:]
 
 
 class Emu:

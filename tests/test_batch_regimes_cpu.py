@@ -6,7 +6,8 @@ import re
 import pytest
 
 from batch_regimes import LAUNCH_LINES, f_grid, s_grid, quad_grid, quad_tickets, quad_shoot_grid, nlp_res_grid, waypoints_grid, \
-    s_below, s_past, f_past, quad_below, quad_past, nlp_res_past, WAYPOINTS_PAST
+    s_below, s_past, f_past, quad_below, quad_past, nlp_res_past, WAYPOINTS_PAST, rowqp_rows, rowqp_splits, rowqp_sizes, \
+    rowqp_inst_stride, rowqp_lds_rows, rowqp_per_cu
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ad_mpc_amd", "csrc")
 
@@ -23,6 +24,9 @@ def _body(src, fn):
 def test_mirrored_launch_line_is_the_librarys(fname, fn, line):
     with open(os.path.join(CSRC, fname)) as f:
         src = f.read()
+    if not fn:                                                   # a definition at file scope
+        assert re.search(r"^%s\s*$" % re.escape(line), src, re.M), "%s no longer holds `%s`: update tests/batch_regimes.py" % (fname, line)
+        return
     assert line in _body(src, fn), "%s:%s no longer holds `%s`: update tests/batch_regimes.py" % (fname, fn, line)
 
 
@@ -41,5 +45,12 @@ def test_sizes_sit_on_the_stated_side_of_every_switch():
                 assert not quad_tickets(g, quad_below(nc))
         assert quad_shoot_grid(nc, quad_past(nc)) < quad_past(nc)
         assert nlp_res_grid(nc, nlp_res_past(nc)) < nlp_res_past(nc)
+        if nc >= 38:
+            sz = rowqp_sizes(nc)
+            assert [rowqp_rows(nc, sz[k]) for k in ("rows1", "rows2", "rows4", "split")] == [1, 2, 4, 4]
+            assert [rowqp_splits(nc, sz[k], rowqp_rows(nc, sz[k])) for k in ("rows1", "rows2", "rows4", "split")] == [False, False, False, True]
+    # the footprint rowqp_rows / rowqp_splits assume holds at the horizon of the fp32 regime test, and the mirror knows where it ends
+    assert rowqp_inst_stride(20) == 656 and rowqp_lds_rows(20, 4) == 4 and rowqp_per_cu(20, 4, 4) == 4
+    assert rowqp_lds_rows(128, 8) == 4 and rowqp_per_cu(128, 8, 4) == 1 and rowqp_per_cu(80, 4, 4) == 4 and rowqp_per_cu(128, 4, 4) == 2
     assert waypoints_grid(WAYPOINTS_PAST) < WAYPOINTS_PAST and waypoints_grid(4096) == 4096
 
