@@ -40,11 +40,17 @@ class FleetStep(NamedTuple):
 
 
 class FleetController:
-    def __init__(self, t_horizon, n_mpc_nodes, opt_dt, B, device=0, resample=True, threshold=SAFE_COUNT_THRESHOLD):
+    def __init__(self, t_horizon, n_mpc_nodes, opt_dt, B, device=0, resample=True, threshold=SAFE_COUNT_THRESHOLD, blend_min=None,
+                 blend_max=None):
+        """``blend_min`` / ``blend_max`` (None: the vehicle's, ad_3d.py) are the ends of the speed band of vel_switch."""
         N, B = int(n_mpc_nodes), int(B)
         if B < 1:
             raise ValueError("B must be positive")
         self.ad = ad = AD3D(noisy=False, noisy_input=False)            # create_ros_ad_mpc.py:26-38
+        if blend_min is not None:
+            ad.blend_min = float(blend_min)
+        if blend_max is not None:
+            ad.blend_max = float(blend_max)
         cfg = ocp_config(ad, t_horizon, N, np.array(_c.Q_DIAG_ROS), np.array(_c.R_DIAG_ROS), "SQP_RTI")
         self._eng = eng = BatchSolver(cfg, device=device)
         self.lib, self.device = eng.lib, eng.device

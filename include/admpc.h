@@ -351,6 +351,9 @@ int admpc_waypoints_batch(int device, int M, int H, double dt, int B,
  * Deliberate deviation from the node: it clamps the speed of the GLOBAL path once per waypoint message at the speed the vehicle had
  * then (:351-368); vehicles at different speeds cannot share that, so the clamp runs on each vehicle's local window at its current
  * speed (admpc_resample_vel_batch).  AdmpcStepParams.resample = 0 turns it off.
+ * The end of the path: admpc_waypoints_batch writes out_stop into the step's workspace and nothing reads it.  The step does not act
+ * on the end of the path, as the node does not: it takes x_ref, y_ref, psi_ref and v_ref from the waypoint dictionary (:422-425) and
+ * never looks at its 'stop' entry (ref_traj.py:151-153).  A caller that has to stop at the end of the path decides that itself.
  * No host synchronisation and no allocation once admpc_reserve(s, B) has run: the chain can be captured into a graph. */
 typedef struct AdmpcPath {
     int32_t M;                 /* waypoints of the global path (>= 2); 0 = unset                                        */

@@ -38,6 +38,10 @@ LAUNCH_LINES = (
     ("admpc_rowqp.hip", "admpc_rowqp_plan", "while (r > 1 && (B + r - 1) / r < num_cu * 4 && (B + r / 2 - 1) / (r / 2) <= num_cu * 4) r >>= 1;"),
     ("admpc_rowqp.hip", "admpc_rowqp_plan", "if (per_cu > 4) per_cu = 4;"),
     ("admpc_kernels.hip", "rowqp_split", "return (s->split_mode == 1 || nquads > grid) ? s->d_split : nullptr;"),
+    # appended, never inserted: the position of an entry is part of its test's id
+    ("admpc_step.hip", "admpc_control_step_batch", "hipLaunchKernelGGL(admpc_step_command_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE)"),
+    ("admpc_step.hip", "admpc_step_command_kernel", "for (int b = blockIdx.x; b < B; b += gridDim.x) {"),
+    ("admpc_step.hip", "admpc_control_step_batch", "const long nP = (long)B * (N + 1);"),
 )
 
 
@@ -122,6 +126,14 @@ def nlp_res_past(nc):
 
 
 WAYPOINTS_PAST = 2 * 4096 + 901
+
+
+def command_grid(B):
+    """admpc_step_command_kernel (admpc_control_step_batch): one wave per vehicle up to 65536 workgroups, a stride loop past it."""
+    return min(B, 65536)
+
+
+COMMAND_PAST = 65536 + 300
 
 
 # ---- kernel R (admpc_rowqp_plan, rowqp_split).  rowqp_rows / rowqp_splits assume a horizon whose LDS footprint allows four instances per

@@ -7,7 +7,7 @@ import pytest
 
 from batch_regimes import LAUNCH_LINES, f_grid, s_grid, quad_grid, quad_tickets, quad_shoot_grid, nlp_res_grid, waypoints_grid, \
     s_below, s_past, f_past, quad_below, quad_past, nlp_res_past, WAYPOINTS_PAST, rowqp_rows, rowqp_splits, rowqp_sizes, \
-    rowqp_inst_stride, rowqp_lds_rows, rowqp_per_cu
+    rowqp_inst_stride, rowqp_lds_rows, rowqp_per_cu, command_grid, COMMAND_PAST
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ad_mpc_amd", "csrc")
 
@@ -53,4 +53,5 @@ def test_sizes_sit_on_the_stated_side_of_every_switch():
     assert rowqp_inst_stride(20) == 656 and rowqp_lds_rows(20, 4) == 4 and rowqp_per_cu(20, 4, 4) == 4
     assert rowqp_lds_rows(128, 8) == 4 and rowqp_per_cu(128, 8, 4) == 1 and rowqp_per_cu(80, 4, 4) == 4 and rowqp_per_cu(128, 4, 4) == 2
     assert waypoints_grid(WAYPOINTS_PAST) < WAYPOINTS_PAST and waypoints_grid(4096) == 4096
+    assert command_grid(COMMAND_PAST) < COMMAND_PAST and command_grid(COMMAND_PAST // 2) == COMMAND_PAST // 2 and COMMAND_PAST % 2 == 0
 
