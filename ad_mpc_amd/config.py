@@ -165,7 +165,8 @@ def set_gp(cfg, gps):
         feats = [int(f) for f in np.atleast_1d(d["feat"]).reshape(-1)]
         nf = len(feats)
         al = np.asarray(d["alpha"], dtype=np.float64).reshape(-1)
-        Z = np.asarray(d["Z"], dtype=np.float64).reshape(al.size, -1)
+        Z = np.asarray(d["Z"], dtype=np.float64)
+        Z = Z.reshape(al.size, -1) if al.size else Z.reshape(0, nf)      # no training point (the mean is ymean): nothing to infer a width from
         ell = np.broadcast_to(np.asarray(d["length_scale"], dtype=np.float64).reshape(-1), (nf,)) if np.size(d["length_scale"]) in (1, nf) else None
         if not (1 <= nf <= GP_MAX_FEAT) or Z.shape[1] != nf or ell is None or al.size > GP_MAX_POINTS:
             raise ValueError("bad GP size")

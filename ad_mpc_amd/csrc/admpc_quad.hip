@@ -114,7 +114,9 @@ __device__ __forceinline__ void quad_f_tan(const Cfg* __restrict__ c, const doub
             for (int i = 0; i < gp.n_points; ++i) {
                 double e = 0, de = 0;
 #pragma unroll
-                for (int k = 0; k < ADMPC_GP_MAX_FEAT; ++k) { const double dzk = zf[k] - gp.Z[k][i]; e += dzk * dzk * il[k]; de += dzk * il[k] * dzf[k]; }
+                for (int k = 0; k < ADMPC_GP_MAX_FEAT; ++k) {      // unused feature: difference 0, whatever the caller left in Z[k]
+                    const double dzk = k < gp.n_feat ? zf[k] - gp.Z[k][i] : 0.0; e += dzk * dzk * il[k]; de += dzk * il[k] * dzf[k];
+                }
                 const double ka = gp.sigma_f * exp(-0.5 * e) * gp.alpha[i];
                 m += ka; dm -= ka * de;
             }

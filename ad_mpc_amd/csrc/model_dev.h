@@ -75,9 +75,11 @@ __device__ __forceinline__ void gp_eval(const AdmpcGp& g, const T (&z)[ADMPC_GP_
             d0 -= ka * e0 * il0;
         }
     } else {
-        const T il1 = (T)g.inv_l2[1], il2 = nf > 2 ? (T)g.inv_l2[2] : (T)0;   // unused feature: weight 0
+        // unused feature: difference 0 and weight 0 (a weight alone would turn a NaN or a huge value in the caller's unused Z[2] into NaN)
+        const bool f2 = nf > 2;
+        const T il1 = (T)g.inv_l2[1], il2 = f2 ? (T)g.inv_l2[2] : (T)0;
         for (int i = sub; i < n; i += 3) {
-            const T e0 = z[0] - (T)g.Z[0][i], e1 = z[1] - (T)g.Z[1][i], e2 = z[2] - (T)g.Z[2][i];
+            const T e0 = z[0] - (T)g.Z[0][i], e1 = z[1] - (T)g.Z[1][i], e2 = f2 ? z[2] - (T)g.Z[2][i] : (T)0;
             const T ka = sf * exp_nonpos((T)-0.5 * (e0 * e0 * il0 + e1 * e1 * il1 + e2 * e2 * il2)) * (T)g.alpha[i];
             m += ka;
             d0 -= ka * e0 * il0; d1 -= ka * e1 * il1; d2 -= ka * e2 * il2;

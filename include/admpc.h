@@ -81,7 +81,9 @@ extern "C" {
  * f[out] += mu(z),  z_d = [x;u][feat[d]]
  *   mu(z) = ymean + sum_i sigma_f * exp(-0.5 * sum_d (z_d - Z[d][i])^2 * inv_l2[d]) * alpha_i
  * (model_fitting/gp.py:81-138,446-471 -- note sigma_f is NOT squared, gp.py:138;
- *  B_z/B_x selection matrices utils/utils.py:773-808; wiring quad_3d_optimizer.py:289-327) */
+ *  B_z/B_x selection matrices utils/utils.py:773-808; wiring quad_3d_optimizer.py:289-327)
+ * Entries beyond n_feat (feat, inv_l2, Z[d][.]) and beyond n_points (Z[.][i], alpha[i]), and the GPs beyond n_gp, are ignored and need
+ * not be initialised.  n_points = 0 is admitted: the mean is ymean. */
 typedef struct AdmpcGp {
     int32_t n_feat;                     /* 1 .. ADMPC_GP_MAX_FEAT (x_features + u_features of the saved regressor, gp.py:495-508) */
     int32_t feat[ADMPC_GP_MAX_FEAT];    /* indices into [x(7);u(2)], each in {3..8}: v_x v_y psi_dot delta a delta_dot */
