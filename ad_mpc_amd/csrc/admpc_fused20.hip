@@ -39,6 +39,8 @@
 //     that changes waves pays ~6 us of dependent trips to the memory side (queue scan, pop, entry, du; the instance's inputs miss the
 //     other XCD's L2) on a 15 us job, more than the shorter ramp returns.  With ONE queue the counter line was the bottleneck
 //     (same-line atomics retire at ~10 ns: 35 % slower), and compare-and-swap pops took 35 ms per step.
+//   - the expansion's LDS reads where hipcc puts them, three waits for reads of its own stage in every stage of the recursion: 40 % more
+//     wave time in phase E on a lone wave, 1.2 % per step at configs[1] (profiles/r4/f20_expand_ring.txt).
 //   - wave-priority classes, a reversed ticket order for the second wave of a SIMD, a trap on the never-taken side of the per-stage
 //     block test, other rungs of the priority ladder (see phase D for the measured ones).
 #include <hip/hip_runtime.h>
@@ -92,7 +94,7 @@ __device__ unsigned long long g_f20_ticks[16];
 //   A   JT [0, 1960) Jacobian tables of the RK stages (over GT, H/L, park; clear of bl and the scheduler table); GT is written when the
 //       tables are dead
 //   C   dq [860, 1008), gam [1008, 1520) in the H/L buffer (dead until the row store of H behind the last stage)
-//   E   dq -> dx [860, 1008), du [1008, 1072) in the H/L buffer (dead behind the interior point)
+//   E   dq -> dx [860, 1008), du [1008, 1072), dump [1072, 1276) in the H/L buffer (dead behind the interior point)
 // Banks: the tables keep stride 98; GT, dq, gam keep their offsets; H/L moves by 840 doubles as a whole (16-byte aligned: the
 // LDS-DMA destination), which keeps the triangular row starts' conflict-free pattern.
 struct FusedLds {
@@ -104,9 +106,11 @@ struct FusedLds {
     static constexpr int JTS = 24, JTK = 4 * JTS + 2;                   // Jacobian entries per (stage, RK stage); doubles per stage: 98, not 96 --
                                                                         // 768 B apart the 20 stages of a table access all hit one bank group
     static constexpr int oJT = 0, oDqC = 860, oGam = oDqC + 148;
+    static constexpr int oDumpE = oGam + 64;                            // phase E: where lanes that hold no state store (behind du, per stage + 7)
     static_assert(oJT + N * JTK <= oBl, "LDS aliases: phase A's tables end before bl and the scheduler table");
     static_assert(oGT + N * GTS <= oH, "LDS aliases: GT survives phases C, D, E (clear of H/L, park and the exchange buffers)");
     static_assert(oDqC >= oH && oDqC + (N + 1) * NX <= oGam && oGam + (NX + 1) * 64 <= oH + NTRI, "LDS aliases: dq, gam (phase C), dx, du (phase E) inside H/L");
+    static_assert(oDumpE >= oGam + 64 && oDumpE + 64 + N * NX <= oH + NTRI, "LDS aliases: phase E's dump area behind du, inside H/L");
     static_assert(oBl >= oCb + 4 * 64 && oBl + N * NX <= oSch && oSch + 64 <= total, "LDS aliases: bl, scheduler table");
     static_assert(oH % 2 == 0 && oCb % 2 == 0, "16-byte alignment: LDS-DMA destination, double2 exchange");
     static_assert(8 * total * 8 <= 160 * 1024, "eight instances per CU");
@@ -787,29 +791,59 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             WSYNC();
             bool bad = false;
             double J = 0.0;
-            static_for<0, N + 1>([&](auto kc) __attribute__((always_inline)) {
+            // Nothing a stage reads from LDS depends on the recursion: du, b_k and GT are final, and slot k of dq is read before dx_k
+            // goes into it.  The operands of stage k are therefore read E_AHEAD stages ahead of it into a register ring (stage j issues the
+            // reads of stage j + E_AHEAD in front of its own arithmetic; LDS answers in order, so the wait in front of stage k's arithmetic
+            // is an lgkmcnt(n) that leaves the younger reads in flight): the chain dx_k -> dx_{k+1} -- a select, two adds, five
+            // v_fmac_f64_dpp, two selects -- never waits for a read of its own stage.  Left to hipcc every stage issued its reads and waited
+            // for them three times in a row, ~60 dependent LDS round trips per instance.  Every lane stores its dx (lanes >= 7 into a dump
+            // area): a store under an EXEC mask made every stage a basic block of its own.  The sched_barriers keep each stage's reads and
+            // the chain dx_k -> dx_{k+1} in their stage.  What is not on the chain hipcc sinks behind the recursion: the cost terms (e, J) and the
+            // 21 tests of `bad` run there on the 21 dq and 21 dx register pairs it keeps live across the recursion (as in the build before the ring;
+            // phase D's 248 VGPRs remain the kernel's peak, no spill).
+            // One stage ahead: 7 reads of stage k, the store of stage k - 1 and 7 reads of stage k + 1 are 15 LDS instructions in flight, the most
+            // lgkmcnt can count -- two stages ahead saturates the counter (the waits then cover younger reads too) and measured the same.
+            constexpr int E_AHEAD = 1, E_RING = E_AHEAD + 1;
+            struct ERing { double dq, bk, g[5], b0, b1, u0, u1; };
+            ERing ring[E_RING];
+            const int sidx = lane < NX ? FusedLds::oDqC + lane : FusedLds::oDumpE + lane;
+            auto e_read = [&](auto kc) __attribute__((always_inline)) {
                 constexpr int k = decltype(kc)::value;
-                const double e = dx + dqE[k * 7 + r7];
-                J += 0.5 * (k < N ? wq : wqe) * e * e;
-                if (!(fabs(dx) <= 1e300)) bad = true;
-                if (lane < NX) dqE[k * 7 + lane] = dx;            // slot k now holds dx_k
+                ERing& r = ring[k % E_RING];
+                r.dq = dqE[k * 7 + r7];
                 if constexpr (k < N) {
                     const double* Gk = GT + k * GTS;
-                    const double u0 = dus[2 * k], u1 = dus[2 * k + 1];
                     // rows 0..5 from the packed record; every lane loads (lanes >= 6 read row 0 and drop the result): seven loads under their
                     // own EXEC masks were 18 scalar instructions per stage.  Row 6 of [A B] is [e6, 0, h]: one multiply-add in lane 6.
-                    const double bk = bl[k * 7 + r7];
-                    double acc = bk + (lane < 2 ? dx : 0.0);
-                    double gg[5];
+                    r.u0 = dus[2 * k]; r.u1 = dus[2 * k + 1];
+                    r.bk = bl[k * 7 + r7];
 #pragma unroll
-                    for (int c = 0; c < 5; ++c) gg[c] = Gk[c * 6 + r6];
-                    const double b0 = Gk[5 * 6 + r6], b1 = Gk[6 * 6 + r6];
+                    for (int c = 0; c < 5; ++c) r.g[c] = Gk[c * 6 + r6];
+                    r.b0 = Gk[5 * 6 + r6]; r.b1 = Gk[6 * 6 + r6];
+                }
+            };
+            static_for<0, E_AHEAD>([&](auto kc) __attribute__((always_inline)) { e_read(kc); });
+            __builtin_amdgcn_sched_barrier(0);
+            static_for<0, N + 1>([&](auto kc) __attribute__((always_inline)) {
+                constexpr int k = decltype(kc)::value;
+                if constexpr (k + E_AHEAD <= N) e_read(std::integral_constant<int, (k + E_AHEAD <= N ? k + E_AHEAD : N)>{});
+                __builtin_amdgcn_sched_barrier(0);
+                const ERing& r = ring[k % E_RING];
+                const double e = dx + r.dq;
+                J += 0.5 * (k < N ? wq : wqe) * e * e;
+                if (!(fabs(dx) <= 1e300)) bad = true;
+                lds_raw[sidx + k * 7] = dx;                       // slot k now holds dx_k
+                if constexpr (k < N) {
+                    const double u0 = r.u0, u1 = r.u1, bk = r.bk, b0 = r.b0, b1 = r.b1;
+                    double acc = bk + (lane < 2 ? dx : 0.0);
                     acc += b0 * u0 + b1 * u1;
                     const double acc6 = fma(h, u1, bk + dx);
-                    fmac_rowbc<2>(acc, dx, gg[0]); fmac_rowbc<3>(acc, dx, gg[1]); fmac_rowbc<4>(acc, dx, gg[2]);
-                    fmac_rowbc<5>(acc, dx, gg[3]); fmac_rowbc<6>(acc, dx, gg[4]);
+                    // (the pad of the first multiply-add covers the write of dx; the others follow it through acc)
+                    fmac_rowbc<2>(acc, dx, r.g[0]); fmac_rowbc_ld<3>(acc, dx, r.g[1]); fmac_rowbc_ld<4>(acc, dx, r.g[2]);
+                    fmac_rowbc_ld<5>(acc, dx, r.g[3]); fmac_rowbc_ld<6>(acc, dx, r.g[4]);
                     dx = lane < 6 ? acc : (lane == 6 ? acc6 : 0.0);
                 }
+                __builtin_amdgcn_sched_barrier(0);
             });
             int tk_e = -1;                                                // the list entry of the next ticket: loaded under the output stores
             if (cap != 0) {
