@@ -9,28 +9,39 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import AdmpcConfig, NX, NU, NY, default_config
+from .config import NX, NU, NY, default_config, set_gp
+from .quad_config import QNX, QNU, QNY, default_quad_config, set_quad_gp
 
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def packed_layout(fields_in, fields_out):
+    """Layout of a staging buffer: every field of ``(name, shape)`` on a 32-double (256-byte) boundary, like an allocation of its own, the
+    inputs first.  Returns ({name: (offset, count)} in doubles, the length of the input part, the total length)."""
+    off, o = {}, 0
+    for k, shp in tuple(fields_in) + tuple(fields_out):
+        n = int(np.prod(shp)); off[k] = (o, n); o += -(-n // 32) * 32
+    return off, (off[fields_out[0][0]][0] if fields_out else o), o
+
+
 class PackedIO:
     """Staging for a single-instance solve through the reference-shaped host classes: every input in ONE pinned host buffer / ONE device buffer
-    (each field on a 256-byte boundary, handed to the engine as a contiguous view), every float output behind them, the status words in a pair of
-    int32 -- a solve is one copy up, the kernels, one copy down (+ the status pair), one stream synchronisation.  (A tensor per field, each with a
-    copy of its own, was 0.2 ms of a 0.58 ms control step of the car.)"""
+    (each field on a 256-byte boundary, handed to the engine as a contiguous view or as its address), every float output behind them, the status
+    words in a pair of int32 -- a solve is one copy up, the kernels, one copy down (+ the status pair), one stream synchronisation.  (A tensor per
+    field, each with a copy of its own, was 0.2 ms of a 0.58 ms control step of the car.)"""
 
     def __init__(self, device, fields_in, fields_out, n_int=2):
         self.device = device
-        self.shape, self.off, o = {}, {}, 0
-        for k, shp in tuple(fields_in) + tuple(fields_out):
-            n = int(np.prod(shp)); self.shape[k] = tuple(shp); self.off[k] = (o, n); o += -(-n // 32) * 32
-        self.n_in = self.off[fields_out[0][0]][0] if fields_out else o
+        self.shape = {k: tuple(shp) for k, shp in tuple(fields_in) + tuple(fields_out)}
+        self.off, self.n_in, o = packed_layout(fields_in, fields_out)
         self.hbuf = torch.zeros(o, dtype=torch.float64).pin_memory(); self.dbuf = torch.zeros(o, dtype=torch.float64, device=device)
         self.hint = torch.zeros(n_int, dtype=torch.int32).pin_memory(); self.dint = torch.zeros(n_int, dtype=torch.int32, device=device)
         self.h, self.hi = self.hbuf.numpy(), self.hint.numpy()
+        # device addresses, computed once: of every field (a caller of the C ABI needs no view per call) and of the int32 words
+        self.ptr = {k: C.c_void_p(self.dbuf.data_ptr() + 8 * o) for k, (o, n) in self.off.items()}
+        self.iptr = tuple(C.c_void_p(self.dint.data_ptr() + 4 * i) for i in range(n_int))
 
     def put(self, k, a):
         o, n = self.off[k]; self.h[o:o + n] = np.asarray(a, dtype=np.float64).reshape(-1)
@@ -51,24 +62,24 @@ class PackedIO:
         torch.cuda.current_stream(self.device).synchronize()
 
 
-class BatchSolver:
-    """One solver object per (config, device).  Replaces the AcadosOcpSolver object of
-    ad_3d_optimizer.py:209 for a whole batch of independent MPC instances."""
+class _Handle:
+    """A library handle on one device: created from a config by the library function named ``create``, destroyed by ``destroy``."""
 
-    def __init__(self, cfg=None, device=0):
+    def __init__(self, create, destroy, cfg, device):
         if not torch.cuda.is_available():
             raise _lib.AdmpcError("no HIP device visible: the AD-MPC engine has no CPU fallback")
         self.lib = _lib.load()
-        self.cfg = (cfg if cfg is not None else default_config()).copy()
+        self.cfg = cfg.copy()
         self.device_index = int(device)
         self.device = torch.device("cuda", self.device_index)
+        self._destroy = getattr(self.lib, destroy)
         h = C.c_void_p(0)
-        _lib.check(self.lib.admpc_create(C.byref(self.cfg), self.device_index, C.byref(h)))
+        _lib.check(getattr(self.lib, create)(C.byref(self.cfg), self.device_index, C.byref(h)))
         self._h = h
 
     def close(self):
         if getattr(self, "_h", None):
-            self.lib.admpc_destroy(self._h)
+            self._destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -77,7 +88,6 @@ class BatchSolver:
         except Exception:
             pass
 
-    # -- helpers -------------------------------------------------------------------------------
     @property
     def N(self):
         return int(self.cfg.N)
@@ -92,23 +102,38 @@ class BatchSolver:
             raise ValueError("expected contiguous %s tensor of shape %s on %s, got %s %s on %s"
                              % (dtype, tuple(shape), self.device, t.dtype, tuple(t.shape), t.device))
 
+    def _chk_outputs(self, B, dt, cost, status, iters):
+        if cost is not None: self._chk(cost, (B,), dt)
+        if status is not None: self._chk(status, (B,), torch.int32)
+        if iters is not None: self._chk(iters, (B,), torch.int32)
+
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+
+class BatchSolver(_Handle):
+    """One solver object per (config, device).  Replaces the AcadosOcpSolver object of
+    ad_3d_optimizer.py:209 for a whole batch of independent MPC instances."""
+
+    def __init__(self, cfg=None, device=0):
+        super().__init__("admpc_create", "admpc_destroy", cfg if cfg is not None else default_config(), device)
+
+    def _chk_solve(self, B, dt, x0, yref, yref_e, p, xbar, ubar, cost=None, status=None, iters=None):
+        """The arguments every solve entry of the car shares."""
+        N = self.N
+        self._chk(x0, (B, NX), dt); self._chk(yref, (B, N, NY), dt); self._chk(yref_e, (B, NX), dt); self._chk(p, (B,), dt)
+        self._chk(xbar, (B, N + 1, NX), dt); self._chk(ubar, (B, N, NU), dt)
+        self._chk_outputs(B, dt, cost, status, iters)
 
     # -- the hot path --------------------------------------------------------------------------
     def solve(self, x0, yref, yref_e, p, xbar, ubar, cost=None, status=None, iters=None):
         """One SQP-RTI step for every instance, in place on xbar/ubar (device tensors).  Asynchronous.
         The dtype of x0 selects the path: float64 (admpc_solve_batch) or float32 (admpc_solve_batch_f32, storage and compute)."""
-        N = self.N
         B = x0.shape[0]
         dt = x0.dtype
         if dt not in (torch.float64, torch.float32):
             raise ValueError("x0 must be float64 or float32")
-        self._chk(x0, (B, NX), dt); self._chk(yref, (B, N, NY), dt); self._chk(yref_e, (B, NX), dt); self._chk(p, (B,), dt)
-        self._chk(xbar, (B, N + 1, NX), dt); self._chk(ubar, (B, N, NU), dt)
-        if cost is not None: self._chk(cost, (B,), dt)
-        if status is not None: self._chk(status, (B,), torch.int32)
-        if iters is not None: self._chk(iters, (B,), torch.int32)
+        self._chk_solve(B, dt, x0, yref, yref_e, p, xbar, ubar, cost, status, iters)
         fn = self.lib.admpc_solve_batch if dt == torch.float64 else self.lib.admpc_solve_batch_f32
         _lib.check(fn(self._h, B, _ptr(x0), _ptr(yref), _ptr(yref_e), _ptr(p), _ptr(xbar), _ptr(ubar),
                       _ptr(cost), _ptr(status), _ptr(iters), self._stream()))
@@ -117,8 +142,7 @@ class BatchSolver:
         """admpc_solve_batch_ex (float64): the step plus pi [B,N+1,7] and ineq [B,N,20] (see include/admpc.h)."""
         N = self.N
         B = x0.shape[0]
-        self._chk(x0, (B, NX)); self._chk(yref, (B, N, NY)); self._chk(yref_e, (B, NX)); self._chk(p, (B,))
-        self._chk(xbar, (B, N + 1, NX)); self._chk(ubar, (B, N, NU))
+        self._chk_solve(B, torch.float64, x0, yref, yref_e, p, xbar, ubar, cost, status, iters)
         pi = torch.empty((B, N + 1, NX), dtype=torch.float64, device=self.device)
         ineq = torch.empty((B, N, 20), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.admpc_solve_batch_ex(self._h, B, _ptr(x0), _ptr(yref), _ptr(yref_e), _ptr(p), _ptr(xbar), _ptr(ubar),
@@ -130,8 +154,8 @@ class BatchSolver:
         (xbar, ubar) with the multipliers solve_with_multipliers returned for it (AcadosOcpSolver.get_residuals())."""
         N = self.N
         B = x0.shape[0]
-        self._chk(x0, (B, NX)); self._chk(yref, (B, N, NY)); self._chk(yref_e, (B, NX)); self._chk(p, (B,))
-        self._chk(xbar, (B, N + 1, NX)); self._chk(ubar, (B, N, NU)); self._chk(pi, (B, N + 1, NX)); self._chk(ineq, (B, N, 20))
+        self._chk_solve(B, torch.float64, x0, yref, yref_e, p, xbar, ubar)
+        self._chk(pi, (B, N + 1, NX)); self._chk(ineq, (B, N, 20))
         res = torch.empty((B, 4), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.admpc_nlp_residuals_batch(self._h, B, _ptr(x0), _ptr(yref), _ptr(yref_e), _ptr(p), _ptr(xbar), _ptr(ubar),
                                                       _ptr(pi), _ptr(ineq), _ptr(res), self._stream()))
@@ -252,26 +276,18 @@ class BatchSolver:
                                                      C.c_void_p(vel_ref.data_ptr()), self._stream()))
 
 
-class EnsembleBatchSolver:
-    """Clustered GP ensembles (SURVEY 8f-4; reference: one AcadosOcpSolver per cluster, quad_3d_optimizer.py:207, chosen per
-    solve by GPEnsemble.select_gp, :452 / :491).  One engine handle per cluster; selection and routing are HIP kernels of the
-    library (admpc_select_cluster_batch, admpc_solve_batch_routed): no gather / scatter, no host synchronisation -- every
-    handle runs over the whole batch and leaves the instances of the other clusters alone.  ``ensemble``: gp_loader.GPEnsemble."""
+class _Ensemble:
+    """One handle per cluster on one device, the centroids K x d in the features ``feats``; selection and routing are HIP kernels of the
+    library (no gather / scatter, no host synchronisation): every handle runs over the whole batch and leaves the instances of the other
+    clusters alone.  A subclass names its model: _SOLVER, _DIMS = (nx, nu) and _SELECT, the library's selection function."""
 
-    def __init__(self, cfg, ensemble, device=0):
-        from .config import set_gp
-        self.ensemble = ensemble
-        self.solvers = []
-        for c in range(ensemble.n_models):
-            cc = cfg.copy()
-            set_gp(cc, ensemble.clusters[c])
-            self.solvers.append(BatchSolver(cc, device=device))
-        self.lib = self.solvers[0].lib
-        self.device = self.solvers[0].device
-        self.device_index = self.solvers[0].device_index
-        self.N = self.solvers[0].N
-        self._cent = torch.as_tensor(np.ascontiguousarray(ensemble.centroids, dtype=np.float64), device=self.device).contiguous()      # K x d
-        feats = [int(f) for f in np.atleast_1d(ensemble.feats)]
+    def __init__(self, cfgs, centroids, feats, device):
+        self.solvers = [self._SOLVER(c, device=device) for c in cfgs]
+        s0 = self.solvers[0]
+        self.lib, self.device, self.device_index, self.N = s0.lib, s0.device, s0.device_index, s0.N
+        cent = np.ascontiguousarray(np.asarray(centroids, dtype=np.float64).reshape(len(self.solvers), -1))
+        self._cent = torch.as_tensor(cent, device=self.device).contiguous()      # K x d
+        feats = [int(f) for f in np.atleast_1d(feats)]
         self._feats = (C.c_int32 * len(feats))(*feats)
         self._handles = (C.c_void_p * len(self.solvers))(*[sv._h for sv in self.solvers])
 
@@ -280,90 +296,79 @@ class EnsembleBatchSolver:
             s.close()
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return self.solvers[0]._stream()
 
     def select(self, x_sel, u_sel, route=None):
-        """Cluster of every instance from the state / input the caller selects on (the reference passes the reference state and
-        the input target): nearest centroid of the ensemble's feature, ties to the lowest index.  float64 [B,7] / [B,2] device
-        tensors in, int32 [B] device tensor out.  Asynchronous."""
+        """Cluster of every instance from the state [B,nx] / input [B,nu] the caller selects on (the reference passes the reference state
+        and the input target): nearest centroid of the ensemble's features, ties to the lowest index.  float64 device tensors in (row
+        views such as ubar[:, 0, :] are welcome), int32 [B] device tensor out.  Asynchronous."""
         B = x_sel.shape[0]
         sv = self.solvers[0]
-        x_sel, u_sel = x_sel.contiguous(), u_sel.contiguous()           # row views (e.g. ubar[:, 0, :]) are welcome
-        sv._chk(x_sel, (B, NX)); sv._chk(u_sel, (B, NU))
+        nx, nu = self._DIMS
+        x_sel, u_sel = x_sel.contiguous(), u_sel.contiguous()
+        sv._chk(x_sel, (B, nx)); sv._chk(u_sel, (B, nu))
         if route is None:
             route = torch.empty(B, dtype=torch.int32, device=self.device)
         sv._chk(route, (B,), torch.int32)
-        _lib.check(self.lib.admpc_select_cluster_batch(self.device_index, B, len(self._feats), self._feats, _ptr(x_sel), _ptr(u_sel),
-                                                       int(self._cent.shape[0]), _ptr(self._cent), _ptr(route), self._stream()))
+        _lib.check(getattr(self.lib, self._SELECT)(self.device_index, B, len(self._feats), self._feats, _ptr(x_sel), _ptr(u_sel),
+                                                   int(self._cent.shape[0]), _ptr(self._cent), _ptr(route), self._stream()))
         return route
+
+    def _route(self, gp_ind, B):
+        """The cluster index per instance as the library takes it: int32 [B] (int64 is converted)."""
+        if gp_ind.dtype != torch.int32:
+            gp_ind = gp_ind.to(torch.int32)
+        self.solvers[0]._chk(gp_ind, (B,), torch.int32)
+        return gp_ind
+
+
+class EnsembleBatchSolver(_Ensemble):
+    """Clustered GP ensembles (SURVEY 8f-4; reference: one AcadosOcpSolver per cluster, quad_3d_optimizer.py:207, chosen per
+    solve by GPEnsemble.select_gp, :452 / :491).  One engine handle per cluster; selection and routing are
+    admpc_select_cluster_batch and admpc_solve_batch_routed.  ``ensemble``: gp_loader.GPEnsemble."""
+    _SOLVER, _DIMS, _SELECT = BatchSolver, (NX, NU), "admpc_select_cluster_batch"
+
+    def __init__(self, cfg, ensemble, device=0):
+        self.ensemble = ensemble
+        cfgs = [cfg.copy() for _ in range(ensemble.n_models)]
+        for cc, gps in zip(cfgs, ensemble.clusters):
+            set_gp(cc, gps)
+        super().__init__(cfgs, ensemble.centroids, ensemble.feats, device)
 
     def solve(self, gp_ind, x0, yref, yref_e, p, xbar, ubar, cost=None, status=None, iters=None):
         """BatchSolver.solve with a cluster index per instance (int32 device tensor, e.g. from `select`; int64 is converted).  In place
         on xbar / ubar.  Asynchronous.  An index outside [0, K) gives status 4 and cost +inf for that instance."""
-        N, B = self.N, x0.shape[0]
-        sv = self.solvers[0]
-        if gp_ind.dtype != torch.int32:
-            gp_ind = gp_ind.to(torch.int32)
-        sv._chk(gp_ind, (B,), torch.int32)
-        sv._chk(x0, (B, NX)); sv._chk(yref, (B, N, NY)); sv._chk(yref_e, (B, NX)); sv._chk(p, (B,))
-        sv._chk(xbar, (B, N + 1, NX)); sv._chk(ubar, (B, N, NU))
-        if cost is not None: sv._chk(cost, (B,))
-        if status is not None: sv._chk(status, (B,), torch.int32)
-        if iters is not None: sv._chk(iters, (B,), torch.int32)
+        B = x0.shape[0]
+        gp_ind = self._route(gp_ind, B)
+        self.solvers[0]._chk_solve(B, torch.float64, x0, yref, yref_e, p, xbar, ubar, cost, status, iters)
         _lib.check(self.lib.admpc_solve_batch_routed(self._handles, len(self.solvers), B, _ptr(gp_ind), _ptr(x0), _ptr(yref), _ptr(yref_e), _ptr(p),
                                                      _ptr(xbar), _ptr(ubar), _ptr(cost), _ptr(status), _ptr(iters), self._stream()))
 
 
-class QuadBatchSolver:
+class QuadBatchSolver(_Handle):
     """The second vehicle model (include/admpc_quad.h): one SQP-RTI step of the reference's quadrotor MPC for a batch.
     Replaces the AcadosOcpSolver of quad_3d_optimizer.py:207 for B independent instances."""
 
     def __init__(self, cfg=None, device=0):
-        from .quad_config import default_quad_config
-        if not torch.cuda.is_available():
-            raise _lib.AdmpcError("no HIP device visible: the AD-MPC engine has no CPU fallback")
-        self.lib = _lib.load()
-        self.cfg = (cfg if cfg is not None else default_quad_config()).copy()
-        self.device_index = int(device)
-        self.device = torch.device("cuda", self.device_index)
-        h = C.c_void_p(0)
-        _lib.check(self.lib.admpc_quad_create(C.byref(self.cfg), self.device_index, C.byref(h)))
-        self._h = h
+        super().__init__("admpc_quad_create", "admpc_quad_destroy", cfg if cfg is not None else default_quad_config(), device)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.admpc_quad_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _chk(self, t, shape, dtype=torch.float64):
-        if t.dtype != dtype or not t.is_contiguous() or t.device != self.device or tuple(t.shape) != tuple(shape):
-            raise ValueError("expected contiguous %s tensor of shape %s on %s" % (dtype, tuple(shape), self.device))
+    def _chk_solve(self, B, x0, yref, yref_e, xbar, ubar, cost=None, status=None, iters=None, gp_state=None):
+        """The arguments every solve entry of the quadrotor shares."""
+        N = self.N
+        self._chk(x0, (B, QNX)); self._chk(yref, (B, N, QNY)); self._chk(yref_e, (B, QNX)); self._chk(xbar, (B, N + 1, QNX)); self._chk(ubar, (B, N, QNU))
+        self._chk_outputs(B, torch.float64, cost, status, iters)
+        if gp_state is not None: self._chk(gp_state, (B, QNX))
 
     def solve(self, x0, yref, yref_e, xbar, ubar, cost=None, status=None, iters=None, gp_state=None):
         """In place on xbar [B,N+1,13] / ubar [B,N,4] (float64 device tensors).  Asynchronous.  gp_state [B,13]: the first node's GP
         state (run_optimization's gp_regression_state); None: the initial state x0, the reference's default."""
-        from .quad_config import QNX, QNU, QNY
-        N, B = int(self.cfg.N), x0.shape[0]
-        self._chk(x0, (B, QNX)); self._chk(yref, (B, N, QNY)); self._chk(yref_e, (B, QNX)); self._chk(xbar, (B, N + 1, QNX)); self._chk(ubar, (B, N, QNU))
-        if cost is not None: self._chk(cost, (B,))
-        if status is not None: self._chk(status, (B,), torch.int32)
-        if iters is not None: self._chk(iters, (B,), torch.int32)
-        if gp_state is not None: self._chk(gp_state, (B, QNX))
+        B = x0.shape[0]
+        self._chk_solve(B, x0, yref, yref_e, xbar, ubar, cost, status, iters, gp_state)
         _lib.check(self.lib.admpc_quad_solve_batch_ex(self._h, B, _ptr(x0), _ptr(yref), _ptr(yref_e), _ptr(gp_state), _ptr(xbar), _ptr(ubar),
                                                       _ptr(cost), _ptr(status), _ptr(iters), self._stream()))
 
     def shoot(self, xbar, ubar, gp_state=None):
-        from .quad_config import QNX, QNU
-        N, B = int(self.cfg.N), xbar.shape[0]
+        N, B = self.N, xbar.shape[0]
         self._chk(xbar, (B, N + 1, QNX)); self._chk(ubar, (B, N, QNU))
         if gp_state is not None: self._chk(gp_state, (B, QNX))
         phi = torch.empty((B, N, QNX), dtype=torch.float64, device=self.device)
@@ -383,63 +388,27 @@ class QuadBatchSolver:
         return tx.cpu().numpy(), tu.cpu().numpy(), cost.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()
 
 
-class QuadEnsembleBatchSolver:
+class QuadEnsembleBatchSolver(_Ensemble):
     """Clustered GP ensembles of the quadrotor (reference: one AcadosOcpSolver per cluster, quad_3d_optimizer.py:207, chosen per solve
-    from the reference state by GPEnsemble.select_gp, :446-452 / :485-491).  One handle per cluster; selection and routing are HIP
-    kernels of the library (admpc_quad_select_cluster_batch, admpc_quad_solve_batch_routed).  ``clusters[c]``: the ``set_quad_gp`` list
-    of cluster c; ``centroids`` K x d in the features ``feats`` (indices into z = [x with the velocity in the body frame; u])."""
+    from the reference state by GPEnsemble.select_gp, :446-452 / :485-491).  One handle per cluster; selection and routing are
+    admpc_quad_select_cluster_batch and admpc_quad_solve_batch_routed.  ``clusters[c]``: the ``set_quad_gp`` list of cluster c;
+    ``centroids`` K x d in the features ``feats`` (indices into z = [x with the velocity in the body frame; u]).  ``select`` takes the
+    reference state with its world-frame velocity: the kernel rotates it to the body frame as the reference does before select_gp."""
+    _SOLVER, _DIMS, _SELECT = QuadBatchSolver, (QNX, QNU), "admpc_quad_select_cluster_batch"
 
     def __init__(self, cfg, clusters, centroids, feats, device=0):
-        from .quad_config import set_quad_gp
-        self.solvers = []
-        for gps in clusters:
-            cc = cfg.copy()
+        cfgs = [cfg.copy() for _ in clusters]
+        for cc, gps in zip(cfgs, clusters):
             set_quad_gp(cc, gps)
-            self.solvers.append(QuadBatchSolver(cc, device=device))
-        s0 = self.solvers[0]
-        self.lib, self.device, self.device_index, self.N = s0.lib, s0.device, s0.device_index, int(s0.cfg.N)
-        self._cent = torch.as_tensor(np.ascontiguousarray(np.asarray(centroids, dtype=np.float64).reshape(len(clusters), -1)), device=self.device).contiguous()
-        feats = [int(f) for f in np.atleast_1d(feats)]
-        if self._cent.shape[1] != len(feats):
+        super().__init__(cfgs, centroids, feats, device)
+        if self._cent.shape[1] != len(self._feats):
             raise ValueError("centroids must be K x len(feats)")
-        self._feats = (C.c_int32 * len(feats))(*feats)
-        self._handles = (C.c_void_p * len(self.solvers))(*[sv._h for sv in self.solvers])
-
-    def close(self):
-        for s in self.solvers:
-            s.close()
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def select(self, x_sel, u_sel, route=None):
-        """Cluster of every instance from the reference state [B,13] (world-frame velocity: the kernel rotates it to the body frame as
-        the reference does before select_gp) and input target [B,4]; int32 [B] device tensor out.  Asynchronous."""
-        from .quad_config import QNX, QNU
-        B = x_sel.shape[0]
-        sv = self.solvers[0]
-        x_sel, u_sel = x_sel.contiguous(), u_sel.contiguous()
-        sv._chk(x_sel, (B, QNX)); sv._chk(u_sel, (B, QNU))
-        if route is None:
-            route = torch.empty(B, dtype=torch.int32, device=self.device)
-        sv._chk(route, (B,), torch.int32)
-        _lib.check(self.lib.admpc_quad_select_cluster_batch(self.device_index, B, len(self._feats), self._feats, _ptr(x_sel), _ptr(u_sel),
-                                                            int(self._cent.shape[0]), _ptr(self._cent), _ptr(route), self._stream()))
-        return route
 
     def solve(self, gp_ind, x0, yref, yref_e, xbar, ubar, cost=None, status=None, iters=None, gp_state=None):
         """QuadBatchSolver.solve with a cluster index per instance (int32 device tensor).  In place on xbar / ubar.  Asynchronous.
         An index outside [0, K) gives status 4 and cost +inf for that instance."""
-        from .quad_config import QNX, QNU, QNY
-        N, B = self.N, x0.shape[0]
-        sv = self.solvers[0]
-        if gp_ind.dtype != torch.int32:
-            gp_ind = gp_ind.to(torch.int32)
-        sv._chk(gp_ind, (B,), torch.int32)
-        sv._chk(x0, (B, QNX)); sv._chk(yref, (B, N, QNY)); sv._chk(yref_e, (B, QNX)); sv._chk(xbar, (B, N + 1, QNX)); sv._chk(ubar, (B, N, QNU))
-        if cost is not None: sv._chk(cost, (B,))
-        if status is not None: sv._chk(status, (B,), torch.int32)
-        if iters is not None: sv._chk(iters, (B,), torch.int32)
-        if gp_state is not None: sv._chk(gp_state, (B, QNX))
+        B = x0.shape[0]
+        gp_ind = self._route(gp_ind, B)
+        self.solvers[0]._chk_solve(B, x0, yref, yref_e, xbar, ubar, cost, status, iters, gp_state)
         _lib.check(self.lib.admpc_quad_solve_batch_routed(self._handles, len(self.solvers), B, _ptr(gp_ind), _ptr(x0), _ptr(yref), _ptr(yref_e), _ptr(gp_state),
                                                           _ptr(xbar), _ptr(ubar), _ptr(cost), _ptr(status), _ptr(iters), self._stream()))

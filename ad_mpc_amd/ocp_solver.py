@@ -7,7 +7,6 @@ the solve on the GPU through admpc_solve_batch (B = 1).  Like the acados object 
 iterate (initially all zeros, acados_solver_sim_car.c:705-731) that is never shifted or reset --
 unless the caller sets ``shift_iterate`` (off by default: an option the reference does not have).
 """
-import ctypes as C
 import json
 import os
 
@@ -16,7 +15,7 @@ import torch
 
 from . import _lib
 from .config import NX, NU, NY
-from .engine import BatchSolver
+from .engine import BatchSolver, PackedIO
 
 
 class AdmpcOcpSolver:
@@ -34,17 +33,10 @@ class AdmpcOcpSolver:
         self._qp_iter = 0
         self._cost = float("nan")
         self.shift_iterate = None                # None: keep the iterate as the reference does; "copy" / "rollout": shift before each solve
-        # One staging buffer on either side: a solve is ONE host-to-device copy (the measured state, the references, p, the iterate), the
-        # kernels, ONE copy back (iterate, cost, multipliers) plus the two status words -- pinned host memory, asynchronous on the solver's
-        # stream, one stream synchronisation.  (Six tensors up and seven down, each its own copy, were 0.2 ms of a 0.58 ms control step.)
-        fields = (("x0", NX), ("yref", N * NY), ("yref_e", NX), ("p", 1), ("x", (N + 1) * NX), ("u", N * NU), ("cost", 1), ("pi", (N + 1) * NX), ("ineq", N * 20))
-        self._off, o = {}, 0
-        for k, n in fields:
-            self._off[k] = (o, n); o += -(-n // 32) * 32          # every field on a 256-byte boundary, like an allocation of its own
-        dev = self._eng.device
-        self._hbuf = torch.zeros(o, dtype=torch.float64).pin_memory(); self._dbuf = torch.zeros(o, dtype=torch.float64, device=dev)
-        self._hint = torch.zeros(2, dtype=torch.int32).pin_memory(); self._dint = torch.zeros(2, dtype=torch.int32, device=dev)
-        self._hnp, self._hint_np = self._hbuf.numpy(), self._hint.numpy()
+        # One staging buffer on either side (engine.PackedIO): a solve is ONE host-to-device copy (the measured state, the references, p, the
+        # iterate), the kernels, ONE copy back (iterate, cost, multipliers) plus the two status words, one stream synchronisation.
+        self._io = PackedIO(self._eng.device, (("x0", (1, NX)), ("yref", (1, N, NY)), ("yref_e", (1, NX)), ("p", (1,)), ("x", (1, N + 1, NX)), ("u", (1, N, NU))),
+                            (("cost", (1,)), ("pi", (1, N + 1, NX)), ("ineq", (1, N, 20))))
 
     # ---- acados-style setters / getters -------------------------------------------------------
     def set(self, stage_, field_, value_):
@@ -115,30 +107,17 @@ class AdmpcOcpSolver:
             tx, tu, tp = d(self._x[None]).clone(), d(self._u[None]).clone(), d(np.array([self._p[0]]))
             self._eng.shift(tx, tu, tp, rollout=self.shift_iterate == "rollout")
             self._x, self._u = tx[0].cpu().numpy(), tu[0].cpu().numpy()
-        h, off = self._hnp, self._off
-        def put(k, a):
-            o, n = off[k]; h[o:o + n] = np.asarray(a, dtype=np.float64).reshape(-1)
-        put("x0", self._lbx0); put("yref", self._yref); put("yref_e", self._yref_e); h[off["p"][0]] = self._p[0]; put("x", self._x); put("u", self._u)
-        n_in, o_out = off["cost"][0], off["x"][0]
-        eng = self._eng
+        io, eng = self._io, self._eng
+        io.put("x0", self._lbx0); io.put("yref", self._yref); io.put("yref_e", self._yref_e); io.put("p", self._p[0]); io.put("x", self._x); io.put("u", self._u)
+        P = io.ptr
         with torch.cuda.device(eng.device):
-            stream = torch.cuda.current_stream(eng.device)
-            self._dbuf[:n_in].copy_(self._hbuf[:n_in], non_blocking=True)
-            base = self._dbuf.data_ptr()
-            P = lambda k: C.c_void_p(base + 8 * off[k][0])
-            ip = self._dint.data_ptr()
-            _lib.check(eng.lib.admpc_solve_batch_ex(eng._h, 1, P("x0"), P("yref"), P("yref_e"), P("p"), P("x"), P("u"), P("cost"),
-                                                    C.c_void_p(ip), C.c_void_p(ip + 4), P("pi"), P("ineq"), C.c_void_p(stream.cuda_stream)))
-            self._hbuf[o_out:].copy_(self._dbuf[o_out:], non_blocking=True)
-            self._hint.copy_(self._dint, non_blocking=True)
-            stream.synchronize()
-        def take(k, shape):
-            o, n = off[k]; return h[o:o + n].reshape(shape).copy()
-        st, it, cost = int(self._hint_np[0]), int(self._hint_np[1]), float(h[off["cost"][0]])
+            io.upload()
+            _lib.check(eng.lib.admpc_solve_batch_ex(eng._h, 1, P["x0"], P["yref"], P["yref_e"], P["p"], P["x"], P["u"], P["cost"],
+                                                    io.iptr[0], io.iptr[1], P["pi"], P["ineq"], eng._stream()))
+            io.download("x")
+        st, it, cost = int(io.hi[0]), int(io.hi[1]), float(io.h[io.off["cost"][0]])
         if st in (0, 2):     # acados leaves the iterate untouched only if the QP failed outright; status 2 (SQP limit) keeps the last iterate
-            N = self.N
-            self._x, self._u = take("x", (N + 1, NX)), take("u", (N, NU))
-            self._pi, self._ineq = take("pi", (N + 1, NX)), take("ineq", (N, 20))
+            self._x, self._u, self._pi, self._ineq = io.take("x")[0], io.take("u")[0], io.take("pi")[0], io.take("ineq")[0]
         self._status, self._qp_iter, self._cost = st, it, cost
         return self._status
 
