@@ -12,7 +12,7 @@ from .quad_config import AdmpcQuadConfig
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libadmpc.so")
 
-# Every prototype of include/admpc.h and include/admpc_quad.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
+# Every prototype of include/admpc.h, include/admpc_quad.h and include/admpc_fleet.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
 # _f32 entries), ip: to ints, vp: opaque (handle, stream, communicator) -- device pointers travel as integers, so all three are c_void_p.
 vp = dp = ip = C.c_void_p
 I, D, S = C.c_int, C.c_double, C.c_char_p
@@ -55,7 +55,14 @@ _QUAD = {
     "admpc_quad_shoot_batch": (I, [vp, I, dp, dp, dp, dp, dp, vp]),
     "admpc_quad_shoot_batch_ex": (I, [vp, I, dp, dp, dp, dp, dp, dp, vp]),
 }
-EXPORTS, QUAD_EXPORTS = tuple(_CAR), tuple(_QUAD)
+_FLEET = {      # include/admpc_fleet.h: a path per vehicle, the best of C candidate paths
+    "admpc_path_bank_create": (I, [I, I, C.POINTER(AdmpcPath), hp]),
+    "admpc_path_bank_destroy": (None, [vp]),
+    "admpc_waypoints_bank_batch": (I, [vp, I, ip] + [dp] * 3 + [dp, dp, ip] + [vp]),
+    "admpc_control_step_bank_batch": (I, [vp, vp, C.POINTER(AdmpcStepParams), I, ip] + [dp] * 7 + [dp] * 5 + [vp] + [dp] * 4 + [dp, vp]),
+    "admpc_argmin_groups": (I, [vp, dp, I, I, dp, ip, vp]),
+}
+EXPORTS, QUAD_EXPORTS, FLEET_EXPORTS = tuple(_CAR), tuple(_QUAD), tuple(_FLEET)
 
 _lib = None
 
@@ -65,7 +72,7 @@ class AdmpcError(RuntimeError):
 
 
 def load():
-    """dlopen libadmpc.so and declare the prototypes of include/admpc.h (no GPU needed for this)."""
+    """dlopen libadmpc.so and declare the prototypes of the three headers under include/ (no GPU needed for this)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -73,7 +80,7 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_CAR, **_QUAD}.items():
+    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -22,6 +22,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/admpc.h"
+#include "../../include/admpc_fleet.h"
 #include "argmin_rule.h"
 
 #define NX ADMPC_NX
@@ -110,105 +111,146 @@ __device__ __forceinline__ double interp_np(const double* __restrict__ xp, const
     return __dadd_rn(__dmul_rn(slope, __dsub_rn(x, xp[lo])), fp[lo]);
 }
 
-__global__ __launch_bounds__(WAVE) void admpc_waypoints_kernel(int M, int H, double dt, int B,
+// The ONE text of the generator: pose b against the path whose columns the caller hands in (the kernels below differ in where those
+// come from and in nothing else).  Called by every lane of the block's single wave; sh: WAVE doubles of LDS.
+__device__ __forceinline__ void waypoints_one(int M, int H, double dt, int b,
         const double* __restrict__ vel, const double* __restrict__ tx, const double* __restrict__ ty,
         const double* __restrict__ tpsi, const double* __restrict__ tpsi_unw, const double* __restrict__ cdist, const double* __restrict__ curv,
         const double* __restrict__ Xi, const double* __restrict__ Yi, const double* __restrict__ Pi,
         double* __restrict__ out_ref /*[B][6][H]: x,y,psi,v,cdist,curv*/, double* __restrict__ out_err /*[B][3]: s0,e_y0,e_psi0*/,
-        int32_t* __restrict__ out_stop)
+        int32_t* __restrict__ out_stop, double* sh)
+{
+    const int lane = threadIdx.x;
+    const double X0 = Xi[b], Y0 = Yi[b];
+    const double psi0 = bound_pi(Pi[b]);
+    // (1) closest waypoint: first index of the minimum of sqrt(dx^2 + dy^2)
+    double best = INFINITY; int bi = 0x7fffffff;
+    for (int m = lane; m < M; m += WAVE) {
+        const double dx = __dsub_rn(tx[m], X0), dy = __dsub_rn(ty[m], Y0);
+        const double d = sqrt(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
+        if (d < best) { best = d; bi = m; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(best, o, WAVE); const int oi = __shfl_xor(bi, o, WAVE);
+        if (ov < best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    const int ci = bi < M ? bi : 0;                           // every distance NaN (a non-finite pose): numpy's argmin gives 0
+    // (2) Frenet errors at the closest waypoint
+    if (lane == 0) {
+        const double pw = tpsi[ci];
+        const double ex = __dsub_rn(X0, tx[ci]), ey = __dsub_rn(Y0, ty[ci]);
+        out_err[b * 3 + 0] = cdist[ci];
+        out_err[b * 3 + 1] = __dadd_rn(__dmul_rn(-sin(pw), ex), __dmul_rn(cos(pw), ey));
+        out_err[b * 3 + 2] = bound_pi(psi0 - pw);
+    }
+    // (3) abscissae: cumulative dt * vel over the horizon (velocities padded with 0.01), lane h -> s_h
+    double s_h = 0.0;
+    {
+        double acc = 0.0;
+        for (int h = 0; h < H; ++h) {                 // serial, identical rounding to the reference's running sum
+            const double v = h < M ? vel[h] : 0.01;
+            acc = h == 0 ? __dmul_rn(dt, v) : __dadd_rn(acc, __dmul_rn(dt, v));
+            if (h == lane) s_h = acc;
+        }
+    }
+    const bool on = lane < H;
+    const double xr = on ? interp_np(cdist, tx, M, s_h) : 0.0;
+    const double yr = on ? interp_np(cdist, ty, M, s_h) : 0.0;
+    const double cr = on ? interp_np(cdist, cdist, M, s_h) : 0.0;
+    const double kr = on ? interp_np(cdist, curv, M, s_h) : 0.0;
+    const double pr = on ? interp_np(cdist, tpsi_unw, M, s_h) : 0.0;
+    // psi: fix_angle_reference (bound, unwrap, add back) then bound (ref_traj.py:32-37,146-148)
+    const double d0 = bound_pi(pr - psi0);
+    sh[lane] = d0;
+    __syncthreads();
+    double corr = 0.0;
+    if (on && lane >= 1) {
+        const double dd = __dsub_rn(d0, sh[lane - 1]);
+        double ddmod = fmod(dd + M_PI, 2.0 * M_PI);
+        if (ddmod < 0.0) ddmod += 2.0 * M_PI;
+        ddmod -= M_PI;
+        if (ddmod == -M_PI && dd > 0.0) ddmod = M_PI;
+        corr = fabs(dd) < M_PI ? 0.0 : __dsub_rn(ddmod, dd);
+    }
+    __syncthreads();
+    // cumulative sum of the corrections (serial order as numpy.cumsum)
+    sh[lane] = corr;
+    __syncthreads();
+    double cum = 0.0;
+    for (int h = 1; h <= lane && h < H; ++h) cum = __dadd_rn(cum, sh[h]);
+    const double psi_fixed = bound_pi(__dadd_rn(psi0, lane >= 1 ? __dadd_rn(d0, cum) : d0));
+    __syncthreads();
+    // v_ref = diff(cdist_ref) / dt, last value repeated
+    sh[lane] = cr;
+    __syncthreads();
+    double vr = 0.0;
+    if (on) {
+        const int h1 = lane < H - 1 ? lane : H - 2;
+        vr = __ddiv_rn(__dsub_rn(sh[h1 + 1], sh[h1]), dt);
+    }
+    if (lane == 0) out_stop[b] = (sh[H - 1] == cdist[M - 1]) ? 1 : 0;
+    __syncthreads();
+    // splice: three points from the current pose to the second waypoint, then waypoints 2..H-2 (ref_traj.py:158-170)
+    double* o = out_ref + (size_t)b * 6 * H;
+    sh[lane] = xr; __syncthreads();
+    const double x1 = sh[1];
+    double xo = 0.0;
+    if (on) { if (lane < 3) { const double st = __ddiv_rn(__dsub_rn(x1, X0), 2.0); xo = lane == 2 ? x1 : __dadd_rn(X0, __dmul_rn((double)lane, st)); } else xo = sh[lane - 1]; }
+    __syncthreads();
+    sh[lane] = yr; __syncthreads();
+    const double y1 = sh[1];
+    double yo = 0.0;
+    if (on) { if (lane < 3) { const double st = __ddiv_rn(__dsub_rn(y1, Y0), 2.0); yo = lane == 2 ? y1 : __dadd_rn(Y0, __dmul_rn((double)lane, st)); } else yo = sh[lane - 1]; }
+    __syncthreads();
+    sh[lane] = psi_fixed; __syncthreads();
+    const double po = on ? (lane < 3 ? sh[0] : sh[lane - 1]) : 0.0;
+    __syncthreads();
+    sh[lane] = vr; __syncthreads();
+    const double vo = on ? (lane < 3 ? sh[2] : sh[lane - 1]) : 0.0;
+    __syncthreads();
+    if (on) { o[0 * H + lane] = xo; o[1 * H + lane] = yo; o[2 * H + lane] = po; o[3 * H + lane] = vo; o[4 * H + lane] = cr; o[5 * H + lane] = kr; }
+}
+
+__global__ __launch_bounds__(WAVE) void admpc_waypoints_kernel(int M, int H, double dt, int B,
+        const double* __restrict__ vel, const double* __restrict__ tx, const double* __restrict__ ty,
+        const double* __restrict__ tpsi, const double* __restrict__ tpsi_unw, const double* __restrict__ cdist, const double* __restrict__ curv,
+        const double* __restrict__ Xi, const double* __restrict__ Yi, const double* __restrict__ Pi,
+        double* __restrict__ out_ref, double* __restrict__ out_err, int32_t* __restrict__ out_stop)
+{
+    __shared__ double sh[WAVE];
+    for (int b = blockIdx.x; b < B; b += gridDim.x)
+        waypoints_one(M, H, dt, b, vel, tx, ty, tpsi, tpsi_unw, cdist, curv, Xi, Yi, Pi, out_ref, out_err, out_stop, sh);
+}
+
+// A bank of K paths (admpc_path_bank_create): one block of doubles that holds every column, and one descriptor per path.
+struct PathDesc {
+    int64_t M;               // waypoints of the path
+    int64_t off[7];          // where its columns start in the bank's block, in doubles: vel, x, y, psi, unwrapped psi, cdist, curv
+};
+
+// The generator with a path per vehicle: vehicle b reads the columns that descriptor path_of[b] names.  An index outside [0, K) reads no
+// path: NaN rows, stop 0 (the solve then fails that vehicle alone).  path_of[b] is uniform over the block, so are the barriers.
+__global__ __launch_bounds__(WAVE) void admpc_waypoints_bank_kernel(int K, int H, double dt, int B,
+        const PathDesc* __restrict__ desc, const double* __restrict__ cols, const int32_t* __restrict__ path_of,
+        const double* __restrict__ Xi, const double* __restrict__ Yi, const double* __restrict__ Pi,
+        double* __restrict__ out_ref, double* __restrict__ out_err, int32_t* __restrict__ out_stop)
 {
     __shared__ double sh[WAVE];
     const int lane = threadIdx.x;
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
-        const double X0 = Xi[b], Y0 = Yi[b];
-        const double psi0 = bound_pi(Pi[b]);
-        // (1) closest waypoint: first index of the minimum of sqrt(dx^2 + dy^2)
-        double best = INFINITY; int bi = 0x7fffffff;
-        for (int m = lane; m < M; m += WAVE) {
-            const double dx = __dsub_rn(tx[m], X0), dy = __dsub_rn(ty[m], Y0);
-            const double d = sqrt(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
-            if (d < best) { best = d; bi = m; }
+        const int k = path_of[b];
+        if (k < 0 || k >= K) {
+            double* o = out_ref + (size_t)b * 6 * H;
+            if (lane < H)
+                for (int r = 0; r < 6; ++r) o[r * H + lane] = NAN;
+            if (lane < 3) out_err[b * 3 + lane] = NAN;
+            if (lane == 0) out_stop[b] = 0;
+            continue;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const double ov = __shfl_xor(best, o, WAVE); const int oi = __shfl_xor(bi, o, WAVE);
-            if (ov < best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        }
-        const int ci = bi < M ? bi : 0;                           // every distance NaN (a non-finite pose): numpy's argmin gives 0
-        // (2) Frenet errors at the closest waypoint
-        if (lane == 0) {
-            const double pw = tpsi[ci];
-            const double ex = __dsub_rn(X0, tx[ci]), ey = __dsub_rn(Y0, ty[ci]);
-            out_err[b * 3 + 0] = cdist[ci];
-            out_err[b * 3 + 1] = __dadd_rn(__dmul_rn(-sin(pw), ex), __dmul_rn(cos(pw), ey));
-            out_err[b * 3 + 2] = bound_pi(psi0 - pw);
-        }
-        // (3) abscissae: cumulative dt * vel over the horizon (velocities padded with 0.01), lane h -> s_h
-        double s_h = 0.0;
-        {
-            double acc = 0.0;
-            for (int h = 0; h < H; ++h) {                 // serial, identical rounding to the reference's running sum
-                const double v = h < M ? vel[h] : 0.01;
-                acc = h == 0 ? __dmul_rn(dt, v) : __dadd_rn(acc, __dmul_rn(dt, v));
-                if (h == lane) s_h = acc;
-            }
-        }
-        const bool on = lane < H;
-        const double xr = on ? interp_np(cdist, tx, M, s_h) : 0.0;
-        const double yr = on ? interp_np(cdist, ty, M, s_h) : 0.0;
-        const double cr = on ? interp_np(cdist, cdist, M, s_h) : 0.0;
-        const double kr = on ? interp_np(cdist, curv, M, s_h) : 0.0;
-        const double pr = on ? interp_np(cdist, tpsi_unw, M, s_h) : 0.0;
-        // psi: fix_angle_reference (bound, unwrap, add back) then bound (ref_traj.py:32-37,146-148)
-        const double d0 = bound_pi(pr - psi0);
-        sh[lane] = d0;
-        __syncthreads();
-        double corr = 0.0;
-        if (on && lane >= 1) {
-            const double dd = __dsub_rn(d0, sh[lane - 1]);
-            double ddmod = fmod(dd + M_PI, 2.0 * M_PI);
-            if (ddmod < 0.0) ddmod += 2.0 * M_PI;
-            ddmod -= M_PI;
-            if (ddmod == -M_PI && dd > 0.0) ddmod = M_PI;
-            corr = fabs(dd) < M_PI ? 0.0 : __dsub_rn(ddmod, dd);
-        }
-        __syncthreads();
-        // cumulative sum of the corrections (serial order as numpy.cumsum)
-        sh[lane] = corr;
-        __syncthreads();
-        double cum = 0.0;
-        for (int h = 1; h <= lane && h < H; ++h) cum = __dadd_rn(cum, sh[h]);
-        const double psi_fixed = bound_pi(__dadd_rn(psi0, lane >= 1 ? __dadd_rn(d0, cum) : d0));
-        __syncthreads();
-        // v_ref = diff(cdist_ref) / dt, last value repeated
-        sh[lane] = cr;
-        __syncthreads();
-        double vr = 0.0;
-        if (on) {
-            const int h1 = lane < H - 1 ? lane : H - 2;
-            vr = __ddiv_rn(__dsub_rn(sh[h1 + 1], sh[h1]), dt);
-        }
-        if (lane == 0) out_stop[b] = (sh[H - 1] == cdist[M - 1]) ? 1 : 0;
-        __syncthreads();
-        // splice: three points from the current pose to the second waypoint, then waypoints 2..H-2 (ref_traj.py:158-170)
-        double* o = out_ref + (size_t)b * 6 * H;
-        sh[lane] = xr; __syncthreads();
-        const double x1 = sh[1];
-        double xo = 0.0;
-        if (on) { if (lane < 3) { const double st = __ddiv_rn(__dsub_rn(x1, X0), 2.0); xo = lane == 2 ? x1 : __dadd_rn(X0, __dmul_rn((double)lane, st)); } else xo = sh[lane - 1]; }
-        __syncthreads();
-        sh[lane] = yr; __syncthreads();
-        const double y1 = sh[1];
-        double yo = 0.0;
-        if (on) { if (lane < 3) { const double st = __ddiv_rn(__dsub_rn(y1, Y0), 2.0); yo = lane == 2 ? y1 : __dadd_rn(Y0, __dmul_rn((double)lane, st)); } else yo = sh[lane - 1]; }
-        __syncthreads();
-        sh[lane] = psi_fixed; __syncthreads();
-        const double po = on ? (lane < 3 ? sh[0] : sh[lane - 1]) : 0.0;
-        __syncthreads();
-        sh[lane] = vr; __syncthreads();
-        const double vo = on ? (lane < 3 ? sh[2] : sh[lane - 1]) : 0.0;
-        __syncthreads();
-        if (on) { o[0 * H + lane] = xo; o[1 * H + lane] = yo; o[2 * H + lane] = po; o[3 * H + lane] = vo; o[4 * H + lane] = cr; o[5 * H + lane] = kr; }
+        const PathDesc d = desc[k];
+        waypoints_one((int)d.M, H, dt, b, cols + d.off[0], cols + d.off[1], cols + d.off[2], cols + d.off[3], cols + d.off[4], cols + d.off[5],
+                      cols + d.off[6], Xi, Yi, Pi, out_ref, out_err, out_stop, sh);
     }
 }
 
@@ -307,6 +349,35 @@ __global__ __launch_bounds__(WAVE) void admpc_argmin_pairs_kernel(const double* 
         argmin_fold(b, ov, oi);
     }
     if (threadIdx.x == 0) { *val = b.v; *idx = argmin_final_index(b); }
+}
+
+// arg-min per group of `group` consecutive costs (admpc_argmin_groups): one wave per group, lane l folds costs l, l + 64, ...; groups of
+// up to 16 costs sit four to a wave, one per 16-lane row, and the butterfly then stays inside the row.  Indices are those of the batch.
+// Same rules as above (argmin_rule.h); a group is never empty, so argmin_final_index returns the index it is given.
+#define ARGMIN_GROUPS_WAVES 4          // waves per block
+#define ARGMIN_GROUPS_GRID 256         // blocks at the most: a stride loop past it
+__global__ __launch_bounds__(ARGMIN_GROUPS_WAVES * WAVE) void admpc_argmin_groups_kernel(const double* __restrict__ cost, int G, int group,
+                                                                                       double* __restrict__ val, int64_t* __restrict__ idx)
+{
+    const int lane = threadIdx.x & (WAVE - 1);
+    const int wave = blockIdx.x * ARGMIN_GROUPS_WAVES + threadIdx.x / WAVE, nwaves = gridDim.x * ARGMIN_GROUPS_WAVES;
+    const bool packed = group <= 16;
+    const int per_wave = packed ? 4 : 1;
+    const int width = packed ? 16 : WAVE;                 // lanes that share a group
+    const int l = lane & (width - 1);
+    for (long g0 = (long)wave * per_wave; g0 < G; g0 += (long)nwaves * per_wave) {
+        const long g = g0 + (packed ? lane >> 4 : 0);
+        const int64_t base = (int64_t)g * group;
+        ArgminBest b = argmin_identity();
+        if (g < G)
+            for (int i = l; i < group; i += width) argmin_fold(b, argmin_cost(cost[base + i]), base + i);
+        for (int o = width >> 1; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(b.v, o, WAVE);
+            const int64_t oi = __shfl_xor((long long)b.i, o, WAVE);
+            argmin_fold(b, ov, oi);
+        }
+        if (l == 0 && g < G) { val[g] = b.v; idx[g] = argmin_final_index(b); }
+    }
 }
 
 // post-solve epilogue: validity test ad_3d_optimizer.py:385-394 + Ackermann mapping
@@ -1264,6 +1335,119 @@ int admpc_waypoints_batch(int device, int M, int H, double dt, int B,
     int grid = B < 4096 ? B : 4096;
     hipLaunchKernelGGL(admpc_waypoints_kernel, dim3(grid), dim3(WAVE), 0, (hipStream_t)stream, M, H, dt, B, vel, x, y, psi, psi_unwrapped, cdist, curv,
                        X_init, Y_init, psi_init, out_ref, out_err, out_stop);
+    HIPCHK(hipGetLastError());
+    return ADMPC_OK;
+}
+
+}  // extern "C"
+
+// =============================================================================================
+// include/admpc_fleet.h: a bank of paths, the generator against it, the arg-min per group
+// =============================================================================================
+struct AdmpcPathBank {
+    int device, K, H;
+    double dt;
+    double* d_block;         // the ONE allocation: K descriptors (64 bytes each), then the columns of every path
+    const PathDesc* d_desc;  // = d_block
+    const double* d_cols;    // = d_block + 8 K
+};
+
+extern "C" {
+
+// for the control step (admpc_step.hip): the horizon every path of the bank was laid out for, and the device it lives on
+__attribute__((visibility("hidden"))) int admpc_path_bank_horizon(const AdmpcPathBank* bank, int* device)
+{
+    if (device) *device = bank->device;
+    return bank->H;
+}
+
+int admpc_path_bank_create(int device, int K, const AdmpcPath* paths, AdmpcPathBank** out)
+{
+    if (!out || !paths) return fail(ADMPC_EINVAL, "admpc_path_bank_create: null argument");
+    if (K < 1) return fail(ADMPC_EINVAL, "admpc_path_bank_create: need K >= 1");
+    size_t total = 0;
+    for (int k = 0; k < K; ++k) {
+        const AdmpcPath& p = paths[k];
+        if (p.M < 2 || !p.vel || !p.x || !p.y || !p.psi || !p.psi_unwrapped || !p.cdist || !p.curv)
+            return fail(ADMPC_EINVAL, "admpc_path_bank_create: path " + std::to_string(k) + " needs M >= 2 and seven columns");
+        if (p.H != paths[0].H || p.dt != paths[0].dt)
+            return fail(ADMPC_EINVAL, "admpc_path_bank_create: path " + std::to_string(k) + " differs from path 0 in H or dt");
+        total += (size_t)7 * (size_t)p.M;
+    }
+    if (paths[0].H < 3 || paths[0].H > WAVE) return fail(ADMPC_EINVAL, "admpc_path_bank_create: H must be in [3, 64] (the waypoint kernel's horizon)");
+    if (!(paths[0].dt > 0)) return fail(ADMPC_EINVAL, "admpc_path_bank_create: the paths need dt > 0");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ADMPC_ENODEV, "no HIP device");
+    if (device < 0 || device >= ndev) return fail(ADMPC_ENODEV, "device index out of range");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return fail(ADMPC_EHIP, "hipSetDevice failed");
+    static_assert(sizeof(PathDesc) == 8 * sizeof(double), "a descriptor takes eight doubles of the block");
+    AdmpcPathBank* b = new (std::nothrow) AdmpcPathBank();
+    PathDesc* host = new (std::nothrow) PathDesc[K];
+    if (!b || !host) { delete b; delete[] host; return fail(ADMPC_ENOMEM, "out of host memory"); }
+    b->device = device; b->K = K; b->H = paths[0].H; b->dt = paths[0].dt; b->d_block = nullptr;
+    const size_t head = (size_t)8 * K;
+    hipError_t e = hipMalloc((void**)&b->d_block, (head + total) * sizeof(double));
+    size_t at = 0;
+    for (int k = 0; e == hipSuccess && k < K; ++k) {
+        const AdmpcPath& p = paths[k];
+        const double* col[7] = { p.vel, p.x, p.y, p.psi, p.psi_unwrapped, p.cdist, p.curv };
+        host[k].M = p.M;
+        for (int c = 0; e == hipSuccess && c < 7; ++c, at += (size_t)p.M) {
+            host[k].off[c] = (int64_t)at;
+            e = hipMemcpy(b->d_block + head + at, col[c], (size_t)p.M * sizeof(double), hipMemcpyDeviceToDevice);
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpy(b->d_block, host, (size_t)K * sizeof(PathDesc), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();               // the caller may free its columns as soon as this returns
+    delete[] host;
+    if (e != hipSuccess) {
+        if (b->d_block) (void)hipFree(b->d_block);
+        delete b;
+        return fail(ADMPC_EHIP, std::string("admpc_path_bank_create: ") + hipGetErrorString(e));
+    }
+    b->d_desc = (const PathDesc*)b->d_block; b->d_cols = b->d_block + head;
+    *out = b;
+    return ADMPC_OK;
+}
+
+void admpc_path_bank_destroy(AdmpcPathBank* bank)
+{
+    if (!bank) return;
+    DeviceGuard guard(bank->device);
+    (void)hipFree(bank->d_block);
+    delete bank;
+}
+
+int admpc_waypoints_bank_batch(const AdmpcPathBank* bank, int B, const int32_t* path_of,
+                               const double* X_init, const double* Y_init, const double* psi_init,
+                               double* out_ref, double* out_err, int32_t* out_stop, void* stream)
+{
+    if (!bank || B < 0) return fail(ADMPC_EINVAL, "admpc_waypoints_bank_batch: null bank or negative batch");
+    if (B == 0) return ADMPC_OK;
+    if (!path_of || !X_init || !Y_init || !psi_init || !out_ref || !out_err || !out_stop) return fail(ADMPC_EINVAL, "null array argument");
+    DeviceGuard guard(bank->device);
+    if (!guard.ok()) return fail(ADMPC_EHIP, "hipSetDevice failed");
+    int grid = B < 4096 ? B : 4096;                                // as admpc_waypoints_batch
+    hipLaunchKernelGGL(admpc_waypoints_bank_kernel, dim3(grid), dim3(WAVE), 0, (hipStream_t)stream, bank->K, bank->H, bank->dt, B, bank->d_desc,
+                       bank->d_cols, path_of, X_init, Y_init, psi_init, out_ref, out_err, out_stop);
+    HIPCHK(hipGetLastError());
+    return ADMPC_OK;
+}
+
+int admpc_argmin_groups(AdmpcSolver* s, const double* cost, int G, int group, double* val, int64_t* idx, void* stream)
+{
+    if (!s || G < 0 || group < 1) return fail(ADMPC_EINVAL, "admpc_argmin_groups: need a solver, G >= 0, group >= 1");
+    if ((long long)G * group > 0x7fffffffLL) return fail(ADMPC_EINVAL, "admpc_argmin_groups: G * group beyond INT32_MAX");
+    if (!val || !idx) return fail(ADMPC_EINVAL, "admpc_argmin_groups: null output array");
+    if (G == 0) return ADMPC_OK;
+    if (!cost) return fail(ADMPC_EINVAL, "admpc_argmin_groups: null cost array");
+    DeviceGuard guard(s->device);
+    if (!guard.ok()) return fail(ADMPC_EHIP, "hipSetDevice failed");
+    const int per_block = ARGMIN_GROUPS_WAVES * (group <= 16 ? 4 : 1);          // groups a block takes per round
+    int grid = (G + per_block - 1) / per_block;
+    if (grid > ARGMIN_GROUPS_GRID) grid = ARGMIN_GROUPS_GRID;
+    hipLaunchKernelGGL(admpc_argmin_groups_kernel, dim3(grid), dim3(ARGMIN_GROUPS_WAVES * WAVE), 0, (hipStream_t)stream, cost, G, group, val, idx);
     HIPCHK(hipGetLastError());
     return ADMPC_OK;
 }

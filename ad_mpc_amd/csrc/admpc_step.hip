@@ -20,6 +20,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "../../include/admpc.h"
+#include "../../include/admpc_fleet.h"
 
 #define NX ADMPC_NX
 #define NU ADMPC_NU
@@ -29,6 +30,7 @@
 
 extern "C" int admpc_set_error(int code, const char* msg);                                  // admpc_kernels.hip
 extern "C" const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);      // admpc_kernels.hip
+extern "C" int admpc_path_bank_horizon(const AdmpcPathBank* bank, int* device);             // admpc_kernels.hip
 
 namespace {
 
@@ -104,51 +106,77 @@ __device__ int path_close(double d, int lane, int n)
 //   gate       check_pred_trj(x_opt, ref) against the node's N-row window, N slots (:203); status > 0 resets safe_count, else +1;
 //              an MPC command needs safe_count >= threshold and a healthy prediction, with the steering command
 //              clip(clip(rate) * 0.1 + measured steering) (:206-223); otherwise the auxiliary controller's brake record (:455-476)
+//   cost       (the step against a bank of paths only; nullptr otherwise) +inf where the solve failed or the prediction is not valid
+// One text for both kernels below: vehicle b, called by every lane of the block's single wave.
+__device__ __forceinline__ void step_command_one(int N, int b, const double* __restrict__ ref, const double* __restrict__ xbar,
+                                          const double* __restrict__ ubar, const int32_t* __restrict__ status, const double* __restrict__ steer,
+                                          int32_t* __restrict__ safe_count, double* __restrict__ prev_u, int32_t* __restrict__ has_valid,
+                                          int threshold, double rate_min, double rate_max, double steer_min, double steer_max,
+                                          float* __restrict__ ack, int32_t* __restrict__ mode, int32_t* __restrict__ valid, double* __restrict__ cost)
+{
+#pragma clang fp contract(off)      // the steering command is two separately rounded operations in the reference (:223)
+    const int lane = threadIdx.x;
+    const double* x = xbar + (size_t)b * (N + 1) * NX;
+    const double* rx = ref + (size_t)b * 6 * N;
+    const double* ry = rx + N;
+    const double* u = ubar + (size_t)b * N * NU;
+    double* pu = prev_u + (size_t)b * N * NU;
+    double d = 0.0;
+    if (lane < N) {
+        const double dxv = rx[lane] - x[lane * NX], dyv = ry[lane] - x[lane * NX + 1];
+        d = __dsqrt_rn(dxv * dxv + dyv * dyv);
+    }
+    const int ok_pred = path_close(d, lane, N + 1);
+    const int healthy = path_close(d, lane, N);
+    const int had = has_valid[b];
+    double w0 = u[0], w1 = u[1];
+    if (!ok_pred && had) { w0 = pu[2]; w1 = pu[3]; }
+    __syncthreads();                                              // every lane has read prev_u before it is overwritten
+    if (ok_pred)
+        for (int i = lane; i < N * NU; i += WAVE) pu[i] = u[i];
+    if (lane == 0) {
+        if (ok_pred) has_valid[b] = 1;
+        const int cnt = status[b] > 0 ? 0 : safe_count[b] + 1;
+        safe_count[b] = cnt;
+        const int ok = (cnt >= threshold && healthy) ? 1 : 0;
+        const double sth = steer[b];
+        if (ok) {
+            const double rate_msg = (double)(float)w1;                   // the value travels through a float32 message field
+            const double sv = fmax(fmin(rate_max, rate_msg), rate_min);
+            const double scaled = sv * 0.1;
+            const double ang = fmax(fmin(steer_max, scaled + sth), steer_min);
+            ack[b * 4 + 0] = (float)ang; ack[b * 4 + 1] = (float)w1; ack[b * 4 + 2] = (float)x[3]; ack[b * 4 + 3] = (float)w0;
+        } else {
+            ack[b * 4 + 0] = (float)sth; ack[b * 4 + 1] = 0.0f; ack[b * 4 + 2] = 0.0f; ack[b * 4 + 3] = (float)(-1e5);
+        }
+        mode[b] = ok;
+        valid[b] = ok_pred;
+        if (cost && (status[b] != 0 || !ok_pred)) cost[b] = INFINITY;
+    }
+}
+
 __global__ __launch_bounds__(WAVE) void admpc_step_command_kernel(int N, int B, const double* __restrict__ ref, const double* __restrict__ xbar,
                                           const double* __restrict__ ubar, const int32_t* __restrict__ status, const double* __restrict__ steer,
                                           int32_t* __restrict__ safe_count, double* __restrict__ prev_u, int32_t* __restrict__ has_valid,
                                           int threshold, double rate_min, double rate_max, double steer_min, double steer_max,
                                           float* __restrict__ ack, int32_t* __restrict__ mode, int32_t* __restrict__ valid)
 {
-#pragma clang fp contract(off)      // the steering command is two separately rounded operations in the reference (:223)
-    const int lane = threadIdx.x;
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
-        const double* x = xbar + (size_t)b * (N + 1) * NX;
-        const double* rx = ref + (size_t)b * 6 * N;
-        const double* ry = rx + N;
-        const double* u = ubar + (size_t)b * N * NU;
-        double* pu = prev_u + (size_t)b * N * NU;
-        double d = 0.0;
-        if (lane < N) {
-            const double dxv = rx[lane] - x[lane * NX], dyv = ry[lane] - x[lane * NX + 1];
-            d = __dsqrt_rn(dxv * dxv + dyv * dyv);
-        }
-        const int ok_pred = path_close(d, lane, N + 1);
-        const int healthy = path_close(d, lane, N);
-        const int had = has_valid[b];
-        double w0 = u[0], w1 = u[1];
-        if (!ok_pred && had) { w0 = pu[2]; w1 = pu[3]; }
-        __syncthreads();                                              // every lane has read prev_u before it is overwritten
-        if (ok_pred)
-            for (int i = lane; i < N * NU; i += WAVE) pu[i] = u[i];
-        if (lane == 0) {
-            if (ok_pred) has_valid[b] = 1;
-            const int cnt = status[b] > 0 ? 0 : safe_count[b] + 1;
-            safe_count[b] = cnt;
-            const int ok = (cnt >= threshold && healthy) ? 1 : 0;
-            const double sth = steer[b];
-            if (ok) {
-                const double rate_msg = (double)(float)w1;                   // the value travels through a float32 message field
-                const double sv = fmax(fmin(rate_max, rate_msg), rate_min);
-                const double scaled = sv * 0.1;
-                const double ang = fmax(fmin(steer_max, scaled + sth), steer_min);
-                ack[b * 4 + 0] = (float)ang; ack[b * 4 + 1] = (float)w1; ack[b * 4 + 2] = (float)x[3]; ack[b * 4 + 3] = (float)w0;
-            } else {
-                ack[b * 4 + 0] = (float)sth; ack[b * 4 + 1] = 0.0f; ack[b * 4 + 2] = 0.0f; ack[b * 4 + 3] = (float)(-1e5);
-            }
-            mode[b] = ok;
-            valid[b] = ok_pred;
-        }
+        step_command_one(N, b, ref, xbar, ubar, status, steer, safe_count, prev_u, has_valid, threshold, rate_min, rate_max, steer_min, steer_max,
+                         ack, mode, valid, nullptr);
+    }
+}
+// the same behind admpc_control_step_bank_batch: cost [B] holds the objective of each solve and is masked in place
+__global__ __launch_bounds__(WAVE) void admpc_step_command_cost_kernel(int N, int B, const double* __restrict__ ref, const double* __restrict__ xbar,
+                                          const double* __restrict__ ubar, const int32_t* __restrict__ status, const double* __restrict__ steer,
+                                          int32_t* __restrict__ safe_count, double* __restrict__ prev_u, int32_t* __restrict__ has_valid,
+                                          int threshold, double rate_min, double rate_max, double steer_min, double steer_max,
+                                          float* __restrict__ ack, int32_t* __restrict__ mode, int32_t* __restrict__ valid,
+                                          double* __restrict__ cost)
+{
+    for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        step_command_one(N, b, ref, xbar, ubar, status, steer, safe_count, prev_u, has_valid, threshold, rate_min, rate_max, steer_min, steer_max,
+                         ack, mode, valid, cost);
     }
 }
 
@@ -234,6 +262,51 @@ int admpc_control_step_batch(AdmpcSolver* s, const AdmpcPath* path, const AdmpcS
                        (const double*)ubar, (const int32_t*)status, steer, safe_count, prev_u, has_valid, prm->threshold,
                        cfg->lbu[1], cfg->ubu[1], cfg->lbx_delta, cfg->ubx_delta, ack, mode, valid);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_command_kernel: launch failed");
+    return ADMPC_OK;
+}
+
+// admpc_control_step_batch with a path per vehicle and the objective of each solve (include/admpc_fleet.h).  The chain is the one above,
+// launch for launch (tests/batch_regimes.py mirrors the lines of admpc_control_step_batch, which therefore keeps its own copy of it); the
+// differences are the waypoint call, `cost` handed to the solve, and the command kernel that masks it.
+int admpc_control_step_bank_batch(AdmpcSolver* s, const AdmpcPathBank* bank, const AdmpcStepParams* prm, int B, const int32_t* path_of,
+                                  const double* px, const double* py, const double* yaw, const double* vx, const double* vy,
+                                  const double* yaw_rate, const double* steer,
+                                  double* xbar, double* ubar, int32_t* safe_count, double* prev_u, int32_t* has_valid,
+                                  void* work, float* ack, int32_t* mode, int32_t* valid, int32_t* status, double* cost, void* stream)
+{
+    if (!s || !prm || B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: null solver / params or negative batch");
+    int device = 0, bank_device = 0;
+    const AdmpcConfig* cfg = admpc_solver_config(s, &device);
+    const int N = cfg->N;
+    if (N < 3 || N > STEP_MAX_H) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: the solver's N must be in [3, 64] (the waypoint kernel's horizon)");
+    if (!bank) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: the bank is not set");
+    if (admpc_path_bank_horizon(bank, &bank_device) != N) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: the bank's horizon H must equal the solver's N");
+    if (bank_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: the bank lives on another device than the solver");
+    if (prm->threshold < 0 || !(prm->blend_max > prm->blend_min)) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: bad step parameters");
+    if (B == 0) return ADMPC_OK;
+    if (!path_of || !px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !xbar || !ubar || !safe_count || !prev_u || !has_valid || !work ||
+        !ack || !mode || !valid || !status)
+        return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: null array argument");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    StepWork w(work, N, B);
+    int rc = admpc_waypoints_bank_batch(bank, B, path_of, px, py, yaw, w.ref, w.err, w.stop, stream);
+    if (rc) return rc;
+    if (prm->resample) {
+        rc = admpc_resample_vel_batch(device, B, N, 6 * N, vx, vy, prm->acc_max, prm->resample_dt, w.ref + 3 * N, stream);
+        if (rc) return rc;
+    }
+    const long nP = (long)B * (N + 1);
+    hipLaunchKernelGGL(admpc_step_assemble_kernel, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, st, N, B, (const double*)w.ref,
+                       px, py, yaw, vx, vy, yaw_rate, steer, prm->blend_min, prm->blend_max, w.x0, w.yref, w.yref_e, w.p);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_assemble_kernel: launch failed");
+    rc = admpc_solve_batch(s, B, w.x0, w.yref, w.yref_e, w.p, xbar, ubar, cost, status, nullptr, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(admpc_step_command_cost_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE), 0, st, N, B, (const double*)w.ref, (const double*)xbar,
+                       (const double*)ubar, (const int32_t*)status, steer, safe_count, prev_u, has_valid, prm->threshold,
+                       cfg->lbu[1], cfg->ubu[1], cfg->lbx_delta, cfg->ubx_delta, ack, mode, valid, cost);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_command_cost_kernel: launch failed");
     return ADMPC_OK;
 }
 

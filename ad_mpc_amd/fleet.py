@@ -1,5 +1,6 @@
 """The control step of a fleet: pose in, Ackermann command out, for B vehicles on one global path
-(include/admpc.h: admpc_control_step_batch; csrc/admpc_step.hip).
+(include/admpc.h: admpc_control_step_batch; csrc/admpc_step.hip), or with a path per vehicle out of a bank of paths and the best of
+every group of candidates (include/admpc_fleet.h: admpc_control_step_bank_batch, admpc_argmin_groups).
 
 ``FleetController`` solves the problem of ``ROSGPMPC(point_reference=False)`` (create_ros_ad_mpc.py:41-101: SQP_RTI, Q_DIAG_ROS /
 R_DIAG_ROS) for every vehicle, and does per step what the reference node does per pose message (gp_ad_mpc_node.py:389-438 ->
@@ -39,6 +40,17 @@ class FleetStep(NamedTuple):
     w_opt: torch.Tensor        # float64 [B,N,2]
 
 
+class FleetPathStep(NamedTuple):
+    """FleetStep of a step against the bank of paths (step_paths), with the objective of every solve."""
+    ack: torch.Tensor
+    mode: torch.Tensor
+    status: torch.Tensor
+    valid: torch.Tensor
+    x_opt: torch.Tensor
+    w_opt: torch.Tensor
+    cost: torch.Tensor         # float64 [B]: objective of the solve; +inf where status != 0 or valid == 0 (NOT where mode == 0: admpc_fleet.h)
+
+
 class FleetController:
     def __init__(self, t_horizon, n_mpc_nodes, opt_dt, B, device=0, resample=True, threshold=SAFE_COUNT_THRESHOLD, blend_min=None,
                  blend_max=None):
@@ -70,9 +82,24 @@ class FleetController:
         self.prev_u, self.has_valid = z(B, N, NU), z(B, dtype=torch.int32)
         self.ack = z(B, 4, dtype=torch.float32)
         self.mode, self.valid, self.status = z(B, dtype=torch.int32), z(B, dtype=torch.int32), z(B, dtype=torch.int32)
+        self.cost = z(B)                                                  # step_paths; best_of reduces it into the two below
+        self._best_val, self._best_idx = z(B), z(B, dtype=torch.int64)
+        self._bank, self._stepped_paths, self.n_paths = None, False, 0
+
+    def _drop_bank(self):
+        if getattr(self, "_bank", None):
+            self.lib.admpc_path_bank_destroy(self._bank)
+        self._bank, self._stepped_paths, self.n_paths = None, False, 0
 
     def close(self):
+        self._drop_bank()
         self._eng.close()
+
+    def __del__(self):
+        try:
+            self._drop_bank()
+        except Exception:
+            pass
 
     def set_traj(self, x_ref, y_ref, psi_ref, vel_ref):
         """The global path every vehicle follows (RefTrajectory.set_traj, ref_traj.py:67-86)."""
@@ -92,6 +119,56 @@ class FleetController:
             _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
             _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), self._eng._stream()))
         return FleetStep(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt)
+
+    def set_paths(self, paths):
+        """A bank of global paths, a list of (x_ref, y_ref, psi_ref, vel_ref), each prepared as set_traj prepares the one path
+        (RefTrajectory.set_traj, ref_traj.py:67-86).  step_paths lays vehicle b against paths[path_of[b]].  Allocates and synchronises."""
+        paths = list(paths)
+        if not paths:
+            raise ValueError("set_paths needs at least one path")
+        rt = RefTrajectory(traj_horizon=self.N, traj_dt=self._path.dt, device=self.device.index)
+        descs, keep = (AdmpcPath * len(paths))(), []
+        for d, p in zip(descs, paths):
+            rt.set_traj(*p)
+            keep.append(rt._cols)                                         # alive until the bank has copied them
+            d.M, d.H, d.dt = int(rt.trajectory.shape[0]), self.N, self._path.dt
+            d.vel, d.x, d.y, d.psi, d.psi_unwrapped, d.cdist, d.curv = [c.data_ptr() for c in rt._cols]
+        torch.cuda.synchronize(self.device)                               # the columns were uploaded on torch's stream
+        bank = C.c_void_p(0)
+        _lib.check(self.lib.admpc_path_bank_create(self.device.index, len(paths), descs, C.byref(bank)))
+        self._drop_bank()
+        self._bank, self.n_paths = bank, len(paths)
+
+    def step_paths(self, path_of, x, y, yaw, vx, vy, yaw_rate, steer):
+        """step() with a path per vehicle: path_of int32 [B] device tensor of indices into the paths of set_paths.  A vehicle whose index
+        is outside the bank ends the step as one whose solve failed (status 4, brake record, cost +inf).  Returns FleetPathStep."""
+        if self._bank is None:
+            raise ValueError("step_paths: no bank of paths, call set_paths first")
+        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
+        self._eng._chk(path_of, (self.B,), torch.int32)
+        for t in ins:
+            self._eng._chk(t, (self.B,))
+        _lib.check(self.lib.admpc_control_step_bank_batch(
+            self._eng._h, self._bank, C.byref(self._prm), self.B, _ptr(path_of), *[_ptr(t) for t in ins],
+            _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
+            _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), _ptr(self.cost), self._eng._stream()))
+        self._stepped_paths = True
+        return FleetPathStep(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt, self.cost)
+
+    def best_of(self, group):
+        """The cheapest usable candidate of every group of `group` consecutive instances of the last step_paths (instance b = v * group + c
+        for vehicle v and candidate c): (val float64 [B / group], idx int64 [B / group]) device tensors, idx into the batch, so the command
+        of vehicle v is ack[idx[v]].  A group without a usable candidate gives (+inf, its first instance).  Asynchronous; the tensors
+        are the controller's own and are overwritten by the next call."""
+        group = int(group)
+        if group < 1 or self.B % group != 0:
+            raise ValueError("best_of: B = %d is not a multiple of group = %d" % (self.B, group))
+        if not self._stepped_paths:
+            raise ValueError("best_of: no step_paths yet")
+        G = self.B // group
+        val, idx = self._best_val[:G], self._best_idx[:G]
+        _lib.check(self.lib.admpc_argmin_groups(self._eng._h, _ptr(self.cost), G, group, _ptr(val), _ptr(idx), self._eng._stream()))
+        return val, idx
 
     def step_numpy(self, x, y, yaw, vx, vy, yaw_rate, steer):
         """step() with host arrays in and host copies out (synchronises)."""

@@ -389,6 +389,9 @@ int admpc_control_step_batch(AdmpcSolver* s, const AdmpcPath* path, const AdmpcS
                              double* xbar, double* ubar, int32_t* safe_count, double* prev_u, int32_t* has_valid,
                              void* work, float* ack, int32_t* mode, int32_t* valid, int32_t* status, void* stream);
 
+/* A path per vehicle out of a bank of paths, the objective of every solve and the arg-min per group of candidates are declared in
+ * admpc_fleet.h, next to this header (same library; the functions of this header keep their code path). */
+
 const char* admpc_last_error(void);
 const char* admpc_version(void);
 

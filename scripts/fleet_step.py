@@ -3,6 +3,12 @@ batch (admpc_solve_batch on the same references) and against the per-vehicle loo
 set_reference, optimize: what a host does for each vehicle without the fleet step).
 
     python scripts/fleet_step.py [--batches 1,64,4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--loop-calls 200]
+    python scripts/fleet_step.py --bank [--batches 4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--repeats 5]
+
+--bank: the same workloads through a bank of paths (admpc_control_step_bank_batch: set_paths / step_paths) with K = 1 and with K = 8 copies
+of the path and round-robin path_of, against the single-path step in the same process, the variants interleaved `repeats` times (one JSON
+line per (N, B) with every repeat and the medians); and admpc_argmin_groups at (G, group) = (4096, 4) and (64, 1024) against admpc_argmin
+over the same number of entries.
 
 One JSON line per (N, B) and one for the per-vehicle loop per N.  Times come from HIP events around `steps` back-to-back steps (fleet,
 bare solve) or wall time around `loop-calls` calls (the per-vehicle loop, which synchronises at every call by construction)."""
@@ -81,6 +87,49 @@ def fleet_and_bare(N, B, p, steps, warmup):
     return t_step, t_solve, float(modes.mean())
 
 
+def bank_against_single(N, B, p, steps, warmup, repeats):
+    """Seconds per step of the single-path step, the bank step with K = 1 and with K = 8 (round-robin path_of), interleaved."""
+    ins = None
+    runs = {}
+    for name, K in (("single", 0), ("bank_k1", 1), ("bank_k8", 8)):
+        fc = FleetController(T_HORIZON, N, OPT_DT, B)
+        if ins is None:
+            ins = [torch.as_tensor(a, dtype=torch.float64, device=fc.device) for a in poses(B, p)]
+        if K == 0:
+            fc.set_traj(*p)
+            runs[name] = (fc, lambda fc=fc: fc.step(*ins))
+        else:
+            fc.set_paths([p] * K)
+            path_of = (torch.arange(B, device=fc.device) % K).to(torch.int32)
+            runs[name] = (fc, lambda fc=fc, path_of=path_of: fc.step_paths(path_of, *ins))
+    times = {name: [] for name in runs}
+    for _ in range(repeats):
+        for name, (fc, fn) in runs.items():
+            times[name].append(timed(fn, steps, warmup))
+    for fc, _ in runs.values():
+        fc.close()
+    return times
+
+
+def argmin_groups_against_argmin(steps, warmup, repeats):
+    """Seconds per call of admpc_argmin_groups at (G, group) and of admpc_argmin over G * group entries."""
+    fc = FleetController(T_HORIZON, 20, OPT_DT, 4)
+    eng, L = fc._eng, fc.lib
+    out = []
+    for G, group in ((4096, 4), (64, 1024)):
+        cost = torch.rand(G * group, dtype=torch.float64, device=fc.device)
+        val, idx = torch.empty(G, dtype=torch.float64, device=fc.device), torch.empty(G, dtype=torch.int64, device=fc.device)
+        p = lambda t: t.data_ptr()
+        groups = lambda: L.admpc_argmin_groups(eng._h, p(cost), G, group, p(val), p(idx), eng._stream())
+        whole = lambda: L.admpc_argmin(eng._h, p(cost), G * group, 0, p(val), p(idx), eng._stream())
+        t = {"groups": [], "argmin": []}
+        for _ in range(repeats):
+            t["groups"].append(timed(groups, steps, warmup)); t["argmin"].append(timed(whole, steps, warmup))
+        out.append((G, group, t))
+    fc.close()
+    return out
+
+
 def per_vehicle_loop(N, p, calls):
     from ad_mpc_amd.ref_traj import RefTrajectory
     mpc = ROSGPMPC(T_HORIZON, N, OPT_DT)
@@ -111,9 +160,26 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--loop-calls", type=int, default=200)
+    ap.add_argument("--bank", action="store_true", help="the bank of paths against the single-path step, and the arg-min per group")
+    ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     p = path()
     gpu = torch.cuda.get_device_name(0)
+    if a.bank:
+        us = lambda ts: [round(t * 1e6, 1) for t in ts]
+        med = lambda ts: float(np.median(ts))
+        for N in [int(v) for v in a.horizons.split(",")]:
+            for B in [int(v) for v in (a.batches if a.batches != "1,64,4096" else "4096").split(",")]:
+                t = bank_against_single(N, B, p, a.steps, a.warmup, a.repeats)
+                print(json.dumps({"what": "fleet_step_bank", "N": N, "B": B, "us_per_step": {k: us(v) for k, v in t.items()},
+                                  "median_us": {k: round(med(v) * 1e6, 1) for k, v in t.items()},
+                                  "vehicles_per_s": {k: round(B / med(v), 1) for k, v in t.items()},
+                                  "bank_k1_over_single": round(med(t["bank_k1"]) / med(t["single"]), 4),
+                                  "bank_k8_over_single": round(med(t["bank_k8"]) / med(t["single"]), 4), "gpu": gpu}), flush=True)
+        for G, group, t in argmin_groups_against_argmin(a.steps, a.warmup, a.repeats):
+            print(json.dumps({"what": "argmin_groups", "G": G, "group": group, "us_per_call": {k: us(v) for k, v in t.items()},
+                              "median_us": {k: round(med(v) * 1e6, 2) for k, v in t.items()}, "gpu": gpu}), flush=True)
+        return
     for N in [int(v) for v in a.horizons.split(",")]:
         t_loop = per_vehicle_loop(N, p, a.loop_calls)
         print(json.dumps({"what": "per_vehicle_rosgpmpc_loop", "N": N, "vehicles_per_s": round(1.0 / t_loop, 1),
