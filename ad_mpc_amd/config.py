@@ -79,6 +79,11 @@ class AdmpcStepParams(C.Structure):
                 ("resample", C.c_int32), ("threshold", C.c_int32)]
 
 
+class AdmpcLaneParams(C.Structure):
+    """The lane of admpc_control_step_lane_batch (include/admpc_lane.h): L waypoints in [34, 256], the search window in waypoints."""
+    _fields_ = [("L", C.c_int32), ("back", C.c_int32), ("ahead", C.c_int32)]
+
+
 # --- vehicle constants: src/ad_mpc/ad_3d.py:47-71 (the 3.14195 "pi" is part of the model) -----------
 VEH_MASS = 1500.0
 VEH_F_MASS = 900.0

@@ -12,7 +12,8 @@
 //
 // The one deliberate deviation: the node clamps the speed of the GLOBAL path once per waypoint message, at the speed the vehicle had
 // then (:351-368).  Vehicles at different speeds cannot share that, so the clamp runs on each vehicle's local window of N speeds at its
-// current speed (what admpc_resample_vel_batch documents); AdmpcStepParams.resample = 0 turns it off.
+// current speed (what admpc_resample_vel_batch documents); AdmpcStepParams.resample = 0 turns it off.  The step along a route
+// (admpc_control_step_lane_batch, at the end of this file) has a lane to clamp and clamps that, as the node does.
 //
 // The assembly computes bit for bit what the host functions of ad_mpc_amd/host.py compute (same operations, same order, no
 // contraction); the command kernel's distance tests sum in the order of a wave reduction (numpy's own sum is pairwise).
@@ -21,6 +22,7 @@
 #include <math.h>
 #include "../../include/admpc.h"
 #include "../../include/admpc_fleet.h"
+#include "../../include/admpc_lane.h"
 
 #define NX ADMPC_NX
 #define NU ADMPC_NU
@@ -31,6 +33,7 @@
 extern "C" int admpc_set_error(int code, const char* msg);                                  // admpc_kernels.hip
 extern "C" const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);      // admpc_kernels.hip
 extern "C" int admpc_path_bank_horizon(const AdmpcPathBank* bank, int* device);             // admpc_kernels.hip
+extern "C" int admpc_lane_params_check(const char* who, const AdmpcLaneParams* lane, const int32_t* lane_idx);   // admpc_lane.hip
 
 namespace {
 
@@ -297,6 +300,51 @@ int admpc_control_step_bank_batch(AdmpcSolver* s, const AdmpcPathBank* bank, con
         rc = admpc_resample_vel_batch(device, B, N, 6 * N, vx, vy, prm->acc_max, prm->resample_dt, w.ref + 3 * N, stream);
         if (rc) return rc;
     }
+    const long nP = (long)B * (N + 1);
+    hipLaunchKernelGGL(admpc_step_assemble_kernel, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, st, N, B, (const double*)w.ref,
+                       px, py, yaw, vx, vy, yaw_rate, steer, prm->blend_min, prm->blend_max, w.x0, w.yref, w.yref_e, w.p);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_assemble_kernel: launch failed");
+    rc = admpc_solve_batch(s, B, w.x0, w.yref, w.yref_e, w.p, xbar, ubar, cost, status, nullptr, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(admpc_step_command_cost_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE), 0, st, N, B, (const double*)w.ref, (const double*)xbar,
+                       (const double*)ubar, (const int32_t*)status, steer, safe_count, prev_u, has_valid, prm->threshold,
+                       cfg->lbu[1], cfg->ubu[1], cfg->lbx_delta, cfg->ubx_delta, ack, mode, valid, cost);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_command_cost_kernel: launch failed");
+    return ADMPC_OK;
+}
+
+// admpc_control_step_bank_batch along a route (include/admpc_lane.h): the lane generator of admpc_lane.hip cuts, clamps and tabulates a
+// local lane per vehicle and lays the window on it, in place of the waypoint call and of the clamp on the window behind it; from the
+// assembly on, the chain is the bank step's, launch for launch.
+int admpc_control_step_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, const AdmpcLaneParams* lane, const AdmpcStepParams* prm, int B,
+                                  const int32_t* path_of, int32_t* lane_idx,
+                                  const double* px, const double* py, const double* yaw, const double* vx, const double* vy,
+                                  const double* yaw_rate, const double* steer,
+                                  double* xbar, double* ubar, int32_t* safe_count, double* prev_u, int32_t* has_valid,
+                                  void* work, float* ack, int32_t* mode, int32_t* valid, int32_t* status, double* cost, void* stream)
+{
+    int rc = admpc_lane_params_check("admpc_control_step_lane_batch", lane, lane_idx);
+    if (rc) return rc;
+    if (!s || !prm || B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: null solver / params or negative batch");
+    int device = 0, bank_device = 0;
+    const AdmpcConfig* cfg = admpc_solver_config(s, &device);
+    const int N = cfg->N;
+    if (N < 3 || N > STEP_MAX_H) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: the solver's N must be in [3, 64] (the waypoint kernel's horizon)");
+    if (!bank) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: the bank is not set");
+    if (admpc_path_bank_horizon(bank, &bank_device) != N) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: the bank's horizon H must equal the solver's N");
+    if (bank_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: the bank lives on another device than the solver");
+    if (prm->threshold < 0 || !(prm->blend_max > prm->blend_min)) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: bad step parameters");
+    if (B == 0) return ADMPC_OK;
+    if (!path_of || !px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !xbar || !ubar || !safe_count || !prev_u || !has_valid || !work ||
+        !ack || !mode || !valid || !status)
+        return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: null array argument");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    hipStream_t st = (hipStream_t)stream;
+    StepWork w(work, N, B);
+    rc = admpc_waypoints_lane_batch(bank, lane, B, path_of, lane_idx, px, py, yaw, vx, vy, prm->resample, prm->acc_max, prm->resample_dt,
+                                    w.ref, w.err, w.stop, stream);
+    if (rc) return rc;
     const long nP = (long)B * (N + 1);
     hipLaunchKernelGGL(admpc_step_assemble_kernel, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, st, N, B, (const double*)w.ref,
                        px, py, yaw, vx, vy, yaw_rate, steer, prm->blend_min, prm->blend_max, w.x0, w.yref, w.yref_e, w.p);

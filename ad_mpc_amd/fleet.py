@@ -1,6 +1,7 @@
 """The control step of a fleet: pose in, Ackermann command out, for B vehicles on one global path
 (include/admpc.h: admpc_control_step_batch; csrc/admpc_step.hip), or with a path per vehicle out of a bank of paths and the best of
-every group of candidates (include/admpc_fleet.h: admpc_control_step_bank_batch, admpc_argmin_groups).
+every group of candidates (include/admpc_fleet.h: admpc_control_step_bank_batch, admpc_argmin_groups), or along a route of that bank,
+wherever on it the vehicle is (include/admpc_lane.h: admpc_control_step_lane_batch).
 
 ``FleetController`` solves the problem of ``ROSGPMPC(point_reference=False)`` (create_ros_ad_mpc.py:41-101: SQP_RTI, Q_DIAG_ROS /
 R_DIAG_ROS) for every vehicle, and does per step what the reference node does per pose message (gp_ad_mpc_node.py:389-438 ->
@@ -11,7 +12,8 @@ tensors of this object.
 
 One deliberate deviation: the node clamps the speed of the GLOBAL path once per waypoint message, at the speed the vehicle had then
 (:351-368).  Vehicles at different speeds cannot share that, so each step clamps each vehicle's local window at its current speed
-(admpc_resample_vel_batch); ``resample=False`` turns the clamp off.
+(admpc_resample_vel_batch); ``resample=False`` turns the clamp off.  ``step_route`` does not deviate here: it cuts a local lane per
+vehicle out of the route, as the node's waypoint message carries one, and clamps that lane as the node does.
 """
 import ctypes as C
 from typing import NamedTuple
@@ -23,7 +25,7 @@ from . import _lib
 from . import config as _c
 from .ad_3d import AD3D
 from .ad_3d_optimizer import ocp_config
-from .config import AdmpcPath, AdmpcStepParams, NX, NU
+from .config import AdmpcLaneParams, AdmpcPath, AdmpcStepParams, NX, NU
 from .engine import BatchSolver, _ptr
 from .ref_traj import RefTrajectory
 
@@ -49,6 +51,18 @@ class FleetPathStep(NamedTuple):
     x_opt: torch.Tensor
     w_opt: torch.Tensor
     cost: torch.Tensor         # float64 [B]: objective of the solve; +inf where status != 0 or valid == 0 (NOT where mode == 0: admpc_fleet.h)
+
+
+class FleetLaneStep(NamedTuple):
+    """FleetPathStep of a step along a route (step_route), with the waypoint at which every vehicle's lane began."""
+    ack: torch.Tensor
+    mode: torch.Tensor
+    status: torch.Tensor
+    valid: torch.Tensor
+    x_opt: torch.Tensor
+    w_opt: torch.Tensor
+    cost: torch.Tensor
+    lane_idx: torch.Tensor     # int32 [B]: the nearest waypoint of the route, where the lane was cut; the next step searches around it
 
 
 class FleetController:
@@ -84,6 +98,7 @@ class FleetController:
         self.mode, self.valid, self.status = z(B, dtype=torch.int32), z(B, dtype=torch.int32), z(B, dtype=torch.int32)
         self.cost = z(B)                                                  # step_paths; best_of reduces it into the two below
         self._best_val, self._best_idx = z(B), z(B, dtype=torch.int64)
+        self.lane_idx = torch.full((B,), -1, dtype=torch.int32, device=self.device)      # step_route; -1: search the whole route
         self._bank, self._stepped_paths, self.n_paths = None, False, 0
 
     def _drop_bank(self):
@@ -155,8 +170,30 @@ class FleetController:
         self._stepped_paths = True
         return FleetPathStep(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt, self.cost)
 
+    def step_route(self, path_of, x, y, yaw, vx, vy, yaw_rate, steer, lane=64, back=8, ahead=64):
+        """step_paths for vehicles anywhere along their route: every step cuts a local lane of `lane` waypoints (34 .. 256) out of route
+        path_of[b], beginning at the waypoint nearest to the vehicle, clamps its speeds at the vehicle's speed (``resample``), tabulates it
+        as set_traj does and lays the reference window on it (include/admpc_lane.h).  The nearest waypoint is searched over the whole
+        route on a vehicle's first step (lane_idx -1) and from `back` waypoints behind to `ahead` waypoints in front of the last answer
+        afterwards.  Returns FleetLaneStep; best_of works as after step_paths."""
+        if self._bank is None:
+            raise ValueError("step_route: no bank of paths, call set_paths first")
+        prm = AdmpcLaneParams(L=int(lane), back=int(back), ahead=int(ahead))
+        if not 34 <= prm.L <= 256 or prm.back < 0 or prm.ahead < 0:
+            raise ValueError("step_route: lane must be in [34, 256], back and ahead must not be negative")
+        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
+        self._eng._chk(path_of, (self.B,), torch.int32)
+        for t in ins:
+            self._eng._chk(t, (self.B,))
+        _lib.check(self.lib.admpc_control_step_lane_batch(
+            self._eng._h, self._bank, C.byref(prm), C.byref(self._prm), self.B, _ptr(path_of), _ptr(self.lane_idx), *[_ptr(t) for t in ins],
+            _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
+            _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), _ptr(self.cost), self._eng._stream()))
+        self._stepped_paths = True
+        return FleetLaneStep(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt, self.cost, self.lane_idx)
+
     def best_of(self, group):
-        """The cheapest usable candidate of every group of `group` consecutive instances of the last step_paths (instance b = v * group + c
+        """The cheapest usable candidate of every group of `group` consecutive instances of the last step_paths or step_route (instance b = v * group + c
         for vehicle v and candidate c): (val float64 [B / group], idx int64 [B / group]) device tensors, idx into the batch, so the command
         of vehicle v is ack[idx[v]].  A group without a usable candidate gives (+inf, its first instance).  Asynchronous; the tensors
         are the controller's own and are overwritten by the next call."""
@@ -179,7 +216,8 @@ class FleetController:
 
     def reset(self, mask=None):
         """Selected vehicles (bool [B], host or device; None: all) start over as a freshly created controller: zero iterate, no
-        previous valid inputs, safe_count 0 -- what re-creating the solver in reset_mpc_optimizer would give (gp_ad_mpc_node.py:154-158)."""
+        previous valid inputs, safe_count 0 -- what re-creating the solver in reset_mpc_optimizer would give (gp_ad_mpc_node.py:154-158) --
+        and, for step_route, a search of the whole route (lane_idx -1)."""
         if mask is None:
             m = slice(None)
         else:
@@ -188,3 +226,4 @@ class FleetController:
                 raise ValueError("mask must have shape (%d,)" % self.B)
         for t in (self.x_opt, self.w_opt, self.safe_count, self.prev_u, self.has_valid):
             t[m] = 0
+        self.lane_idx[m] = -1

@@ -4,11 +4,15 @@ set_reference, optimize: what a host does for each vehicle without the fleet ste
 
     python scripts/fleet_step.py [--batches 1,64,4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--loop-calls 200]
     python scripts/fleet_step.py --bank [--batches 4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--repeats 5]
+    python scripts/fleet_step.py --lane [--batches 4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--repeats 5]
 
 --bank: the same workloads through a bank of paths (admpc_control_step_bank_batch: set_paths / step_paths) with K = 1 and with K = 8 copies
 of the path and round-robin path_of, against the single-path step in the same process, the variants interleaved `repeats` times (one JSON
 line per (N, B) with every repeat and the medians); and admpc_argmin_groups at (G, group) = (4096, 4) and (64, 1024) against admpc_argmin
 over the same number of entries.
+
+--lane: the step along a route (admpc_control_step_lane_batch: step_route with L = 64) for B vehicles spread along one route of 2000
+waypoints, against the single-path step and the bank step (K = 1) for B vehicles at the start of the same route, interleaved as above.
 
 One JSON line per (N, B) and one for the per-vehicle loop per N.  Times come from HIP events around `steps` back-to-back steps (fleet,
 bare solve) or wall time around `loop-calls` calls (the per-vehicle loop, which synchronises at every call by construction)."""
@@ -111,6 +115,40 @@ def bank_against_single(N, B, p, steps, warmup, repeats):
     return times
 
 
+def lane_against_bank(N, B, steps, warmup, repeats, M=2000, lane=64):
+    """Seconds per step of the single-path step, the bank step (K = 1) and the lane step on one route of M waypoints.  The first two can
+    only serve vehicles at the route's start and get those; the lane step gets vehicles spread over the route, 0.3 m off it."""
+    p = path(M)
+    x, y, psi, _ = p
+    rng = np.random.default_rng(1)
+    at = rng.integers(0, M - 50, size=B)
+    e = 0.3 * (-1.0) ** np.arange(B)
+    spread = [x[at] - e * np.sin(psi[at]), y[at] + e * np.cos(psi[at]), psi[at] + rng.uniform(-0.05, 0.05, size=B), rng.uniform(5.0, 9.0, size=B),
+              rng.uniform(-0.1, 0.1, size=B), rng.uniform(-0.05, 0.05, size=B), rng.uniform(-0.03, 0.03, size=B)]
+    runs, ins = {}, {}
+    for name in ("single", "bank_k1", "lane"):
+        fc = FleetController(T_HORIZON, N, OPT_DT, B)
+        ins[name] = [torch.as_tensor(a, dtype=torch.float64, device=fc.device) for a in (spread if name == "lane" else poses(B, p))]
+        zero = torch.zeros(B, dtype=torch.int32, device=fc.device)
+        if name == "single":
+            fc.set_traj(*p)
+            runs[name] = (fc, lambda fc=fc: fc.step(*ins["single"]))
+        elif name == "bank_k1":
+            fc.set_paths([p])
+            runs[name] = (fc, lambda fc=fc, zero=zero: fc.step_paths(zero, *ins["bank_k1"]))
+        else:
+            fc.set_paths([p])
+            runs[name] = (fc, lambda fc=fc, zero=zero: fc.step_route(zero, *ins["lane"], lane=lane))
+    times = {name: [] for name in runs}
+    for _ in range(repeats):
+        for name, (fc, fn) in runs.items():
+            times[name].append(timed(fn, steps, warmup))
+    share = {name: float(fc.valid.float().mean().item()) for name, (fc, _) in runs.items()}
+    for fc, _ in runs.values():
+        fc.close()
+    return times, share
+
+
 def argmin_groups_against_argmin(steps, warmup, repeats):
     """Seconds per call of admpc_argmin_groups at (G, group) and of admpc_argmin over G * group entries."""
     fc = FleetController(T_HORIZON, 20, OPT_DT, 4)
@@ -161,10 +199,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--loop-calls", type=int, default=200)
     ap.add_argument("--bank", action="store_true", help="the bank of paths against the single-path step, and the arg-min per group")
+    ap.add_argument("--lane", action="store_true", help="the step along a route against the bank step and the single-path step")
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     p = path()
     gpu = torch.cuda.get_device_name(0)
+    if a.lane:
+        us = lambda ts: [round(t * 1e6, 1) for t in ts]
+        med = lambda ts: float(np.median(ts))
+        for N in [int(v) for v in a.horizons.split(",")]:
+            for B in [int(v) for v in (a.batches if a.batches != "1,64,4096" else "4096").split(",")]:
+                t, share = lane_against_bank(N, B, a.steps, a.warmup, a.repeats)
+                print(json.dumps({"what": "fleet_step_lane", "N": N, "B": B, "route_waypoints": 2000, "L": 64,
+                                  "us_per_step": {k: us(v) for k, v in t.items()}, "median_us": {k: round(med(v) * 1e6, 1) for k, v in t.items()},
+                                  "vehicles_per_s": {k: round(B / med(v), 1) for k, v in t.items()},
+                                  "lane_rate_over_bank_rate": round(med(t["bank_k1"]) / med(t["lane"]), 4), "valid_share": share, "gpu": gpu}), flush=True)
+        return
     if a.bank:
         us = lambda ts: [round(t * 1e6, 1) for t in ts]
         med = lambda ts: float(np.median(ts))
