@@ -11,7 +11,9 @@
 //              from the tables -- the split keeps the phase inside the 256-register budget of two waves per SIMD)
 //   C  H2-H4  Gauss-Newton cost, bounds, full condensing                ad_3d_optimizer.py:146-199; acados_solver_sim_car.c:145
 //   D  H5     unconstrained trial, Mehrotra predictor-corrector on the dense 40-input QP (reference: HPIPM, :688-692);
-//             the 40 x 40 LDL' and its solve are dense40.h's dense40_factorise / dense40_solve (shared with admpc_quad.hip)
+//             the 40 x 40 LDL' and its solve are dense40.h's dense40_factorise / dense40_solve (shared with admpc_quad.hip); the
+//             right-hand sides that are known in front of a factorisation (the trial's, the predictor's) go through it as row 40
+//             of the matrix and are finished by dense40_solve_back: no forward substitution for them
 //   E  H6     state expansion, full step, cost, status                  acados_solver_sim_car.c:647-648,677
 // The phase bodies descend from the four-kernel pipeline of rounds 1-2 (kernels A, C, D, E; C, D, E removed, last
 // present at commit a808f29); what changed is where the data lives and that no instance waits for a kernel boundary: the slowest instance
@@ -88,7 +90,8 @@ __device__ unsigned long long g_f20_ticks[16];
 //   H/L [840, 1660)  H (from phase C's row store to the row build of a factorisation) and the factor L (from there to the last
 //        substitution of the iteration) in ONE buffer: H waits in the wave's slot of global memory and is fetched back (slot_fetch)
 //   park [1660, 1980), cb / invd / sb / sb2 [1980, 2236)  per-lane constants and exchange buffers of phase D (the relative layout
-//        dense40.h's col_head assumes: sb = cb + 128)
+//        dense40.h's col_head assumes: sb = cb + 128); sb2 doubles as the right-hand-side row of the factorisations (Dense40Lds::rhs:
+//        y in, D^-1 L^-1 y out), invd carries the suffix sums of e from the residual pass to the predictor's right-hand side
 //   bl [2236, 2376)  defects b_k, written by phase A, read by phases C and E;  scheduler table [2376, 2440)
 // The other phases alias it:
 //   A   JT [0, 1960) Jacobian tables of the RK stages (over GT, H/L, park; clear of bl and the scheduler table); GT is written when the
@@ -166,13 +169,17 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
 
     // Factorisation of the Newton matrix M = H + diag(dbar) + (s_odd on the odd columns of the u1 rows) into L D L' (LDS: Lp, invd) and
     // the solve M x = y through the factor: dense40.h, the functions the quadrotor's kernel calls.
-    const Dense40Lds W{Hp, Lp, cb, invd};
+    // Both factorisations of this kernel know their first right-hand side before they start (the trial's -g0, the predictor's, a function of
+    // the iterate): it is published in sb2 and rides through the factorisation as row 40 (dense40.h), which leaves D^-1 L^-1 y in sb2 -- the
+    // forward substitution and the scaling of that solve are never run.  The corrector's right-hand side needs the predictor's result and
+    // takes the whole solve.
+    const Dense40Lds W{Hp, Lp, cb, invd, sb2};
     auto factorise = [&](const double dbar_, const double sodd_, const int lz_) __attribute__((always_inline)) {
         dense40_factorise(W, lz_, dbar_, sodd_, lz_, [&](double (&)[n]) __attribute__((always_inline)) {
             // H's rows are in registers: its buffer becomes the factor's.  Diagonal slots of the packed factor: 0.0 (the factorisation stores the
             // strictly-lower part only; the substitution assembly lets the source lane of a step take part with this multiplier)
             if (lz_ < n) Lp[lz_ * (lz_ + 1) / 2 + lz_] = 0.0;
-        });
+        }, std::true_type{});
     };
 
     // ---------------- persistent loop: first ticket = block index, later ones from one global counter ----------------
@@ -528,6 +535,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                 for (int i = 0; i < 2; ++i) { Dt[i] = r0[i] > thr ? r0[i] : thr; Dlam[i] = mu0 * rcp_nr(Dt[i]); }
             }
             PK_DL = dl_i; PK_DUU = duu_i; PK_G0 = g0; PK_DDL = Ddl; PK_DDU = Ddu;      // parked in LDS: registers are the scarce resource
+            if (try_unc) sb2[lane] = uact ? -g0 : 0.0;                                 // the trial's right-hand side: row 40 of its factorisation
             WSYNC();
 
             double rmax_prev = 0.0, step = 1e300, stp_local = 1e300, alpha_prev = 1.0;
@@ -535,7 +543,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             if (try_unc) {
                 int lt = lane; asm volatile("" : "+v"(lt));
                 factorise(uact ? Rj : 1.0, 0.0, lt);
-                const double xt = dense40_solve(W, uact ? -g0 : 0.0, lt);
+                const double xt = dense40_solve_back(W, lt);
                 const double duc = uact ? xt : 0.0;
                 cb[lane] = duc;
                 WSYNC();
@@ -598,17 +606,32 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                 double ru, mu, Dbar, S_i;
                 {
                     double musum = 0.0, cmax = 0.0, rmax = 0.0;
-                    double G0, G1, G2, G3;
-                    {
-                        const double i0 = rcp_nr(t[0]), i1 = rcp_nr(t[1]), i2_ = rcp_nr(t[2]), i3 = rcp_nr(t[3]);
-                        G0 = lam[0] * i0; G1 = lam[1] * i1; G2 = lam[2] * i2_; G3 = lam[3] * i3;
-                    }
+                    const double i0 = rcp_nr(t[0]), i1 = rcp_nr(t[1]), i2_ = rcp_nr(t[2]), i3 = rcp_nr(t[3]);
+                    const double G0 = lam[0] * i0, G1 = lam[1] * i1, G2 = lam[2] * i2_, G3 = lam[3] * i3;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) { const double rci = t[i] * lam[i]; musum += uact ? rci : 0.0; cmax = fmax(cmax, uact ? rci : 0.0); }
 #pragma unroll
                     for (int i = 0; i < 2; ++i) { const double rci = Dt[i] * Dlam[i]; musum += dact ? rci : 0.0; cmax = fmax(cmax, dact ? rci : 0.0); }
-                    const double G56 = Dlam[0] * rcp_nr(Dt[0]) + Dlam[1] * rcp_nr(Dt[1]);
-                    Dbar = uact ? Rj + G0 * G2 * rcp_nr(G0 + G2) + G1 * G3 * rcp_nr(G1 + G3) : 1.0;       // idle lanes: identity rows
+                    const double Di0 = rcp_nr(Dt[0]), Di1 = rcp_nr(Dt[1]);
+                    const double G56 = Dlam[0] * Di0 + Dlam[1] * Di1;
+                    const double iG02 = rcp_nr(G0 + G2), iG13 = rcp_nr(G1 + G3);
+                    Dbar = uact ? Rj + G0 * G2 * iG02 + G1 * G3 * iG13 : 1.0;       // idle lanes: identity rows
+                    // The predictor's right-hand side depends on the iterate alone (pass 0 below: rc = t lam, the same formulas): all of it but
+                    // ru and the suffix sum of e is ready here, and only these two values live across the mat-vec
+                    double etal, etau;
+                    {
+                        const double rd0 = du + sl - PK_DL - t[0], rd1 = -du + su + PK_DUU - t[1], rd2 = sl - t[2], rd3 = su - t[3];
+                        const double rsl = rho_l - lam[0] - lam[2], rsu = rho_u - lam[1] - lam[3];
+                        const double c0 = (t[0] * lam[0]) * i0, c1 = (t[1] * lam[1]) * i1, c2 = (t[2] * lam[2]) * i2_, c3 = (t[3] * lam[3]) * i3;
+                        const double e1 = rsl + c0 + c2 + G0 * rd0 + G2 * rd2;
+                        const double e2 = rsu + c1 + c3 + G1 * rd1 + G3 * rd3;
+                        etal = c0 + G0 * rd0 - G0 * e1 * iG02;
+                        etau = -c1 - G1 * rd1 + G1 * e2 * iG13;
+                        const double Drd0 = dx6 - PK_DDL - Dt[0], Drd1 = PK_DDU - dx6 - Dt[1];
+                        const double ek = dact ? ((Dt[0] * Dlam[0]) * Di0 + (Dlam[0] * Di0) * Drd0) - ((Dt[1] * Dlam[1]) * Di1 + (Dlam[1] * Di1) * Drd1) : 0.0;
+                        const double epref = wave_scan_incl<OpSum>(ek);
+                        invd[lane] = rdlane(epref, 63) - epref;             // suffix over stages > lane; invd is free up to the factorisation
+                    }
                     cb[lane] = uact ? du : 0.0;
                     const double dlam_pref = wave_scan_incl<OpSum>(dact ? (Dlam[1] - Dlam[0]) : 0.0);     // lanes = stages
                     sb[lane] = rdlane(dlam_pref, 63) - dlam_pref;           // suffix over stages > lane
@@ -630,6 +653,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     }
                     ru = hdu + Rj * du + PK_G0 - lam[0] + lam[1] + (ji ? h * sb[uact ? ki : 0] : 0.0);
                     S_i = h * h * sb2[uact ? ki : 0];                        // lane = input: S_{k_i}
+                    const double esuf = invd[uact ? ki : 0];
                     {
                         const double rd0 = du + sl - PK_DL - t[0], rd1 = -du + su + PK_DUU - t[1], rd2 = sl - t[2], rd3 = su - t[3];
                         const double rsl = rho_l - lam[0] - lam[2], rsu = rho_u - lam[1] - lam[3];
@@ -647,6 +671,9 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     if (cmax <= tol_comp && step <= tol_step &&
                         (rmax <= tol_res || (it > 0 && rmax > 0.1 * rmax_prev && rmax <= ADMPC_IPM_FLOOR_CAP * tol_res))) break;      // admpc.h: stopping test
                     rmax_prev = rmax;
+                    // published behind the read of S_i (same wave, LDS in program order); the WSYNC in front of the factorisation orders
+                    // it against lane 40's row build
+                    sb2[lane] = uact ? -(ru + etal + etau + (ji ? h * esuf : 0.0)) : 0.0;
                 }
                 if (fbit > 0 && !cons && it >= fbit) {            // (no factorisation behind the fetch yet: H stays in LDS for the restart)
                     cons = true; warmed = false;
@@ -655,6 +682,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     --it;
                     continue;
                 }
+                WSYNC();
                 factorise(Dbar, (uz && ji) ? S_i : 0.0, lz);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(t[i]), "+v"(lam[i]));
@@ -678,14 +706,19 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     const double c0 = rc[0] * it_[0], c1 = rc[1] * it_[1], c2 = rc[2] * it_[2], c3 = rc[3] * it_[3];
                     const double e1 = rsl + c0 + c2 + G0 * rd0 + G2 * rd2;
                     const double e2 = rsu + c1 + c3 + G1 * rd1 + G3 * rd3;
-                    const double etal = c0 + G0 * rd0 - G0 * e1 * iG02;
-                    const double etau = -c1 - G1 * rd1 + G1 * e2 * iG13;
-                    const double ek = dact ? (Drc[0] * Dit[0] + G5 * Drd0) - (Drc[1] * Dit[1] + G6 * Drd1) : 0.0;
-                    const double epref = wave_scan_incl<OpSum>(ek);
-                    sb[lane] = rdlane(epref, 63) - epref;
-                    WSYNC();
-                    double y = uact ? -(ru + etal + etau + (ji ? h * sb[ki] : 0.0)) : 0.0;
-                    const double x = dense40_solve(W, y, lz);
+                    double z;
+                    if (pass == 0) z = dense40_rhs_row(W, lz);                 // the predictor's forward solve came with the factorisation
+                    else {
+                        const double etal = c0 + G0 * rd0 - G0 * e1 * iG02;
+                        const double etau = -c1 - G1 * rd1 + G1 * e2 * iG13;
+                        const double ek = dact ? (Drc[0] * Dit[0] + G5 * Drd0) - (Drc[1] * Dit[1] + G6 * Drd1) : 0.0;
+                        const double epref = wave_scan_incl<OpSum>(ek);
+                        sb[lane] = rdlane(epref, 63) - epref;
+                        WSYNC();
+                        const double y = uact ? -(ru + etal + etau + (ji ? h * sb[ki] : 0.0)) : 0.0;
+                        z = dense40_solve_fwd(W, y, lz);
+                    }
+                    const double x = dense40_solve_bwd(W, z, lz);
                     if (pass == 1) slot_fetch<FusedLds::NTRI, slot_aux>(Hp, slot, lz);     // the factor is dead: next iteration's H under the step-length work
                     ddu = uact ? x : 0.0;
                     cb[lane] = ddu;

@@ -208,6 +208,8 @@ def main():
         txt += emit("ADMPC_FWD_SUBST_ASM_%d_R%d" % (n, nr), fwd(n, nr)) + "\n"
         txt += emit("ADMPC_ROWBUILD_ASM_%d_A_R%d" % (n, nr), rowbuild(n, 0, n // 2, nr)) + "\n" + emit("ADMPC_ROWBUILD_ASM_%d_B_R%d" % (n, nr), rowbuild(n, n // 2, n, nr)) + "\n"
         txt += emit("ADMPC_SYMROW_ASM_%d_A_R%d" % (n, nr), symrow(n, 0, n // 2, nr)) + "\n" + emit("ADMPC_SYMROW_ASM_%d_B_R%d" % (n, nr), symrow(n, n // 2, n, nr)) + "\n"
+    # right-hand-side row (dense40_factorise with a row 40, kernel F): lane n carries the right-hand side of the solve through the factorisation
+    txt += emit("ADMPC_ROWBUILD_ASM_%d_A_R%d" % (n, n + 1), rowbuild(n, 0, n // 2, n + 1)) + "\n" + emit("ADMPC_ROWBUILD_ASM_%d_B_R%d" % (n, n + 1), rowbuild(n, n // 2, n, n + 1)) + "\n"
     txt += "#define ADMPC_SUBST_CLOBBERS %s, \"memory\"\n" % clob
     open(sys.argv[1] if len(sys.argv) > 1 else "subst_asm.inc", "w").write(txt)
 
