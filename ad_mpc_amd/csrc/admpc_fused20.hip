@@ -174,12 +174,16 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
     // forward substitution and the scaling of that solve are never run.  The corrector's right-hand side needs the predictor's result and
     // takes the whole solve.
     const Dense40Lds W{Hp, Lp, cb, invd, sb2};
-    auto factorise = [&](const double dbar_, const double sodd_, const int lz_) __attribute__((always_inline)) {
+    // The row build pulls H unmasked and takes the diagonal term through LDS where that is exact (dense40.h, PULL: 2 the trial, s_odd = 0
+    // in every lane; 1 the iterations, s_odd = 0 in the even lanes).  H's diagonal slots are rewritten in place: the buffer turns into
+    // the factor's right behind, and H comes back from the slot -- phase C's stage_in(slot, Hp) has read H from LDS before the trial's
+    // rewrite (program order, one wave), and every fetch lands before the mat-vec in front of the next rewrite.
+    auto factorise = [&](const double dbar_, const double sodd_, const int lz_, auto pull) __attribute__((always_inline)) {
         dense40_factorise(W, lz_, dbar_, sodd_, lz_, [&](double (&)[n]) __attribute__((always_inline)) {
             // H's rows are in registers: its buffer becomes the factor's.  Diagonal slots of the packed factor: 0.0 (the factorisation stores the
             // strictly-lower part only; the substitution assembly lets the source lane of a step take part with this multiplier)
             if (lz_ < n) Lp[lz_ * (lz_ + 1) / 2 + lz_] = 0.0;
-        }, std::true_type{});
+        }, std::true_type{}, pull);
     };
 
     // ---------------- persistent loop: first ticket = block index, later ones from one global counter ----------------
@@ -538,17 +542,17 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             if (try_unc) sb2[lane] = uact ? -g0 : 0.0;                                 // the trial's right-hand side: row 40 of its factorisation
             WSYNC();
 
-            double rmax_prev = 0.0, step = 1e300, stp_local = 1e300, alpha_prev = 1.0;
+            double rmax_prev = 0.0, stp_local = 1e300, alpha_prev = 1.0;
             bool solved = false, warmed = false, cons = false;
             if (try_unc) {
                 int lt = lane; asm volatile("" : "+v"(lt));
-                factorise(uact ? Rj : 1.0, 0.0, lt);
+                factorise(uact ? Rj : 1.0, 0.0, lt, std::integral_constant<int, 2>{});
                 const double xt = dense40_solve_back(W, lt);
                 const double duc = uact ? xt : 0.0;
                 cb[lane] = duc;
                 WSYNC();
                 const double du1_stage = lane < N ? cb[2 * lane + 1] : 0.0;
-                const double pre = wave_scan_incl<OpSum>(du1_stage);
+                const double pre = wave_scan_incl32<OpSum>(du1_stage);       // lanes >= 20 hold 0.0; used in lanes < 20
                 const double dx6c = xh6_own + h * (pre - du1_stage);
                 const bool ok = (!uact || (duc >= dl_i && duc <= duu_i)) && (!dact || (dx6c >= Ddl && dx6c <= Ddu));
                 WSYNC();
@@ -629,14 +633,14 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         etau = -c1 - G1 * rd1 + G1 * e2 * iG13;
                         const double Drd0 = dx6 - PK_DDL - Dt[0], Drd1 = PK_DDU - dx6 - Dt[1];
                         const double ek = dact ? ((Dt[0] * Dlam[0]) * Di0 + (Dlam[0] * Di0) * Drd0) - ((Dt[1] * Dlam[1]) * Di1 + (Dlam[1] * Di1) * Drd1) : 0.0;
-                        const double epref = wave_scan_incl<OpSum>(ek);
-                        invd[lane] = rdlane(epref, 63) - epref;             // suffix over stages > lane; invd is free up to the factorisation
+                        const double epref = wave_scan_incl32<OpSum>(ek);   // (the scans' operands are 0.0 from lane 20 on: five steps, total in lane 31)
+                        invd[lane] = rdlane(epref, 31) - epref;             // suffix over stages > lane (read by lanes < 20); invd is free up to the factorisation
                     }
                     cb[lane] = uact ? du : 0.0;
-                    const double dlam_pref = wave_scan_incl<OpSum>(dact ? (Dlam[1] - Dlam[0]) : 0.0);     // lanes = stages
-                    sb[lane] = rdlane(dlam_pref, 63) - dlam_pref;           // suffix over stages > lane
-                    const double Ssuf_incl = wave_scan_incl<OpSum>(dact ? G56 : 0.0);
-                    sb2[lane] = rdlane(Ssuf_incl, 63) - Ssuf_incl;          // lane = stage: sum over stages > lane
+                    const double dlam_pref = wave_scan_incl32<OpSum>(dact ? (Dlam[1] - Dlam[0]) : 0.0);     // lanes = stages
+                    sb[lane] = rdlane(dlam_pref, 31) - dlam_pref;           // suffix over stages > lane
+                    const double Ssuf_incl = wave_scan_incl32<OpSum>(dact ? G56 : 0.0);
+                    sb2[lane] = rdlane(Ssuf_incl, 31) - Ssuf_incl;          // lane = stage: sum over stages > lane
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // H has landed (fetched in front of the loop or behind the last solve)
                     WSYNC();
                     double hdu = 0.0;
@@ -645,7 +649,9 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
 #pragma unroll
                         for (int m = 0; m < 3; ++m) Rd3[m] = cb[16 * m + (lane & 15)];
                         double hv[n];
-                        sym_row_40(hv, lds_byte_addr(Hp + (uz ? trz : 0)), lds_byte_addr(Hp + (uz ? lz : 0)));
+                        // no presets: lanes >= 40 load nothing, their hv, hdu and ru are stale register contents (possibly NaN).  Every use of
+                        // ru is a select on uact: rmax, the predictor's and the corrector's right-hand side
+                        sym_row_40_np(hv, lds_byte_addr(Hp + (uz ? trz : 0)), lds_byte_addr(Hp + (uz ? lz : 0)));
                         static_for<0, n>([&](auto cc) __attribute__((always_inline)) {
                             constexpr int c = decltype(cc)::value;
                             fmac_rowbc_ld<c % 16>(hdu, Rd3[c / 16], hv[c]);
@@ -664,11 +670,13 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         rmax = OpMaxNan::f(uact ? ra : 0.0, dact ? rb : 0.0);
                     }
                     mu = wave_reduce<OpSum>(musum) * inv_nineq;
-                    cmax = wave_reduce<OpMax0>(cmax);
                     rmax = wave_reduce<OpMaxNan0>(rmax);
-                    step = wave_reduce<OpMax0>(stp_local);
+                    // complementarity and step are only compared with their tolerances: a wave vote instead of a max-reduction each.  The
+                    // reduction's fmax skips NaN operands and starts from 0.0, so a NaN lane must not veto (the negated greater-than) and the
+                    // idle lanes' 0.0 and the first iteration's 1e300 vote like everybody else
+                    const bool comp_ok = __all(!(cmax > tol_comp)), step_ok = __all(!(stp_local > tol_step));
                     if (!(mu == mu) || !(rmax == rmax)) { failed = true; break; }
-                    if (cmax <= tol_comp && step <= tol_step &&
+                    if (comp_ok && step_ok &&
                         (rmax <= tol_res || (it > 0 && rmax > 0.1 * rmax_prev && rmax <= ADMPC_IPM_FLOOR_CAP * tol_res))) break;      // admpc.h: stopping test
                     rmax_prev = rmax;
                     // published behind the read of S_i (same wave, LDS in program order); the WSYNC in front of the factorisation orders
@@ -683,7 +691,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     continue;
                 }
                 WSYNC();
-                factorise(Dbar, (uz && ji) ? S_i : 0.0, lz);
+                factorise(Dbar, (uz && ji) ? S_i : 0.0, lz, std::integral_constant<int, 1>{});
 #pragma unroll
                 for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(t[i]), "+v"(lam[i]));
 #pragma unroll
@@ -712,8 +720,8 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         const double etal = c0 + G0 * rd0 - G0 * e1 * iG02;
                         const double etau = -c1 - G1 * rd1 + G1 * e2 * iG13;
                         const double ek = dact ? (Drc[0] * Dit[0] + G5 * Drd0) - (Drc[1] * Dit[1] + G6 * Drd1) : 0.0;
-                        const double epref = wave_scan_incl<OpSum>(ek);
-                        sb[lane] = rdlane(epref, 63) - epref;
+                        const double epref = wave_scan_incl32<OpSum>(ek);
+                        sb[lane] = rdlane(epref, 31) - epref;
                         WSYNC();
                         const double y = uact ? -(ru + etal + etau + (ji ? h * sb[ki] : 0.0)) : 0.0;
                         z = dense40_solve_fwd(W, y, lz);
@@ -724,7 +732,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     cb[lane] = ddu;
                     WSYNC();
                     const double du1_stage = lane < N ? cb[2 * lane + 1] : 0.0;
-                    const double pre = wave_scan_incl<OpSum>(du1_stage);
+                    const double pre = wave_scan_incl32<OpSum>(du1_stage);       // lanes >= 20 hold 0.0; used in lanes < 20
                     const double ddx6 = h * (pre - du1_stage);
                     dsl = -(e1 + G0 * ddu) * iG02;
                     dsu = -(e2 - G1 * ddu) * iG13;

@@ -44,6 +44,18 @@ __device__ __forceinline__ double wave_scan_incl(double v) {      // inclusive p
     v = Op::f(v, dpp_mov<0x143, 0xc>(Op::id(), v));
     return v;
 }
+// The same for an operand that holds the operation's identity in lanes 32..63 (kernel F: per-stage quantities, lanes 0..19): without the
+// row_bcast:31 step, which changes lanes 32..63 only.  Lanes 0..31 hold the bits wave_scan_incl gives them, lane 31 the total; lanes
+// 32..63 are NOT the prefix (rows 2 and 3 never see the lower half).
+template <class Op>
+__device__ __forceinline__ double wave_scan_incl32(double v) {
+    v = Op::f(v, dpp_shr<0x111, Op::zf>(Op::id(), v));
+    v = Op::f(v, dpp_shr<0x112, Op::zf>(Op::id(), v));
+    v = Op::f(v, dpp_shr<0x114, Op::zf>(Op::id(), v));
+    v = Op::f(v, dpp_shr<0x118, Op::zf>(Op::id(), v));
+    v = Op::f(v, dpp_mov<0x142, 0xa>(Op::id(), v));
+    return v;
+}
 
 __device__ __forceinline__ int wave_scan_incl_int(int v) {        // inclusive prefix sum over lanes 0..lane
     v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);

@@ -156,6 +156,38 @@ def rowbuild(n, lo, hi, nrows=None):
     return out
 
 
+def rowpull(n, lo, hi, sodd=True, diag="all"):
+    """Newton-matrix row of this lane, columns lo..hi-1, for a factorisation that never reads an entry above the diagonal of a row
+    (dense40.h: every rank-1 update is lane-local, the pivot of column j is read from lane j, the factor column store is masked to the
+    lanes below j): one UNMASKED load per column at row base + 8 c, no zero presets.  Lane i < n holds H[i][c] for c <= i and the entries
+    of the rows behind its own for c > i (inside the packed buffer: n (n + 1) / 2 - 1 is the last double any of them reaches); a lane
+    whose base is a buffer of n doubles holds that buffer (the right-hand-side row); a lane parked on row 0 holds rows 0 .. 7.
+      sodd = False: no s_odd adds (a caller whose s_odd is 0.0 in every lane)
+      diag = "all" : dbar is added to lane c of column c, as rowbuild does
+             "odd" : to the odd lanes only -- the caller has rewritten the diagonal slot of every even lane with H_cc + dbar
+             "none": to no lane -- the caller has rewritten all of them (it passes s_odd = 0: (H_cc + 0.0) + dbar is H_cc + dbar)
+    Operands as rowbuild: %0..%(hi-lo-1) the row entries, the row address, dbar, s_odd."""
+    assert diag in ("all", "odd", "none")
+    assert 0 <= lo < hi <= n                # lane n - 1 reads up to (n - 1) n / 2 + hi - 1 <= n (n + 1) / 2 - 1: inside the packed buffer
+    cnt = hi - lo; A, DB, SO = cnt, cnt + 1, cnt + 2
+    out = []
+    for q in range(cnt):
+        out.append("ds_read_b64 %%%d, %%%d offset:%d" % (q, A, 8 * (lo + q)))
+    out.append("s_waitcnt lgkmcnt(0)")
+    if sodd:
+        for q in range(cnt):
+            if (lo + q) & 1:
+                out.append("v_add_f64 %%%d, %%%d, %%%d" % (q, q, SO))
+    cols = [c for c in range(lo, hi) if diag == "all" or (diag == "odd" and c & 1)]
+    if cols:
+        out.append("s_mov_b64 s[%d:%d], exec" % (SAVE, SAVE + 1))
+        for c in cols:
+            out.append("s_bfm_b64 exec, 1, %d" % c)                                # lane c
+            out.append("v_add_f64 %%%d, %%%d, %%%d" % (c - lo, c - lo, DB))
+        out.append("s_mov_b64 exec, s[%d:%d]" % (SAVE, SAVE + 1))
+    return out
+
+
 def rowstore(n, lo, hi):
     """Packed lower-triangular row of this lane, columns lo..hi-1, to LDS: lanes c .. n-1 store column c (EXEC mask), one base
     address + immediate offsets.  Operands: %0..%(hi-lo-1) the row entries, then the lane's row address."""
@@ -169,14 +201,14 @@ def rowstore(n, lo, hi):
     return out
 
 
-def symrow(n, lo, hi, nrows=None):
+def symrow(n, lo, hi, nrows=None, preset=True):
     """Row of the symmetric matrix stored as packed lower-triangular rows, columns lo..hi-1, for the mat-vec: lanes >= c read
     H[lane][c] (row address + 8 c), lanes < c read H[c][lane] (column address + 8 c (c + 1) / 2) -- two EXEC-masked loads per
     column into the same register, all in flight together.  Operands: %0..%(hi-lo-1) outputs, then row address, column address.
-    Lanes >= n keep 0."""
+    Lanes >= n keep 0 (preset = False: whatever the registers held -- for a caller that masks every use of those lanes' product)."""
     cnt = hi - lo; RA, CA = cnt, cnt + 1
     out = []
-    for q in range(cnt):
+    for q in range(cnt if preset else 0):
         out.append("v_mov_b64 %%%d, 0" % q)
     for q in range(cnt):
         c = lo + q
@@ -210,6 +242,11 @@ def main():
         txt += emit("ADMPC_SYMROW_ASM_%d_A_R%d" % (n, nr), symrow(n, 0, n // 2, nr)) + "\n" + emit("ADMPC_SYMROW_ASM_%d_B_R%d" % (n, nr), symrow(n, n // 2, n, nr)) + "\n"
     # right-hand-side row (dense40_factorise with a row 40, kernel F): lane n carries the right-hand side of the solve through the factorisation
     txt += emit("ADMPC_ROWBUILD_ASM_%d_A_R%d" % (n, n + 1), rowbuild(n, 0, n // 2, n + 1)) + "\n" + emit("ADMPC_ROWBUILD_ASM_%d_B_R%d" % (n, n + 1), rowbuild(n, n // 2, n, n + 1)) + "\n"
+    # kernel F: unmasked row pull (_I: interior-point iterations, the even lanes' diagonal comes through LDS; _T: the trial, every lane's does
+    # and s_odd is 0.0) and the symmetric row without zero presets
+    txt += emit("ADMPC_ROWPULL_ASM_%d_A_I" % n, rowpull(n, 0, n // 2, True, "odd")) + "\n" + emit("ADMPC_ROWPULL_ASM_%d_B_I" % n, rowpull(n, n // 2, n, True, "odd")) + "\n"
+    txt += emit("ADMPC_ROWPULL_ASM_%d_A_T" % n, rowpull(n, 0, n // 2, False, "none")) + "\n" + emit("ADMPC_ROWPULL_ASM_%d_B_T" % n, rowpull(n, n // 2, n, False, "none")) + "\n"
+    txt += emit("ADMPC_SYMROW_ASM_%d_A_NP" % n, symrow(n, 0, n // 2, preset=False)) + "\n" + emit("ADMPC_SYMROW_ASM_%d_B_NP" % n, symrow(n, n // 2, n, preset=False)) + "\n"
     txt += "#define ADMPC_SUBST_CLOBBERS %s, \"memory\"\n" % clob
     open(sys.argv[1] if len(sys.argv) > 1 else "subst_asm.inc", "w").write(txt)
 
