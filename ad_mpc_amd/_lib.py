@@ -6,13 +6,13 @@ surface raises.  The CPU oracle under ``oracle/`` is test infrastructure and is 
 import ctypes as C
 import os
 
-from .config import AdmpcConfig, AdmpcLaneParams, AdmpcPath, AdmpcStepParams
+from .config import AdmpcConfig, AdmpcLaneParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
 from .quad_config import AdmpcQuadConfig
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libadmpc.so")
 
-# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h and include/admpc_lane.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
+# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h, include/admpc_lane.h and include/admpc_plant.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
 # _f32 entries), ip: to ints, vp: opaque (handle, stream, communicator) -- device pointers travel as integers, so all three are c_void_p.
 vp = dp = ip = C.c_void_p
 I, D, S = C.c_int, C.c_double, C.c_char_p
@@ -67,7 +67,13 @@ _LANE = {       # include/admpc_lane.h: the fleet step along a route, a local la
     "admpc_control_step_lane_batch": (I, [vp, vp, C.POINTER(AdmpcLaneParams), C.POINTER(AdmpcStepParams), I, ip, ip] + [dp] * 7 + [dp] * 5 + [vp] +
                                       [dp] * 4 + [dp, vp]),
 }
+_PLANT = {      # include/admpc_plant.h: the plant step, and T closed-loop steps along a route per call
+    "admpc_plant_step_batch": (I, [vp, C.POINTER(AdmpcPlantParams), I, dp, ip] + [dp] * 7 + [vp]),
+    "admpc_rollout_lane_batch": (I, [vp, vp, C.POINTER(AdmpcLaneParams), C.POINTER(AdmpcStepParams), vp, C.POINTER(AdmpcPlantParams), I, I, ip, ip] +
+                                 [dp] * 7 + [dp] * 5 + [vp] + [dp] * 4 + [dp] + [dp, ip, dp, vp]),
+}
 EXPORTS, QUAD_EXPORTS, FLEET_EXPORTS, LANE_EXPORTS = tuple(_CAR), tuple(_QUAD), tuple(_FLEET), tuple(_LANE)
+PLANT_EXPORTS = tuple(_PLANT)
 
 _lib = None
 
@@ -77,7 +83,7 @@ class AdmpcError(RuntimeError):
 
 
 def load():
-    """dlopen libadmpc.so and declare the prototypes of the four headers under include/ (no GPU needed for this)."""
+    """dlopen libadmpc.so and declare the prototypes of the five headers under include/ (no GPU needed for this)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -85,7 +91,7 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE}.items():
+    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -84,6 +84,13 @@ class AdmpcLaneParams(C.Structure):
     _fields_ = [("L", C.c_int32), ("back", C.c_int32), ("ahead", C.c_int32)]
 
 
+class AdmpcPlantParams(C.Structure):
+    """The plant of admpc_plant_step_batch / admpc_rollout_lane_batch (include/admpc_plant.h): the period a command is held for, the
+    plant's own speed band, the acceleration under a brake record, the floor of v_x, the RK4 sub-steps per period (1 .. 64)."""
+    _fields_ = [("dt", C.c_double), ("blend_min", C.c_double), ("blend_max", C.c_double), ("brake_acc", C.c_double), ("v_min", C.c_double),
+                ("substeps", C.c_int32), ("reserved", C.c_int32)]
+
+
 # --- vehicle constants: src/ad_mpc/ad_3d.py:47-71 (the 3.14195 "pi" is part of the model) -----------
 VEH_MASS = 1500.0
 VEH_F_MASS = 900.0

@@ -565,6 +565,8 @@ __attribute__((visibility("hidden"))) const AdmpcConfig* admpc_solver_config(con
     if (device) *device = s->device;
     return &s->cfg;
 }
+// for the plant step (admpc_plant.hip): the device copy of that problem, as the kernels read it
+__attribute__((visibility("hidden"))) const AdmpcConfig* admpc_solver_config_device(const AdmpcSolver* s) { return s->d_cfg; }
 
 int admpc_default_config(AdmpcConfig* c, int N, double Ts)
 {

@@ -23,6 +23,7 @@
 #include "../../include/admpc.h"
 #include "../../include/admpc_fleet.h"
 #include "../../include/admpc_lane.h"
+#include "../../include/admpc_plant.h"
 
 #define NX ADMPC_NX
 #define NU ADMPC_NU
@@ -34,6 +35,10 @@ extern "C" int admpc_set_error(int code, const char* msg);                      
 extern "C" const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);      // admpc_kernels.hip
 extern "C" int admpc_path_bank_horizon(const AdmpcPathBank* bank, int* device);             // admpc_kernels.hip
 extern "C" int admpc_lane_params_check(const char* who, const AdmpcLaneParams* lane, const int32_t* lane_idx);   // admpc_lane.hip
+extern "C" int admpc_plant_params_check(const char* who, const AdmpcPlantParams* plant);                         // admpc_plant.hip
+extern "C" int admpc_plant_launch(const AdmpcSolver* model, const AdmpcPlantParams* plant, int B, const float* ack, const int32_t* mode,
+                                  double* const* st, const double* err, const int32_t* status, const int32_t* valid, double* tally,
+                                  int32_t* counts, double* traj_pre, double* traj_post, void* stream);             // admpc_plant.hip
 
 namespace {
 
@@ -355,6 +360,53 @@ int admpc_control_step_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, con
                        (const double*)ubar, (const int32_t*)status, steer, safe_count, prev_u, has_valid, prm->threshold,
                        cfg->lbu[1], cfg->ubu[1], cfg->lbx_delta, cfg->ubx_delta, ack, mode, valid, cost);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_command_cost_kernel: launch failed");
+    return ADMPC_OK;
+}
+
+// T closed-loop steps along a route (include/admpc_plant.h): admpc_control_step_lane_batch above, called as it stands, and behind each call
+// one launch of admpc_plant_kernel (admpc_plant.hip) that moves the vehicles under the record just issued and tallies the tracking errors
+// the step's generator left in the workspace.  Everything is enqueued on `stream`; nothing waits for the device.
+int admpc_rollout_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, const AdmpcLaneParams* lane, const AdmpcStepParams* prm,
+                             const AdmpcSolver* plant_model, const AdmpcPlantParams* plant, int B, int T,
+                             const int32_t* path_of, int32_t* lane_idx,
+                             double* px, double* py, double* yaw, double* vx, double* vy, double* yaw_rate, double* steer,
+                             double* xbar, double* ubar, int32_t* safe_count, double* prev_u, int32_t* has_valid, void* work,
+                             float* ack, int32_t* mode, int32_t* valid, int32_t* status, double* cost,
+                             double* tally, int32_t* counts, double* traj, void* stream)
+{
+    int rc = admpc_lane_params_check("admpc_rollout_lane_batch", lane, lane_idx);
+    if (rc) return rc;
+    rc = admpc_plant_params_check("admpc_rollout_lane_batch", plant);
+    if (rc) return rc;
+    // the lane step's own refusals, by the lane step: an empty batch passes every check but the one of its arrays and enqueues nothing
+    rc = admpc_control_step_lane_batch(s, bank, lane, prm, B < 0 ? B : 0, path_of, lane_idx, px, py, yaw, vx, vy, yaw_rate, steer, xbar, ubar,
+                                       safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost, stream);
+    if (rc) return rc;
+    if (B > 0 && (!path_of || !px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !xbar || !ubar || !safe_count || !prev_u || !has_valid ||
+                  !work || !ack || !mode || !valid || !status))
+        return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_lane_batch: null array argument");
+    if (T < 0 || T > 4096) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_lane_batch: T must be in [0, 4096]");
+    int device = 0, plant_device = 0;
+    const int N = admpc_solver_config(s, &device)->N;
+    const AdmpcSolver* pm = plant_model ? plant_model : s;
+    (void)admpc_solver_config(pm, &plant_device);
+    if (plant_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_lane_batch: the plant model lives on another device than the solver");
+    if (B == 0 || T == 0) return ADMPC_OK;
+    if (!tally || !counts) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_lane_batch: null tally or counts");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    StepWork w(work, N, B);
+    double* st[NX] = { px, py, yaw, vx, vy, yaw_rate, steer };
+    const size_t slot = (size_t)NX * B;
+    for (int t = 0; t < T; ++t) {
+        rc = admpc_control_step_lane_batch(s, bank, lane, prm, B, path_of, lane_idx, px, py, yaw, vx, vy, yaw_rate, steer, xbar, ubar,
+                                           safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost, stream);
+        if (rc) return rc;
+        // slot 0 is written by the first launch; every launch writes the state it leaves into the next slot
+        rc = admpc_plant_launch(pm, plant, B, ack, mode, st, w.err, status, valid, tally, counts, (traj && t == 0) ? traj : nullptr,
+                                traj ? traj + (t + 1) * slot : nullptr, stream);
+        if (rc) return rc;
+    }
     return ADMPC_OK;
 }
 

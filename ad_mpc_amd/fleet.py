@@ -1,7 +1,9 @@
 """The control step of a fleet: pose in, Ackermann command out, for B vehicles on one global path
 (include/admpc.h: admpc_control_step_batch; csrc/admpc_step.hip), or with a path per vehicle out of a bank of paths and the best of
 every group of candidates (include/admpc_fleet.h: admpc_control_step_bank_batch, admpc_argmin_groups), or along a route of that bank,
-wherever on it the vehicle is (include/admpc_lane.h: admpc_control_step_lane_batch).
+wherever on it the vehicle is (include/admpc_lane.h: admpc_control_step_lane_batch), or closes the loop on the device: a plant step under
+the record just issued, and T steps of controller and plant per call (include/admpc_plant.h: admpc_plant_step_batch,
+admpc_rollout_lane_batch).
 
 ``FleetController`` solves the problem of ``ROSGPMPC(point_reference=False)`` (create_ros_ad_mpc.py:41-101: SQP_RTI, Q_DIAG_ROS /
 R_DIAG_ROS) for every vehicle, and does per step what the reference node does per pose message (gp_ad_mpc_node.py:389-438 ->
@@ -25,7 +27,7 @@ from . import _lib
 from . import config as _c
 from .ad_3d import AD3D
 from .ad_3d_optimizer import ocp_config
-from .config import AdmpcLaneParams, AdmpcPath, AdmpcStepParams, NX, NU
+from .config import AdmpcLaneParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams, NX, NU
 from .engine import BatchSolver, _ptr
 from .ref_traj import RefTrajectory
 
@@ -65,6 +67,21 @@ class FleetLaneStep(NamedTuple):
     lane_idx: torch.Tensor     # int32 [B]: the nearest waypoint of the route, where the lane was cut; the next step searches around it
 
 
+class FleetRollout(NamedTuple):
+    """FleetLaneStep of the last step of a rollout (rollout_route), with what the closed loop did over its steps."""
+    ack: torch.Tensor
+    mode: torch.Tensor
+    status: torch.Tensor
+    valid: torch.Tensor
+    x_opt: torch.Tensor
+    w_opt: torch.Tensor
+    cost: torch.Tensor
+    lane_idx: torch.Tensor
+    tally: torch.Tensor        # float64 [B,3]: sum of e_y^2, sum of e_psi^2, max |e_y| over the steps (the generator's tracking errors)
+    counts: torch.Tensor       # int32 [B,3]: steps taken, steps with an MPC command, unusable steps (status != 0 or valid == 0)
+    traj: torch.Tensor         # float64 [steps+1,7,B] or None: the poses at the start of every step, and the final ones
+
+
 class FleetController:
     def __init__(self, t_horizon, n_mpc_nodes, opt_dt, B, device=0, resample=True, threshold=SAFE_COUNT_THRESHOLD, blend_min=None,
                  blend_max=None):
@@ -100,6 +117,9 @@ class FleetController:
         self._best_val, self._best_idx = z(B), z(B, dtype=torch.int64)
         self.lane_idx = torch.full((B,), -1, dtype=torch.int32, device=self.device)      # step_route; -1: search the whole route
         self._bank, self._stepped_paths, self.n_paths = None, False, 0
+        self.tally, self.counts = z(B, 3), z(B, 3, dtype=torch.int32)    # rollout_route
+        self._plant_model = None
+        self.set_plant()
 
     def _drop_bank(self):
         if getattr(self, "_bank", None):
@@ -192,19 +212,88 @@ class FleetController:
         self._stepped_paths = True
         return FleetLaneStep(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt, self.cost, self.lane_idx)
 
-    def best_of(self, group):
+    def set_plant(self, dt=None, substeps=1, blend_min=None, blend_max=None, brake_acc=None, v_min=0.0, model=None):
+        """The plant of plant_step and rollout_route (include/admpc_plant.h): a command is held for `dt` (None: opt_dt) and the model is
+        integrated over it in `substeps` RK4 steps, blended over the plant's own speed band (None: the controller's); a brake record
+        decelerates at `brake_acc` (None: the vehicle's acc_min) and v_x never falls below `v_min`.  `model`: a BatchSolver whose vehicle
+        constants, bounds and GP residual the plant uses in place of the controller's own."""
+        prm = AdmpcPlantParams(dt=float(self.opt_dt if dt is None else dt),
+                               blend_min=float(self._prm.blend_min if blend_min is None else blend_min),
+                               blend_max=float(self._prm.blend_max if blend_max is None else blend_max),
+                               brake_acc=float(self.ad.acc_min if brake_acc is None else brake_acc), v_min=float(v_min),
+                               substeps=int(substeps), reserved=0)
+        if not (prm.dt > 0 and np.isfinite(prm.dt)) or not prm.blend_max > prm.blend_min or not prm.brake_acc <= 0 or not prm.v_min >= 0 \
+                or not 1 <= prm.substeps <= 64:
+            raise ValueError("set_plant: dt must be positive and finite, blend_max above blend_min, brake_acc <= 0, v_min >= 0, "
+                             "substeps in [1, 64]")
+        if model is not None and (not isinstance(model, BatchSolver) or model.device != self.device):
+            raise ValueError("set_plant: model must be a BatchSolver on %s" % self.device)
+        self._plant, self._plant_model = prm, model
+
+    def plant_step(self, x, y, yaw, vx, vy, yaw_rate, steer):
+        """Advances the seven float64 [B] device tensors in place by one period of the plant (set_plant) under the controller's last
+        ack and mode.  Asynchronous on the current stream."""
+        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
+        for t in ins:
+            self._eng._chk(t, (self.B,))
+        model = self._plant_model if self._plant_model is not None else self._eng
+        _lib.check(self.lib.admpc_plant_step_batch(model._h, C.byref(self._plant), self.B, _ptr(self.ack), _ptr(self.mode),
+                                                   *[_ptr(t) for t in ins], self._eng._stream()))
+
+    def rollout_route(self, path_of, x, y, yaw, vx, vy, yaw_rate, steer, steps, lane=64, back=8, ahead=64, record=False, accumulate=False):
+        """`steps` closed-loop steps on the device in one call: step_route, then the plant step on the pose tensors, which are advanced
+        in place; no host round trip between the steps.  ``tally`` and ``counts`` are the controller's own tensors, zeroed on the current
+        stream at the start of the call unless `accumulate`; `record` also returns the poses of every step.  Returns FleetRollout;
+        best_of works as after step_route."""
+        if self._bank is None:
+            raise ValueError("rollout_route: no bank of paths, call set_paths first")
+        prm = AdmpcLaneParams(L=int(lane), back=int(back), ahead=int(ahead))
+        if not 34 <= prm.L <= 256 or prm.back < 0 or prm.ahead < 0:
+            raise ValueError("rollout_route: lane must be in [34, 256], back and ahead must not be negative")
+        T = int(steps)
+        if not 0 <= T <= 4096:
+            raise ValueError("rollout_route: steps must be in [0, 4096]")
+        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
+        self._eng._chk(path_of, (self.B,), torch.int32)
+        for t in ins:
+            self._eng._chk(t, (self.B,))
+        if not accumulate:
+            self.tally.zero_()
+            self.counts.zero_()
+        traj = torch.empty((T + 1, NX, self.B), dtype=torch.float64, device=self.device) if record else None
+        if record and T == 0:
+            for i, t in enumerate(ins):
+                traj[0, i].copy_(t)
+        model = self._plant_model._h if self._plant_model is not None else None
+        _lib.check(self.lib.admpc_rollout_lane_batch(
+            self._eng._h, self._bank, C.byref(prm), C.byref(self._prm), model, C.byref(self._plant), self.B, T,
+            _ptr(path_of), _ptr(self.lane_idx), *[_ptr(t) for t in ins],
+            _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
+            _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), _ptr(self.cost),
+            _ptr(self.tally), _ptr(self.counts), _ptr(traj) if record else None, self._eng._stream()))
+        self._stepped_paths = True
+        return FleetRollout(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt, self.cost, self.lane_idx, self.tally,
+                            self.counts, traj)
+
+    def best_of(self, group, cost=None):
         """The cheapest usable candidate of every group of `group` consecutive instances of the last step_paths or step_route (instance b = v * group + c
         for vehicle v and candidate c): (val float64 [B / group], idx int64 [B / group]) device tensors, idx into the batch, so the command
-        of vehicle v is ack[idx[v]].  A group without a usable candidate gives (+inf, its first instance).  Asynchronous; the tensors
-        are the controller's own and are overwritten by the next call."""
+        of vehicle v is ack[idx[v]].  A group without a usable candidate gives (+inf, its first instance).  `cost`, a float64 [B] device
+        tensor, takes the place of the last step's cost: candidates can be chosen by a closed-loop score of rollout_route, for instance
+        tally[:, 0] with +inf where counts[:, 2] > 0.  Asynchronous; the tensors are the controller's own and are overwritten by the next
+        call."""
         group = int(group)
         if group < 1 or self.B % group != 0:
             raise ValueError("best_of: B = %d is not a multiple of group = %d" % (self.B, group))
         if not self._stepped_paths:
             raise ValueError("best_of: no step_paths yet")
+        if cost is None:
+            cost = self.cost
+        else:
+            self._eng._chk(cost, (self.B,))
         G = self.B // group
         val, idx = self._best_val[:G], self._best_idx[:G]
-        _lib.check(self.lib.admpc_argmin_groups(self._eng._h, _ptr(self.cost), G, group, _ptr(val), _ptr(idx), self._eng._stream()))
+        _lib.check(self.lib.admpc_argmin_groups(self._eng._h, _ptr(cost), G, group, _ptr(val), _ptr(idx), self._eng._stream()))
         return val, idx
 
     def step_numpy(self, x, y, yaw, vx, vy, yaw_rate, steer):

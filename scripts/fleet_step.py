@@ -5,6 +5,7 @@ set_reference, optimize: what a host does for each vehicle without the fleet ste
     python scripts/fleet_step.py [--batches 1,64,4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--loop-calls 200]
     python scripts/fleet_step.py --bank [--batches 4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--repeats 5]
     python scripts/fleet_step.py --lane [--batches 4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--repeats 5]
+    python scripts/fleet_step.py --rollout 50 [--batches 4096] [--horizons 20,40] [--repeats 5]
 
 --bank: the same workloads through a bank of paths (admpc_control_step_bank_batch: set_paths / step_paths) with K = 1 and with K = 8 copies
 of the path and round-robin path_of, against the single-path step in the same process, the variants interleaved `repeats` times (one JSON
@@ -13,6 +14,11 @@ over the same number of entries.
 
 --lane: the step along a route (admpc_control_step_lane_batch: step_route with L = 64) for B vehicles spread along one route of 2000
 waypoints, against the single-path step and the bank step (K = 1) for B vehicles at the start of the same route, interleaved as above.
+
+--rollout T: one rollout_route of T closed-loop steps (admpc_rollout_lane_batch: the lane step and the plant kernel, T times, one call)
+against T back-to-back step_route calls, for the same B vehicles spread along the route of --lane, seconds per step, interleaved as above;
+every repeat starts from the same poses.  The plant kernel's own time is read from a kernel trace of this command in a run of its own
+(rocprofv3 --kernel-trace --stats -- python scripts/fleet_step.py --rollout T --repeats 1: the row of admpc_plant_kernel).
 
 One JSON line per (N, B) and one for the per-vehicle loop per N.  Times come from HIP events around `steps` back-to-back steps (fleet,
 bare solve) or wall time around `loop-calls` calls (the per-vehicle loop, which synchronises at every call by construction)."""
@@ -149,6 +155,53 @@ def lane_against_bank(N, B, steps, warmup, repeats, M=2000, lane=64):
     return times, share
 
 
+def rollout_against_steps(N, B, T, repeats, M=2000, lane=64):
+    """Seconds per step of one rollout_route of T steps and of T back-to-back step_route calls, on the route and the poses of
+    lane_against_bank.  The rollout moves its vehicles, so every repeat copies the first poses back and sends lane_idx back to a search
+    of the whole route, for both variants, outside the timed window."""
+    p = path(M)
+    x, y, psi, _ = p
+    rng = np.random.default_rng(1)
+    at = rng.integers(0, M - 50, size=B)
+    e = 0.3 * (-1.0) ** np.arange(B)
+    spread = [x[at] - e * np.sin(psi[at]), y[at] + e * np.cos(psi[at]), psi[at] + rng.uniform(-0.05, 0.05, size=B), rng.uniform(5.0, 9.0, size=B),
+              rng.uniform(-0.1, 0.1, size=B), rng.uniform(-0.05, 0.05, size=B), rng.uniform(-0.03, 0.03, size=B)]
+    runs = {}
+    for name in ("rollout", "step_route"):
+        fc = FleetController(T_HORIZON, N, OPT_DT, B)
+        fc.set_paths([p])
+        first = [torch.as_tensor(a, dtype=torch.float64, device=fc.device) for a in spread]
+        ins = [t.clone() for t in first]
+        zero = torch.zeros(B, dtype=torch.int32, device=fc.device)
+        if name == "rollout":
+            fn = lambda fc=fc, ins=ins, zero=zero: fc.rollout_route(zero, *ins, steps=T, lane=lane)
+        else:
+            def fn(fc=fc, ins=ins, zero=zero):
+                for _ in range(T):
+                    fc.step_route(zero, *ins, lane=lane)
+        runs[name] = (fc, fn, first, ins)
+    times = {name: [] for name in runs}
+    for r in range(repeats + 1):                                   # the first round is the warm-up
+        for name, (fc, fn, first, ins) in runs.items():
+            fc.reset()
+            for t, f in zip(ins, first):
+                t.copy_(f)
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            if r:
+                times[name].append(a.elapsed_time(b) * 1e-3 / T)
+    fc = runs["rollout"][0]
+    counts, tally = fc.counts.cpu().numpy(), fc.tally.cpu().numpy()
+    info = {"mpc_share": float(counts[:, 1].mean() / T), "unusable_share": float(counts[:, 2].mean() / T), "max_abs_e_y": float(tally[:, 2].max())}
+    for fc, _, _, _ in runs.values():
+        fc.close()
+    return times, info
+
+
 def argmin_groups_against_argmin(steps, warmup, repeats):
     """Seconds per call of admpc_argmin_groups at (G, group) and of admpc_argmin over G * group entries."""
     fc = FleetController(T_HORIZON, 20, OPT_DT, 4)
@@ -200,10 +253,23 @@ def main():
     ap.add_argument("--loop-calls", type=int, default=200)
     ap.add_argument("--bank", action="store_true", help="the bank of paths against the single-path step, and the arg-min per group")
     ap.add_argument("--lane", action="store_true", help="the step along a route against the bank step and the single-path step")
+    ap.add_argument("--rollout", type=int, default=0, metavar="T", help="one rollout of T closed-loop steps against T step_route calls")
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     p = path()
     gpu = torch.cuda.get_device_name(0)
+    if a.rollout:
+        us = lambda ts: [round(t * 1e6, 1) for t in ts]
+        med = lambda ts: float(np.median(ts))
+        for N in [int(v) for v in a.horizons.split(",")]:
+            for B in [int(v) for v in (a.batches if a.batches != "1,64,4096" else "4096").split(",")]:
+                t, info = rollout_against_steps(N, B, a.rollout, a.repeats)
+                print(json.dumps({"what": "fleet_rollout", "N": N, "B": B, "T": a.rollout, "route_waypoints": 2000, "L": 64,
+                                  "us_per_step": {k: us(v) for k, v in t.items()}, "median_us": {k: round(med(v) * 1e6, 1) for k, v in t.items()},
+                                  "spread_us": {k: round((max(v) - min(v)) * 1e6, 1) for k, v in t.items()},
+                                  "rollout_minus_step_route_us": round((med(t["rollout"]) - med(t["step_route"])) * 1e6, 1), **info, "gpu": gpu}),
+                      flush=True)
+        return
     if a.lane:
         us = lambda ts: [round(t * 1e6, 1) for t in ts]
         med = lambda ts: float(np.median(ts))
