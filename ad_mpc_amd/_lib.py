@@ -6,13 +6,13 @@ surface raises.  The CPU oracle under ``oracle/`` is test infrastructure and is 
 import ctypes as C
 import os
 
-from .config import AdmpcConfig, AdmpcLaneParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
+from .config import AdmpcConfig, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
 from .quad_config import AdmpcQuadConfig
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libadmpc.so")
 
-# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h, include/admpc_lane.h and include/admpc_plant.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
+# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h, include/admpc_lane.h, include/admpc_plant.h and include/admpc_learn.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
 # _f32 entries), ip: to ints, vp: opaque (handle, stream, communicator) -- device pointers travel as integers, so all three are c_void_p.
 vp = dp = ip = C.c_void_p
 I, D, S = C.c_int, C.c_double, C.c_char_p
@@ -74,6 +74,15 @@ _PLANT = {      # include/admpc_plant.h: the plant step, and T closed-loop steps
 }
 EXPORTS, QUAD_EXPORTS, FLEET_EXPORTS, LANE_EXPORTS = tuple(_CAR), tuple(_QUAD), tuple(_FLEET), tuple(_LANE)
 PLANT_EXPORTS = tuple(_PLANT)
+op = C.POINTER(AdmpcObserveParams)
+_LEARN = {      # include/admpc_learn.h: observe -> bin -> fit -> install of a handle's residual GP on the device
+    "admpc_observe_latch_batch": (I, [I, I] + [dp] * 7 + [dp, vp]),
+    "admpc_observe_batch": (I, [vp, C.POINTER(AdmpcPlantParams), op, I, dp, ip] + [dp] * 7 + [dp, dp, dp, ip, vp]),
+    "admpc_gp_fit": (I, [I, op, I, dp, vp, ip, vp]),
+    "admpc_gp_install": (I, [vp, I, vp, ip, vp]),
+    "admpc_rollout_observe_lane_batch": (I, _PLANT["admpc_rollout_lane_batch"][1][:-1] + [vp, op, dp, dp, dp, ip, vp]),
+}
+LEARN_EXPORTS = tuple(_LEARN)
 
 _lib = None
 
@@ -83,7 +92,7 @@ class AdmpcError(RuntimeError):
 
 
 def load():
-    """dlopen libadmpc.so and declare the prototypes of the five headers under include/ (no GPU needed for this)."""
+    """dlopen libadmpc.so and declare the prototypes of the six headers under include/ (no GPU needed for this)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -91,7 +100,7 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT}.items():
+    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT, **_LEARN}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

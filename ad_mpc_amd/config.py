@@ -91,6 +91,21 @@ class AdmpcPlantParams(C.Structure):
                 ("substeps", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AdmpcGpBins(C.Structure):
+    """One regressor to learn (include/admpc_learn.h): its features and output row as in AdmpcGp, the grid of bins over the features
+    (product of nb at most GP_MAX_POINTS), and the fixed hyperparameters of the fit."""
+    _fields_ = [("n_feat", C.c_int32), ("feat", C.c_int32 * GP_MAX_FEAT), ("out", C.c_int32), ("nb", C.c_int32 * GP_MAX_FEAT),
+                ("lo", C.c_double * GP_MAX_FEAT), ("hi", C.c_double * GP_MAX_FEAT), ("sigma_f", C.c_double),
+                ("length", C.c_double * GP_MAX_FEAT), ("noise", C.c_double), ("count_noise", C.c_double)]
+
+
+class AdmpcObserveParams(C.Structure):
+    """The observation of a step (include/admpc_learn.h): the period between two poses, the MODEL's speed band, the RK4 sub-steps of
+    the prediction, and the regressors to learn."""
+    _fields_ = [("dt", C.c_double), ("blend_min", C.c_double), ("blend_max", C.c_double), ("substeps", C.c_int32), ("n_gp", C.c_int32),
+                ("gp", AdmpcGpBins * GP_MAX)]
+
+
 # --- vehicle constants: src/ad_mpc/ad_3d.py:47-71 (the 3.14195 "pi" is part of the model) -----------
 VEH_MASS = 1500.0
 VEH_F_MASS = 900.0
@@ -205,3 +220,38 @@ def tight_ipm(cfg):
 def tight_config(*a, **kw):
     """default_config with the tight stopping levels (tests that compare with exact minimisers, iteration-count tables of rounds 1-2)."""
     return tight_ipm(default_config(*a, **kw))
+
+
+def learn_bins(learn):
+    """The AdmpcGpBins of FleetController(learn=...): a list of dicts with the keys feat (an index into [x;u] in 3 .. 8, or a list of up
+    to 3), out (3 .. 5), lo, hi, bins (one per feature; the product at most GP_MAX_POINTS), length_scale (a scalar or one per feature),
+    sigma_f = 1.0, noise = 1e-6, count_noise = 0.0.  Raises ValueError on bad bins; the library refuses the same."""
+    learn = list(learn)
+    if not 1 <= len(learn) <= GP_MAX:
+        raise ValueError("learn: 1 to %d regressors" % GP_MAX)
+    out = (AdmpcGpBins * GP_MAX)()
+    for g, d in enumerate(learn):
+        feats = [int(f) for f in np.atleast_1d(d["feat"]).reshape(-1)]
+        nf = len(feats)
+        if not 1 <= nf <= GP_MAX_FEAT or any(not 3 <= f <= 8 for f in feats) or not 3 <= int(d["out"]) <= 5:
+            raise ValueError("learn[%d]: 1 to 3 features in 3 .. 8, out in 3 .. 5" % g)
+        vec = lambda k: np.asarray(d[k], dtype=np.float64).reshape(-1)
+        lo, hi, nb, ell = vec("lo"), vec("hi"), np.atleast_1d(d["bins"]).reshape(-1), vec("length_scale")
+        if ell.size == 1:
+            ell = np.repeat(ell, nf)
+        if not (lo.size == hi.size == nb.size == ell.size == nf):
+            raise ValueError("learn[%d]: lo, hi, bins and length_scale need one entry per feature" % g)
+        nb = [int(k) for k in nb]
+        sf, noise, cn = float(d.get("sigma_f", 1.0)), float(d.get("noise", 1e-6)), float(d.get("count_noise", 0.0))
+        if min(nb) < 1 or int(np.prod(nb)) > GP_MAX_POINTS or not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+            raise ValueError("learn[%d]: bad bins: every count >= 1, their product <= %d, lo and hi finite with hi > lo" % (g, GP_MAX_POINTS))
+        if not (np.isfinite(ell).all() and (ell > 0).all() and np.isfinite(sf) and sf > 0 and np.isfinite(noise) and noise > 0
+                and np.isfinite(cn) and cn >= 0):
+            raise ValueError("learn[%d]: length_scale, sigma_f and noise must be positive and finite, count_noise >= 0" % g)
+        b = out[g]
+        b.n_feat, b.out, b.sigma_f, b.noise, b.count_noise = nf, int(d["out"]), sf, noise, cn
+        for k in range(GP_MAX_FEAT):
+            used = k < nf
+            b.feat[k], b.nb[k] = (feats[k], nb[k]) if used else (0, 1)
+            b.lo[k], b.hi[k], b.length[k] = (lo[k], hi[k], ell[k]) if used else (0.0, 0.0, 0.0)
+    return out, len(learn)

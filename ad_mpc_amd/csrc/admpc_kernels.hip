@@ -567,6 +567,8 @@ __attribute__((visibility("hidden"))) const AdmpcConfig* admpc_solver_config(con
 }
 // for the plant step (admpc_plant.hip): the device copy of that problem, as the kernels read it
 __attribute__((visibility("hidden"))) const AdmpcConfig* admpc_solver_config_device(const AdmpcSolver* s) { return s->d_cfg; }
+// for the install of a fitted GP (admpc_learn.hip): the same copy, to be written
+__attribute__((visibility("hidden"))) AdmpcConfig* admpc_solver_config_device_rw(AdmpcSolver* s) { return s->d_cfg; }
 
 int admpc_default_config(AdmpcConfig* c, int N, double Ts)
 {

@@ -1,0 +1,531 @@
+// admpc_learn.hip -- fitting a handle's residual GP on the device from the steps a fleet has taken (include/admpc_learn.h):
+//
+//   observe  admpc_observe_kernel  the model's own prediction of the period that has just passed, from the latched poses and the record
+//                                  the step issued; what the plant did beyond it, per second, is the sample (three lanes per vehicle,
+//                                  the plant kernel's map: gp_eval shares its sums among a triple)
+//   bin      admpc_bin_kernel      one wave per (regressor, bin): count, feature sums and target sum of the samples of that bin, in a
+//                                  stated order, so that numpy reproduces them bit for bit
+//   fit      admpc_gp_fit_kernel   one wave per regressor: the bin means are the points; K by exp_nonpos; Cholesky with one row per
+//                                  lane, the matrix in LDS (33 doubles a row), pivots passed by lane reads.  The same with the row in
+//                                  registers and every loop unrolled took 256 VGPRs, 256 AGPRs and 728 bytes of scratch per lane.
+//   install  admpc_gp_install_kernel   one wave: checks each record and copies it into the handle's device configuration
+//
+// The hyperparameters are given (admpc_learn.h: scope).  The rollout with observation is at the end of the file.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <math.h>
+#include "../../include/admpc.h"
+#include "../../include/admpc_learn.h"
+
+#define NX ADMPC_NX
+#define NU ADMPC_NU
+#define NY ADMPC_NY
+#define WAVE 64
+#define LIN_TASKS 63     // tasks per block (multiple of 3), as in admpc_kernels.hip
+#define NPT ADMPC_GP_MAX_POINTS
+#define REC 10           // doubles per sample record
+#define ACC 5            // doubles per bin
+#define GP_WORDS (sizeof(AdmpcGp) / 8)
+
+static_assert(sizeof(AdmpcGp) % 8 == 0 && offsetof(AdmpcConfig, gp) % 8 == 0, "AdmpcGp is copied in 8-byte words");
+static_assert(NPT == 32, "the fit maps one row to each lane of half a wave");
+
+extern "C" int admpc_set_error(int code, const char* msg);                                  // admpc_kernels.hip
+extern "C" const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);      // admpc_kernels.hip
+extern "C" const AdmpcConfig* admpc_solver_config_device(const AdmpcSolver* s);            // admpc_kernels.hip
+extern "C" AdmpcConfig* admpc_solver_config_device_rw(AdmpcSolver* s);                     // admpc_kernels.hip
+extern "C" int admpc_plant_params_check(const char* who, const AdmpcPlantParams* plant);   // admpc_plant.hip
+
+// what one launch of the observe kernel works on (passed by value)
+struct ObserveArgs {
+    double h, dt, blend_min, blend_max, brake;
+    int M, B;
+    const float* ack;            // [B][4]
+    const int32_t* mode;         // [B]
+    const double* st[NX];        // px, py, yaw, vx, vy, yaw_rate, steer: [B] each, the poses now
+    double* prev;                // [7][B] the poses one period ago, in/out
+    double* samples;             // [B][REC]
+};
+
+// one regressor as the bin kernel and the fit kernel read it
+struct LearnGp {
+    int n_feat, feat[3], out, nb[3], nbins;
+    double lo[3], scale[3];      // scale_d = nb_d / (hi_d - lo_d)
+    double sigma_f, inv_l2[3], noise, count_noise;
+};
+
+struct LearnArgs {
+    int B, n_gp;
+    double min_count;
+    LearnGp gp[ADMPC_GP_MAX];
+    const double* samples;       // [B][REC]
+    double* bins;                // [n_gp][NPT][ACC]
+    int32_t* dropped;            // [ADMPC_GP_MAX + 1]
+    AdmpcGp* out;                // [n_gp]
+    int32_t* info;               // [n_gp]
+};
+
+namespace {
+
+#include "model_dev.h"
+#include "plant_dev.h"
+
+// the record of one vehicle and the latch; every operation rounded on its own, so that numpy reproduces the flag bit for bit
+__device__ __forceinline__ void observe_record(const ObserveArgs& a, long b, const double* z, const double* u, const double* now, const double* xh)
+{
+#pragma clang fp contract(off)
+    double* r = a.samples + b * REC;
+    bool fin = isfinite(u[0]) && isfinite(u[1]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { r[i] = z[i]; fin = fin && isfinite(z[i]); }
+    r[4] = u[0]; r[5] = u[1];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double y = (now[3 + j] - xh[3 + j]) / a.dt;
+        r[6 + j] = y;
+        fin = fin && isfinite(y);
+    }
+    r[9] = fin ? 1.0 : 0.0;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) a.prev[(long)i * a.B + b] = now[i];
+}
+
+__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+}  // namespace
+
+__global__ void admpc_latch_kernel(int B, const double* p0, const double* p1, const double* p2, const double* p3, const double* p4,
+                                   const double* p5, const double* p6, double* __restrict__ prev)
+{
+    const double* st[NX] = { p0, p1, p2, p3, p4, p5, p6 };
+    for (long b = (long)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (long)gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) prev[(long)i * B + b] = st[i][b];
+    }
+}
+
+__global__ __launch_bounds__(WAVE) void admpc_observe_kernel(const AdmpcConfig* __restrict__ cfg, const ObserveArgs a)
+{
+    const long total = (long)a.B * 3;
+    if (threadIdx.x >= LIN_TASKS) return;                // the task -> lane map of the shooting kernels (gp_eval relies on it)
+    const double lbu0 = cfg->lbu[0], ubu0 = cfg->ubu[0], lbu1 = cfg->lbu[1], ubu1 = cfg->ubu[1];
+    for (long tsk = (long)blockIdx.x * LIN_TASKS + threadIdx.x; tsk < total; tsk += (long)gridDim.x * LIN_TASKS) {
+        const long b = tsk / 3; const int g = (int)(tsk % 3);
+        double x[NX], now[NX], z[4], u[NU];
+#pragma unroll
+        for (int i = 0; i < NX; ++i) { x[i] = a.prev[(long)i * a.B + b]; now[i] = a.st[i][b]; }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) z[i] = x[3 + i];
+        const double p = plant_blend(x[3], a.blend_min, a.blend_max);
+        const double acc = (double)a.ack[b * 4 + 3], rate = (double)a.ack[b * 4 + 1];
+        const bool mpc = a.mode[b] == 1 && isfinite(acc) && isfinite(rate);
+        u[0] = mpc ? fmin(fmax(acc, lbu0), ubu0) : a.brake;
+        u[1] = mpc ? fmin(fmax(rate, lbu1), ubu1) : 0.0;
+        for (int m = 0; m < a.M; ++m) {                  // uniform over the wave: the shuffles of gp_eval see every lane of a triple
+            double phi[NX];
+            rk4_state(cfg, x, u, p, a.h, phi);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) x[i] = phi[i];
+        }
+        // the latch is behind the integration: every lane of the triple has consumed its loads of prev before lane 0 of it stores
+        if (g == 0) observe_record(a, b, z, u, now, x);
+    }
+}
+
+// grid n_gp * NPT: block (g, bin).  Bin 0 of a regressor also counts what fell outside its box, block 0 also what was not valid.
+__global__ __launch_bounds__(WAVE) void admpc_bin_kernel(const LearnArgs a)
+{
+#pragma clang fp contract(off)
+    const int g = (int)blockIdx.x / NPT, bin = (int)blockIdx.x % NPT;
+    const LearnGp& G = a.gp[g];
+    if (bin >= G.nbins) return;
+    const int lane = lane_id();
+    double part[ACC] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    int outside = 0, invalid = 0;
+    for (long b = lane; b < a.B; b += WAVE) {
+        const double* r = a.samples + b * REC;
+        if (!(r[9] == 1.0)) { ++invalid; continue; }
+        double z[3] = { 0.0, 0.0, 0.0 };
+        bool in = true;
+        int k = 0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            if (d < G.n_feat) {
+                z[d] = r[G.feat[d] - 3];
+                const double t = (z[d] - G.lo[d]) * G.scale[d];
+                const double kd = floor(t);
+                const bool ok = t >= 0.0 && kd < (double)G.nb[d];
+                in = in && ok;
+                k = k * G.nb[d] + (ok ? (int)kd : 0);
+            }
+        }
+        if (!in) { ++outside; continue; }
+        if (k == bin) {
+            part[0] = part[0] + 1.0;
+            part[1] = part[1] + z[0]; part[2] = part[2] + z[1]; part[3] = part[3] + z[2];
+            part[4] = part[4] + r[6 + G.out - 3];
+        }
+    }
+    double* o = a.bins + ((long)g * NPT + bin) * ACC;
+    double acc[ACC];
+#pragma unroll
+    for (int c = 0; c < ACC; ++c) acc[c] = o[c];
+    for (int l = 0; l < WAVE; ++l) {
+#pragma unroll
+        for (int c = 0; c < ACC; ++c) acc[c] = acc[c] + __shfl(part[c], l);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < ACC; ++c) o[c] = acc[c];
+    }
+    if (bin == 0) {
+        for (int w = WAVE / 2; w > 0; w >>= 1) { outside += __shfl_xor(outside, w); invalid += __shfl_xor(invalid, w); }
+        if (lane == 0) {
+            a.dropped[g] = a.dropped[g] + outside;
+            if (g == 0) a.dropped[ADMPC_GP_MAX] = a.dropped[ADMPC_GP_MAX] + invalid;
+        }
+    }
+}
+
+// grid n_gp, one wave each.  Lane r < 32 owns point r and row r of K; lanes 32 .. 63 mirror lanes 0 .. 31 and store nothing.
+__global__ __launch_bounds__(WAVE) void admpc_gp_fit_kernel(const LearnArgs a)
+{
+    __shared__ double Zs[3][NPT], ts[NPT], cs[NPT], As[NPT][NPT + 1];
+    const int g = (int)blockIdx.x;
+    const LearnGp& G = a.gp[g];
+    const int lane = lane_id(), r = lane & (NPT - 1);
+    const bool act = lane < NPT;
+    const int nf = G.n_feat;
+    // the points: the bins with enough samples, in ascending order
+    const double* bn = a.bins + ((long)g * NPT + r) * ACC;
+    double cnt = 0.0;
+    bool ok = false;
+    if (act && r < G.nbins) { cnt = bn[0]; ok = cnt >= a.min_count; }
+    const unsigned long long m = __ballot(ok);
+    const int n = __popcll(m), pos = __popcll(m & ((1ull << lane) - 1ull));
+    if (ok) {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) Zs[d][pos] = d < nf ? bn[1 + d] / cnt : 0.0;
+        ts[pos] = bn[4] / cnt;
+        cs[pos] = cnt;
+    }
+    if (act && r >= n) { Zs[0][r] = 0.0; Zs[1][r] = 0.0; Zs[2][r] = 0.0; ts[r] = 0.0; cs[r] = 1.0; }
+    __syncthreads();
+    double ymean = 0.0;
+    {
+#pragma clang fp contract(off)
+        double sum = 0.0;
+        for (int i = 0; i < n; ++i) sum = sum + ts[i];
+        if (n > 0) ymean = sum / (double)n;
+    }
+    // row r of K in LDS (lower triangle and diagonal: what the factorisation reads)
+    const double il0 = G.inv_l2[0], il1 = nf > 1 ? G.inv_l2[1] : 0.0, il2 = nf > 2 ? G.inv_l2[2] : 0.0;
+    const double z0 = Zs[0][r], z1 = Zs[1][r], z2 = Zs[2][r];
+    const double diag = G.noise + G.count_noise / cs[r];
+    if (act && r < n) {
+#pragma unroll 1
+        for (int j = 0; j <= r; ++j) {
+            const double e0 = z0 - Zs[0][j], e1 = z1 - Zs[1][j], e2 = z2 - Zs[2][j];
+            As[r][j] = G.sigma_f * exp_nonpos(-0.5 * (e0 * e0 * il0 + e1 * e1 * il1 + e2 * e2 * il2)) + (j == r ? diag : 0.0);
+        }
+    }
+    __syncthreads();
+    // left-looking Cholesky, a column per step: lane r >= k forms L[r][k] from row r and row k of the columns already there
+    int fail = 0;
+#pragma unroll 1
+    for (int k = 0; k < n; ++k) {
+        double s = 0.0;
+        if (r >= k && r < n) {
+            s = As[r][k];
+#pragma unroll 1
+            for (int j = 0; j < k; ++j) s = s - As[r][j] * As[k][j];
+        }
+        const double d = __shfl(s, k), tk = ts[k];
+        if (!(d > 0.0 && isfinite(d) && isfinite(tk))) { fail = k + 1; break; }      // uniform over the wave
+        const double l = sqrt(d);
+        if (act && r >= k && r < n) As[r][k] = r == k ? l : s / l;
+        __syncthreads();
+    }
+    double bb = r < n ? ts[r] - ymean : 0.0;
+    if (!fail) {
+#pragma unroll 1
+        for (int k = 0; k < n; ++k) {                      // L w = t - ymean
+            const double wk = __shfl(bb, k) / As[k][k];
+            if (r == k) bb = wk;
+            else if (r > k && r < n) bb = bb - As[r][k] * wk;
+        }
+#pragma unroll 1
+        for (int k = n - 1; k >= 0; --k) {                 // L' alpha = w
+            const double ak = __shfl(bb, k) / As[k][k];
+            if (r == k) bb = ak;
+            else if (r < k) bb = bb - As[k][r] * ak;
+        }
+    }
+    const int np = fail ? 0 : n;
+    AdmpcGp* o = a.out + g;
+    if (act) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) o->Z[d][r] = (r < np && d < nf) ? Zs[d][r] : 0.0;
+        o->alpha[r] = r < np ? bb : 0.0;
+    }
+    if (lane == 0) {
+        o->n_feat = nf;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { o->feat[d] = d < nf ? G.feat[d] : 0; o->inv_l2[d] = d < nf ? G.inv_l2[d] : 0.0; }
+        o->out = G.out;
+        o->n_points = np;
+        o->sigma_f = G.sigma_f;
+        o->ymean = fail ? 0.0 : ymean;
+        a.info[g] = fail ? -fail : n;
+    }
+}
+
+// one wave.  src [n_gp] -> cfg->gp[0 .. n_gp); a record that fails the check is replaced by the empty GP.
+__global__ __launch_bounds__(WAVE) void admpc_gp_install_kernel(AdmpcConfig* cfg, int n_gp, const AdmpcGp* src, int32_t* installed)
+{
+    const int lane = lane_id();
+    for (int g = 0; g < n_gp; ++g) {
+        const AdmpcGp* s = src + g;
+        const int nf = s->n_feat, n = s->n_points, out = s->out;
+        bool head = nf >= 1 && nf <= ADMPC_GP_MAX_FEAT && out >= 3 && out <= 5 && n >= 0 && n <= NPT;
+        head = head && isfinite(s->sigma_f) && isfinite(s->ymean);
+#pragma unroll
+        for (int d = 0; d < ADMPC_GP_MAX_FEAT; ++d)
+            if (d < nf) head = head && s->feat[d] >= 3 && s->feat[d] <= 8 && isfinite(s->inv_l2[d]);
+        bool bad = false;
+        if (head && lane < n) {
+            bad = !isfinite(s->alpha[lane]);
+#pragma unroll
+            for (int d = 0; d < ADMPC_GP_MAX_FEAT; ++d)
+                if (d < nf) bad = bad || !isfinite(s->Z[d][lane]);
+        }
+        const bool take = head && __ballot(bad) == 0ull;
+        const uint64_t* sw = (const uint64_t*)s;
+        uint64_t* dw = (uint64_t*)&cfg->gp[g];
+        for (int w = lane; w < (int)GP_WORDS; w += WAVE) {
+            // the empty GP: n_feat 1, feat 3 0 0, out 3, n_points 0, every double zero (the six int32 of the head are words 0 .. 2)
+            const uint64_t empty = w == 0 ? (1ull | (3ull << 32)) : (w == 2 ? 3ull : 0ull);
+            dw[w] = take ? sw[w] : empty;
+        }
+        if (lane == 0) installed[g] = take ? 1 : 0;
+    }
+}
+
+namespace {
+
+struct DeviceGuard {
+    int prev; bool switched; bool good;
+    explicit DeviceGuard(int dev) : prev(-1), switched(false), good(true) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) { good = hipSetDevice(dev) == hipSuccess; switched = good; }
+    }
+    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
+    bool ok() const { return good; }
+};
+
+// The refusals of the observe parameters, for the entry points that take them (`who` leads the message).
+int observe_params_check(const char* who, const AdmpcObserveParams* obs)
+{
+    char msg[200], what[120];
+    what[0] = 0;
+    if (!obs) snprintf(what, sizeof what, "the observe parameters are not set");
+    else if (!(obs->dt > 0) || !isfinite(obs->dt)) snprintf(what, sizeof what, "dt must be positive and finite");
+    else if (!(obs->blend_max > obs->blend_min)) snprintf(what, sizeof what, "blend_max must exceed blend_min");
+    else if (obs->substeps < 1 || obs->substeps > 64) snprintf(what, sizeof what, "substeps must be in [1, 64]");
+    else if (obs->n_gp < 1 || obs->n_gp > ADMPC_GP_MAX) snprintf(what, sizeof what, "n_gp must be in [1, %d]", ADMPC_GP_MAX);
+    for (int g = 0; !what[0] && g < obs->n_gp; ++g) {
+        const AdmpcGpBins& b = obs->gp[g];
+        const int nf = b.n_feat;
+        const char* bad = nullptr;
+        if (nf < 1 || nf > ADMPC_GP_MAX_FEAT) bad = "n_feat must be in [1, 3]";
+        for (int d = 0; !bad && d < nf; ++d) if (b.feat[d] < 3 || b.feat[d] > 8) bad = "feat must be in [3, 8]";
+        if (!bad && (b.out < 3 || b.out > 5)) bad = "out must be in [3, 5]";
+        long prod = 1;
+        for (int d = 0; !bad && d < 3; ++d) {
+            if (b.nb[d] < 1 || (d >= nf && b.nb[d] != 1)) bad = "nb must be >= 1, and 1 for an unused feature";
+            else if ((prod *= b.nb[d]) > NPT) bad = "the product of nb must not exceed 32";
+        }
+        for (int d = 0; !bad && d < nf; ++d) if (!isfinite(b.lo[d]) || !isfinite(b.hi[d]) || !(b.hi[d] > b.lo[d])) bad = "lo and hi must be finite, hi > lo";
+        if (!bad && (!(b.sigma_f > 0) || !isfinite(b.sigma_f))) bad = "sigma_f must be positive and finite";
+        for (int d = 0; !bad && d < nf; ++d) if (!(b.length[d] > 0) || !isfinite(b.length[d])) bad = "length must be positive and finite";
+        if (!bad && (!(b.noise > 0) || !isfinite(b.noise))) bad = "noise must be positive and finite";
+        if (!bad && (!(b.count_noise >= 0) || !isfinite(b.count_noise))) bad = "count_noise must not be negative";
+        if (bad) snprintf(what, sizeof what, "regressor %d: %s", g, bad);
+    }
+    if (!what[0]) return ADMPC_OK;
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return admpc_set_error(ADMPC_EINVAL, msg);
+}
+
+void fill_learn(LearnArgs& a, const AdmpcObserveParams* obs)
+{
+    a.n_gp = obs->n_gp;
+    for (int g = 0; g < ADMPC_GP_MAX; ++g) {
+        LearnGp& G = a.gp[g];
+        G = LearnGp();
+        if (g >= obs->n_gp) continue;
+        const AdmpcGpBins& b = obs->gp[g];
+        G.n_feat = b.n_feat; G.out = b.out; G.nbins = 1;
+        for (int d = 0; d < 3; ++d) {
+            const bool used = d < b.n_feat;
+            G.feat[d] = used ? b.feat[d] : 3; G.nb[d] = used ? b.nb[d] : 1; G.nbins *= G.nb[d];
+            G.lo[d] = used ? b.lo[d] : 0.0;
+            G.scale[d] = used ? (double)b.nb[d] / (b.hi[d] - b.lo[d]) : 0.0;
+            G.inv_l2[d] = used ? 1.0 / (b.length[d] * b.length[d]) : 0.0;
+        }
+        G.sigma_f = b.sigma_f; G.noise = b.noise; G.count_noise = b.count_noise;
+    }
+}
+
+// The two launches of an observation for checked arguments, B > 0, on the model's device (the caller holds it).
+int observe_launch(const AdmpcSolver* model, const AdmpcPlantParams* plant, const AdmpcObserveParams* obs, int B, const float* ack,
+                   const int32_t* mode, const double* const* st, double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
+{
+    const AdmpcConfig* cfg = admpc_solver_config(model, nullptr);
+    ObserveArgs a;
+    a.h = obs->dt / obs->substeps; a.dt = obs->dt;
+    a.blend_min = obs->blend_min; a.blend_max = obs->blend_max;
+    a.brake = plant->brake_acc > cfg->lbu[0] ? plant->brake_acc : cfg->lbu[0];
+    a.M = obs->substeps; a.B = B;
+    a.ack = ack; a.mode = mode;
+    for (int i = 0; i < NX; ++i) a.st[i] = st[i];
+    a.prev = prev; a.samples = samples;
+    const int nblk = (int)(((long)B * 3 + LIN_TASKS - 1) / LIN_TASKS);
+    const int grid = nblk < 4096 ? nblk : 4096;
+    hipLaunchKernelGGL(admpc_observe_kernel, dim3((unsigned)grid), dim3(WAVE), 0, (hipStream_t)stream, admpc_solver_config_device(model), a);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_observe_kernel: launch failed");
+    LearnArgs l = LearnArgs();
+    fill_learn(l, obs);
+    l.B = B; l.samples = samples; l.bins = bins; l.dropped = dropped;
+    hipLaunchKernelGGL(admpc_bin_kernel, dim3((unsigned)(obs->n_gp * NPT)), dim3(WAVE), 0, (hipStream_t)stream, l);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_bin_kernel: launch failed");
+    return ADMPC_OK;
+}
+
+int latch_launch(int B, const double* const* st, double* prev, void* stream)
+{
+    const int nblk = (B + 255) / 256;
+    hipLaunchKernelGGL(admpc_latch_kernel, dim3((unsigned)(nblk < 4096 ? nblk : 4096)), dim3(256), 0, (hipStream_t)stream, B, st[0], st[1], st[2],
+                       st[3], st[4], st[5], st[6], prev);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_latch_kernel: launch failed");
+    return ADMPC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int admpc_observe_latch_batch(int device, int B, const double* px, const double* py, const double* yaw, const double* vx, const double* vy,
+                              const double* yaw_rate, const double* steer, double* prev, void* stream)
+{
+    if (B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_observe_latch_batch: negative batch");
+    if (B == 0) return ADMPC_OK;
+    if (!px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !prev)
+        return admpc_set_error(ADMPC_EINVAL, "admpc_observe_latch_batch: null array argument");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    const double* st[NX] = { px, py, yaw, vx, vy, yaw_rate, steer };
+    return latch_launch(B, st, prev, stream);
+}
+
+int admpc_observe_batch(const AdmpcSolver* model, const AdmpcPlantParams* plant, const AdmpcObserveParams* obs, int B,
+                        const float* ack, const int32_t* mode,
+                        const double* px, const double* py, const double* yaw, const double* vx, const double* vy,
+                        const double* yaw_rate, const double* steer,
+                        double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
+{
+    int rc = observe_params_check("admpc_observe_batch", obs);
+    if (rc) return rc;
+    rc = admpc_plant_params_check("admpc_observe_batch", plant);
+    if (rc) return rc;
+    if (!model || B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_observe_batch: null model or negative batch");
+    if (B == 0) return ADMPC_OK;
+    if (!ack || !mode || !px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !prev || !samples || !bins || !dropped)
+        return admpc_set_error(ADMPC_EINVAL, "admpc_observe_batch: null array argument");
+    int device = 0;
+    (void)admpc_solver_config(model, &device);
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    const double* st[NX] = { px, py, yaw, vx, vy, yaw_rate, steer };
+    return observe_launch(model, plant, obs, B, ack, mode, st, prev, samples, bins, dropped, stream);
+}
+
+int admpc_gp_fit(int device, const AdmpcObserveParams* obs, int min_count, const double* bins, AdmpcGp* gp_out, int32_t* info, void* stream)
+{
+    const int rc = observe_params_check("admpc_gp_fit", obs);
+    if (rc) return rc;
+    if (min_count < 1) return admpc_set_error(ADMPC_EINVAL, "admpc_gp_fit: min_count must be at least 1");
+    if (!bins || !gp_out || !info) return admpc_set_error(ADMPC_EINVAL, "admpc_gp_fit: null array argument");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    LearnArgs l = LearnArgs();
+    fill_learn(l, obs);
+    l.min_count = (double)min_count; l.bins = const_cast<double*>(bins); l.out = gp_out; l.info = info;
+    hipLaunchKernelGGL(admpc_gp_fit_kernel, dim3((unsigned)obs->n_gp), dim3(WAVE), 0, (hipStream_t)stream, l);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_gp_fit_kernel: launch failed");
+    return ADMPC_OK;
+}
+
+int admpc_gp_install(AdmpcSolver* s, int n_gp, const AdmpcGp* gp_dev, int32_t* installed, void* stream)
+{
+    if (!s) return admpc_set_error(ADMPC_EINVAL, "admpc_gp_install: null solver");
+    int device = 0;
+    const int have = admpc_solver_config(s, &device)->n_gp;
+    if (have < 1 || n_gp != have) {
+        char msg[160];
+        snprintf(msg, sizeof msg, "admpc_gp_install: n_gp = %d, but the handle was created with %d GPs (create it with placeholder GPs of n_points = 0)", n_gp, have);
+        return admpc_set_error(ADMPC_EINVAL, msg);
+    }
+    if (!gp_dev || !installed) return admpc_set_error(ADMPC_EINVAL, "admpc_gp_install: null array argument");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    hipLaunchKernelGGL(admpc_gp_install_kernel, dim3(1), dim3(WAVE), 0, (hipStream_t)stream, admpc_solver_config_device_rw(s), n_gp, gp_dev, installed);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_gp_install_kernel: launch failed");
+    return ADMPC_OK;
+}
+
+int admpc_rollout_observe_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, const AdmpcLaneParams* lane, const AdmpcStepParams* prm,
+                                     const AdmpcSolver* plant_model, const AdmpcPlantParams* plant, int B, int T,
+                                     const int32_t* path_of, int32_t* lane_idx,
+                                     double* px, double* py, double* yaw, double* vx, double* vy, double* yaw_rate, double* steer,
+                                     double* xbar, double* ubar, int32_t* safe_count, double* prev_u, int32_t* has_valid, void* work,
+                                     float* ack, int32_t* mode, int32_t* valid, int32_t* status, double* cost,
+                                     double* tally, int32_t* counts, double* traj,
+                                     const AdmpcSolver* model, const AdmpcObserveParams* obs,
+                                     double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
+{
+    int rc = observe_params_check("admpc_rollout_observe_lane_batch", obs);
+    if (rc) return rc;
+    if (!model) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_observe_lane_batch: null model");
+    // the rollout's own refusals, by the rollout: an empty batch passes every check but those of its arrays and enqueues nothing
+    rc = admpc_rollout_lane_batch(s, bank, lane, prm, plant_model, plant, B < 0 ? B : 0, T, path_of, lane_idx, px, py, yaw, vx, vy, yaw_rate, steer,
+                                  xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost, tally, counts, traj, stream);
+    if (rc) return rc;
+    int device = 0, model_device = 0;
+    (void)admpc_solver_config(s, &device);
+    (void)admpc_solver_config(model, &model_device);
+    if (model_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_observe_lane_batch: the model lives on another device than the solver");
+    if (B == 0 || T == 0) return ADMPC_OK;
+    if (!path_of || !px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !xbar || !ubar || !safe_count || !prev_u || !has_valid || !work ||
+        !ack || !mode || !valid || !status || !tally || !counts || !prev || !samples || !bins || !dropped)
+        return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_observe_lane_batch: null array argument");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    const double* st[NX] = { px, py, yaw, vx, vy, yaw_rate, steer };
+    rc = latch_launch(B, st, prev, stream);
+    if (rc) return rc;
+    const size_t slot = (size_t)NX * B;
+    for (int t = 0; t < T; ++t) {
+        rc = admpc_rollout_lane_batch(s, bank, lane, prm, plant_model, plant, B, 1, path_of, lane_idx, px, py, yaw, vx, vy, yaw_rate, steer,
+                                      xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost, tally, counts,
+                                      traj ? traj + t * slot : nullptr, stream);
+        if (rc) return rc;
+        rc = observe_launch(model, plant, obs, B, ack, mode, st, prev, samples, bins, dropped, stream);
+        if (rc) return rc;
+    }
+    return ADMPC_OK;
+}
+
+}  // extern "C"

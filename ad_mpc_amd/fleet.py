@@ -3,7 +3,8 @@
 every group of candidates (include/admpc_fleet.h: admpc_control_step_bank_batch, admpc_argmin_groups), or along a route of that bank,
 wherever on it the vehicle is (include/admpc_lane.h: admpc_control_step_lane_batch), or closes the loop on the device: a plant step under
 the record just issued, and T steps of controller and plant per call (include/admpc_plant.h: admpc_plant_step_batch,
-admpc_rollout_lane_batch).
+admpc_rollout_lane_batch), or learns the residual GP of its model from the steps it has taken, on the device (include/admpc_learn.h:
+observe -> bin -> fit -> install).
 
 ``FleetController`` solves the problem of ``ROSGPMPC(point_reference=False)`` (create_ros_ad_mpc.py:41-101: SQP_RTI, Q_DIAG_ROS /
 R_DIAG_ROS) for every vehicle, and does per step what the reference node does per pose message (gp_ad_mpc_node.py:389-438 ->
@@ -27,7 +28,7 @@ from . import _lib
 from . import config as _c
 from .ad_3d import AD3D
 from .ad_3d_optimizer import ocp_config
-from .config import AdmpcLaneParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams, NX, NU
+from .config import AdmpcGp, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams, GP_MAX, GP_MAX_POINTS, NX, NU
 from .engine import BatchSolver, _ptr
 from .ref_traj import RefTrajectory
 
@@ -84,8 +85,12 @@ class FleetRollout(NamedTuple):
 
 class FleetController:
     def __init__(self, t_horizon, n_mpc_nodes, opt_dt, B, device=0, resample=True, threshold=SAFE_COUNT_THRESHOLD, blend_min=None,
-                 blend_max=None):
-        """``blend_min`` / ``blend_max`` (None: the vehicle's, ad_3d.py) are the ends of the speed band of vel_switch."""
+                 blend_max=None, learn=None):
+        """``blend_min`` / ``blend_max`` (None: the vehicle's, ad_3d.py) are the ends of the speed band of vel_switch.  ``learn``: a list
+        of regressors to learn (config.learn_bins: feat, out, lo, hi, bins, length_scale, sigma_f, noise, count_noise).  With it the
+        engine is created with placeholder GPs of no points, which fit_gp overwrites on the device; a second, nominal engine (no GP, same
+        vehicle) predicts for observe.  At N = 40 a controller that learns runs kernel R where one that does not runs kernel S
+        (include/admpc_learn.h)."""
         N, B = int(n_mpc_nodes), int(B)
         if B < 1:
             raise ValueError("B must be positive")
@@ -95,6 +100,13 @@ class FleetController:
         if blend_max is not None:
             ad.blend_max = float(blend_max)
         cfg = ocp_config(ad, t_horizon, N, np.array(_c.Q_DIAG_ROS), np.array(_c.R_DIAG_ROS), "SQP_RTI")
+        self._learn = None
+        if learn is not None:
+            learn = [dict(d) for d in learn]
+            bins, n_gp = _c.learn_bins(learn)                            # ValueError on bad bins, before anything is created
+            self._nominal = BatchSolver(cfg, device=device)
+            cfg = _c.set_gp(cfg.copy(), [dict(feat=d["feat"], out=d["out"], Z=[], alpha=[], length_scale=d["length_scale"],
+                                              sigma_f=d.get("sigma_f", 1.0)) for d in learn])
         self._eng = eng = BatchSolver(cfg, device=device)
         self.lib, self.device = eng.lib, eng.device
         self.N, self.B, self.opt_dt = N, B, opt_dt
@@ -120,6 +132,14 @@ class FleetController:
         self.tally, self.counts = z(B, 3), z(B, 3, dtype=torch.int32)    # rollout_route
         self._plant_model = None
         self.set_plant()
+        if learn is not None:
+            self._learn, self.n_learn = learn, n_gp
+            self._obs = AdmpcObserveParams(dt=0.0, blend_min=ad.blend_min, blend_max=ad.blend_max, substeps=1, n_gp=n_gp, gp=bins)
+            self._observer = self._nominal
+            self._prev, self.samples = z(NX, B), z(B, 10)
+            self.bins, self.dropped = z(GP_MAX, GP_MAX_POINTS, 5), z(GP_MAX + 1, dtype=torch.int32)
+            self._gp_dev = z(GP_MAX * C.sizeof(AdmpcGp), dtype=torch.uint8)
+            self.fit_info, self.installed = z(GP_MAX, dtype=torch.int32), z(GP_MAX, dtype=torch.int32)
 
     def _drop_bank(self):
         if getattr(self, "_bank", None):
@@ -128,7 +148,9 @@ class FleetController:
 
     def close(self):
         self._drop_bank()
-        self._eng.close()
+        for eng in (getattr(self, "_eng", None), getattr(self, "_nominal", None)):
+            if eng is not None:
+                eng.close()
 
     def __del__(self):
         try:
@@ -240,11 +262,13 @@ class FleetController:
         _lib.check(self.lib.admpc_plant_step_batch(model._h, C.byref(self._plant), self.B, _ptr(self.ack), _ptr(self.mode),
                                                    *[_ptr(t) for t in ins], self._eng._stream()))
 
-    def rollout_route(self, path_of, x, y, yaw, vx, vy, yaw_rate, steer, steps, lane=64, back=8, ahead=64, record=False, accumulate=False):
+    def rollout_route(self, path_of, x, y, yaw, vx, vy, yaw_rate, steer, steps, lane=64, back=8, ahead=64, record=False, accumulate=False,
+                      observe=False):
         """`steps` closed-loop steps on the device in one call: step_route, then the plant step on the pose tensors, which are advanced
         in place; no host round trip between the steps.  ``tally`` and ``counts`` are the controller's own tensors, zeroed on the current
-        stream at the start of the call unless `accumulate`; `record` also returns the poses of every step.  Returns FleetRollout;
-        best_of works as after step_route."""
+        stream at the start of the call unless `accumulate`; `record` also returns the poses of every step.  `observe`: every step is
+        observed as observe_latch before the first and observe behind each would (needs ``learn``).  Returns FleetRollout; best_of works
+        as after step_route."""
         if self._bank is None:
             raise ValueError("rollout_route: no bank of paths, call set_paths first")
         prm = AdmpcLaneParams(L=int(lane), back=int(back), ahead=int(ahead))
@@ -265,15 +289,108 @@ class FleetController:
             for i, t in enumerate(ins):
                 traj[0, i].copy_(t)
         model = self._plant_model._h if self._plant_model is not None else None
-        _lib.check(self.lib.admpc_rollout_lane_batch(
-            self._eng._h, self._bank, C.byref(prm), C.byref(self._prm), model, C.byref(self._plant), self.B, T,
-            _ptr(path_of), _ptr(self.lane_idx), *[_ptr(t) for t in ins],
-            _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
-            _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), _ptr(self.cost),
-            _ptr(self.tally), _ptr(self.counts), _ptr(traj) if record else None, self._eng._stream()))
+        args = (self._eng._h, self._bank, C.byref(prm), C.byref(self._prm), model, C.byref(self._plant), self.B, T,
+                _ptr(path_of), _ptr(self.lane_idx), *[_ptr(t) for t in ins],
+                _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
+                _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), _ptr(self.cost),
+                _ptr(self.tally), _ptr(self.counts), _ptr(traj) if record else None)
+        if observe:
+            obs = self._observe_params("rollout_route")
+            _lib.check(self.lib.admpc_rollout_observe_lane_batch(*args, self._observer._h, C.byref(obs), _ptr(self._prev), _ptr(self.samples),
+                                                                 _ptr(self.bins), _ptr(self.dropped), self._eng._stream()))
+        else:
+            _lib.check(self.lib.admpc_rollout_lane_batch(*args, self._eng._stream()))
         self._stepped_paths = True
         return FleetRollout(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt, self.cost, self.lane_idx, self.tally,
                             self.counts, traj)
+
+    # -- learning the residual GP (include/admpc_learn.h) ------------------------------------------------------------------------------
+    def _learns(self, who):
+        if self._learn is None:
+            raise ValueError("%s: this controller does not learn, create it with learn=[...]" % who)
+
+    def _observe_params(self, who, observing=True):
+        """The parameters of an observation as things stand: the plant's period and sub-steps, the controller's own speed band.  A call
+        that observes is refused when the plant model's input bounds are not the controller's."""
+        self._learns(who)
+        pm = self._plant_model if observing else None
+        if pm is not None and (list(pm.cfg.lbu) != list(self._eng.cfg.lbu) or list(pm.cfg.ubu) != list(self._eng.cfg.ubu)):
+            raise ValueError("%s: the plant model's input bounds lbu / ubu differ from the controller's: the inputs the plant applied "
+                             "cannot be told from the record" % who)
+        o = self._obs
+        o.dt, o.substeps, o.blend_min, o.blend_max = self._plant.dt, self._plant.substeps, self._prm.blend_min, self._prm.blend_max
+        return o
+
+    def set_observer(self, learned=False):
+        """Which model predicts in observe: the nominal one (default; its residual is what fit_gp has to learn) or the controller's own
+        handle with whatever GP is installed (what is left of the residual after learning)."""
+        self._learns("set_observer")
+        self._observer = self._eng if learned else self._nominal
+
+    def observe_reset(self):
+        """Forgets every sample: bins and dropped are zeroed on the current stream."""
+        self._learns("observe_reset")
+        self.bins.zero_()
+        self.dropped.zero_()
+
+    def observe_latch(self, x, y, yaw, vx, vy, yaw_rate, steer):
+        """Takes the poses the next observe will predict from.  Asynchronous on the current stream."""
+        self._observe_params("observe_latch")
+        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
+        for t in ins:
+            self._eng._chk(t, (self.B,))
+        _lib.check(self.lib.admpc_observe_latch_batch(self.device.index, self.B, *[_ptr(t) for t in ins], _ptr(self._prev), self._eng._stream()))
+
+    def observe(self, x, y, yaw, vx, vy, yaw_rate, steer):
+        """The poses one plant period after the latched ones, under the controller's last ack and mode: what the observer's model did not
+        predict of v_x, v_y and the yaw rate, per second, goes into ``samples`` [B,10] and from there into ``bins`` [4,32,5] (count, feature
+        sums, target sum per bin) and ``dropped`` [5]; the poses are latched for the next call.  Asynchronous on the current stream."""
+        obs = self._observe_params("observe")
+        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
+        for t in ins:
+            self._eng._chk(t, (self.B,))
+        _lib.check(self.lib.admpc_observe_batch(self._observer._h, C.byref(self._plant), C.byref(obs), self.B, _ptr(self.ack), _ptr(self.mode),
+                                                *[_ptr(t) for t in ins], _ptr(self._prev), _ptr(self.samples), _ptr(self.bins),
+                                                _ptr(self.dropped), self._eng._stream()))
+
+    def fit_gp(self, min_count=1, install=True):
+        """Fits every regressor to the means of its bins with at least `min_count` samples, at the hyperparameters given to ``learn``, and
+        (`install`) overwrites the GPs of the controller's handle on the device.  Asynchronous on the current stream; returns the device
+        tensors (info int32 [n], installed int32 [n] or None): info[g] is the number of points, or -(k + 1) where pivot k failed and the
+        GP is empty; installed[g] is 1 where the record passed the install's check."""
+        obs = self._observe_params("fit_gp", observing=False)
+        n = self.n_learn
+        _lib.check(self.lib.admpc_gp_fit(self.device.index, C.byref(obs), int(min_count), _ptr(self.bins), _ptr(self._gp_dev), _ptr(self.fit_info),
+                                         self._eng._stream()))
+        if not install:
+            return self.fit_info[:n], None
+        _lib.check(self.lib.admpc_gp_install(self._eng._h, n, _ptr(self._gp_dev), _ptr(self.installed), self._eng._stream()))
+        return self.fit_info[:n], self.installed[:n]
+
+    def learned_gps(self):
+        """The GPs of the last fit_gp as the list of dicts config.set_gp takes (synchronises): to save the model, or to create another
+        handle with it.  length_scale is the one given to ``learn``.  A record the install refuses (a number that is not finite) is
+        returned as the install leaves it in the handle: the empty GP, feature 3, row 3, no points, mean 0."""
+        self._learns("learned_gps")
+        torch.cuda.current_stream(self.device).synchronize()
+        raw = self._gp_dev.cpu().numpy().tobytes()
+        out = []
+        for g, d in enumerate(self._learn):
+            gp = AdmpcGp.from_buffer_copy(raw, g * C.sizeof(AdmpcGp))
+            nf, n = int(gp.n_feat), int(gp.n_points)
+            if nf == 0:                                                  # no fit yet: the placeholder
+                out.append(dict(feat=d["feat"], out=d["out"], Z=[], alpha=[], length_scale=d["length_scale"], sigma_f=d.get("sigma_f", 1.0), ymean=0.0))
+                continue
+            nums = [gp.sigma_f, gp.ymean] + [gp.inv_l2[k] for k in range(nf)] + [gp.alpha[i] for i in range(n)] + \
+                [gp.Z[k][i] for k in range(nf) for i in range(n)]
+            if not np.isfinite(np.array(nums, dtype=np.float64)).all():      # (the fit writes no other head than the one given to learn)
+                out.append(dict(feat=3, out=3, Z=[], alpha=[], length_scale=1.0, sigma_f=0.0, ymean=0.0))
+                continue
+            out.append(dict(feat=[int(gp.feat[k]) for k in range(nf)], out=int(gp.out),
+                            Z=np.array([[gp.Z[k][i] for k in range(nf)] for i in range(n)], dtype=np.float64).reshape(n, nf),
+                            alpha=np.array([gp.alpha[i] for i in range(n)], dtype=np.float64), length_scale=d["length_scale"],
+                            sigma_f=float(gp.sigma_f), ymean=float(gp.ymean)))
+        return out
 
     def best_of(self, group, cost=None):
         """The cheapest usable candidate of every group of `group` consecutive instances of the last step_paths or step_route (instance b = v * group + c

@@ -6,6 +6,7 @@ set_reference, optimize: what a host does for each vehicle without the fleet ste
     python scripts/fleet_step.py --bank [--batches 4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--repeats 5]
     python scripts/fleet_step.py --lane [--batches 4096] [--horizons 20,40] [--steps 50] [--warmup 10] [--repeats 5]
     python scripts/fleet_step.py --rollout 50 [--batches 4096] [--horizons 20,40] [--repeats 5]
+    python scripts/fleet_step.py --rollout 50 --observe [--batches 4096] [--horizons 20,40] [--repeats 5]
 
 --bank: the same workloads through a bank of paths (admpc_control_step_bank_batch: set_paths / step_paths) with K = 1 and with K = 8 copies
 of the path and round-robin path_of, against the single-path step in the same process, the variants interleaved `repeats` times (one JSON
@@ -19,6 +20,11 @@ waypoints, against the single-path step and the bank step (K = 1) for B vehicles
 against T back-to-back step_route calls, for the same B vehicles spread along the route of --lane, seconds per step, interleaved as above;
 every repeat starts from the same poses.  The plant kernel's own time is read from a kernel trace of this command in a run of its own
 (rocprofv3 --kernel-trace --stats -- python scripts/fleet_step.py --rollout T --repeats 1: the row of admpc_plant_kernel).
+
+--rollout T --observe: the rollout of a controller that does not learn, of one that learns three regressors (placeholder GPs in its
+model: the GP kernel paths) without observing, and of the same with every step observed (admpc_rollout_observe_lane_batch: the latch, and
+admpc_observe_kernel and admpc_bin_kernel behind every step), seconds per step, interleaved as above; and seconds per fit_gp with its
+install on filled bins (8, 32 and 32 points factorised), on a controller of its own.  The kernels' own times are read from a kernel trace of this command in a run of its own (--repeats 1).
 
 One JSON line per (N, B) and one for the per-vehicle loop per N.  Times come from HIP events around `steps` back-to-back steps (fleet,
 bare solve) or wall time around `loop-calls` calls (the per-vehicle loop, which synchronises at every call by construction)."""
@@ -155,17 +161,82 @@ def lane_against_bank(N, B, steps, warmup, repeats, M=2000, lane=64):
     return times, share
 
 
-def rollout_against_steps(N, B, T, repeats, M=2000, lane=64):
-    """Seconds per step of one rollout_route of T steps and of T back-to-back step_route calls, on the route and the poses of
-    lane_against_bank.  The rollout moves its vehicles, so every repeat copies the first poses back and sends lane_idx back to a search
-    of the whole route, for both variants, outside the timed window."""
+def route_poses(M, B):
+    """The route of M waypoints and B poses 0.3 m beside it, 5 .. 9 m/s."""
     p = path(M)
     x, y, psi, _ = p
     rng = np.random.default_rng(1)
     at = rng.integers(0, M - 50, size=B)
     e = 0.3 * (-1.0) ** np.arange(B)
-    spread = [x[at] - e * np.sin(psi[at]), y[at] + e * np.cos(psi[at]), psi[at] + rng.uniform(-0.05, 0.05, size=B), rng.uniform(5.0, 9.0, size=B),
-              rng.uniform(-0.1, 0.1, size=B), rng.uniform(-0.05, 0.05, size=B), rng.uniform(-0.03, 0.03, size=B)]
+    return p, [x[at] - e * np.sin(psi[at]), y[at] + e * np.cos(psi[at]), psi[at] + rng.uniform(-0.05, 0.05, size=B), rng.uniform(5.0, 9.0, size=B),
+               rng.uniform(-0.1, 0.1, size=B), rng.uniform(-0.05, 0.05, size=B), rng.uniform(-0.03, 0.03, size=B)]
+
+
+LEARN = [dict(feat=3, out=3, lo=[2.0], hi=[12.0], bins=[8], length_scale=2.0),
+         dict(feat=[3, 6], out=4, lo=[2.0, -0.3], hi=[12.0, 0.3], bins=[8, 4], length_scale=[2.0, 0.2]),
+         dict(feat=[3, 6], out=5, lo=[2.0, -0.3], hi=[12.0, 0.3], bins=[8, 4], length_scale=[2.0, 0.2])]
+
+
+def rollout_observed(N, B, T, repeats, M=2000, lane=64):
+    """Seconds per step of one rollout_route of T steps: of a controller that does not learn (`nominal`), of one that learns three
+    regressors, its placeholder GPs in the model, without observing (`learn`) and observing every step (`observe`); and seconds per
+    fit_gp with the install (`fit_install`) on a fourth controller whose bins are all filled (8, 32 and 32 points).  Interleaved, poses and lane_idx sent back before every repeat as in rollout_against_steps."""
+    p, spread = route_poses(M, B)
+    runs = {}
+    for name in ("nominal", "learn", "observe"):
+        fc = FleetController(T_HORIZON, N, OPT_DT, B, learn=None if name == "nominal" else LEARN)
+        fc.set_paths([p])
+        first = [torch.as_tensor(a, dtype=torch.float64, device=fc.device) for a in spread]
+        ins = [t.clone() for t in first]
+        zero = torch.zeros(B, dtype=torch.int32, device=fc.device)
+        fn = lambda fc=fc, ins=ins, zero=zero, obs=name == "observe": fc.rollout_route(zero, *ins, steps=T, lane=lane, observe=obs)
+        runs[name] = (fc, fn, first, ins)
+    # the fit is timed on a controller of its own, whose rollout is not: every bin of its three regressors holds hand-made statistics
+    fitter = FleetController(T_HORIZON, N, OPT_DT, 64, learn=LEARN)
+    stats = np.zeros((4, 32, 5))
+    for g, d in enumerate(LEARN):
+        nb = list(d["bins"])
+        for k in range(int(np.prod(nb))):
+            idx = np.unravel_index(k, nb)
+            z = [d["lo"][i] + (idx[i] + 0.5) * (d["hi"][i] - d["lo"][i]) / nb[i] for i in range(len(nb))]
+            stats[g, k, 0], stats[g, k, 1:1 + len(nb)], stats[g, k, 4] = 5.0, 5.0 * np.array(z), 5.0 * np.sin(z[0]) * np.cos(3.0 * z[-1])
+    fitter.bins.copy_(torch.as_tensor(stats, device=fitter.device))
+    times = {name: [] for name in list(runs) + ["fit_install"]}
+    for r in range(repeats + 1):                                   # the first round is the warm-up
+        for name, (fc, fn, first, ins) in runs.items():
+            fc.reset()
+            for t, f in zip(ins, first):
+                t.copy_(f)
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            if r:
+                times[name].append(a.elapsed_time(b) * 1e-3 / T)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fit_info, fit_installed = fitter.fit_gp(min_count=1)       # filled bins: 8, 32 and 32 points are factorised and installed
+        b.record()
+        torch.cuda.synchronize()
+        if r:
+            times["fit_install"].append(a.elapsed_time(b) * 1e-3)
+    fc = runs["observe"][0]
+    bins, dropped = fc.bins.cpu().numpy(), fc.dropped.cpu().numpy()
+    info = {"samples_binned": [float(v) for v in bins[:3, :, 0].sum(axis=1)], "dropped": [int(v) for v in dropped],
+            "fit_points": fit_info.cpu().tolist(), "fit_installed": fit_installed.cpu().tolist()}
+    fitter.close()
+    for fc, _, _, _ in runs.values():
+        fc.close()
+    return times, info
+
+
+def rollout_against_steps(N, B, T, repeats, M=2000, lane=64):
+    """Seconds per step of one rollout_route of T steps and of T back-to-back step_route calls, on the route and the poses of
+    lane_against_bank.  The rollout moves its vehicles, so every repeat copies the first poses back and sends lane_idx back to a search
+    of the whole route, for both variants, outside the timed window."""
+    p, spread = route_poses(M, B)
     runs = {}
     for name in ("rollout", "step_route"):
         fc = FleetController(T_HORIZON, N, OPT_DT, B)
@@ -254,6 +325,7 @@ def main():
     ap.add_argument("--bank", action="store_true", help="the bank of paths against the single-path step, and the arg-min per group")
     ap.add_argument("--lane", action="store_true", help="the step along a route against the bank step and the single-path step")
     ap.add_argument("--rollout", type=int, default=0, metavar="T", help="one rollout of T closed-loop steps against T step_route calls")
+    ap.add_argument("--observe", action="store_true", help="with --rollout T: the rollout with and without the observation of every step")
     ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     p = path()
@@ -263,6 +335,14 @@ def main():
         med = lambda ts: float(np.median(ts))
         for N in [int(v) for v in a.horizons.split(",")]:
             for B in [int(v) for v in (a.batches if a.batches != "1,64,4096" else "4096").split(",")]:
+                if a.observe:
+                    t, info = rollout_observed(N, B, a.rollout, a.repeats)
+                    print(json.dumps({"what": "fleet_rollout_observe", "N": N, "B": B, "T": a.rollout, "route_waypoints": 2000, "L": 64, "regressors": len(LEARN),
+                                      "us": {k: us(v) for k, v in t.items()}, "median_us": {k: round(med(v) * 1e6, 1) for k, v in t.items()},
+                                      "spread_us": {k: round((max(v) - min(v)) * 1e6, 1) for k, v in t.items()},
+                                      "observe_minus_learn_us": round((med(t["observe"]) - med(t["learn"])) * 1e6, 1),
+                                      "learn_minus_nominal_us": round((med(t["learn"]) - med(t["nominal"])) * 1e6, 1), **info, "gpu": gpu}), flush=True)
+                    continue
                 t, info = rollout_against_steps(N, B, a.rollout, a.repeats)
                 print(json.dumps({"what": "fleet_rollout", "N": N, "B": B, "T": a.rollout, "route_waypoints": 2000, "L": 64,
                                   "us_per_step": {k: us(v) for k, v in t.items()}, "median_us": {k: round(med(v) * 1e6, 1) for k, v in t.items()},
