@@ -6,13 +6,13 @@ surface raises.  The CPU oracle under ``oracle/`` is test infrastructure and is 
 import ctypes as C
 import os
 
-from .config import AdmpcConfig, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
+from .config import AdmpcConfig, AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
 from .quad_config import AdmpcQuadConfig
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libadmpc.so")
 
-# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h, include/admpc_lane.h, include/admpc_plant.h and include/admpc_learn.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
+# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h, include/admpc_lane.h, include/admpc_plant.h, include/admpc_learn.h and include/admpc_hyper.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
 # _f32 entries), ip: to ints, vp: opaque (handle, stream, communicator) -- device pointers travel as integers, so all three are c_void_p.
 vp = dp = ip = C.c_void_p
 I, D, S = C.c_int, C.c_double, C.c_char_p
@@ -83,6 +83,11 @@ _LEARN = {      # include/admpc_learn.h: observe -> bin -> fit -> install of a h
     "admpc_rollout_observe_lane_batch": (I, _PLANT["admpc_rollout_lane_batch"][1][:-1] + [vp, op, dp, dp, dp, ip, vp]),
 }
 LEARN_EXPORTS = tuple(_LEARN)
+_HYPER = {      # include/admpc_hyper.h: the search of a regressor's hyperparameters on the device, and the fit at the optimum
+    "admpc_gp_search": (I, [I, op, C.POINTER(AdmpcGpSearchParams), I, I, dp, dp, dp, ip, vp]),
+    "admpc_gp_refit": (I, [I, op, I, dp, dp, vp, ip, vp]),
+}
+HYPER_EXPORTS = tuple(_HYPER)
 
 _lib = None
 
@@ -92,7 +97,7 @@ class AdmpcError(RuntimeError):
 
 
 def load():
-    """dlopen libadmpc.so and declare the prototypes of the six headers under include/ (no GPU needed for this)."""
+    """dlopen libadmpc.so and declare the prototypes of the seven headers under include/ (no GPU needed for this)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -100,7 +105,7 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT, **_LEARN}.items():
+    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT, **_LEARN, **_HYPER}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -106,6 +106,23 @@ class AdmpcObserveParams(C.Structure):
                 ("gp", AdmpcGpBins * GP_MAX)]
 
 
+GP_SEARCH_MAX = 4096       # candidates per regressor and round of the hyperparameter search (include/admpc_hyper.h)
+GP_HYPER = 16              # doubles of search state per regressor
+GP_NO_OPTIMUM = -33        # info of a re-fit whose search found no finite NLL
+
+
+class AdmpcGpSearchBox(C.Structure):
+    """The box of one regressor's search (include/admpc_hyper.h): slots length[0 .. 2], sigma_f, noise in natural units; lo == hi
+    fixes a slot."""
+    _fields_ = [("lo", C.c_double * 5), ("hi", C.c_double * 5)]
+
+
+class AdmpcGpSearchParams(C.Structure):
+    """The zooming grid search of the hyperparameters (include/admpc_hyper.h): grid points per free slot (3, 5, 7 or 9), rounds, the
+    factor the grid's step shrinks by after every round, and a box per regressor."""
+    _fields_ = [("grid", C.c_int32), ("rounds", C.c_int32), ("shrink", C.c_double), ("box", AdmpcGpSearchBox * GP_MAX)]
+
+
 # --- vehicle constants: src/ad_mpc/ad_3d.py:47-71 (the 3.14195 "pi" is part of the model) -----------
 VEH_MASS = 1500.0
 VEH_F_MASS = 900.0
@@ -255,3 +272,36 @@ def learn_bins(learn):
             b.feat[k], b.nb[k] = (feats[k], nb[k]) if used else (0, 1)
             b.lo[k], b.hi[k], b.length[k] = (lo[k], hi[k], ell[k]) if used else (0.0, 0.0, 0.0)
     return out, len(learn)
+
+
+# the reference's bounds of the search (src/model_fitting/gp.py:337-338): lengths and sigma_f in [1e-5, 1e1], sigma_n in [1e-8, 1] --
+# the noise searched here is sigma_n^2
+SEARCH_BOUNDS = dict(length_scale=(1e-5, 1e1), sigma_f=(1e-5, 1e1), noise=(1e-16, 1.0))
+
+
+def search_boxes(learn, bounds=None):
+    """The AdmpcGpSearchBox of every regressor of ``learn`` (the list learn_bins takes).  ``bounds``: None for the reference's
+    (SEARCH_BOUNDS), or one dict per regressor with any of length_scale (one (lo, hi) or one per feature), sigma_f, noise; lo == hi
+    fixes a slot.  Raises ValueError on a bound that is not 0 < lo <= hi, finite; the library refuses the same."""
+    learn = list(learn)
+    if bounds is None:
+        bounds = [{}] * len(learn)
+    bounds = list(bounds)
+    if len(bounds) != len(learn):
+        raise ValueError("bounds: one dict per regressor (%d), got %d" % (len(learn), len(bounds)))
+    out = (AdmpcGpSearchBox * GP_MAX)()
+    for g, (d, b) in enumerate(zip(learn, bounds)):
+        nf = np.atleast_1d(d["feat"]).size
+        b = dict(SEARCH_BOUNDS, **(b or {}))
+        ell = np.asarray(b["length_scale"], dtype=np.float64).reshape(-1, 2)
+        if ell.shape[0] == 1:
+            ell = np.repeat(ell, nf, axis=0)
+        if ell.shape[0] != nf:
+            raise ValueError("bounds[%d]: length_scale needs one (lo, hi) or one per feature" % g)
+        rows = [ell[k] if k < nf else (1.0, 1.0) for k in range(GP_MAX_FEAT)] + [b["sigma_f"], b["noise"]]
+        for k, (lo, hi) in enumerate(rows):
+            lo, hi = float(lo), float(hi)
+            if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= hi):
+                raise ValueError("bounds[%d]: every bound needs 0 < lo <= hi, finite; got (%r, %r)" % (g, lo, hi))
+            out[g].lo[k], out[g].hi[k] = lo, hi
+    return out

@@ -10,7 +10,8 @@
 //                                  registers and every loop unrolled took 256 VGPRs, 256 AGPRs and 728 bytes of scratch per lane.
 //   install  admpc_gp_install_kernel   one wave: checks each record and copies it into the handle's device configuration
 //
-// The hyperparameters are given (admpc_learn.h: scope).  The rollout with observation is at the end of the file.
+// The hyperparameters are given (admpc_learn.h: scope); the body of the fit is in gp_fit_dev.h, which admpc_hyper.hip shares for the fit at
+// searched hyperparameters.  The rollout with observation is at the end of the file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -21,15 +22,12 @@
 #define NX ADMPC_NX
 #define NU ADMPC_NU
 #define NY ADMPC_NY
-#define WAVE 64
+#include "gp_fit_dev.h"   // WAVE, NPT, ACC; LearnGp, LearnArgs; the body of the fit
 #define LIN_TASKS 63     // tasks per block (multiple of 3), as in admpc_kernels.hip
-#define NPT ADMPC_GP_MAX_POINTS
 #define REC 10           // doubles per sample record
-#define ACC 5            // doubles per bin
 #define GP_WORDS (sizeof(AdmpcGp) / 8)
 
 static_assert(sizeof(AdmpcGp) % 8 == 0 && offsetof(AdmpcConfig, gp) % 8 == 0, "AdmpcGp is copied in 8-byte words");
-static_assert(NPT == 32, "the fit maps one row to each lane of half a wave");
 
 extern "C" int admpc_set_error(int code, const char* msg);                                  // admpc_kernels.hip
 extern "C" const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);      // admpc_kernels.hip
@@ -46,24 +44,6 @@ struct ObserveArgs {
     const double* st[NX];        // px, py, yaw, vx, vy, yaw_rate, steer: [B] each, the poses now
     double* prev;                // [7][B] the poses one period ago, in/out
     double* samples;             // [B][REC]
-};
-
-// one regressor as the bin kernel and the fit kernel read it
-struct LearnGp {
-    int n_feat, feat[3], out, nb[3], nbins;
-    double lo[3], scale[3];      // scale_d = nb_d / (hi_d - lo_d)
-    double sigma_f, inv_l2[3], noise, count_noise;
-};
-
-struct LearnArgs {
-    int B, n_gp;
-    double min_count;
-    LearnGp gp[ADMPC_GP_MAX];
-    const double* samples;       // [B][REC]
-    double* bins;                // [n_gp][NPT][ACC]
-    int32_t* dropped;            // [ADMPC_GP_MAX + 1]
-    AdmpcGp* out;                // [n_gp]
-    int32_t* info;               // [n_gp]
 };
 
 namespace {
@@ -188,98 +168,13 @@ __global__ __launch_bounds__(WAVE) void admpc_bin_kernel(const LearnArgs a)
     }
 }
 
-// grid n_gp, one wave each.  Lane r < 32 owns point r and row r of K; lanes 32 .. 63 mirror lanes 0 .. 31 and store nothing.
+// grid n_gp, one wave each: the fit at the hyperparameters given to the regressor (gp_fit_dev.h has the body, which admpc_hyper.hip shares).
 __global__ __launch_bounds__(WAVE) void admpc_gp_fit_kernel(const LearnArgs a)
 {
-    __shared__ double Zs[3][NPT], ts[NPT], cs[NPT], As[NPT][NPT + 1];
     const int g = (int)blockIdx.x;
     const LearnGp& G = a.gp[g];
-    const int lane = lane_id(), r = lane & (NPT - 1);
-    const bool act = lane < NPT;
-    const int nf = G.n_feat;
-    // the points: the bins with enough samples, in ascending order
-    const double* bn = a.bins + ((long)g * NPT + r) * ACC;
-    double cnt = 0.0;
-    bool ok = false;
-    if (act && r < G.nbins) { cnt = bn[0]; ok = cnt >= a.min_count; }
-    const unsigned long long m = __ballot(ok);
-    const int n = __popcll(m), pos = __popcll(m & ((1ull << lane) - 1ull));
-    if (ok) {
-#pragma clang fp contract(off)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) Zs[d][pos] = d < nf ? bn[1 + d] / cnt : 0.0;
-        ts[pos] = bn[4] / cnt;
-        cs[pos] = cnt;
-    }
-    if (act && r >= n) { Zs[0][r] = 0.0; Zs[1][r] = 0.0; Zs[2][r] = 0.0; ts[r] = 0.0; cs[r] = 1.0; }
-    __syncthreads();
-    double ymean = 0.0;
-    {
-#pragma clang fp contract(off)
-        double sum = 0.0;
-        for (int i = 0; i < n; ++i) sum = sum + ts[i];
-        if (n > 0) ymean = sum / (double)n;
-    }
-    // row r of K in LDS (lower triangle and diagonal: what the factorisation reads)
-    const double il0 = G.inv_l2[0], il1 = nf > 1 ? G.inv_l2[1] : 0.0, il2 = nf > 2 ? G.inv_l2[2] : 0.0;
-    const double z0 = Zs[0][r], z1 = Zs[1][r], z2 = Zs[2][r];
-    const double diag = G.noise + G.count_noise / cs[r];
-    if (act && r < n) {
-#pragma unroll 1
-        for (int j = 0; j <= r; ++j) {
-            const double e0 = z0 - Zs[0][j], e1 = z1 - Zs[1][j], e2 = z2 - Zs[2][j];
-            As[r][j] = G.sigma_f * exp_nonpos(-0.5 * (e0 * e0 * il0 + e1 * e1 * il1 + e2 * e2 * il2)) + (j == r ? diag : 0.0);
-        }
-    }
-    __syncthreads();
-    // left-looking Cholesky, a column per step: lane r >= k forms L[r][k] from row r and row k of the columns already there
-    int fail = 0;
-#pragma unroll 1
-    for (int k = 0; k < n; ++k) {
-        double s = 0.0;
-        if (r >= k && r < n) {
-            s = As[r][k];
-#pragma unroll 1
-            for (int j = 0; j < k; ++j) s = s - As[r][j] * As[k][j];
-        }
-        const double d = __shfl(s, k), tk = ts[k];
-        if (!(d > 0.0 && isfinite(d) && isfinite(tk))) { fail = k + 1; break; }      // uniform over the wave
-        const double l = sqrt(d);
-        if (act && r >= k && r < n) As[r][k] = r == k ? l : s / l;
-        __syncthreads();
-    }
-    double bb = r < n ? ts[r] - ymean : 0.0;
-    if (!fail) {
-#pragma unroll 1
-        for (int k = 0; k < n; ++k) {                      // L w = t - ymean
-            const double wk = __shfl(bb, k) / As[k][k];
-            if (r == k) bb = wk;
-            else if (r > k && r < n) bb = bb - As[r][k] * wk;
-        }
-#pragma unroll 1
-        for (int k = n - 1; k >= 0; --k) {                 // L' alpha = w
-            const double ak = __shfl(bb, k) / As[k][k];
-            if (r == k) bb = ak;
-            else if (r < k) bb = bb - As[k][r] * ak;
-        }
-    }
-    const int np = fail ? 0 : n;
-    AdmpcGp* o = a.out + g;
-    if (act) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) o->Z[d][r] = (r < np && d < nf) ? Zs[d][r] : 0.0;
-        o->alpha[r] = r < np ? bb : 0.0;
-    }
-    if (lane == 0) {
-        o->n_feat = nf;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { o->feat[d] = d < nf ? G.feat[d] : 0; o->inv_l2[d] = d < nf ? G.inv_l2[d] : 0.0; }
-        o->out = G.out;
-        o->n_points = np;
-        o->sigma_f = G.sigma_f;
-        o->ymean = fail ? 0.0 : ymean;
-        a.info[g] = fail ? -fail : n;
-    }
+    const GpHyper h = { G.sigma_f, { G.inv_l2[0], G.inv_l2[1], G.inv_l2[2] }, G.noise, 0 };
+    gp_fit_body(a, g, h);
 }
 
 // one wave.  src [n_gp] -> cfg->gp[0 .. n_gp); a record that fails the check is replaced by the empty GP.
@@ -414,6 +309,13 @@ int latch_launch(int B, const double* const* st, double* prev, void* stream)
 }
 
 }  // namespace
+
+// for admpc_hyper.hip: the refusals of the observe parameters, and a regressor as the fit reads it
+extern "C" __attribute__((visibility("hidden"))) int admpc_observe_params_check(const char* who, const AdmpcObserveParams* obs)
+{
+    return observe_params_check(who, obs);
+}
+__attribute__((visibility("hidden"))) void admpc_learn_fill(LearnArgs& a, const AdmpcObserveParams* obs) { fill_learn(a, obs); }
 
 extern "C" {
 

@@ -1,0 +1,149 @@
+// gp_fit_dev.h -- the body of the GP fit (include/admpc_learn.h: admpc_gp_fit), shared by the kernel that fits at the hyperparameters
+// GIVEN to it (admpc_learn.hip) and the one that fits at the hyperparameters a search has found (admpc_hyper.hip: admpc_gp_refit), and
+// the formation of a regressor's points from its bins, which the search's NLL kernel shares with both.
+// Include at file scope; the translation unit includes model_dev.h in its anonymous namespace (exp_nonpos, declared below).  NPT, ACC
+// and WAVE are defined here.
+#pragma once
+#include "../../include/admpc_hyper.h"
+
+namespace { __device__ __forceinline__ double exp_nonpos(const double x); }      // model_dev.h
+
+#define WAVE 64
+#define NPT ADMPC_GP_MAX_POINTS
+#define ACC 5            // doubles per bin
+
+static_assert(NPT == 32, "the fit maps one row to each lane of half a wave");
+
+// one regressor as the bin kernel and the fit kernel read it
+struct LearnGp {
+    int n_feat, feat[3], out, nb[3], nbins;
+    double lo[3], scale[3];      // scale_d = nb_d / (hi_d - lo_d)
+    double sigma_f, inv_l2[3], noise, count_noise;
+};
+
+struct LearnArgs {
+    int B, n_gp;
+    double min_count;
+    LearnGp gp[ADMPC_GP_MAX];
+    const double* samples;       // [B][REC]
+    double* bins;                // [n_gp][NPT][ACC]
+    int32_t* dropped;            // [ADMPC_GP_MAX + 1]
+    AdmpcGp* out;                // [n_gp]
+    int32_t* info;               // [n_gp]
+};
+
+// where a fit takes its hyperparameters from: the regressor's own (given), or the natural values a search left in device memory
+struct GpHyper {
+    double sigma_f, inv_l2[3], noise;
+    int no_optimum;              // the search found no finite NLL: the empty GP, info ADMPC_GP_NO_OPTIMUM (0 for a fit at given values)
+};
+
+static __device__ __forceinline__ int gp_lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// The points of regressor g, by ONE wave: the bins with enough samples, in ascending order, into Zs [3][NPT], ts, cs (LDS); the rows
+// past the last point are filled with zeros and a count of 1.  Returns n, the same on every lane.  Lane r < 32 reads bin r.
+static __device__ __forceinline__ int gp_points(const LearnArgs& a, const int g, const int lane, double (*Zs)[NPT], double* ts, double* cs)
+{
+    const LearnGp& G = a.gp[g];
+    const int r = lane & (NPT - 1), nf = G.n_feat;
+    const bool act = lane < NPT;
+    const double* bn = a.bins + ((long)g * NPT + r) * ACC;
+    double cnt = 0.0;
+    bool ok = false;
+    if (act && r < G.nbins) { cnt = bn[0]; ok = cnt >= a.min_count; }
+    const unsigned long long m = __ballot(ok);
+    const int n = __popcll(m), pos = __popcll(m & ((1ull << lane) - 1ull));
+    if (ok) {
+#pragma clang fp contract(off)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) Zs[d][pos] = d < nf ? bn[1 + d] / cnt : 0.0;
+        ts[pos] = bn[4] / cnt;
+        cs[pos] = cnt;
+    }
+    if (act && r >= n) { Zs[0][r] = 0.0; Zs[1][r] = 0.0; Zs[2][r] = 0.0; ts[r] = 0.0; cs[r] = 1.0; }
+    return n;
+}
+
+// the serial sum of the targets, divided by n; every operation rounded on its own
+static __device__ __forceinline__ double gp_ymean(const double* ts, const int n)
+{
+#pragma clang fp contract(off)
+    double sum = 0.0;
+    for (int i = 0; i < n; ++i) sum = sum + ts[i];
+    return n > 0 ? sum / (double)n : 0.0;
+}
+
+// One wave (a block of its own) fits regressor g at the hyperparameters h.  Lane r < 32 owns point r and row r of K; lanes 32 .. 63
+// mirror lanes 0 .. 31 and store nothing.
+static __device__ __forceinline__ void gp_fit_body(const LearnArgs& a, const int g, const GpHyper& h)
+{
+    __shared__ double Zs[3][NPT], ts[NPT], cs[NPT], As[NPT][NPT + 1];
+    const LearnGp& G = a.gp[g];
+    const int lane = gp_lane_id(), r = lane & (NPT - 1);
+    const bool act = lane < NPT;
+    const int nf = G.n_feat;
+    const int n = gp_points(a, g, lane, Zs, ts, cs);
+    __syncthreads();
+    const double ymean = gp_ymean(ts, n);
+    // row r of K in LDS (lower triangle and diagonal: what the factorisation reads)
+    const double il0 = h.inv_l2[0], il1 = nf > 1 ? h.inv_l2[1] : 0.0, il2 = nf > 2 ? h.inv_l2[2] : 0.0;
+    const double z0 = Zs[0][r], z1 = Zs[1][r], z2 = Zs[2][r];
+    const double diag = h.noise + G.count_noise / cs[r];
+    if (act && r < n) {
+#pragma unroll 1
+        for (int j = 0; j <= r; ++j) {
+            const double e0 = z0 - Zs[0][j], e1 = z1 - Zs[1][j], e2 = z2 - Zs[2][j];
+            As[r][j] = h.sigma_f * exp_nonpos(-0.5 * (e0 * e0 * il0 + e1 * e1 * il1 + e2 * e2 * il2)) + (j == r ? diag : 0.0);
+        }
+    }
+    __syncthreads();
+    // left-looking Cholesky, a column per step: lane r >= k forms L[r][k] from row r and row k of the columns already there
+    int fail = h.no_optimum ? -ADMPC_GP_NO_OPTIMUM : 0;
+    const int steps = h.no_optimum ? 0 : n;
+#pragma unroll 1
+    for (int k = 0; k < steps; ++k) {
+        double s = 0.0;
+        if (r >= k && r < n) {
+            s = As[r][k];
+#pragma unroll 1
+            for (int j = 0; j < k; ++j) s = s - As[r][j] * As[k][j];
+        }
+        const double d = __shfl(s, k), tk = ts[k];
+        if (!(d > 0.0 && isfinite(d) && isfinite(tk))) { fail = k + 1; break; }      // uniform over the wave
+        const double l = sqrt(d);
+        if (act && r >= k && r < n) As[r][k] = r == k ? l : s / l;
+        __syncthreads();
+    }
+    double bb = r < n ? ts[r] - ymean : 0.0;
+    if (!fail) {
+#pragma unroll 1
+        for (int k = 0; k < n; ++k) {                      // L w = t - ymean
+            const double wk = __shfl(bb, k) / As[k][k];
+            if (r == k) bb = wk;
+            else if (r > k && r < n) bb = bb - As[r][k] * wk;
+        }
+#pragma unroll 1
+        for (int k = n - 1; k >= 0; --k) {                 // L' alpha = w
+            const double ak = __shfl(bb, k) / As[k][k];
+            if (r == k) bb = ak;
+            else if (r < k) bb = bb - As[k][r] * ak;
+        }
+    }
+    const int np = fail ? 0 : n;
+    AdmpcGp* o = a.out + g;
+    if (act) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) o->Z[d][r] = (r < np && d < nf) ? Zs[d][r] : 0.0;
+        o->alpha[r] = r < np ? bb : 0.0;
+    }
+    if (lane == 0) {
+        o->n_feat = nf;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) { o->feat[d] = d < nf ? G.feat[d] : 0; o->inv_l2[d] = d < nf ? h.inv_l2[d] : 0.0; }
+        o->out = G.out;
+        o->n_points = np;
+        o->sigma_f = h.sigma_f;
+        o->ymean = fail ? 0.0 : ymean;
+        a.info[g] = fail ? -fail : n;
+    }
+}

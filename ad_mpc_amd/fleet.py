@@ -4,7 +4,8 @@ every group of candidates (include/admpc_fleet.h: admpc_control_step_bank_batch,
 wherever on it the vehicle is (include/admpc_lane.h: admpc_control_step_lane_batch), or closes the loop on the device: a plant step under
 the record just issued, and T steps of controller and plant per call (include/admpc_plant.h: admpc_plant_step_batch,
 admpc_rollout_lane_batch), or learns the residual GP of its model from the steps it has taken, on the device (include/admpc_learn.h:
-observe -> bin -> fit -> install).
+observe -> bin -> fit -> install), and searches the hyperparameters of that GP on the device (include/admpc_hyper.h: search -> re-fit ->
+install).
 
 ``FleetController`` solves the problem of ``ROSGPMPC(point_reference=False)`` (create_ros_ad_mpc.py:41-101: SQP_RTI, Q_DIAG_ROS /
 R_DIAG_ROS) for every vehicle, and does per step what the reference node does per pose message (gp_ad_mpc_node.py:389-438 ->
@@ -28,7 +29,7 @@ from . import _lib
 from . import config as _c
 from .ad_3d import AD3D
 from .ad_3d_optimizer import ocp_config
-from .config import AdmpcGp, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams, GP_MAX, GP_MAX_POINTS, NX, NU
+from .config import AdmpcGp, AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams, GP_MAX, GP_MAX_POINTS, NX, NU
 from .engine import BatchSolver, _ptr
 from .ref_traj import RefTrajectory
 
@@ -140,6 +141,10 @@ class FleetController:
             self.bins, self.dropped = z(GP_MAX, GP_MAX_POINTS, 5), z(GP_MAX + 1, dtype=torch.int32)
             self._gp_dev = z(GP_MAX * C.sizeof(AdmpcGp), dtype=torch.uint8)
             self.fit_info, self.installed = z(GP_MAX, dtype=torch.int32), z(GP_MAX, dtype=torch.int32)
+            # the hyperparameter search (search_gp): its state, a scratch of one NLL per candidate, and what the last round picked
+            self.hyper, self._nll = z(GP_MAX, _c.GP_HYPER), z(GP_MAX, _c.GP_SEARCH_MAX)
+            self.search_info = z(GP_MAX, 2, dtype=torch.int32)
+            self._has_hyper = self._searched = False                      # a search has run; _gp_dev holds a re-fit at searched values
 
     def _drop_bank(self):
         if getattr(self, "_bank", None):
@@ -362,20 +367,66 @@ class FleetController:
         n = self.n_learn
         _lib.check(self.lib.admpc_gp_fit(self.device.index, C.byref(obs), int(min_count), _ptr(self.bins), _ptr(self._gp_dev), _ptr(self.fit_info),
                                          self._eng._stream()))
+        self._searched = False
         if not install:
             return self.fit_info[:n], None
         _lib.check(self.lib.admpc_gp_install(self._eng._h, n, _ptr(self._gp_dev), _ptr(self.installed), self._eng._stream()))
         return self.fit_info[:n], self.installed[:n]
 
+    def search_gp(self, min_count=1, grid=5, rounds=10, shrink=0.5, bounds=None, resume=False, install=True):
+        """Searches the length scales, sigma_f and the noise of every regressor for the smallest negative log marginal likelihood of its
+        points (the bins with at least `min_count` samples), fits at what it found and (`install`) overwrites the GPs of the controller's
+        handle on the device: 2 * rounds + 2 launches on the current stream (one more where the search starts), no synchronisation, no allocation.  Every round evaluates
+        a regular grid of `grid` points per free slot in the logarithm of the slots, around the best candidate so far, and multiplies
+        the grid's step by `shrink`; the first round spans the box.  ``bounds``: config.search_boxes (None: the reference's box;
+        lo == hi keeps a slot at that value).  ``resume`` continues the last search on the same statistics with the steps where they
+        stand.  Returns the device tensors (info int32 [n] as fit_gp's, or -33 where no candidate had a finite NLL; installed int32
+        [n] or None; hyper float64 [n, 16]: the centre's logarithms, the steps, the natural values and the best NLL)."""
+        obs = self._observe_params("search_gp", observing=False)
+        n = self.n_learn
+        sp = AdmpcGpSearchParams(grid=int(grid), rounds=int(rounds), shrink=float(shrink), box=_c.search_boxes(self._learn, bounds))
+        s = self._eng._stream()
+        _lib.check(self.lib.admpc_gp_search(self.device.index, C.byref(obs), C.byref(sp), int(min_count), 1 if resume else 0, _ptr(self.bins),
+                                            _ptr(self.hyper), _ptr(self._nll), _ptr(self.search_info), s))
+        _lib.check(self.lib.admpc_gp_refit(self.device.index, C.byref(obs), int(min_count), _ptr(self.bins), _ptr(self.hyper), _ptr(self._gp_dev),
+                                           _ptr(self.fit_info), s))
+        self._has_hyper = self._searched = True
+        if not install:
+            return self.fit_info[:n], None, self.hyper[:n]
+        _lib.check(self.lib.admpc_gp_install(self._eng._h, n, _ptr(self._gp_dev), _ptr(self.installed), s))
+        return self.fit_info[:n], self.installed[:n], self.hyper[:n]
+
+    def learned_hyper(self):
+        """The hyperparameters of every regressor as the last search_gp left them (synchronises): a list of dicts with length_scale (one
+        per feature), sigma_f, noise and nll, the negative log marginal likelihood there.  Before any search: the values given to
+        ``learn`` and nll = inf."""
+        self._learns("learned_hyper")
+        torch.cuda.current_stream(self.device).synchronize()
+        hy = self.hyper.cpu().numpy()
+        out = []
+        for g, d in enumerate(self._learn):
+            b = self._obs.gp[g]
+            nf = int(b.n_feat)
+            if not self._has_hyper:
+                out.append(dict(length_scale=[float(b.length[k]) for k in range(nf)], sigma_f=float(b.sigma_f), noise=float(b.noise), nll=float("inf")))
+            else:
+                out.append(dict(length_scale=[float(hy[g, 10 + k]) for k in range(nf)], sigma_f=float(hy[g, 13]), noise=float(hy[g, 14]),
+                                nll=float(hy[g, 15])))
+        return out
+
     def learned_gps(self):
-        """The GPs of the last fit_gp as the list of dicts config.set_gp takes (synchronises): to save the model, or to create another
-        handle with it.  length_scale is the one given to ``learn``.  A record the install refuses (a number that is not finite) is
-        returned as the install leaves it in the handle: the empty GP, feature 3, row 3, no points, mean 0."""
+        """The GPs of the last fit_gp or search_gp as the list of dicts config.set_gp takes (synchronises): to save the model, or to
+        create another handle with it.  length_scale is the one given to ``learn`` after a fit_gp, and the one found after a search_gp:
+        the device's own double, from which set_gp forms the inv_l2 that was installed.  A record the install refuses (a number that is
+        not finite) is returned as the install leaves it in the handle: the empty GP, feature 3, row 3, no points, mean 0."""
         self._learns("learned_gps")
         torch.cuda.current_stream(self.device).synchronize()
         raw = self._gp_dev.cpu().numpy().tobytes()
+        hy = self.hyper.cpu().numpy()
         out = []
         for g, d in enumerate(self._learn):
+            if self._searched:
+                d = dict(d, length_scale=[float(hy[g, 10 + k]) for k in range(int(self._obs.gp[g].n_feat))], sigma_f=float(hy[g, 13]))
             gp = AdmpcGp.from_buffer_copy(raw, g * C.sizeof(AdmpcGp))
             nf, n = int(gp.n_feat), int(gp.n_points)
             if nf == 0:                                                  # no fit yet: the placeholder

@@ -6,8 +6,8 @@
  * front of the first device call.
  *
  * Scope: the hyperparameters of every regressor (length scales, sigma_f, noise) are GIVEN.  The reference searches them with L-BFGS over
- * the marginal likelihood (model_fitting/gp.py:302-320, DESIGN section 8: GP fitting); that search is not part of this library.  What is
- * fitted here is the weight vector alpha = K^-1 (t - ymean) and ymean of a squared-exponential GP at fixed hyperparameters, over at most
+ * the marginal likelihood (model_fitting/gp.py:302-320, DESIGN section 8: GP fitting); that search is not part of this library.  (A grid
+ * search of the same likelihood on the device, which feeds the install below, is in admpc_hyper.h.)  What is fitted here is the weight vector alpha = K^-1 (t - ymean) and ymean of a squared-exponential GP at fixed hyperparameters, over at most
  * ADMPC_GP_MAX_POINTS points, each the mean of the samples that fell into one bin of a regular grid over the features.  The quadrotor
  * is not touched.
  *
