@@ -1,0 +1,69 @@
+// admpc_host.h -- what the host sides of admpc_kernels.hip, admpc_step.hip, admpc_lane.hip, admpc_plant.hip, admpc_learn.hip and
+// admpc_hyper.hip share: the device guard, and one declaration of every hidden function that one of them defines for another.  The
+// defining unit includes this header too, so that the compiler holds each definition against its declaration.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/admpc.h"
+#include "../../include/admpc_fleet.h"
+#include "../../include/admpc_lane.h"
+#include "../../include/admpc_plant.h"
+#include "../../include/admpc_learn.h"
+
+// Every entry point runs on the solver's device and restores the caller's current device on return (a host with several GPUs
+// keeps its own current device: torch allocations and default-stream work of the caller are not redirected).
+struct DeviceGuard {
+    int prev; bool switched; bool good;
+    explicit DeviceGuard(int dev) : prev(-1), switched(false), good(true) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev) { good = hipSetDevice(dev) == hipSuccess; switched = good; }
+    }
+    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
+    bool ok() const { return good; }
+};
+
+// what a control step writes, and the workspace it runs in (cost: null for the step on one global path)
+struct StepOut {
+    double *xbar, *ubar;
+    int32_t* safe_count;
+    double* prev_u;
+    int32_t* has_valid;
+    void* work;
+    float* ack;
+    int32_t *mode, *valid, *status;
+    double* cost;
+};
+
+// admpc_rollout_lane_batch's arguments but T, traj and the stream: st holds the seven pose arrays, px .. steer
+struct RolloutArgs {
+    AdmpcSolver* s; const AdmpcPathBank* bank; const AdmpcLaneParams* lane; const AdmpcStepParams* prm;
+    const AdmpcSolver* plant_model; const AdmpcPlantParams* plant;
+    int B;
+    const int32_t* path_of; int32_t* lane_idx;
+    double* st[ADMPC_NX];
+    StepOut out;
+    double* tally; int32_t* counts;
+};
+
+#define ADMPC_HIDDEN extern "C" __attribute__((visibility("hidden")))
+
+// admpc_kernels.hip: the thread-local message behind admpc_last_error(); the problem a handle solves and the device it lives on; the
+// device copy of that problem, to be read and to be written; the horizon of a bank and its device; a bank's table (returns H)
+ADMPC_HIDDEN int admpc_set_error(int code, const char* msg);
+ADMPC_HIDDEN const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);
+ADMPC_HIDDEN const AdmpcConfig* admpc_solver_config_device(const AdmpcSolver* s);
+ADMPC_HIDDEN AdmpcConfig* admpc_solver_config_device_rw(AdmpcSolver* s);
+ADMPC_HIDDEN int admpc_path_bank_horizon(const AdmpcPathBank* bank, int* device);
+ADMPC_HIDDEN int admpc_path_bank_table(const AdmpcPathBank* bank, int* device, int* K, double* dt, const void** desc, const double** cols);
+// admpc_lane.hip, admpc_plant.hip, admpc_learn.hip: the refusals of a parameter block (`who` leads the message)
+ADMPC_HIDDEN int admpc_lane_params_check(const char* who, const AdmpcLaneParams* lane, const int32_t* lane_idx);
+ADMPC_HIDDEN int admpc_plant_params_check(const char* who, const AdmpcPlantParams* plant);
+ADMPC_HIDDEN int admpc_observe_params_check(const char* who, const AdmpcObserveParams* obs);
+// admpc_plant.hip: one launch of the plant kernel for checked arguments
+ADMPC_HIDDEN int admpc_plant_launch(const AdmpcSolver* model, const AdmpcPlantParams* plant, int B, const float* ack, const int32_t* mode,
+                                    double* const* st, const double* err, const int32_t* status, const int32_t* valid, double* tally,
+                                    int32_t* counts, double* traj_pre, double* traj_post, void* stream);
+// admpc_step.hip: the refusals of a rollout up to its arrays, those behind them (T, the plant's device), and one checked period
+ADMPC_HIDDEN int admpc_rollout_check_step(const RolloutArgs& a);
+ADMPC_HIDDEN int admpc_rollout_check_run(const RolloutArgs& a, int T);
+ADMPC_HIDDEN int admpc_rollout_enqueue(const RolloutArgs& a, double* traj_pre, double* traj_post, void* stream);

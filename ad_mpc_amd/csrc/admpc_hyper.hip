@@ -12,12 +12,9 @@
 //   pick   admpc_gp_pick_kernel         a wave per regressor: the lowest index of the minimum, the new centre by the NLL kernel's own
 //                                       decoding of it (search_candidate), the step shrunk
 //   refit  admpc_gp_refit_kernel        the fit's body (gp_fit_dev.h) at the natural values the search left in `hyper`
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdio.h>
 #include <math.h>
-#include "../../include/admpc.h"
-#include "../../include/admpc_learn.h"
+#include "admpc_host.h"
 #include "../../include/admpc_hyper.h"
 
 #define NX ADMPC_NX
@@ -33,8 +30,6 @@
 static_assert(HYP == 3 * NSLOT + 1, "centre, step and natural value per slot, and the best NLL");
 static_assert(NLL_CAND * TRI * 8 + 6 * NPT * 8 <= 80 * 1024, "two blocks of the NLL kernel fit the LDS of a CU");
 
-extern "C" int admpc_set_error(int code, const char* msg);                                         // admpc_kernels.hip
-extern "C" int admpc_observe_params_check(const char* who, const AdmpcObserveParams* obs);        // admpc_learn.hip
 void admpc_learn_fill(LearnArgs& a, const AdmpcObserveParams* obs);                                // admpc_learn.hip
 
 // the search of one regressor as the kernels read it (passed by value)
@@ -237,16 +232,6 @@ __global__ __launch_bounds__(WAVE) void admpc_gp_refit_kernel(const LearnArgs a,
 }
 
 namespace {
-
-struct DeviceGuard {
-    int prev; bool switched; bool good;
-    explicit DeviceGuard(int dev) : prev(-1), switched(false), good(true) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { good = hipSetDevice(dev) == hipSuccess; switched = good; }
-    }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-    bool ok() const { return good; }
-};
 
 int refuse(const char* what)
 {

@@ -21,8 +21,7 @@
 #include <type_traits>
 #include <stdint.h>
 #include <math.h>
-#include "../../include/admpc.h"
-#include "../../include/admpc_fleet.h"
+#include "admpc_host.h"
 #include "argmin_rule.h"
 
 #define NX ADMPC_NX
@@ -514,18 +513,6 @@ struct AdmpcSolver {
     double* d_pairs;         // [1 + 256] 16-byte (cost, index) records: this rank's, then the all-gathered ones (admpc_argmin_global)
 };
 
-// Every entry point runs on the solver's device and restores the caller's current device on return (a host with several GPUs
-// keeps its own current device: torch allocations and default-stream work of the caller are not redirected).
-struct DeviceGuard {
-    int prev; bool switched; bool good;
-    explicit DeviceGuard(int dev) : prev(-1), switched(false), good(true) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { good = hipSetDevice(dev) == hipSuccess; switched = good; }
-    }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-    bool ok() const { return good; }
-};
-
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail(ADMPC_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
@@ -557,18 +544,18 @@ extern "C" {
 
 const char* admpc_last_error(void) { return g_err.c_str(); }
 // for the other translation units of the library (admpc_quad.hip)
-__attribute__((visibility("hidden"))) int admpc_set_error(int code, const char* msg) { return fail(code, msg ? msg : ""); }
+int admpc_set_error(int code, const char* msg) { return fail(code, msg ? msg : ""); }
 const char* admpc_version(void) { return "admpc-mi355x 0.1 (gfx950)"; }
 // for the control step (admpc_step.hip): the problem a handle solves and the device it lives on
-__attribute__((visibility("hidden"))) const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device)
+const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device)
 {
     if (device) *device = s->device;
     return &s->cfg;
 }
 // for the plant step (admpc_plant.hip): the device copy of that problem, as the kernels read it
-__attribute__((visibility("hidden"))) const AdmpcConfig* admpc_solver_config_device(const AdmpcSolver* s) { return s->d_cfg; }
+const AdmpcConfig* admpc_solver_config_device(const AdmpcSolver* s) { return s->d_cfg; }
 // for the install of a fitted GP (admpc_learn.hip): the same copy, to be written
-__attribute__((visibility("hidden"))) AdmpcConfig* admpc_solver_config_device_rw(AdmpcSolver* s) { return s->d_cfg; }
+AdmpcConfig* admpc_solver_config_device_rw(AdmpcSolver* s) { return s->d_cfg; }
 
 int admpc_default_config(AdmpcConfig* c, int N, double Ts)
 {
@@ -1236,15 +1223,14 @@ struct AdmpcPathBank {
 extern "C" {
 
 // for the control step (admpc_step.hip): the horizon every path of the bank was laid out for, and the device it lives on
-__attribute__((visibility("hidden"))) int admpc_path_bank_horizon(const AdmpcPathBank* bank, int* device)
+int admpc_path_bank_horizon(const AdmpcPathBank* bank, int* device)
 {
     if (device) *device = bank->device;
     return bank->H;
 }
 
 // for the lane generator (admpc_lane.hip): the bank's table of K descriptors and its block of columns, its dt and its device; returns H
-__attribute__((visibility("hidden"))) int admpc_path_bank_table(const AdmpcPathBank* bank, int* device, int* K, double* dt,
-                                                                const void** desc, const double** cols)
+int admpc_path_bank_table(const AdmpcPathBank* bank, int* device, int* K, double* dt, const void** desc, const double** cols)
 {
     *device = bank->device; *K = bank->K; *dt = bank->dt; *desc = bank->d_desc; *cols = bank->d_cols;
     return bank->H;

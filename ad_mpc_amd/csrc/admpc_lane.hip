@@ -15,13 +15,9 @@
 // The lane lives in LDS (LANE_LDS_DOUBLES doubles, static); there is no per-vehicle workspace in global memory.  Every serial sum of the
 // reference (cdist, the unwrap's cumsum, the clamp's bound) is summed serially, in the reference's order: the terms are computed by all
 // lanes in parallel, the running sum is carried by every lane in registers, and lane i % 64 keeps element i.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <math.h>
 #include <stdio.h>
-#include "../../include/admpc.h"
-#include "../../include/admpc_fleet.h"
-#include "../../include/admpc_lane.h"
+#include "admpc_host.h"
 
 #define WAVE 64
 #define LANE_MIN_L 34                 // scipy's filtfilt refuses inputs of 3 * 11 = 33 samples or fewer
@@ -31,9 +27,6 @@
 #define LANE_TAPS 11
 #define LANE_GRID 4096                // as admpc_waypoints_batch
 #define LANE_LDS_DOUBLES (7 * LANE_MAX_L + 2 * (LANE_MAX_L + 2 * LANE_PAD) + WAVE)
-
-extern "C" int admpc_set_error(int code, const char* msg);                                                     // admpc_kernels.hip
-extern "C" int admpc_path_bank_table(const AdmpcPathBank* bank, int* device, int* K, double* dt, const void** desc, const double** cols);
 
 namespace {
 
@@ -201,16 +194,6 @@ __global__ __launch_bounds__(WAVE) void admpc_waypoints_lane_kernel(int K, int H
     }
 }
 
-struct DeviceGuard {
-    int prev; bool switched; bool good;
-    explicit DeviceGuard(int dev) : prev(-1), switched(false), good(true) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { good = hipSetDevice(dev) == hipSuccess; switched = good; }
-    }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-    bool ok() const { return good; }
-};
-
 static_assert(LANE_LDS_DOUBLES * sizeof(double) < 64 * 1024, "the lane fits the static LDS limit");
 
 }  // namespace
@@ -218,7 +201,7 @@ static_assert(LANE_LDS_DOUBLES * sizeof(double) < 64 * 1024, "the lane fits the 
 extern "C" {
 
 // the refusals every entry point of admpc_lane.h shares; they touch neither the device nor another argument
-__attribute__((visibility("hidden"))) int admpc_lane_params_check(const char* who, const AdmpcLaneParams* lane, const int32_t* lane_idx)
+int admpc_lane_params_check(const char* who, const AdmpcLaneParams* lane, const int32_t* lane_idx)
 {
     char msg[160];
     const char* what = nullptr;

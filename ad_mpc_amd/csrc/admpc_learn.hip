@@ -12,12 +12,9 @@
 //
 // The hyperparameters are given (admpc_learn.h: scope); the body of the fit is in gp_fit_dev.h, which admpc_hyper.hip shares for the fit at
 // searched hyperparameters.  The rollout with observation is at the end of the file.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdio.h>
 #include <math.h>
-#include "../../include/admpc.h"
-#include "../../include/admpc_learn.h"
+#include "admpc_host.h"
 
 #define NX ADMPC_NX
 #define NU ADMPC_NU
@@ -28,12 +25,6 @@
 #define GP_WORDS (sizeof(AdmpcGp) / 8)
 
 static_assert(sizeof(AdmpcGp) % 8 == 0 && offsetof(AdmpcConfig, gp) % 8 == 0, "AdmpcGp is copied in 8-byte words");
-
-extern "C" int admpc_set_error(int code, const char* msg);                                  // admpc_kernels.hip
-extern "C" const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);      // admpc_kernels.hip
-extern "C" const AdmpcConfig* admpc_solver_config_device(const AdmpcSolver* s);            // admpc_kernels.hip
-extern "C" AdmpcConfig* admpc_solver_config_device_rw(AdmpcSolver* s);                     // admpc_kernels.hip
-extern "C" int admpc_plant_params_check(const char* who, const AdmpcPlantParams* plant);   // admpc_plant.hip
 
 // what one launch of the observe kernel works on (passed by value)
 struct ObserveArgs {
@@ -210,16 +201,6 @@ __global__ __launch_bounds__(WAVE) void admpc_gp_install_kernel(AdmpcConfig* cfg
 
 namespace {
 
-struct DeviceGuard {
-    int prev; bool switched; bool good;
-    explicit DeviceGuard(int dev) : prev(-1), switched(false), good(true) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { good = hipSetDevice(dev) == hipSuccess; switched = good; }
-    }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-    bool ok() const { return good; }
-};
-
 // The refusals of the observe parameters, for the entry points that take them (`who` leads the message).
 int observe_params_check(const char* who, const AdmpcObserveParams* obs)
 {
@@ -311,10 +292,7 @@ int latch_launch(int B, const double* const* st, double* prev, void* stream)
 }  // namespace
 
 // for admpc_hyper.hip: the refusals of the observe parameters, and a regressor as the fit reads it
-extern "C" __attribute__((visibility("hidden"))) int admpc_observe_params_check(const char* who, const AdmpcObserveParams* obs)
-{
-    return observe_params_check(who, obs);
-}
+extern "C" int admpc_observe_params_check(const char* who, const AdmpcObserveParams* obs) { return observe_params_check(who, obs); }
 __attribute__((visibility("hidden"))) void admpc_learn_fill(LearnArgs& a, const AdmpcObserveParams* obs) { fill_learn(a, obs); }
 
 extern "C" {
@@ -398,12 +376,14 @@ int admpc_rollout_observe_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, 
                                      const AdmpcSolver* model, const AdmpcObserveParams* obs,
                                      double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
 {
+    const RolloutArgs a = { s, bank, lane, prm, plant_model, plant, B, path_of, lane_idx, { px, py, yaw, vx, vy, yaw_rate, steer },
+                            { xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost }, tally, counts };
     int rc = observe_params_check("admpc_rollout_observe_lane_batch", obs);
     if (rc) return rc;
     if (!model) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_observe_lane_batch: null model");
-    // the rollout's own refusals, by the rollout: an empty batch passes every check but those of its arrays and enqueues nothing
-    rc = admpc_rollout_lane_batch(s, bank, lane, prm, plant_model, plant, B < 0 ? B : 0, T, path_of, lane_idx, px, py, yaw, vx, vy, yaw_rate, steer,
-                                  xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost, tally, counts, traj, stream);
+    // the rollout's own refusals but those of its arrays, which are among the ones below
+    rc = admpc_rollout_check_step(a);
+    if (!rc) rc = admpc_rollout_check_run(a, T);
     if (rc) return rc;
     int device = 0, model_device = 0;
     (void)admpc_solver_config(s, &device);
@@ -415,19 +395,14 @@ int admpc_rollout_observe_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, 
         return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_observe_lane_batch: null array argument");
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    const double* st[NX] = { px, py, yaw, vx, vy, yaw_rate, steer };
-    rc = latch_launch(B, st, prev, stream);
-    if (rc) return rc;
+    rc = latch_launch(B, a.st, prev, stream);
     const size_t slot = (size_t)NX * B;
-    for (int t = 0; t < T; ++t) {
-        rc = admpc_rollout_lane_batch(s, bank, lane, prm, plant_model, plant, B, 1, path_of, lane_idx, px, py, yaw, vx, vy, yaw_rate, steer,
-                                      xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost, tally, counts,
-                                      traj ? traj + t * slot : nullptr, stream);
-        if (rc) return rc;
-        rc = observe_launch(model, plant, obs, B, ack, mode, st, prev, samples, bins, dropped, stream);
-        if (rc) return rc;
+    // slot 0 is written by the first launch; every launch writes the state it leaves into the next slot
+    for (int t = 0; t < T && !rc; ++t) {
+        rc = admpc_rollout_enqueue(a, (traj && t == 0) ? traj : nullptr, traj ? traj + (t + 1) * slot : nullptr, stream);
+        if (!rc) rc = observe_launch(model, plant, obs, B, ack, mode, a.st, prev, samples, bins, dropped, stream);
     }
-    return ADMPC_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -11,22 +11,15 @@
 //
 // Three lanes per vehicle and 63 tasks per 64-thread block, the lane map of admpc_shoot_kernel / admpc_shift_kernel: gp_eval shares its
 // kernel sums among the three lanes of a task.  All three carry the same state through the sub-steps; lane 0 of the triple stores.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
 #include <stdio.h>
 #include <math.h>
-#include "../../include/admpc.h"
-#include "../../include/admpc_plant.h"
+#include "admpc_host.h"
 
 #define NX ADMPC_NX
 #define NU ADMPC_NU
 #define NY ADMPC_NY
 #define WAVE 64
 #define LIN_TASKS 63     // tasks per block (multiple of 3), as in admpc_kernels.hip
-
-extern "C" int admpc_set_error(int code, const char* msg);                                  // admpc_kernels.hip
-extern "C" const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);      // admpc_kernels.hip
-extern "C" const AdmpcConfig* admpc_solver_config_device(const AdmpcSolver* s);            // admpc_kernels.hip
 
 // what one launch works on (passed by value); the rollout's pointers are null for a plant-only step
 struct PlantArgs {
@@ -120,24 +113,10 @@ __global__ __launch_bounds__(WAVE) void admpc_plant_kernel(const AdmpcConfig* __
     }
 }
 
-namespace {
-
-struct DeviceGuard {
-    int prev; bool switched; bool good;
-    explicit DeviceGuard(int dev) : prev(-1), switched(false), good(true) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { good = hipSetDevice(dev) == hipSuccess; switched = good; }
-    }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-    bool ok() const { return good; }
-};
-
-}  // namespace
-
 extern "C" {
 
 // The refusals of the plant parameters, for the entry points that take them (`who` leads the message).
-__attribute__((visibility("hidden"))) int admpc_plant_params_check(const char* who, const AdmpcPlantParams* plant)
+int admpc_plant_params_check(const char* who, const AdmpcPlantParams* plant)
 {
     char msg[160];
     const char* what = nullptr;
@@ -154,9 +133,9 @@ __attribute__((visibility("hidden"))) int admpc_plant_params_check(const char* w
 
 // One launch of admpc_plant_kernel for checked arguments, B > 0, on the model's device (the caller holds it).  st: the seven pose
 // arrays; err .. counts null for a plant-only step; traj_pre / traj_post null or [7][B].
-__attribute__((visibility("hidden"))) int admpc_plant_launch(const AdmpcSolver* model, const AdmpcPlantParams* plant, int B,
-        const float* ack, const int32_t* mode, double* const* st, const double* err, const int32_t* status, const int32_t* valid,
-        double* tally, int32_t* counts, double* traj_pre, double* traj_post, void* stream)
+int admpc_plant_launch(const AdmpcSolver* model, const AdmpcPlantParams* plant, int B, const float* ack, const int32_t* mode,
+                       double* const* st, const double* err, const int32_t* status, const int32_t* valid, double* tally,
+                       int32_t* counts, double* traj_pre, double* traj_post, void* stream)
 {
     const AdmpcConfig* cfg = admpc_solver_config(model, nullptr);
     PlantArgs a;

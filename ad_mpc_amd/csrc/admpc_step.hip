@@ -17,28 +17,15 @@
 //
 // The assembly computes bit for bit what the host functions of ad_mpc_amd/host.py compute (same operations, same order, no
 // contraction); the command kernel's distance tests sum in the order of a wave reduction (numpy's own sum is pairwise).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include <stdio.h>
 #include <math.h>
-#include "../../include/admpc.h"
-#include "../../include/admpc_fleet.h"
-#include "../../include/admpc_lane.h"
-#include "../../include/admpc_plant.h"
+#include "admpc_host.h"
 
 #define NX ADMPC_NX
 #define NU ADMPC_NU
 #define NY ADMPC_NY
 #define WAVE 64
 #define STEP_MAX_H WAVE     // admpc_waypoints_batch, and the command kernel: one lane per slot of the horizon
-
-extern "C" int admpc_set_error(int code, const char* msg);                                  // admpc_kernels.hip
-extern "C" const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);      // admpc_kernels.hip
-extern "C" int admpc_path_bank_horizon(const AdmpcPathBank* bank, int* device);             // admpc_kernels.hip
-extern "C" int admpc_lane_params_check(const char* who, const AdmpcLaneParams* lane, const int32_t* lane_idx);   // admpc_lane.hip
-extern "C" int admpc_plant_params_check(const char* who, const AdmpcPlantParams* plant);                         // admpc_plant.hip
-extern "C" int admpc_plant_launch(const AdmpcSolver* model, const AdmpcPlantParams* plant, int B, const float* ack, const int32_t* mode,
-                                  double* const* st, const double* err, const int32_t* status, const int32_t* valid, double* tally,
-                                  int32_t* counts, double* traj_pre, double* traj_post, void* stream);             // admpc_plant.hip
 
 namespace {
 
@@ -115,7 +102,7 @@ __device__ int path_close(double d, int lane, int n)
 //              an MPC command needs safe_count >= threshold and a healthy prediction, with the steering command
 //              clip(clip(rate) * 0.1 + measured steering) (:206-223); otherwise the auxiliary controller's brake record (:455-476)
 //   cost       (the step against a bank of paths only; nullptr otherwise) +inf where the solve failed or the prediction is not valid
-// One text for both kernels below: vehicle b, called by every lane of the block's single wave.
+// Vehicle b, called by every lane of the block's single wave.
 __device__ __forceinline__ void step_command_one(int N, int b, const double* __restrict__ ref, const double* __restrict__ xbar,
                                           const double* __restrict__ ubar, const int32_t* __restrict__ status, const double* __restrict__ steer,
                                           int32_t* __restrict__ safe_count, double* __restrict__ prev_u, int32_t* __restrict__ has_valid,
@@ -163,19 +150,8 @@ __device__ __forceinline__ void step_command_one(int N, int b, const double* __r
     }
 }
 
+// cost [B]: null, or (the steps against a bank) the objective of each solve, masked in place
 __global__ __launch_bounds__(WAVE) void admpc_step_command_kernel(int N, int B, const double* __restrict__ ref, const double* __restrict__ xbar,
-                                          const double* __restrict__ ubar, const int32_t* __restrict__ status, const double* __restrict__ steer,
-                                          int32_t* __restrict__ safe_count, double* __restrict__ prev_u, int32_t* __restrict__ has_valid,
-                                          int threshold, double rate_min, double rate_max, double steer_min, double steer_max,
-                                          float* __restrict__ ack, int32_t* __restrict__ mode, int32_t* __restrict__ valid)
-{
-    for (int b = blockIdx.x; b < B; b += gridDim.x) {
-        step_command_one(N, b, ref, xbar, ubar, status, steer, safe_count, prev_u, has_valid, threshold, rate_min, rate_max, steer_min, steer_max,
-                         ack, mode, valid, nullptr);
-    }
-}
-// the same behind admpc_control_step_bank_batch: cost [B] holds the objective of each solve and is masked in place
-__global__ __launch_bounds__(WAVE) void admpc_step_command_cost_kernel(int N, int B, const double* __restrict__ ref, const double* __restrict__ xbar,
                                           const double* __restrict__ ubar, const int32_t* __restrict__ status, const double* __restrict__ steer,
                                           int32_t* __restrict__ safe_count, double* __restrict__ prev_u, int32_t* __restrict__ has_valid,
                                           int threshold, double rate_min, double rate_max, double steer_min, double steer_max,
@@ -208,15 +184,78 @@ struct StepWork {
     }
 };
 
-struct DeviceGuard {
-    int prev; bool switched; bool good;
-    explicit DeviceGuard(int dev) : prev(-1), switched(false), good(true) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { good = hipSetDevice(dev) == hipSuccess; switched = good; }
-    }
-    ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-    bool ok() const { return good; }
-};
+const char STEP[] = "admpc_control_step_batch", BANK[] = "admpc_control_step_bank_batch", LANE[] = "admpc_control_step_lane_batch",
+           ROLLOUT[] = "admpc_rollout_lane_batch";
+
+int refuse(const char* who, const char* what)
+{
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return admpc_set_error(ADMPC_EINVAL, msg);
+}
+
+// The refusals the three steps share, in the order every one of them makes them: check_solver, then those of the step's own reference
+// source, then check_params; an empty batch returns there, and the others need arrays_set.
+int check_solver(const char* who, const AdmpcSolver* s, const AdmpcStepParams* prm, int B, const AdmpcConfig** cfg, int* device)
+{
+    if (!s || !prm || B < 0) return refuse(who, "null solver / params or negative batch");
+    *cfg = admpc_solver_config(s, device);
+    if ((*cfg)->N < 3 || (*cfg)->N > STEP_MAX_H) return refuse(who, "the solver's N must be in [3, 64] (the waypoint kernel's horizon)");
+    return ADMPC_OK;
+}
+
+int check_params(const char* who, const AdmpcStepParams* prm)
+{
+    if (prm->threshold < 0 || !(prm->blend_max > prm->blend_min)) return refuse(who, "bad step parameters");
+    return ADMPC_OK;
+}
+
+// all of them for a step whose reference source is a bank
+int check_bank_step(const char* who, const AdmpcSolver* s, const AdmpcPathBank* bank, const AdmpcStepParams* prm, int B, const AdmpcConfig** cfg,
+                    int* device)
+{
+    int bank_device = 0;
+    const int rc = check_solver(who, s, prm, B, cfg, device);
+    if (rc) return rc;
+    if (!bank) return refuse(who, "the bank is not set");
+    if (admpc_path_bank_horizon(bank, &bank_device) != (*cfg)->N) return refuse(who, "the bank's horizon H must equal the solver's N");
+    if (bank_device != *device) return refuse(who, "the bank lives on another device than the solver");
+    return check_params(who, prm);
+}
+
+// st: the seven pose arrays, px .. steer
+bool arrays_set(const double* const* st, const StepOut& o)
+{
+    for (int i = 0; i < NX; ++i) if (!st[i]) return false;
+    return o.xbar && o.ubar && o.safe_count && o.prev_u && o.has_valid && o.work && o.ack && o.mode && o.valid && o.status;
+}
+
+// The chain behind the reference generator, which has left ref [B][6][N] in the workspace: assembly, solve, command.  For checked
+// arguments and B > 0, on the solver's device (the caller holds it).
+int step_tail(AdmpcSolver* s, const AdmpcConfig* cfg, const AdmpcStepParams* prm, int B, const StepWork& w, const double* const* st,
+              const StepOut& o, void* stream)
+{
+    const int N = cfg->N;
+    const double* steer = st[6];
+    const long nP = (long)B * (N + 1);
+    hipLaunchKernelGGL(admpc_step_assemble_kernel, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, (hipStream_t)stream, N, B, (const double*)w.ref,
+                       st[0], st[1], st[2], st[3], st[4], st[5], steer, prm->blend_min, prm->blend_max, w.x0, w.yref, w.yref_e, w.p);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_assemble_kernel: launch failed");
+    const int rc = admpc_solve_batch(s, B, w.x0, w.yref, w.yref_e, w.p, o.xbar, o.ubar, o.cost, o.status, nullptr, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(admpc_step_command_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE), 0, (hipStream_t)stream, N, B, (const double*)w.ref,
+                       (const double*)o.xbar, (const double*)o.ubar, (const int32_t*)o.status, steer, o.safe_count, o.prev_u, o.has_valid,
+                       prm->threshold, cfg->lbu[1], cfg->ubu[1], cfg->lbx_delta, cfg->ubx_delta, o.ack, o.mode, o.valid, o.cost);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_command_kernel: launch failed");
+    return ADMPC_OK;
+}
+
+// the speed clamp on each vehicle's window, behind the waypoint call of the steps that have no lane to clamp
+int clamp_window(const AdmpcStepParams* prm, int device, int N, int B, const double* const* st, const StepWork& w, void* stream)
+{
+    if (!prm->resample) return ADMPC_OK;
+    return admpc_resample_vel_batch(device, B, N, 6 * N, st[3], st[4], prm->acc_max, prm->resample_dt, w.ref + 3 * N, stream);
+}
 
 }  // namespace
 
@@ -235,92 +274,54 @@ int admpc_control_step_batch(AdmpcSolver* s, const AdmpcPath* path, const AdmpcS
                              double* xbar, double* ubar, int32_t* safe_count, double* prev_u, int32_t* has_valid,
                              void* work, float* ack, int32_t* mode, int32_t* valid, int32_t* status, void* stream)
 {
-    if (!s || !prm || B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_batch: null solver / params or negative batch");
+    const double* st[NX] = { px, py, yaw, vx, vy, yaw_rate, steer };
+    const StepOut o = { xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, nullptr };
+    const AdmpcConfig* cfg = nullptr;
     int device = 0;
-    const AdmpcConfig* cfg = admpc_solver_config(s, &device);
+    int rc = check_solver(STEP, s, prm, B, &cfg, &device);
+    if (rc) return rc;
     const int N = cfg->N;
-    if (N < 3 || N > STEP_MAX_H) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_batch: the solver's N must be in [3, 64] (the waypoint kernel's horizon)");
     if (!path || path->M < 2 || !path->vel || !path->x || !path->y || !path->psi || !path->psi_unwrapped || !path->cdist || !path->curv)
-        return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_batch: the path is not set");
-    if (path->H != N) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_batch: the path horizon H must equal the solver's N");
-    if (!(path->dt > 0)) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_batch: the path needs dt > 0");
-    if (prm->threshold < 0 || !(prm->blend_max > prm->blend_min)) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_batch: bad step parameters");
-    if (B == 0) return ADMPC_OK;
-    if (!px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !xbar || !ubar || !safe_count || !prev_u || !has_valid || !work ||
-        !ack || !mode || !valid || !status)
-        return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_batch: null array argument");
+        return refuse(STEP, "the path is not set");
+    if (path->H != N) return refuse(STEP, "the path horizon H must equal the solver's N");
+    if (!(path->dt > 0)) return refuse(STEP, "the path needs dt > 0");
+    rc = check_params(STEP, prm);
+    if (rc || B == 0) return rc;
+    if (!arrays_set(st, o)) return refuse(STEP, "null array argument");
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    StepWork w(work, N, B);
-    int rc = admpc_waypoints_batch(device, path->M, N, path->dt, B, path->vel, path->x, path->y, path->psi, path->psi_unwrapped,
-                                   path->cdist, path->curv, px, py, yaw, w.ref, w.err, w.stop, stream);
-    if (rc) return rc;
-    if (prm->resample) {
-        rc = admpc_resample_vel_batch(device, B, N, 6 * N, vx, vy, prm->acc_max, prm->resample_dt, w.ref + 3 * N, stream);
-        if (rc) return rc;
-    }
-    const long nP = (long)B * (N + 1);
-    hipLaunchKernelGGL(admpc_step_assemble_kernel, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, st, N, B, (const double*)w.ref,
-                       px, py, yaw, vx, vy, yaw_rate, steer, prm->blend_min, prm->blend_max, w.x0, w.yref, w.yref_e, w.p);
-    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_assemble_kernel: launch failed");
-    rc = admpc_solve_batch(s, B, w.x0, w.yref, w.yref_e, w.p, xbar, ubar, nullptr, status, nullptr, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(admpc_step_command_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE), 0, st, N, B, (const double*)w.ref, (const double*)xbar,
-                       (const double*)ubar, (const int32_t*)status, steer, safe_count, prev_u, has_valid, prm->threshold,
-                       cfg->lbu[1], cfg->ubu[1], cfg->lbx_delta, cfg->ubx_delta, ack, mode, valid);
-    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_command_kernel: launch failed");
-    return ADMPC_OK;
+    const StepWork w(work, N, B);
+    rc = admpc_waypoints_batch(device, path->M, N, path->dt, B, path->vel, path->x, path->y, path->psi, path->psi_unwrapped,
+                               path->cdist, path->curv, px, py, yaw, w.ref, w.err, w.stop, stream);
+    if (!rc) rc = clamp_window(prm, device, N, B, st, w, stream);
+    return rc ? rc : step_tail(s, cfg, prm, B, w, st, o, stream);
 }
 
-// admpc_control_step_batch with a path per vehicle and the objective of each solve (include/admpc_fleet.h).  The chain is the one above,
-// launch for launch (tests/batch_regimes.py mirrors the lines of admpc_control_step_batch, which therefore keeps its own copy of it); the
-// differences are the waypoint call, `cost` handed to the solve, and the command kernel that masks it.
+// admpc_control_step_batch with a path per vehicle and the objective of each solve (include/admpc_fleet.h): the differences are the
+// waypoint call and `cost`, which the solve fills and the command kernel masks.
 int admpc_control_step_bank_batch(AdmpcSolver* s, const AdmpcPathBank* bank, const AdmpcStepParams* prm, int B, const int32_t* path_of,
                                   const double* px, const double* py, const double* yaw, const double* vx, const double* vy,
                                   const double* yaw_rate, const double* steer,
                                   double* xbar, double* ubar, int32_t* safe_count, double* prev_u, int32_t* has_valid,
                                   void* work, float* ack, int32_t* mode, int32_t* valid, int32_t* status, double* cost, void* stream)
 {
-    if (!s || !prm || B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: null solver / params or negative batch");
-    int device = 0, bank_device = 0;
-    const AdmpcConfig* cfg = admpc_solver_config(s, &device);
-    const int N = cfg->N;
-    if (N < 3 || N > STEP_MAX_H) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: the solver's N must be in [3, 64] (the waypoint kernel's horizon)");
-    if (!bank) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: the bank is not set");
-    if (admpc_path_bank_horizon(bank, &bank_device) != N) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: the bank's horizon H must equal the solver's N");
-    if (bank_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: the bank lives on another device than the solver");
-    if (prm->threshold < 0 || !(prm->blend_max > prm->blend_min)) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: bad step parameters");
-    if (B == 0) return ADMPC_OK;
-    if (!path_of || !px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !xbar || !ubar || !safe_count || !prev_u || !has_valid || !work ||
-        !ack || !mode || !valid || !status)
-        return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_bank_batch: null array argument");
+    const double* st[NX] = { px, py, yaw, vx, vy, yaw_rate, steer };
+    const StepOut o = { xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost };
+    const AdmpcConfig* cfg = nullptr;
+    int device = 0;
+    int rc = check_bank_step(BANK, s, bank, prm, B, &cfg, &device);
+    if (rc || B == 0) return rc;
+    if (!path_of || !arrays_set(st, o)) return refuse(BANK, "null array argument");
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    StepWork w(work, N, B);
-    int rc = admpc_waypoints_bank_batch(bank, B, path_of, px, py, yaw, w.ref, w.err, w.stop, stream);
-    if (rc) return rc;
-    if (prm->resample) {
-        rc = admpc_resample_vel_batch(device, B, N, 6 * N, vx, vy, prm->acc_max, prm->resample_dt, w.ref + 3 * N, stream);
-        if (rc) return rc;
-    }
-    const long nP = (long)B * (N + 1);
-    hipLaunchKernelGGL(admpc_step_assemble_kernel, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, st, N, B, (const double*)w.ref,
-                       px, py, yaw, vx, vy, yaw_rate, steer, prm->blend_min, prm->blend_max, w.x0, w.yref, w.yref_e, w.p);
-    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_assemble_kernel: launch failed");
-    rc = admpc_solve_batch(s, B, w.x0, w.yref, w.yref_e, w.p, xbar, ubar, cost, status, nullptr, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(admpc_step_command_cost_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE), 0, st, N, B, (const double*)w.ref, (const double*)xbar,
-                       (const double*)ubar, (const int32_t*)status, steer, safe_count, prev_u, has_valid, prm->threshold,
-                       cfg->lbu[1], cfg->ubu[1], cfg->lbx_delta, cfg->ubx_delta, ack, mode, valid, cost);
-    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_command_cost_kernel: launch failed");
-    return ADMPC_OK;
+    const StepWork w(work, cfg->N, B);
+    rc = admpc_waypoints_bank_batch(bank, B, path_of, px, py, yaw, w.ref, w.err, w.stop, stream);
+    if (!rc) rc = clamp_window(prm, device, cfg->N, B, st, w, stream);
+    return rc ? rc : step_tail(s, cfg, prm, B, w, st, o, stream);
 }
 
 // admpc_control_step_bank_batch along a route (include/admpc_lane.h): the lane generator of admpc_lane.hip cuts, clamps and tabulates a
-// local lane per vehicle and lays the window on it, in place of the waypoint call and of the clamp on the window behind it; from the
-// assembly on, the chain is the bank step's, launch for launch.
+// local lane per vehicle and lays the window on it, in place of the waypoint call and of the clamp on the window behind it.
 int admpc_control_step_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, const AdmpcLaneParams* lane, const AdmpcStepParams* prm, int B,
                                   const int32_t* path_of, int32_t* lane_idx,
                                   const double* px, const double* py, const double* yaw, const double* vx, const double* vy,
@@ -328,44 +329,59 @@ int admpc_control_step_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, con
                                   double* xbar, double* ubar, int32_t* safe_count, double* prev_u, int32_t* has_valid,
                                   void* work, float* ack, int32_t* mode, int32_t* valid, int32_t* status, double* cost, void* stream)
 {
-    int rc = admpc_lane_params_check("admpc_control_step_lane_batch", lane, lane_idx);
-    if (rc) return rc;
-    if (!s || !prm || B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: null solver / params or negative batch");
-    int device = 0, bank_device = 0;
-    const AdmpcConfig* cfg = admpc_solver_config(s, &device);
-    const int N = cfg->N;
-    if (N < 3 || N > STEP_MAX_H) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: the solver's N must be in [3, 64] (the waypoint kernel's horizon)");
-    if (!bank) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: the bank is not set");
-    if (admpc_path_bank_horizon(bank, &bank_device) != N) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: the bank's horizon H must equal the solver's N");
-    if (bank_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: the bank lives on another device than the solver");
-    if (prm->threshold < 0 || !(prm->blend_max > prm->blend_min)) return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: bad step parameters");
-    if (B == 0) return ADMPC_OK;
-    if (!path_of || !px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !xbar || !ubar || !safe_count || !prev_u || !has_valid || !work ||
-        !ack || !mode || !valid || !status)
-        return admpc_set_error(ADMPC_EINVAL, "admpc_control_step_lane_batch: null array argument");
+    const double* st[NX] = { px, py, yaw, vx, vy, yaw_rate, steer };
+    const StepOut o = { xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost };
+    const AdmpcConfig* cfg = nullptr;
+    int device = 0;
+    int rc = admpc_lane_params_check(LANE, lane, lane_idx);
+    if (!rc) rc = check_bank_step(LANE, s, bank, prm, B, &cfg, &device);
+    if (rc || B == 0) return rc;
+    if (!path_of || !arrays_set(st, o)) return refuse(LANE, "null array argument");
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    StepWork w(work, N, B);
+    const StepWork w(work, cfg->N, B);
     rc = admpc_waypoints_lane_batch(bank, lane, B, path_of, lane_idx, px, py, yaw, vx, vy, prm->resample, prm->acc_max, prm->resample_dt,
                                     w.ref, w.err, w.stop, stream);
-    if (rc) return rc;
-    const long nP = (long)B * (N + 1);
-    hipLaunchKernelGGL(admpc_step_assemble_kernel, dim3((unsigned)((nP + 255) / 256)), dim3(256), 0, st, N, B, (const double*)w.ref,
-                       px, py, yaw, vx, vy, yaw_rate, steer, prm->blend_min, prm->blend_max, w.x0, w.yref, w.yref_e, w.p);
-    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_assemble_kernel: launch failed");
-    rc = admpc_solve_batch(s, B, w.x0, w.yref, w.yref_e, w.p, xbar, ubar, cost, status, nullptr, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(admpc_step_command_cost_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE), 0, st, N, B, (const double*)w.ref, (const double*)xbar,
-                       (const double*)ubar, (const int32_t*)status, steer, safe_count, prev_u, has_valid, prm->threshold,
-                       cfg->lbu[1], cfg->ubu[1], cfg->lbx_delta, cfg->ubx_delta, ack, mode, valid, cost);
-    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_step_command_cost_kernel: launch failed");
+    return rc ? rc : step_tail(s, cfg, prm, B, w, st, o, stream);
+}
+
+// The refusals of a rollout before those of its arrays: its own of the lane and plant parameters, then the lane step's, under that step's name.
+int admpc_rollout_check_step(const RolloutArgs& a)
+{
+    const AdmpcConfig* cfg = nullptr;
+    int device = 0;
+    int rc = admpc_lane_params_check(ROLLOUT, a.lane, a.lane_idx);
+    if (!rc) rc = admpc_plant_params_check(ROLLOUT, a.plant);
+    return rc ? rc : check_bank_step(LANE, a.s, a.bank, a.prm, a.B, &cfg, &device);
+}
+
+// Those behind its arrays, for arguments that have passed admpc_rollout_check_step.
+int admpc_rollout_check_run(const RolloutArgs& a, int T)
+{
+    if (T < 0 || T > 4096) return refuse(ROLLOUT, "T must be in [0, 4096]");
+    int device = 0, plant_device = 0;
+    (void)admpc_solver_config(a.s, &device);
+    (void)admpc_solver_config(a.plant_model ? a.plant_model : a.s, &plant_device);
+    if (plant_device != device) return refuse(ROLLOUT, "the plant model lives on another device than the solver");
     return ADMPC_OK;
 }
 
-// T closed-loop steps along a route (include/admpc_plant.h): admpc_control_step_lane_batch above, called as it stands, and behind each call
-// one launch of admpc_plant_kernel (admpc_plant.hip) that moves the vehicles under the record just issued and tallies the tracking errors
-// the step's generator left in the workspace.  Everything is enqueued on `stream`; nothing waits for the device.
+// One closed-loop period for checked arguments, B > 0, on the solver's device (the caller holds it): the lane step's chain, and behind
+// it one launch of admpc_plant_kernel (admpc_plant.hip) that moves the vehicles under the record just issued and tallies the tracking
+// errors the step's generator left in the workspace.  traj_pre / traj_post: null or [7][B], the states before and after the period.
+int admpc_rollout_enqueue(const RolloutArgs& a, double* traj_pre, double* traj_post, void* stream)
+{
+    const AdmpcConfig* cfg = admpc_solver_config(a.s, nullptr);
+    const StepWork w(a.out.work, cfg->N, a.B);
+    int rc = admpc_waypoints_lane_batch(a.bank, a.lane, a.B, a.path_of, a.lane_idx, a.st[0], a.st[1], a.st[2], a.st[3], a.st[4], a.prm->resample,
+                                        a.prm->acc_max, a.prm->resample_dt, w.ref, w.err, w.stop, stream);
+    if (!rc) rc = step_tail(a.s, cfg, a.prm, a.B, w, a.st, a.out, stream);
+    if (rc) return rc;
+    return admpc_plant_launch(a.plant_model ? a.plant_model : a.s, a.plant, a.B, a.out.ack, a.out.mode, a.st, w.err, a.out.status, a.out.valid,
+                              a.tally, a.counts, traj_pre, traj_post, stream);
+}
+
+// T closed-loop steps along a route (include/admpc_plant.h).  Everything is enqueued on `stream`; nothing waits for the device.
 int admpc_rollout_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, const AdmpcLaneParams* lane, const AdmpcStepParams* prm,
                              const AdmpcSolver* plant_model, const AdmpcPlantParams* plant, int B, int T,
                              const int32_t* path_of, int32_t* lane_idx,
@@ -374,40 +390,23 @@ int admpc_rollout_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, const Ad
                              float* ack, int32_t* mode, int32_t* valid, int32_t* status, double* cost,
                              double* tally, int32_t* counts, double* traj, void* stream)
 {
-    int rc = admpc_lane_params_check("admpc_rollout_lane_batch", lane, lane_idx);
+    const RolloutArgs a = { s, bank, lane, prm, plant_model, plant, B, path_of, lane_idx, { px, py, yaw, vx, vy, yaw_rate, steer },
+                            { xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost }, tally, counts };
+    int rc = admpc_rollout_check_step(a);
     if (rc) return rc;
-    rc = admpc_plant_params_check("admpc_rollout_lane_batch", plant);
-    if (rc) return rc;
-    // the lane step's own refusals, by the lane step: an empty batch passes every check but the one of its arrays and enqueues nothing
-    rc = admpc_control_step_lane_batch(s, bank, lane, prm, B < 0 ? B : 0, path_of, lane_idx, px, py, yaw, vx, vy, yaw_rate, steer, xbar, ubar,
-                                       safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost, stream);
-    if (rc) return rc;
-    if (B > 0 && (!path_of || !px || !py || !yaw || !vx || !vy || !yaw_rate || !steer || !xbar || !ubar || !safe_count || !prev_u || !has_valid ||
-                  !work || !ack || !mode || !valid || !status))
-        return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_lane_batch: null array argument");
-    if (T < 0 || T > 4096) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_lane_batch: T must be in [0, 4096]");
-    int device = 0, plant_device = 0;
-    const int N = admpc_solver_config(s, &device)->N;
-    const AdmpcSolver* pm = plant_model ? plant_model : s;
-    (void)admpc_solver_config(pm, &plant_device);
-    if (plant_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_lane_batch: the plant model lives on another device than the solver");
-    if (B == 0 || T == 0) return ADMPC_OK;
-    if (!tally || !counts) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_lane_batch: null tally or counts");
+    if (B > 0 && (!path_of || !arrays_set(a.st, a.out))) return refuse(ROLLOUT, "null array argument");
+    rc = admpc_rollout_check_run(a, T);
+    if (rc || B == 0 || T == 0) return rc;
+    if (!tally || !counts) return refuse(ROLLOUT, "null tally or counts");
+    int device = 0;
+    (void)admpc_solver_config(s, &device);
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    StepWork w(work, N, B);
-    double* st[NX] = { px, py, yaw, vx, vy, yaw_rate, steer };
     const size_t slot = (size_t)NX * B;
-    for (int t = 0; t < T; ++t) {
-        rc = admpc_control_step_lane_batch(s, bank, lane, prm, B, path_of, lane_idx, px, py, yaw, vx, vy, yaw_rate, steer, xbar, ubar,
-                                           safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost, stream);
-        if (rc) return rc;
-        // slot 0 is written by the first launch; every launch writes the state it leaves into the next slot
-        rc = admpc_plant_launch(pm, plant, B, ack, mode, st, w.err, status, valid, tally, counts, (traj && t == 0) ? traj : nullptr,
-                                traj ? traj + (t + 1) * slot : nullptr, stream);
-        if (rc) return rc;
-    }
-    return ADMPC_OK;
+    // slot 0 is written by the first launch; every launch writes the state it leaves into the next slot
+    for (int t = 0; t < T && !rc; ++t)
+        rc = admpc_rollout_enqueue(a, (traj && t == 0) ? traj : nullptr, traj ? traj + (t + 1) * slot : nullptr, stream);
+    return rc;
 }
 
 }  // extern "C"

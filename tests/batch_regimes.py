@@ -39,9 +39,9 @@ LAUNCH_LINES = (
     ("admpc_rowqp.hip", "admpc_rowqp_plan", "if (per_cu > 4) per_cu = 4;"),
     ("admpc_kernels.hip", "rowqp_split", "return (s->split_mode == 1 || nquads > grid) ? s->d_split : nullptr;"),
     # appended, never inserted: the position of an entry is part of its test's id
-    ("admpc_step.hip", "admpc_control_step_batch", "hipLaunchKernelGGL(admpc_step_command_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE)"),
+    ("admpc_step.hip", "step_tail", "hipLaunchKernelGGL(admpc_step_command_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE)"),
     ("admpc_step.hip", "admpc_step_command_kernel", "for (int b = blockIdx.x; b < B; b += gridDim.x) {"),
-    ("admpc_step.hip", "admpc_control_step_batch", "const long nP = (long)B * (N + 1);"),
+    ("admpc_step.hip", "step_tail", "const long nP = (long)B * (N + 1);"),
 )
 
 

@@ -1,4 +1,4 @@
-"""The C-ABI library loads on a machine without a GPU and exports every symbol include/admpc.h declares;
+"""The C-ABI library loads on a machine without a GPU and exports every symbol the headers under include/ declare;
 its host-side entry points agree with the Python mirror.  No compute call is made here."""
 import ctypes as C
 import os
@@ -32,6 +32,13 @@ def test_every_declared_symbol_is_exported(lib):
     assert qdecl == set(_lib.QUAD_EXPORTS), qdecl ^ set(_lib.QUAD_EXPORTS)
     for name in qdecl:
         assert getattr(lib, name) is not None
+    for hname, table in (("admpc_fleet.h", _lib.FLEET_EXPORTS), ("admpc_lane.h", _lib.LANE_EXPORTS), ("admpc_plant.h", _lib.PLANT_EXPORTS),
+                         ("admpc_learn.h", _lib.LEARN_EXPORTS), ("admpc_hyper.h", _lib.HYPER_EXPORTS)):
+        h = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", hname)).read(), flags=re.S)
+        decl = set(re.findall(r"\b(admpc_[a-z0-9_]+)\s*\(", h))
+        assert decl == set(table), (hname, decl ^ set(table))
+        for name in decl:
+            assert getattr(lib, name) is not None
 
 
 def test_quad_default_config_matches_python_mirror(lib):
