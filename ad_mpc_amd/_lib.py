@@ -7,12 +7,12 @@ import ctypes as C
 import os
 
 from .config import AdmpcConfig, AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
-from .quad_config import AdmpcQuadConfig
+from .quad_config import AdmpcQuadConfig, AdmpcQuadPlantParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libadmpc.so")
 
-# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h, include/admpc_lane.h, include/admpc_plant.h, include/admpc_learn.h and include/admpc_hyper.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
+# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h, include/admpc_lane.h, include/admpc_plant.h, include/admpc_learn.h, include/admpc_hyper.h and include/admpc_quad_fleet.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
 # _f32 entries), ip: to ints, vp: opaque (handle, stream, communicator) -- device pointers travel as integers, so all three are c_void_p.
 vp = dp = ip = C.c_void_p
 I, D, S = C.c_int, C.c_double, C.c_char_p
@@ -88,6 +88,16 @@ _HYPER = {      # include/admpc_hyper.h: the search of a regressor's hyperparame
     "admpc_gp_refit": (I, [I, op, I, dp, dp, vp, ip, vp]),
 }
 HYPER_EXPORTS = tuple(_HYPER)
+pp = C.POINTER(AdmpcQuadPlantParams)
+_QUAD_FLEET = {     # include/admpc_quad_fleet.h: the quadrotor's plant step, trajectory bank, reference window and closed-loop rollout
+    "admpc_quad_plant_step_batch": (I, [pp, I, I, dp, C.c_int64, dp, vp]),
+    "admpc_quad_traj_bank_create": (I, [I, I, fp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), hp]),
+    "admpc_quad_traj_bank_destroy": (None, [vp]),
+    "admpc_quad_ref_chunk_batch": (I, [vp, I, I, I, ip, ip, dp, dp, dp, vp]),
+    "admpc_quad_rollout_batch": (I, [vp, vp, pp, I, I, I, ip, ip] + [dp] * 6 + [ip, ip, dp, ip, dp, dp, vp]),
+    "admpc_quad_solver_info": (I, [vp, fp, fp, fp]),
+}
+QUAD_FLEET_EXPORTS = tuple(_QUAD_FLEET)
 
 _lib = None
 
@@ -97,7 +107,7 @@ class AdmpcError(RuntimeError):
 
 
 def load():
-    """dlopen libadmpc.so and declare the prototypes of the seven headers under include/ (no GPU needed for this)."""
+    """dlopen libadmpc.so and declare the prototypes of the eight headers under include/ (no GPU needed for this)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -105,7 +115,7 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT, **_LEARN, **_HYPER}.items():
+    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT, **_LEARN, **_HYPER, **_QUAD_FLEET}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

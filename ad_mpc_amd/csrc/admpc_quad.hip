@@ -21,6 +21,7 @@
 #include <type_traits>
 #include "../../include/admpc.h"
 #include "../../include/admpc_quad.h"
+#include "../../include/admpc_quad_fleet.h"      // admpc_quad_solver_info
 
 extern "C" int admpc_set_error(int code, const char* msg);          // admpc_kernels.hip: thread-local message behind admpc_last_error()
 
@@ -1289,6 +1290,16 @@ void admpc_quad_destroy(AdmpcQuadSolver* s)
     if (s->d_fst) (void)hipFree(s->d_fst);
     if (s->d_st) (void)hipFree(s->d_st);
     delete s;
+}
+
+// include/admpc_quad_fleet.h: what the rollout needs of a handle
+int admpc_quad_solver_info(const AdmpcQuadSolver* s, int* device, int* N, int* sqp_iters)
+{
+    if (!s) return admpc_set_error(ADMPC_EINVAL, "null solver");
+    if (device) *device = s->device;
+    if (N) *N = s->cfg.N;
+    if (sqp_iters) *sqp_iters = s->cfg.sqp_iters;
+    return ADMPC_OK;
 }
 
 static int quad_solve(AdmpcQuadSolver* s, int B, const double* x0, const double* yref, const double* yref_e, const double* gp_state,

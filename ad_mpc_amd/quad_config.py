@@ -1,5 +1,6 @@
 """ctypes mirror of include/admpc_quad.h (AdmpcQuadConfig) and the shipped quadrotor problem
-(acados_models/my_quad_acados_ocp.json, src/quad_mpc/quad_3d.py:40-74)."""
+(acados_models/my_quad_acados_ocp.json, src/quad_mpc/quad_3d.py:40-74); of include/admpc_quad_fleet.h (AdmpcQuadPlantParams), the
+simulator's vehicle (src/quad_mpc/quad_3d.py:22-95)."""
 import ctypes as C
 import math
 
@@ -78,3 +79,82 @@ def tight_quad_ipm(cfg):
 
 def tight_quad_config(*a, **kw):
     return tight_quad_ipm(default_quad_config(*a, **kw))
+
+
+class AdmpcQuadPlantParams(C.Structure):
+    """include/admpc_quad_fleet.h: the SIMULATOR's vehicle (Quadrotor3D), passed by value into the plant kernel."""
+    _fields_ = [
+        ("dt", C.c_double), ("mass", C.c_double), ("J", C.c_double * 3), ("max_thrust", C.c_double),
+        ("x_f", C.c_double * 4), ("y_f", C.c_double * 4), ("z_l_tau", C.c_double * 4), ("g", C.c_double),
+        ("rotor_drag", C.c_double * 3), ("aero_drag", C.c_double), ("payload_mass", C.c_double),
+        ("u_min", C.c_double), ("u_max", C.c_double),
+        ("substeps", C.c_int32), ("drag", C.c_int32),
+    ]
+
+    def copy(self):
+        c = AdmpcQuadPlantParams()
+        C.memmove(C.byref(c), C.byref(self), C.sizeof(self))
+        return c
+
+
+class SimQuad:
+    """The attributes of the reference's ``Quadrotor3D`` (quad_3d.py:22-95) that the plant reads, with its values: the vehicle of
+    ``quad_plant_params(None, ...)`` and of the tests."""
+
+    def __init__(self, drag=False, payload=False):
+        self.max_thrust = 20
+        self.max_input_value, self.min_input_value = 1, 0
+        self.J = np.array([.03, .03, .06])
+        self.mass = 1.0
+        self.length = 0.47 / 2
+        h = np.cos(np.pi / 4) * self.length
+        self.x_f = np.array([h, -h, -h, h])
+        self.y_f = np.array([-h, -h, h, h])
+        self.c = 0.013
+        self.z_l_tau = np.array([-self.c, self.c, -self.c, self.c])
+        self.g = np.array([[0], [0], [9.81]])
+        self.rotor_drag_xy, self.rotor_drag_z = 0.3, 0.0
+        self.aero_drag = 0.08
+        self.drag, self.noisy, self.motor_noise = drag, False, False
+        self.payload_mass = 0.3 * payload
+
+
+def quad_substeps(simulation_dt, control_period):
+    """The sub-steps of one control period as trajectory_test.py:114-119 counts them: ``while t < control_period: t += simulation_dt``
+    in floating point (40 at N = 10, 20 at N = 20, 80 at N = 5 with t_horizon 1 s, over-sampling 5 and simulation_dt 5e-4)."""
+    simulation_dt, control_period = float(simulation_dt), float(control_period)
+    if not (simulation_dt > 0 and math.isfinite(simulation_dt) and math.isfinite(control_period)):
+        raise ValueError("simulation_dt must be positive and finite, control_period finite")
+    t, n = 0.0, 0
+    while t < control_period:
+        t += simulation_dt
+        n += 1
+        if n > 1024:
+            raise ValueError("more than 1024 sub-steps per control period")
+    if n < 1:
+        raise ValueError("control_period must be positive")
+    return n
+
+
+def quad_plant_params(quad, simulation_dt, control_period):
+    """AdmpcQuadPlantParams of a ``Quadrotor3D``-shaped object (None: ``SimQuad()``): mass, J, max_thrust, x_f, y_f, z_l_tau, g (a scalar
+    or the reference's 3 x 1 vector), drag, rotor_drag_xy / rotor_drag_z, aero_drag, payload_mass, min_input_value / max_input_value.
+    The random disturbances of the simulator are not offered: ``noisy`` or ``motor_noise`` set raises NotImplementedError."""
+    if quad is None:
+        quad = SimQuad()
+    if getattr(quad, "noisy", False) or getattr(quad, "motor_noise", False):
+        raise NotImplementedError("the simulator's random disturbances (noisy, motor_noise: np.random per sub-step) are not offered by the plant on the device")
+    p = AdmpcQuadPlantParams()
+    p.dt, p.substeps = float(simulation_dt), quad_substeps(simulation_dt, control_period)
+    p.mass, p.max_thrust = float(quad.mass), float(quad.max_thrust)
+    p.g = float(np.asarray(quad.g, dtype=np.float64).reshape(-1)[-1])
+    for i in range(3):
+        p.J[i] = float(quad.J[i])
+    for i in range(4):
+        p.x_f[i], p.y_f[i], p.z_l_tau[i] = float(quad.x_f[i]), float(quad.y_f[i]), float(quad.z_l_tau[i])
+    p.drag = 1 if getattr(quad, "drag", False) else 0
+    p.rotor_drag[0] = p.rotor_drag[1] = float(getattr(quad, "rotor_drag_xy", 0.0))
+    p.rotor_drag[2] = float(getattr(quad, "rotor_drag_z", 0.0))
+    p.aero_drag, p.payload_mass = float(getattr(quad, "aero_drag", 0.0)), float(getattr(quad, "payload_mass", 0.0))
+    p.u_min, p.u_max = float(getattr(quad, "min_input_value", 0.0)), float(getattr(quad, "max_input_value", 1.0))
+    return p

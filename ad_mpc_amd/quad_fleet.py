@@ -1,0 +1,197 @@
+"""A fleet of quadrotors in closed loop on the device (include/admpc_quad_fleet.h): the loop of the reference's
+``experiments/trajectory_test.py`` -- slide a window over an over-sampled reference trajectory, one RTI step, apply the first input to the
+simplified simulator for ``control_period / simulation_dt`` sub-steps -- for B vehicles, T steps per call, with a tally of the tracking
+error.  Built on ``QuadBatchSolver``; the OCP is shaped as ``Quad3DOptimizer`` shapes it (weight expansion for the quaternion, the
+vehicle's constants, the linear drag, one cluster of residual GPs)."""
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .engine import QuadBatchSolver, _ptr
+from .quad_config import QNX, QNU, QNY, default_quad_config, quad_plant_params, set_quad_gp
+
+QuadRollout = namedtuple("QuadRollout", ("x", "idx", "tally", "counts", "traj", "u"))
+T_MAX = 4096
+
+
+def fleet_quad_config(quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, gp_regressors=None, rdrv_d_mat=None):
+    """The AdmpcQuadConfig ``Quad3DOptimizer`` builds from the same arguments (quad_3d_optimizer.py:29-207), SQP_RTI."""
+    from .quad_3d_optimizer import QuadGPEnsemble
+    if q_cost is None:
+        q_cost = np.array([10, 10, 10, 0.1, 0.1, 0.1, 0.05, 0.05, 0.05, 0.05, 0.05, 0.05])
+    if r_cost is None:
+        r_cost = np.array([0.1, 0.1, 0.1, 0.1])
+    cfg = default_quad_config(N=int(n_nodes), t_horizon=float(t_horizon))
+    q_cost = np.asarray(q_cost, dtype=np.float64)
+    q_diagonal = np.concatenate((q_cost[:3], np.mean(q_cost[3:6])[np.newaxis], q_cost[3:]))       # :140-143
+    for i in range(QNX):
+        cfg.W[i], cfg.We[i] = float(q_diagonal[i]), 0.0
+    for m in range(QNU):
+        cfg.W[QNX + m] = float(np.asarray(r_cost)[m])
+    if quad is not None:
+        cfg.mass, cfg.max_thrust = float(quad.mass), float(quad.max_thrust)
+        for i in range(3):
+            cfg.J[i] = float(quad.J[i])
+        for i in range(4):
+            cfg.x_f[i], cfg.y_f[i], cfg.z_l_tau[i] = float(quad.x_f[i]), float(quad.y_f[i]), float(quad.z_l_tau[i])
+        lo = getattr(quad, "min_u", getattr(quad, "min_input_value", 0.0)); hi = getattr(quad, "max_u", getattr(quad, "max_input_value", 1.0))
+        for m in range(QNU):
+            cfg.lbu[m], cfg.ubu[m] = float(lo), float(hi)
+    if rdrv_d_mat is not None:
+        d = np.asarray(rdrv_d_mat, dtype=np.float64)
+        if d.shape != (3, 3) or np.abs(d - np.diag(np.diag(d))).max() != 0.0:
+            raise ValueError("rdrv_d_mat must be a 3 x 3 diagonal matrix (quad_3d_optimizer.py:364-381)")
+        for i in range(3):
+            cfg.rdrv[i] = float(d[i, i])
+    if gp_regressors is not None:
+        if isinstance(gp_regressors, QuadGPEnsemble):
+            if gp_regressors.n_models > 1:
+                raise NotImplementedError("clustered GP ensembles are not served by the rollout (one handle drives the whole fleet)")
+            gp_regressors = gp_regressors.clusters[0]
+        set_quad_gp(cfg, list(gp_regressors))
+    return cfg
+
+
+class QuadFleet:
+    """B quadrotors, each on one of K reference trajectories.  State on the device: ``x`` [B,13], ``idx`` [B] int32 (the sliding index),
+    ``traj_of`` [B] int32, the persistent never-shifted iterate ``x_opt`` [B,N+1,13] / ``w_opt`` [B,N,4], the window ``yref`` / ``yref_e``,
+    ``cost`` / ``status`` / ``iters`` of the last step, ``tally`` [B,3] (sum |e|, sum |e|^2, max |e|) and ``counts`` [B,3] int32 (steps,
+    steps with status != 0, steps with a replaced activation)."""
+
+    def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
+                 gp_regressors=None, rdrv_d_mat=None, device=0):
+        self.B, self.N, self.over = int(B), int(n_nodes), int(reference_over_sampling)
+        if self.B < 1 or self.over < 1:
+            raise ValueError("QuadFleet: B and reference_over_sampling must be at least 1")
+        self.control_period = float(t_horizon) / (self.N * self.over)                      # trajectory_test.py: t_horizon / (n_mpc_nodes * over)
+        self._plant = quad_plant_params(quad, simulation_dt, self.control_period)          # refuses noisy / motor_noise before a handle exists
+        cfg = fleet_quad_config(quad, t_horizon, n_nodes, q_cost, r_cost, gp_regressors, rdrv_d_mat)
+        self._eng = QuadBatchSolver(cfg, device=device)
+        self.lib, self.device, self.device_index, self.cfg = self._eng.lib, self._eng.device, self._eng.device_index, self._eng.cfg
+        self._bank, self._M = None, None
+        B, N, dev = self.B, self.N, self.device
+        f64 = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+        i32 = lambda *s: torch.zeros(s, dtype=torch.int32, device=dev)
+        self.x, self.x_opt, self.w_opt = f64(B, QNX), f64(B, N + 1, QNX), f64(B, N, QNU)
+        self.yref, self.yref_e = f64(B, N, QNY), f64(B, QNX)
+        self.cost, self.status, self.iters = f64(B), i32(B), i32(B)
+        self.tally, self.counts = f64(B, 3), i32(B, 3)
+        self.traj_of, self.idx = i32(B), i32(B)
+        # one eager solve: the N = 20 handle allocates its slot buffer at its first solve, so a later graph capture of rollout() is legal
+        self.x[:, 3] = 1.0
+        self.yref[:, :, 3] = 1.0; self.yref_e[:, 3] = 1.0
+        self._eng.solve(self.x, self.yref, self.yref_e, f64(B, N + 1, QNX), f64(B, N, QNU))
+        torch.cuda.synchronize(dev)
+
+    # -- lifetime ---------------------------------------------------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_bank", None):
+            self.lib.admpc_quad_traj_bank_destroy(self._bank)
+            self._bank = None
+        if getattr(self, "_eng", None):
+            self._eng.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return self._eng._stream()
+
+    # -- the references ---------------------------------------------------------------------------------------------------------------
+    def set_trajectories(self, trajectories):
+        """[(traj [M,13], u [M,4]), ...]: the over-sampled reference trajectories (one row per control period) and their inputs."""
+        tr = [(np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)) for t, u in trajectories]
+        if not tr:
+            raise ValueError("set_trajectories: at least one trajectory")
+        for t, u in tr:
+            if t.ndim != 2 or t.shape[1] != QNX or u.shape != (t.shape[0], QNU) or t.shape[0] < 1:
+                raise ValueError("set_trajectories: every trajectory is (traj [M,13], u [M,4]) with M >= 1")
+        K = len(tr)
+        M = (C.c_int32 * K)(*[t.shape[0] for t, _ in tr])
+        tp = (C.c_void_p * K)(*[t.ctypes.data for t, _ in tr])
+        up = (C.c_void_p * K)(*[u.ctypes.data for _, u in tr])
+        h = C.c_void_p(0)
+        _lib.check(self.lib.admpc_quad_traj_bank_create(self.device_index, K, M, tp, up, C.byref(h)))
+        if self._bank:
+            torch.cuda.synchronize(self.device)
+            self.lib.admpc_quad_traj_bank_destroy(self._bank)
+        self._bank, self._M, self._traj = h, np.array([t.shape[0] for t, _ in tr]), tr
+
+    def _need_bank(self, who):
+        if not self._bank:
+            raise ValueError("%s: call set_trajectories first" % who)
+
+    def reset(self, traj_of, idx0=0, x0=None):
+        """Vehicle b follows trajectory traj_of[b] from row idx0 (a number or [B]); it starts at x0 [B,13] or, as the reference does, at
+        that row of its trajectory.  The iterate, the tally and the counts are zeroed."""
+        self._need_bank("reset")
+        tk = np.broadcast_to(np.asarray(traj_of, dtype=np.int64), (self.B,))
+        i0 = np.broadcast_to(np.asarray(idx0, dtype=np.int64), (self.B,))
+        if x0 is None:
+            if (tk < 0).any() or (tk >= len(self._M)).any() or (i0 < 0).any() or (i0 >= self._M[tk]).any():
+                raise ValueError("reset: x0 is needed for a vehicle whose traj_of or idx0 is out of range")
+            x0 = np.stack([self._traj[k][0][i] for k, i in zip(tk, i0)])
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        if x0.shape != (self.B, QNX):
+            raise ValueError("reset: x0 must be [B,13]")
+        self.traj_of.copy_(torch.as_tensor(tk.astype(np.int32)))
+        self.idx.copy_(torch.as_tensor(i0.astype(np.int32)))
+        self.x.copy_(torch.as_tensor(x0))
+        for t in (self.x_opt, self.w_opt, self.tally, self.counts, self.cost, self.status, self.iters):
+            t.zero_()
+
+    def ref_chunk(self, pos_ref=None):
+        """The window of every vehicle at its idx into yref / yref_e (admpc_quad_ref_chunk_batch); pos_ref [B,3] if given."""
+        self._need_bank("ref_chunk")
+        if pos_ref is not None:
+            self._eng._chk(pos_ref, (self.B, 3))
+        _lib.check(self.lib.admpc_quad_ref_chunk_batch(self._bank, self.B, self.N, self.over, _ptr(self.traj_of), _ptr(self.idx), _ptr(self.yref),
+                                                       _ptr(self.yref_e), _ptr(pos_ref), self._stream()))
+
+    # -- the plant --------------------------------------------------------------------------------------------------------------------
+    def plant_step(self, u, x=None):
+        """One control period of the simulator under u [B,4] (or any float64 view with rows of 4 and a row stride, such as
+        ``w_opt[:, 0, :]``), in place on x (default: the fleet's state)."""
+        x = self.x if x is None else x
+        self._eng._chk(x, (x.shape[0], QNX))
+        Bx = x.shape[0]
+        if u.dtype != torch.float64 or u.device != self.device or tuple(u.shape) != (Bx, QNU) or u.stride(1) != 1 or (Bx > 1 and u.stride(0) < QNU):
+            raise ValueError("plant_step: u must be float64 [B,4] on the fleet's device with unit inner stride")
+        stride = u.stride(0) if Bx > 1 else QNU
+        _lib.check(self.lib.admpc_quad_plant_step_batch(C.byref(self._plant), self.device_index, Bx, C.c_void_p(u.data_ptr()), stride, _ptr(x),
+                                                        self._stream()))
+
+    # -- the closed loop --------------------------------------------------------------------------------------------------------------
+    def rollout(self, T, record=False):
+        """T closed-loop steps (admpc_quad_rollout_batch): no host synchronisation.  Returns QuadRollout(x, idx, tally, counts, traj, u):
+        the fleet's own tensors, and with record traj [T+1,B,13] (slot t: the state at the start of step t) and u [T,B,4]."""
+        self._need_bank("rollout")
+        T = int(T)
+        if T < 0 or T > T_MAX:
+            raise ValueError("rollout: T must be in [0, %d]" % T_MAX)
+        traj = u = None
+        if record:
+            traj = torch.empty((T + 1, self.B, QNX), dtype=torch.float64, device=self.device)
+            u = torch.empty((T, self.B, QNU), dtype=torch.float64, device=self.device)
+            if T == 0:
+                traj[0].copy_(self.x)
+        _lib.check(self.lib.admpc_quad_rollout_batch(self._eng._h, self._bank, C.byref(self._plant), self.over, self.B, T, _ptr(self.traj_of),
+                                                     _ptr(self.idx), _ptr(self.x), _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.yref),
+                                                     _ptr(self.yref_e), _ptr(self.cost), _ptr(self.status), _ptr(self.iters), _ptr(self.tally),
+                                                     _ptr(self.counts), _ptr(traj), _ptr(u), self._stream()))
+        return QuadRollout(self.x, self.idx, self.tally, self.counts, traj, u)
+
+    def step(self):
+        """One closed-loop step."""
+        return self.rollout(1)
+
+    def tracking_rmse(self):
+        """trajectory_test.py:137's figure per vehicle: the mean of the position error norms over the steps taken (tally[:, 0] / steps);
+        NaN for a vehicle that has taken no step.  A device tensor [B]."""
+        return self.tally[:, 0] / self.counts[:, 0].to(torch.float64)
