@@ -7,12 +7,12 @@ import ctypes as C
 import os
 
 from .config import AdmpcConfig, AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
-from .quad_config import AdmpcQuadConfig, AdmpcQuadPlantParams
+from .quad_config import AdmpcQuadConfig, AdmpcQuadObserveParams, AdmpcQuadPlantParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libadmpc.so")
 
-# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h, include/admpc_lane.h, include/admpc_plant.h, include/admpc_learn.h, include/admpc_hyper.h and include/admpc_quad_fleet.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
+# Every prototype of include/admpc.h, include/admpc_quad.h, include/admpc_fleet.h, include/admpc_lane.h, include/admpc_plant.h, include/admpc_learn.h, include/admpc_hyper.h, include/admpc_quad_fleet.h and include/admpc_quad_learn.h: name -> (restype, argtypes).  dp: device pointer to doubles (floats on the
 # _f32 entries), ip: to ints, vp: opaque (handle, stream, communicator) -- device pointers travel as integers, so all three are c_void_p.
 vp = dp = ip = C.c_void_p
 I, D, S = C.c_int, C.c_double, C.c_char_p
@@ -98,6 +98,15 @@ _QUAD_FLEET = {     # include/admpc_quad_fleet.h: the quadrotor's plant step, tr
     "admpc_quad_solver_info": (I, [vp, fp, fp, fp]),
 }
 QUAD_FLEET_EXPORTS = tuple(_QUAD_FLEET)
+qop = C.POINTER(AdmpcQuadObserveParams)
+_QUAD_LEARN = {     # include/admpc_quad_learn.h: observe -> bin -> fit -> install of a quadrotor handle's body-frame residual GPs
+    "admpc_quad_observe_latch_batch": (I, [I, I, dp, dp, vp]),
+    "admpc_quad_observe_batch": (I, [vp, pp, qop, I, dp, C.c_int64, dp, dp, dp, dp, ip, vp]),
+    "admpc_quad_gp_fit": (I, [I, qop, I, dp, vp, ip, vp]),
+    "admpc_quad_gp_install": (I, [vp, I, vp, ip, vp]),
+    "admpc_quad_rollout_observe_batch": (I, _QUAD_FLEET["admpc_quad_rollout_batch"][1][:-1] + [vp, qop, dp, dp, dp, ip, vp]),
+}
+QUAD_LEARN_EXPORTS = tuple(_QUAD_LEARN)
 
 _lib = None
 
@@ -107,7 +116,7 @@ class AdmpcError(RuntimeError):
 
 
 def load():
-    """dlopen libadmpc.so and declare the prototypes of the eight headers under include/ (no GPU needed for this)."""
+    """dlopen libadmpc.so and declare the prototypes of the nine headers under include/ (no GPU needed for this)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -115,7 +124,7 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT, **_LEARN, **_HYPER, **_QUAD_FLEET}.items():
+    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT, **_LEARN, **_HYPER, **_QUAD_FLEET, **_QUAD_LEARN}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

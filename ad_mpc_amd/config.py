@@ -239,19 +239,21 @@ def tight_config(*a, **kw):
     return tight_ipm(default_config(*a, **kw))
 
 
-def learn_bins(learn):
+def learn_bins(learn, feat_range=(3, 8), out_range=(3, 5), gp_max=GP_MAX):
     """The AdmpcGpBins of FleetController(learn=...): a list of dicts with the keys feat (an index into [x;u] in 3 .. 8, or a list of up
     to 3), out (3 .. 5), lo, hi, bins (one per feature; the product at most GP_MAX_POINTS), length_scale (a scalar or one per feature),
-    sigma_f = 1.0, noise = 1e-6, count_noise = 0.0.  Raises ValueError on bad bins; the library refuses the same."""
+    sigma_f = 1.0, noise = 1e-6, count_noise = 0.0.  Raises ValueError on bad bins; the library refuses the same.  ``feat_range``,
+    ``out_range`` and ``gp_max`` are the car's; quad_config.quad_learn_bins passes the quadrotor's."""
     learn = list(learn)
-    if not 1 <= len(learn) <= GP_MAX:
-        raise ValueError("learn: 1 to %d regressors" % GP_MAX)
-    out = (AdmpcGpBins * GP_MAX)()
+    (f_lo, f_hi), (o_lo, o_hi) = feat_range, out_range
+    if not 1 <= len(learn) <= gp_max:
+        raise ValueError("learn: 1 to %d regressors" % gp_max)
+    out = (AdmpcGpBins * gp_max)()
     for g, d in enumerate(learn):
         feats = [int(f) for f in np.atleast_1d(d["feat"]).reshape(-1)]
         nf = len(feats)
-        if not 1 <= nf <= GP_MAX_FEAT or any(not 3 <= f <= 8 for f in feats) or not 3 <= int(d["out"]) <= 5:
-            raise ValueError("learn[%d]: 1 to 3 features in 3 .. 8, out in 3 .. 5" % g)
+        if not 1 <= nf <= GP_MAX_FEAT or any(not f_lo <= f <= f_hi for f in feats) or not o_lo <= int(d["out"]) <= o_hi:
+            raise ValueError("learn[%d]: 1 to 3 features in %d .. %d, out in %d .. %d" % (g, f_lo, f_hi, o_lo, o_hi))
         vec = lambda k: np.asarray(d[k], dtype=np.float64).reshape(-1)
         lo, hi, nb, ell = vec("lo"), vec("hi"), np.atleast_1d(d["bins"]).reshape(-1), vec("length_scale")
         if ell.size == 1:

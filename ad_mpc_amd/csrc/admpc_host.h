@@ -1,5 +1,5 @@
-// admpc_host.h -- what the host sides of admpc_kernels.hip, admpc_step.hip, admpc_lane.hip, admpc_plant.hip, admpc_learn.hip and
-// admpc_hyper.hip share: the device guard, and one declaration of every hidden function that one of them defines for another.  The
+// admpc_host.h -- what the host sides of admpc_kernels.hip, admpc_step.hip, admpc_lane.hip, admpc_plant.hip, admpc_learn.hip,
+// admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip and admpc_quad_learn.hip share: the device guard, and one declaration of every hidden function that one of them defines for another.  The
 // defining unit includes this header too, so that the compiler holds each definition against its declaration.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,6 +9,9 @@
 #include "../../include/admpc_lane.h"
 #include "../../include/admpc_plant.h"
 #include "../../include/admpc_learn.h"
+#include "../../include/admpc_quad.h"
+#include "../../include/admpc_quad_fleet.h"
+#include "../../include/admpc_quad_learn.h"
 
 // Every entry point runs on the solver's device and restores the caller's current device on return (a host with several GPUs
 // keeps its own current device: torch allocations and default-stream work of the caller are not redirected).
@@ -67,3 +70,8 @@ ADMPC_HIDDEN int admpc_plant_launch(const AdmpcSolver* model, const AdmpcPlantPa
 ADMPC_HIDDEN int admpc_rollout_check_step(const RolloutArgs& a);
 ADMPC_HIDDEN int admpc_rollout_check_run(const RolloutArgs& a, int T);
 ADMPC_HIDDEN int admpc_rollout_enqueue(const RolloutArgs& a, double* traj_pre, double* traj_post, void* stream);
+// admpc_quad.hip: the device copy of a quadrotor handle's problem, which admpc_quad_learn.hip reads (observe) and writes (install), and
+// the n_gp the handle was created with (n_gp may be NULL); next to admpc_quad_solver_info of include/admpc_quad_fleet.h
+ADMPC_HIDDEN AdmpcQuadConfig* admpc_quad_solver_config_device(const AdmpcQuadSolver* s, int* n_gp);
+// admpc_quad_fleet.hip: the refusals of the quadrotor's plant parameters
+ADMPC_HIDDEN int admpc_quad_plant_params_check(const char* who, const AdmpcQuadPlantParams* plant);

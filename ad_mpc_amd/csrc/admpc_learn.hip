@@ -107,56 +107,7 @@ __global__ __launch_bounds__(WAVE) void admpc_observe_kernel(const AdmpcConfig* 
 // grid n_gp * NPT: block (g, bin).  Bin 0 of a regressor also counts what fell outside its box, block 0 also what was not valid.
 __global__ __launch_bounds__(WAVE) void admpc_bin_kernel(const LearnArgs a)
 {
-#pragma clang fp contract(off)
-    const int g = (int)blockIdx.x / NPT, bin = (int)blockIdx.x % NPT;
-    const LearnGp& G = a.gp[g];
-    if (bin >= G.nbins) return;
-    const int lane = lane_id();
-    double part[ACC] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
-    int outside = 0, invalid = 0;
-    for (long b = lane; b < a.B; b += WAVE) {
-        const double* r = a.samples + b * REC;
-        if (!(r[9] == 1.0)) { ++invalid; continue; }
-        double z[3] = { 0.0, 0.0, 0.0 };
-        bool in = true;
-        int k = 0;
-#pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            if (d < G.n_feat) {
-                z[d] = r[G.feat[d] - 3];
-                const double t = (z[d] - G.lo[d]) * G.scale[d];
-                const double kd = floor(t);
-                const bool ok = t >= 0.0 && kd < (double)G.nb[d];
-                in = in && ok;
-                k = k * G.nb[d] + (ok ? (int)kd : 0);
-            }
-        }
-        if (!in) { ++outside; continue; }
-        if (k == bin) {
-            part[0] = part[0] + 1.0;
-            part[1] = part[1] + z[0]; part[2] = part[2] + z[1]; part[3] = part[3] + z[2];
-            part[4] = part[4] + r[6 + G.out - 3];
-        }
-    }
-    double* o = a.bins + ((long)g * NPT + bin) * ACC;
-    double acc[ACC];
-#pragma unroll
-    for (int c = 0; c < ACC; ++c) acc[c] = o[c];
-    for (int l = 0; l < WAVE; ++l) {
-#pragma unroll
-        for (int c = 0; c < ACC; ++c) acc[c] = acc[c] + __shfl(part[c], l);
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < ACC; ++c) o[c] = acc[c];
-    }
-    if (bin == 0) {
-        for (int w = WAVE / 2; w > 0; w >>= 1) { outside += __shfl_xor(outside, w); invalid += __shfl_xor(invalid, w); }
-        if (lane == 0) {
-            a.dropped[g] = a.dropped[g] + outside;
-            if (g == 0) a.dropped[ADMPC_GP_MAX] = a.dropped[ADMPC_GP_MAX] + invalid;
-        }
-    }
+    gp_bin_body<REC, 3, 6, ADMPC_GP_MAX>(a, (int)blockIdx.x / NPT, (int)blockIdx.x % NPT);      // gp_fit_dev.h: shared with the quadrotor's
 }
 
 // grid n_gp, one wave each: the fit at the hyperparameters given to the regressor (gp_fit_dev.h has the body, which admpc_hyper.hip shares).

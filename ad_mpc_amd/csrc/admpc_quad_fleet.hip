@@ -293,6 +293,9 @@ QuadPlantArgs plant_only(const AdmpcQuadPlantParams* plant, int B, const double*
 
 }  // namespace
 
+// for admpc_quad_learn.hip: the refusals of the plant parameters
+extern "C" int admpc_quad_plant_params_check(const char* who, const AdmpcQuadPlantParams* plant) { return plant_params_check(who, plant); }
+
 extern "C" {
 
 int admpc_quad_plant_step_batch(const AdmpcQuadPlantParams* plant, int device, int B, const double* u, int64_t u_stride, double* x,

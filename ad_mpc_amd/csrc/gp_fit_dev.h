@@ -25,9 +25,9 @@ struct LearnArgs {
     int B, n_gp;
     double min_count;
     LearnGp gp[ADMPC_GP_MAX];
-    const double* samples;       // [B][REC]
+    const double* samples;       // [B][REC] of the vehicle: 10 doubles a record for the car, 14 for the quadrotor
     double* bins;                // [n_gp][NPT][ACC]
-    int32_t* dropped;            // [ADMPC_GP_MAX + 1]
+    int32_t* dropped;            // [ADMPC_GP_MAX + 1]; the quadrotor: [ADMPC_QUAD_GP_MAX + 1]
     AdmpcGp* out;                // [n_gp]
     int32_t* info;               // [n_gp]
 };
@@ -71,6 +71,64 @@ static __device__ __forceinline__ double gp_ymean(const double* ts, const int n)
     double sum = 0.0;
     for (int i = 0; i < n; ++i) sum = sum + ts[i];
     return n > 0 ? sum / (double)n : 0.0;
+}
+
+// The statistics of bin `bin` of regressor g, by ONE wave (a block of its own; include/admpc_learn.h, admpc_bin_kernel, has the contract:
+// acceptance, the bin index, the lane-ordered sums).  The record layout is the caller's: REC_ doubles, the last of them the flag; feature
+// index f reads entry f - FEAT0_, output `out` reads entry Y0_ + out - FEAT0_; the records that are not valid go into dropped[INVALID_].
+// Bin 0 of a regressor also counts what fell outside its box, regressor 0 also what was not valid.
+template <int REC_, int FEAT0_, int Y0_, int INVALID_>
+static __device__ __forceinline__ void gp_bin_body(const LearnArgs& a, const int g, const int bin)
+{
+#pragma clang fp contract(off)
+    const LearnGp& G = a.gp[g];
+    if (bin >= G.nbins) return;
+    const int lane = gp_lane_id();
+    double part[ACC] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
+    int outside = 0, invalid = 0;
+    for (long b = lane; b < a.B; b += WAVE) {
+        const double* r = a.samples + b * REC_;
+        if (!(r[REC_ - 1] == 1.0)) { ++invalid; continue; }
+        double z[3] = { 0.0, 0.0, 0.0 };
+        bool in = true;
+        int k = 0;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            if (d < G.n_feat) {
+                z[d] = r[G.feat[d] - FEAT0_];
+                const double t = (z[d] - G.lo[d]) * G.scale[d];
+                const double kd = floor(t);
+                const bool ok = t >= 0.0 && kd < (double)G.nb[d];
+                in = in && ok;
+                k = k * G.nb[d] + (ok ? (int)kd : 0);
+            }
+        }
+        if (!in) { ++outside; continue; }
+        if (k == bin) {
+            part[0] = part[0] + 1.0;
+            part[1] = part[1] + z[0]; part[2] = part[2] + z[1]; part[3] = part[3] + z[2];
+            part[4] = part[4] + r[Y0_ + G.out - FEAT0_];
+        }
+    }
+    double* o = a.bins + ((long)g * NPT + bin) * ACC;
+    double acc[ACC];
+#pragma unroll
+    for (int c = 0; c < ACC; ++c) acc[c] = o[c];
+    for (int l = 0; l < WAVE; ++l) {
+#pragma unroll
+        for (int c = 0; c < ACC; ++c) acc[c] = acc[c] + __shfl(part[c], l);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < ACC; ++c) o[c] = acc[c];
+    }
+    if (bin == 0) {
+        for (int w = WAVE / 2; w > 0; w >>= 1) { outside += __shfl_xor(outside, w); invalid += __shfl_xor(invalid, w); }
+        if (lane == 0) {
+            a.dropped[g] = a.dropped[g] + outside;
+            if (g == 0) a.dropped[INVALID_] = a.dropped[INVALID_] + invalid;
+        }
+    }
 }
 
 // One wave (a block of its own) fits regressor g at the hyperparameters h.  Lane r < 32 owns point r and row r of K; lanes 32 .. 63

@@ -1,12 +1,13 @@
 """ctypes mirror of include/admpc_quad.h (AdmpcQuadConfig) and the shipped quadrotor problem
 (acados_models/my_quad_acados_ocp.json, src/quad_mpc/quad_3d.py:40-74); of include/admpc_quad_fleet.h (AdmpcQuadPlantParams), the
-simulator's vehicle (src/quad_mpc/quad_3d.py:22-95)."""
+simulator's vehicle (src/quad_mpc/quad_3d.py:22-95); of include/admpc_quad_learn.h (AdmpcQuadObserveParams), the regressors a fleet
+learns on the device."""
 import ctypes as C
 import math
 
 import numpy as np
 
-from .config import AdmpcGp, GP_MAX_FEAT, GP_MAX_POINTS
+from .config import AdmpcGp, AdmpcGpBins, GP_MAX_FEAT, GP_MAX_POINTS, learn_bins
 
 QNX, QNU, QNY, QUAD_MAX_N, QUAD_GP_MAX = 13, 4, 17, 24, 3
 
@@ -95,6 +96,20 @@ class AdmpcQuadPlantParams(C.Structure):
         c = AdmpcQuadPlantParams()
         C.memmove(C.byref(c), C.byref(self), C.sizeof(self))
         return c
+
+
+class AdmpcQuadObserveParams(C.Structure):
+    """include/admpc_quad_learn.h: the period between two states, the RK4 sub-steps of the prediction, the regressors to learn."""
+    _fields_ = [("dt", C.c_double), ("substeps", C.c_int32), ("n_gp", C.c_int32), ("gp", AdmpcGpBins * QUAD_GP_MAX)]
+
+
+QUAD_REC = 14       # doubles per sample record: v_b (3), body rates (3), activations (4), y (3), the flag
+
+
+def quad_learn_bins(learn):
+    """The AdmpcGpBins of QuadFleet(learn=...): ``config.learn_bins`` with the quadrotor's ranges -- feat in 7 .. 16 (an index into
+    z = [x with the velocity in the body frame; u], or a list of up to 3), out in 7 .. 9, at most QUAD_GP_MAX regressors."""
+    return learn_bins(learn, feat_range=(7, QNX + QNU - 1), out_range=(7, 9), gp_max=QUAD_GP_MAX)
 
 
 class SimQuad:

@@ -9,7 +9,8 @@
  * the marginal likelihood (model_fitting/gp.py:302-320, DESIGN section 8: GP fitting); that search is not part of this library.  (A grid
  * search of the same likelihood on the device, which feeds the install below, is in admpc_hyper.h.)  What is fitted here is the weight vector alpha = K^-1 (t - ymean) and ymean of a squared-exponential GP at fixed hyperparameters, over at most
  * ADMPC_GP_MAX_POINTS points, each the mean of the samples that fell into one bin of a regular grid over the features.  The quadrotor
- * is not touched.
+ * learns through admpc_quad_learn.h, which takes AdmpcGpBins from here and shares the bodies of the bin kernel and of the fit
+ * (csrc/gp_fit_dev.h); the entries below serve the car.
  *
  *   reference call site (data_driven_mpc/ros_gp_mpc/...)                                replaced by
  *   ----------------------------------------------------------------------------------  ------------------------------------
