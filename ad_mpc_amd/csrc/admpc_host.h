@@ -1,6 +1,9 @@
-// admpc_host.h -- what the host sides of admpc_kernels.hip, admpc_step.hip, admpc_lane.hip, admpc_plant.hip, admpc_learn.hip,
-// admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip and admpc_quad_learn.hip share: the device guard, and one declaration of every hidden function that one of them defines for another.  The
-// defining unit includes this header too, so that the compiler holds each definition against its declaration.
+// admpc_host.h -- what the host sides of the fleet units share: the device guard, the argument blocks of the two rollouts, and one
+// declaration of every hidden function that one unit defines for another.  The defining unit includes this header too, so that the
+// compiler holds each definition against its declaration.  Included by admpc_kernels.hip, admpc_step.hip, admpc_lane.hip,
+// admpc_plant.hip, admpc_learn.hip, admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip and admpc_quad_learn.hip.  The learning host
+// side that admpc_learn.hip defines for admpc_quad_learn.hip and admpc_hyper.hip is declared in gp_fit_dev.h, next to the LearnArgs it
+// speaks of.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,6 +51,16 @@ struct RolloutArgs {
     double* tally; int32_t* counts;
 };
 
+// admpc_quad_rollout_batch's arguments but T, the records (traj_out, u_out) and the stream
+struct QuadRolloutArgs {
+    AdmpcQuadSolver* s; const AdmpcQuadTrajBank* bank; const AdmpcQuadPlantParams* plant;
+    int over, B;
+    const int32_t* traj_of; int32_t* idx;
+    double *x, *xbar, *ubar, *yref, *yref_e, *cost;
+    int32_t *status, *iters;
+    double* tally; int32_t* counts;
+};
+
 #define ADMPC_HIDDEN extern "C" __attribute__((visibility("hidden")))
 
 // admpc_kernels.hip: the thread-local message behind admpc_last_error(); the problem a handle solves and the device it lives on; the
@@ -75,3 +88,6 @@ ADMPC_HIDDEN int admpc_rollout_enqueue(const RolloutArgs& a, double* traj_pre, d
 ADMPC_HIDDEN AdmpcQuadConfig* admpc_quad_solver_config_device(const AdmpcQuadSolver* s, int* n_gp);
 // admpc_quad_fleet.hip: the refusals of the quadrotor's plant parameters
 ADMPC_HIDDEN int admpc_quad_plant_params_check(const char* who, const AdmpcQuadPlantParams* plant);
+// admpc_quad_fleet.hip: the refusals of a rollout up to those of its arrays (under admpc_quad_rollout_batch's name), and one checked period
+ADMPC_HIDDEN int admpc_quad_rollout_check(const QuadRolloutArgs& a, int T);
+ADMPC_HIDDEN int admpc_quad_rollout_enqueue(const QuadRolloutArgs& a, double* traj_pre, double* traj_post, double* u_out, void* stream);

@@ -30,8 +30,6 @@
 static_assert(HYP == 3 * NSLOT + 1, "centre, step and natural value per slot, and the best NLL");
 static_assert(NLL_CAND * TRI * 8 + 6 * NPT * 8 <= 80 * 1024, "two blocks of the NLL kernel fit the LDS of a CU");
 
-void admpc_learn_fill(LearnArgs& a, const AdmpcObserveParams* obs);                                // admpc_learn.hip
-
 // the search of one regressor as the kernels read it (passed by value)
 struct SearchGp {
     int C, free_[NSLOT];                     // candidates per round; which slots are searched
@@ -290,7 +288,7 @@ int admpc_gp_search(int device, const AdmpcObserveParams* obs, const AdmpcGpSear
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     LearnArgs l = LearnArgs();
-    admpc_learn_fill(l, obs);
+    admpc_learn_fill(l, obs->n_gp, obs->gp, CAR_LEARN.feat_lo);
     l.min_count = (double)min_count; l.bins = const_cast<double*>(bins);
     q.hyper = hyper; q.nll = nll; q.info = search_info;
     const dim3 one((unsigned)obs->n_gp), cand((unsigned)((cmax + NLL_CAND - 1) / NLL_CAND), (unsigned)obs->n_gp);
@@ -317,7 +315,7 @@ int admpc_gp_refit(int device, const AdmpcObserveParams* obs, int min_count, con
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     LearnArgs l = LearnArgs();
-    admpc_learn_fill(l, obs);
+    admpc_learn_fill(l, obs->n_gp, obs->gp, CAR_LEARN.feat_lo);
     l.min_count = (double)min_count; l.bins = const_cast<double*>(bins); l.out = gp_out; l.info = info;
     hipLaunchKernelGGL(admpc_gp_refit_kernel, dim3((unsigned)obs->n_gp), dim3(WAVE), 0, (hipStream_t)stream, l, hyper);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_gp_refit_kernel: launch failed");

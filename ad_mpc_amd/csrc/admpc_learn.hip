@@ -22,9 +22,6 @@
 #include "gp_fit_dev.h"   // WAVE, NPT, ACC; LearnGp, LearnArgs; the body of the fit
 #define LIN_TASKS 63     // tasks per block (multiple of 3), as in admpc_kernels.hip
 #define REC 10           // doubles per sample record
-#define GP_WORDS (sizeof(AdmpcGp) / 8)
-
-static_assert(sizeof(AdmpcGp) % 8 == 0 && offsetof(AdmpcConfig, gp) % 8 == 0, "AdmpcGp is copied in 8-byte words");
 
 // what one launch of the observe kernel works on (passed by value)
 struct ObserveArgs {
@@ -61,8 +58,6 @@ __device__ __forceinline__ void observe_record(const ObserveArgs& a, long b, con
 #pragma unroll
     for (int i = 0; i < NX; ++i) a.prev[(long)i * a.B + b] = now[i];
 }
-
-__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 }  // namespace
 
@@ -119,56 +114,35 @@ __global__ __launch_bounds__(WAVE) void admpc_gp_fit_kernel(const LearnArgs a)
     gp_fit_body(a, g, h);
 }
 
-// one wave.  src [n_gp] -> cfg->gp[0 .. n_gp); a record that fails the check is replaced by the empty GP.
+// one wave.  src [n_gp] -> cfg->gp[0 .. n_gp); a record that fails the check is replaced by the empty GP (gp_fit_dev.h has the body).
 __global__ __launch_bounds__(WAVE) void admpc_gp_install_kernel(AdmpcConfig* cfg, int n_gp, const AdmpcGp* src, int32_t* installed)
 {
-    const int lane = lane_id();
-    for (int g = 0; g < n_gp; ++g) {
-        const AdmpcGp* s = src + g;
-        const int nf = s->n_feat, n = s->n_points, out = s->out;
-        bool head = nf >= 1 && nf <= ADMPC_GP_MAX_FEAT && out >= 3 && out <= 5 && n >= 0 && n <= NPT;
-        head = head && isfinite(s->sigma_f) && isfinite(s->ymean);
-#pragma unroll
-        for (int d = 0; d < ADMPC_GP_MAX_FEAT; ++d)
-            if (d < nf) head = head && s->feat[d] >= 3 && s->feat[d] <= 8 && isfinite(s->inv_l2[d]);
-        bool bad = false;
-        if (head && lane < n) {
-            bad = !isfinite(s->alpha[lane]);
-#pragma unroll
-            for (int d = 0; d < ADMPC_GP_MAX_FEAT; ++d)
-                if (d < nf) bad = bad || !isfinite(s->Z[d][lane]);
-        }
-        const bool take = head && __ballot(bad) == 0ull;
-        const uint64_t* sw = (const uint64_t*)s;
-        uint64_t* dw = (uint64_t*)&cfg->gp[g];
-        for (int w = lane; w < (int)GP_WORDS; w += WAVE) {
-            // the empty GP: n_feat 1, feat 3 0 0, out 3, n_points 0, every double zero (the six int32 of the head are words 0 .. 2)
-            const uint64_t empty = w == 0 ? (1ull | (3ull << 32)) : (w == 2 ? 3ull : 0ull);
-            dw[w] = take ? sw[w] : empty;
-        }
-        if (lane == 0) installed[g] = take ? 1 : 0;
-    }
+    gp_install_body<CAR_LEARN.feat_lo, CAR_LEARN.feat_hi, CAR_LEARN.out_lo, CAR_LEARN.out_hi>(cfg->gp, n_gp, src, installed);
 }
 
-namespace {
+// ---- the host side both vehicles share (gp_fit_dev.h declares it; admpc_quad_learn.hip and admpc_hyper.hip call it) ----
 
-// The refusals of the observe parameters, for the entry points that take them (`who` leads the message).
-int observe_params_check(const char* who, const AdmpcObserveParams* obs)
+extern "C" int admpc_learn_refuse(const char* who, const char* what)
 {
-    char msg[200], what[120];
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return admpc_set_error(ADMPC_EINVAL, msg);
+}
+
+// The refusals of the regressors of a parameter block, behind those of its head, which is the vehicle's own.
+extern "C" int admpc_learn_regressors_check(const char* who, int n_gp, const AdmpcGpBins* gp, const LearnRanges& r)
+{
+    char what[120], range[40];
     what[0] = 0;
-    if (!obs) snprintf(what, sizeof what, "the observe parameters are not set");
-    else if (!(obs->dt > 0) || !isfinite(obs->dt)) snprintf(what, sizeof what, "dt must be positive and finite");
-    else if (!(obs->blend_max > obs->blend_min)) snprintf(what, sizeof what, "blend_max must exceed blend_min");
-    else if (obs->substeps < 1 || obs->substeps > 64) snprintf(what, sizeof what, "substeps must be in [1, 64]");
-    else if (obs->n_gp < 1 || obs->n_gp > ADMPC_GP_MAX) snprintf(what, sizeof what, "n_gp must be in [1, %d]", ADMPC_GP_MAX);
-    for (int g = 0; !what[0] && g < obs->n_gp; ++g) {
-        const AdmpcGpBins& b = obs->gp[g];
+    if (n_gp < 1 || n_gp > r.n_gp_max) snprintf(what, sizeof what, "n_gp must be in [1, %d]", r.n_gp_max);
+    for (int g = 0; !what[0] && g < n_gp; ++g) {
+        const AdmpcGpBins& b = gp[g];
         const int nf = b.n_feat;
         const char* bad = nullptr;
         if (nf < 1 || nf > ADMPC_GP_MAX_FEAT) bad = "n_feat must be in [1, 3]";
-        for (int d = 0; !bad && d < nf; ++d) if (b.feat[d] < 3 || b.feat[d] > 8) bad = "feat must be in [3, 8]";
-        if (!bad && (b.out < 3 || b.out > 5)) bad = "out must be in [3, 5]";
+        for (int d = 0; !bad && d < nf; ++d)
+            if (b.feat[d] < r.feat_lo || b.feat[d] > r.feat_hi) { snprintf(range, sizeof range, "feat must be in [%d, %d]", r.feat_lo, r.feat_hi); bad = range; }
+        if (!bad && (b.out < r.out_lo || b.out > r.out_hi)) { snprintf(range, sizeof range, "out must be in [%d, %d]", r.out_lo, r.out_hi); bad = range; }
         long prod = 1;
         for (int d = 0; !bad && d < 3; ++d) {
             if (b.nb[d] < 1 || (d >= nf && b.nb[d] != 1)) bad = "nb must be >= 1, and 1 for an unused feature";
@@ -181,23 +155,22 @@ int observe_params_check(const char* who, const AdmpcObserveParams* obs)
         if (!bad && (!(b.count_noise >= 0) || !isfinite(b.count_noise))) bad = "count_noise must not be negative";
         if (bad) snprintf(what, sizeof what, "regressor %d: %s", g, bad);
     }
-    if (!what[0]) return ADMPC_OK;
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return admpc_set_error(ADMPC_EINVAL, msg);
+    return what[0] ? admpc_learn_refuse(who, what) : ADMPC_OK;
 }
 
-void fill_learn(LearnArgs& a, const AdmpcObserveParams* obs)
+// The regressors as the bin kernels and the fit read them; an unused feature slot names feature `unused_feat`, which nothing reads.
+extern "C" void admpc_learn_fill(LearnArgs& a, int n_gp, const AdmpcGpBins* gp, int unused_feat)
 {
-    a.n_gp = obs->n_gp;
+    a.n_gp = n_gp;
     for (int g = 0; g < ADMPC_GP_MAX; ++g) {
         LearnGp& G = a.gp[g];
         G = LearnGp();
-        if (g >= obs->n_gp) continue;
-        const AdmpcGpBins& b = obs->gp[g];
+        if (g >= n_gp) continue;
+        const AdmpcGpBins& b = gp[g];
         G.n_feat = b.n_feat; G.out = b.out; G.nbins = 1;
         for (int d = 0; d < 3; ++d) {
             const bool used = d < b.n_feat;
-            G.feat[d] = used ? b.feat[d] : 3; G.nb[d] = used ? b.nb[d] : 1; G.nbins *= G.nb[d];
+            G.feat[d] = used ? b.feat[d] : unused_feat; G.nb[d] = used ? b.nb[d] : 1; G.nbins *= G.nb[d];
             G.lo[d] = used ? b.lo[d] : 0.0;
             G.scale[d] = used ? (double)b.nb[d] / (b.hi[d] - b.lo[d]) : 0.0;
             G.inv_l2[d] = used ? 1.0 / (b.length[d] * b.length[d]) : 0.0;
@@ -205,6 +178,34 @@ void fill_learn(LearnArgs& a, const AdmpcObserveParams* obs)
         G.sigma_f = b.sigma_f; G.noise = b.noise; G.count_noise = b.count_noise;
     }
 }
+
+// admpc_gp_fit and admpc_quad_gp_fit behind the check of their parameter block: a __global__ function is launched from its own unit.
+extern "C" int admpc_learn_fit(const char* who, int device, int n_gp, const AdmpcGpBins* gp, int unused_feat, int min_count, const double* bins,
+                               AdmpcGp* gp_out, int32_t* info, void* stream)
+{
+    if (min_count < 1) return admpc_learn_refuse(who, "min_count must be at least 1");
+    if (!bins || !gp_out || !info) return admpc_learn_refuse(who, "null array argument");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    LearnArgs l = LearnArgs();
+    admpc_learn_fill(l, n_gp, gp, unused_feat);
+    l.min_count = (double)min_count; l.bins = const_cast<double*>(bins); l.out = gp_out; l.info = info;
+    hipLaunchKernelGGL(admpc_gp_fit_kernel, dim3((unsigned)n_gp), dim3(WAVE), 0, (hipStream_t)stream, l);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_gp_fit_kernel: launch failed");
+    return ADMPC_OK;
+}
+
+// The refusals of the observe parameters, for the entry points that take them (`who` leads the message); admpc_hyper.hip's too.
+extern "C" int admpc_observe_params_check(const char* who, const AdmpcObserveParams* obs)
+{
+    if (!obs) return admpc_learn_refuse(who, "the observe parameters are not set");
+    if (!(obs->dt > 0) || !isfinite(obs->dt)) return admpc_learn_refuse(who, "dt must be positive and finite");
+    if (!(obs->blend_max > obs->blend_min)) return admpc_learn_refuse(who, "blend_max must exceed blend_min");
+    if (obs->substeps < 1 || obs->substeps > 64) return admpc_learn_refuse(who, "substeps must be in [1, 64]");
+    return admpc_learn_regressors_check(who, obs->n_gp, obs->gp, CAR_LEARN);
+}
+
+namespace {
 
 // The two launches of an observation for checked arguments, B > 0, on the model's device (the caller holds it).
 int observe_launch(const AdmpcSolver* model, const AdmpcPlantParams* plant, const AdmpcObserveParams* obs, int B, const float* ack,
@@ -224,7 +225,7 @@ int observe_launch(const AdmpcSolver* model, const AdmpcPlantParams* plant, cons
     hipLaunchKernelGGL(admpc_observe_kernel, dim3((unsigned)grid), dim3(WAVE), 0, (hipStream_t)stream, admpc_solver_config_device(model), a);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_observe_kernel: launch failed");
     LearnArgs l = LearnArgs();
-    fill_learn(l, obs);
+    admpc_learn_fill(l, obs->n_gp, obs->gp, CAR_LEARN.feat_lo);
     l.B = B; l.samples = samples; l.bins = bins; l.dropped = dropped;
     hipLaunchKernelGGL(admpc_bin_kernel, dim3((unsigned)(obs->n_gp * NPT)), dim3(WAVE), 0, (hipStream_t)stream, l);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_bin_kernel: launch failed");
@@ -241,10 +242,6 @@ int latch_launch(int B, const double* const* st, double* prev, void* stream)
 }
 
 }  // namespace
-
-// for admpc_hyper.hip: the refusals of the observe parameters, and a regressor as the fit reads it
-extern "C" int admpc_observe_params_check(const char* who, const AdmpcObserveParams* obs) { return observe_params_check(who, obs); }
-__attribute__((visibility("hidden"))) void admpc_learn_fill(LearnArgs& a, const AdmpcObserveParams* obs) { fill_learn(a, obs); }
 
 extern "C" {
 
@@ -267,7 +264,7 @@ int admpc_observe_batch(const AdmpcSolver* model, const AdmpcPlantParams* plant,
                         const double* yaw_rate, const double* steer,
                         double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
 {
-    int rc = observe_params_check("admpc_observe_batch", obs);
+    int rc = admpc_observe_params_check("admpc_observe_batch", obs);
     if (rc) return rc;
     rc = admpc_plant_params_check("admpc_observe_batch", plant);
     if (rc) return rc;
@@ -285,18 +282,8 @@ int admpc_observe_batch(const AdmpcSolver* model, const AdmpcPlantParams* plant,
 
 int admpc_gp_fit(int device, const AdmpcObserveParams* obs, int min_count, const double* bins, AdmpcGp* gp_out, int32_t* info, void* stream)
 {
-    const int rc = observe_params_check("admpc_gp_fit", obs);
-    if (rc) return rc;
-    if (min_count < 1) return admpc_set_error(ADMPC_EINVAL, "admpc_gp_fit: min_count must be at least 1");
-    if (!bins || !gp_out || !info) return admpc_set_error(ADMPC_EINVAL, "admpc_gp_fit: null array argument");
-    DeviceGuard guard(device);
-    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    LearnArgs l = LearnArgs();
-    fill_learn(l, obs);
-    l.min_count = (double)min_count; l.bins = const_cast<double*>(bins); l.out = gp_out; l.info = info;
-    hipLaunchKernelGGL(admpc_gp_fit_kernel, dim3((unsigned)obs->n_gp), dim3(WAVE), 0, (hipStream_t)stream, l);
-    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_gp_fit_kernel: launch failed");
-    return ADMPC_OK;
+    const int rc = admpc_observe_params_check("admpc_gp_fit", obs);
+    return rc ? rc : admpc_learn_fit("admpc_gp_fit", device, obs->n_gp, obs->gp, CAR_LEARN.feat_lo, min_count, bins, gp_out, info, stream);
 }
 
 int admpc_gp_install(AdmpcSolver* s, int n_gp, const AdmpcGp* gp_dev, int32_t* installed, void* stream)
@@ -329,7 +316,7 @@ int admpc_rollout_observe_lane_batch(AdmpcSolver* s, const AdmpcPathBank* bank, 
 {
     const RolloutArgs a = { s, bank, lane, prm, plant_model, plant, B, path_of, lane_idx, { px, py, yaw, vx, vy, yaw_rate, steer },
                             { xbar, ubar, safe_count, prev_u, has_valid, work, ack, mode, valid, status, cost }, tally, counts };
-    int rc = observe_params_check("admpc_rollout_observe_lane_batch", obs);
+    int rc = admpc_observe_params_check("admpc_rollout_observe_lane_batch", obs);
     if (rc) return rc;
     if (!model) return admpc_set_error(ADMPC_EINVAL, "admpc_rollout_observe_lane_batch: null model");
     // the rollout's own refusals but those of its arrays, which are among the ones below

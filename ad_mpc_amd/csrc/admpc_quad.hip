@@ -13,18 +13,12 @@
 //   4. expansion of the states, full step, cost, status.
 // The generic path follows oracle/quad_oracle.c operation by operation where the order matters (Cholesky, forward substitution); the
 // fast path reaches the same iterates (identical iteration counts on every tested batch).  DESIGN section 7 has the numbers.
-#include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
 #include <new>
 #include <type_traits>
-#include "../../include/admpc.h"
-#include "../../include/admpc_quad.h"
-#include "../../include/admpc_quad_fleet.h"      // admpc_quad_solver_info
-#include "admpc_host.h"                          // admpc_quad_solver_config_device
-
-extern "C" int admpc_set_error(int code, const char* msg);          // admpc_kernels.hip: thread-local message behind admpc_last_error()
+#include "admpc_host.h"      // the public headers; DeviceGuard, admpc_set_error, admpc_quad_solver_config_device
 
 #ifdef ADMPC_QUAD_TIMERS
 // per-wave accumulators, flushed once at the end of the kernel (an atomic per stamp costs more than most phases)
@@ -1056,17 +1050,6 @@ struct AdmpcQuadSolver {
     int32_t *d_act, *d_fst, *d_st;
 };
 
-namespace {
-struct QGuard {
-    int prev; bool switched, good;
-    explicit QGuard(int dev) : prev(-1), switched(false), good(true) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) { good = hipSetDevice(dev) == hipSuccess; switched = good; }
-    }
-    ~QGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-};
-}
-
 extern "C" {
 
 void admpc_quad_default_config(AdmpcQuadConfig* c)
@@ -1107,8 +1090,8 @@ int admpc_quad_create(const AdmpcQuadConfig* cfg, int device, AdmpcQuadSolver** 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return admpc_set_error(ADMPC_ENODEV, "no HIP device");
     if (device < 0 || device >= ndev) return admpc_set_error(ADMPC_ENODEV, "no such device");
-    QGuard guard(device);
-    if (!guard.good) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     AdmpcQuadSolver* s = new (std::nothrow) AdmpcQuadSolver();
     if (!s) return admpc_set_error(ADMPC_ENOMEM, "out of host memory");
     s->cfg = *cfg; s->device = device; s->d_cfg = nullptr; s->d_ticket = nullptr;
@@ -1138,7 +1121,7 @@ int admpc_quad_create(const AdmpcQuadConfig* cfg, int device, AdmpcQuadSolver** 
 void admpc_quad_destroy(AdmpcQuadSolver* s)
 {
     if (!s) return;
-    QGuard guard(s->device);
+    DeviceGuard guard(s->device);
     if (s->d_cfg) (void)hipFree(s->d_cfg);
     if (s->d_ticket) (void)hipFree(s->d_ticket);
     if (s->d_slot) (void)hipFree(s->d_slot);
@@ -1198,8 +1181,8 @@ int admpc_quad_solve_batch_ex(AdmpcQuadSolver* s, int B, const double* x0, const
     if (B < 0) return admpc_set_error(ADMPC_EINVAL, "negative batch");
     if (B == 0) return ADMPC_OK;
     if (!x0 || !yref || !yref_e || !xbar || !ubar) return admpc_set_error(ADMPC_EINVAL, "null array argument");
-    QGuard guard(s->device);
-    if (!guard.good) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    DeviceGuard guard(s->device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     const int nsqp = s->cfg.sqp_iters > 1 ? s->cfg.sqp_iters : 1;
     if (nsqp == 1) return quad_solve(s, B, x0, yref, yref_e, gp_state, xbar, ubar, cost, status, iters, nullptr, 0, st);
@@ -1253,8 +1236,8 @@ int admpc_quad_select_cluster_batch(int device, int B, int n_feat, const int32_t
     if (B == 0) return ADMPC_OK;
     if (!x_sel || !u_sel || !centroids || !route) return admpc_set_error(ADMPC_EINVAL, "null array argument");
     for (int j = 0; j < n_feat; ++j) if (feats[j] < 0 || feats[j] >= QY) return admpc_set_error(ADMPC_EINVAL, "feature index outside z = [x; u]");
-    QGuard guard(device);
-    if (!guard.good) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    DeviceGuard guard(device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     hipLaunchKernelGGL(admpc_quad_select_cluster_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, B, n_feat, feats[0], n_feat > 1 ? feats[1] : 0,
                        n_feat > 2 ? feats[2] : 0, x_sel, u_sel, K, centroids, route);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "quad select kernel launch failed");
@@ -1274,8 +1257,8 @@ int admpc_quad_solve_batch_routed(AdmpcQuadSolver* const* solvers, int K, int B,
         if (solvers[c]->device != solvers[0]->device || solvers[c]->cfg.N != solvers[0]->cfg.N) return admpc_set_error(ADMPC_EINVAL, "the cluster solvers must share device and horizon");
         if (solvers[c]->cfg.sqp_iters > 1) return admpc_set_error(ADMPC_EINVAL, "quad: solver_type SQP (sqp_iters > 1) is not implemented for routed (clustered GP) solves");
     }
-    QGuard guard(solvers[0]->device);
-    if (!guard.good) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    DeviceGuard guard(solvers[0]->device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(admpc_quad_route_invalid_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, route, K, status, cost, iters);
     for (int c = 0; c < K; ++c) {
@@ -1291,8 +1274,8 @@ int admpc_quad_shoot_batch_ex(AdmpcQuadSolver* s, int B, const double* xbar, con
     if (!s) return admpc_set_error(ADMPC_EINVAL, "null solver");
     if (B <= 0) return B == 0 ? ADMPC_OK : admpc_set_error(ADMPC_EINVAL, "negative batch");
     if (!xbar || !ubar || !phi || !A || !Bm) return admpc_set_error(ADMPC_EINVAL, "null array argument");
-    QGuard guard(s->device);
-    if (!guard.good) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    DeviceGuard guard(s->device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     int grid = s->num_cu * 2; if (grid > B) grid = B;
     hipLaunchKernelGGL(admpc_quad_shoot_kernel, dim3(grid), dim3(64), s->lds_bytes, (hipStream_t)stream, s->d_cfg, B, xbar, ubar, gp_state, phi, A, Bm);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "quad shoot kernel launch failed");

@@ -380,46 +380,60 @@ int admpc_quad_ref_chunk_batch(const AdmpcQuadTrajBank* bank, int B, int N, int 
     return chunk_launch(bank, B, N, over, traj_of, idx, yref, yref_e, pos_ref, (hipStream_t)stream);
 }
 
+// The refusals of a rollout up to those of its arrays.
+int admpc_quad_rollout_check(const QuadRolloutArgs& a, int T)
+{
+    int device = 0, sqp = 0;
+    if (!a.s) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: null solver");
+    (void)admpc_quad_solver_info(a.s, &device, nullptr, &sqp);
+    if (sqp > 1) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: a solver in SQP mode (sqp_iters > 1) is not served: the rollout is the RTI loop");
+    if (!a.bank) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: null bank");
+    if (a.bank->device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: the bank is on another device than the solver");
+    const int rc = plant_params_check("admpc_quad_rollout_batch", a.plant);
+    if (rc) return rc;
+    if (a.over < 1) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: over must be at least 1");
+    if (a.B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: negative batch");
+    if (T < 0 || T > 4096) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: T must be in [0, 4096]");
+    return ADMPC_OK;
+}
+
+// One closed-loop period for checked arguments, B > 0, on the solver's device (the caller holds it): window -> RTI step -> plant.
+// traj_pre / traj_post: null or [B][13], the states before and after the period; u_out: null or [B][4], the input applied in it.
+int admpc_quad_rollout_enqueue(const QuadRolloutArgs& r, double* traj_pre, double* traj_post, double* u_out, void* stream)
+{
+    int N = 0;
+    (void)admpc_quad_solver_info(r.s, nullptr, &N, nullptr);
+    int rc = chunk_launch(r.bank, r.B, N, r.over, r.traj_of, r.idx, r.yref, r.yref_e, nullptr, (hipStream_t)stream);
+    if (!rc) rc = admpc_quad_solve_batch_ex(r.s, r.B, r.x, r.yref, r.yref_e, nullptr, r.xbar, r.ubar, r.cost, r.status, r.iters, stream);
+    if (rc) return rc;
+    QuadPlantArgs a = plant_only(r.plant, r.B, r.ubar, (long long)N * QU, r.x);
+    a.K = r.bank->K; a.desc = r.bank->d_desc;
+    a.yref = r.yref; a.yref_stride = (long long)N * QY; a.status = r.status; a.tally = r.tally; a.counts = r.counts;
+    a.traj_of = r.traj_of; a.idx = r.idx;
+    a.traj_pre = traj_pre; a.traj_post = traj_post; a.u_out = u_out;
+    return plant_launch(a, (hipStream_t)stream);
+}
+
 int admpc_quad_rollout_batch(AdmpcQuadSolver* s, const AdmpcQuadTrajBank* bank, const AdmpcQuadPlantParams* plant, int over, int B, int T,
                              const int32_t* traj_of, int32_t* idx, double* x, double* xbar, double* ubar,
                              double* yref, double* yref_e, double* cost, int32_t* status, int32_t* iters,
                              double* tally, int32_t* counts, double* traj_out, double* u_out, void* stream)
 {
-    int device = 0, N = 0, sqp = 0;
-    if (!s) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: null solver");
-    (void)admpc_quad_solver_info(s, &device, &N, &sqp);
-    if (sqp > 1) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: a solver in SQP mode (sqp_iters > 1) is not served: the rollout is the RTI loop");
-    if (!bank) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: null bank");
-    if (bank->device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: the bank is on another device than the solver");
-    const int rc = plant_params_check("admpc_quad_rollout_batch", plant);
-    if (rc) return rc;
-    if (over < 1) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: over must be at least 1");
-    if (B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: negative batch");
-    if (T < 0 || T > 4096) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: T must be in [0, 4096]");
-    if (B == 0 || T == 0) return ADMPC_OK;
+    const QuadRolloutArgs a = { s, bank, plant, over, B, traj_of, idx, x, xbar, ubar, yref, yref_e, cost, status, iters, tally, counts };
+    int rc = admpc_quad_rollout_check(a, T);
+    if (rc || B == 0 || T == 0) return rc;
     if (!traj_of || !idx || !x || !xbar || !ubar || !yref || !yref_e || !status)
         return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: null array argument");
     if (!tally || !counts) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: null tally or counts");
+    int device = 0;
+    (void)admpc_quad_solver_info(s, &device, nullptr, nullptr);
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    hipStream_t st = (hipStream_t)stream;
-    QuadPlantArgs a = plant_only(plant, B, ubar, (long long)N * QU, x);
-    a.K = bank->K; a.desc = bank->d_desc;
-    a.yref = yref; a.yref_stride = (long long)N * QY; a.status = status; a.tally = tally; a.counts = counts;
-    a.traj_of = traj_of; a.idx = idx;
-    const size_t slot = (size_t)B * QX;
-    for (int t = 0; t < T; ++t) {
-        int e = chunk_launch(bank, B, N, over, traj_of, idx, yref, yref_e, nullptr, st);
-        if (e) return e;
-        e = admpc_quad_solve_batch_ex(s, B, x, yref, yref_e, nullptr, xbar, ubar, cost, status, iters, stream);
-        if (e) return e;
-        a.traj_pre = traj_out && t == 0 ? traj_out : nullptr;
-        a.traj_post = traj_out ? traj_out + (size_t)(t + 1) * slot : nullptr;
-        a.u_out = u_out ? u_out + (size_t)t * B * QU : nullptr;
-        e = plant_launch(a, st);
-        if (e) return e;
-    }
-    return ADMPC_OK;
+    // slot 0 of traj_out is written by the first period; every period writes the state it leaves into the next slot
+    for (int t = 0; t < T && !rc; ++t)
+        rc = admpc_quad_rollout_enqueue(a, t == 0 ? traj_out : nullptr, traj_out ? traj_out + (size_t)(t + 1) * B * QX : nullptr,
+                                        u_out ? u_out + (size_t)t * B * QU : nullptr, stream);
+    return rc;
 }
 
 }  // extern "C"

@@ -7,24 +7,23 @@
 //                                          model is quad_f_tan of quad_model_dev.h, the text the solve kernels integrate, called with zero
 //                                          tangents: the doubled arithmetic is nothing next to a solve
 //   bin      admpc_quad_bin_kernel         one wave per (regressor, bin): the body of the car's bin kernel (gp_fit_dev.h) on this record
-//   fit      admpc_quad_gp_fit_kernel      one wave per regressor: gp_fit_body of gp_fit_dev.h, unchanged
-//   install  admpc_quad_gp_install_kernel  one wave: checks each record and copies it into the handle's device configuration
+//   fit      admpc_gp_fit_kernel           the car's kernel, launched by admpc_learn.hip (admpc_learn_fit): it reads nothing of a vehicle
+//   install  admpc_quad_gp_install_kernel  one wave: checks each record and copies it into the handle's device configuration; the body
+//                                          of the car's (gp_fit_dev.h) with the quadrotor's ranges
 //
-// The hyperparameters are given (admpc_quad_learn.h: what is not offered).  The rollout with observation is at the end of the file.
+// The hyperparameters are given (admpc_quad_learn.h: what is not offered).  The refusals of the regressors, their form for the kernels
+// and the fit entry are admpc_learn.hip's (declared in gp_fit_dev.h).  The rollout with observation is at the end of the file.
 #include <stdio.h>
 #include <math.h>
 #include "admpc_host.h"
 
-#define NX ADMPC_NX           // model_dev.h (exp_nonpos, which the fit evaluates the kernel with) wants the car's dimensions defined
+#define NX ADMPC_NX           // model_dev.h (exp_nonpos, which the fit body of gp_fit_dev.h names) wants the car's dimensions defined
 #define NU ADMPC_NU
 #define NY ADMPC_NY
-#include "gp_fit_dev.h"       // WAVE, NPT, ACC; LearnGp, LearnArgs; the bodies of the bin kernel and of the fit
+#include "gp_fit_dev.h"       // WAVE, NPT, ACC; LearnGp, LearnArgs, LearnRanges; the bodies of the bin and install kernels; admpc_learn_*
 #define QREC 14               // doubles per sample record: v_b (3), body rates (3), activations (4), y (3), the flag
 #define QO_GRID 4096          // blocks of the observe kernel at most, as the plant kernel's; more vehicles go round the stride loop
-#define GP_WORDS (sizeof(AdmpcGp) / 8)
 
-static_assert(sizeof(AdmpcGp) % 8 == 0 && offsetof(AdmpcQuadConfig, gp) % 8 == 0, "AdmpcGp is copied in 8-byte words");
-static_assert(ADMPC_QUAD_GP_MAX <= ADMPC_GP_MAX, "LearnArgs holds the regressors of either vehicle");
 static_assert(sizeof(AdmpcQuadObserveParams) == 16 + ADMPC_QUAD_GP_MAX * sizeof(AdmpcGpBins) && sizeof(AdmpcGpBins) == 128, "the layout the Python side mirrors");
 
 // what one launch of the observe kernel works on (passed by value)
@@ -83,8 +82,6 @@ __device__ __forceinline__ void body_velocity(const double (&s)[QX], double (&vb
     for (int i = 0; i < 3; ++i) vb[i] = (R[0][i] * s[7] + R[1][i] * s[8]) + R[2][i] * s[9];
 }
 
-__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
 }  // namespace
 
 __global__ void admpc_quad_latch_kernel(long long n, const double* __restrict__ x, double* __restrict__ prev)
@@ -141,101 +138,22 @@ __global__ __launch_bounds__(WAVE) void admpc_quad_bin_kernel(const LearnArgs a)
     gp_bin_body<QREC, 7, 10, ADMPC_QUAD_GP_MAX>(a, (int)blockIdx.x / NPT, (int)blockIdx.x % NPT);
 }
 
-// grid n_gp, one wave each: the fit at the hyperparameters given to the regressor
-__global__ __launch_bounds__(WAVE) void admpc_quad_gp_fit_kernel(const LearnArgs a)
-{
-    const int g = (int)blockIdx.x;
-    const LearnGp& G = a.gp[g];
-    const GpHyper h = { G.sigma_f, { G.inv_l2[0], G.inv_l2[1], G.inv_l2[2] }, G.noise, 0 };
-    gp_fit_body(a, g, h);
-}
-
-// one wave.  src [n_gp] -> cfg->gp[0 .. n_gp); a record that fails the check is replaced by the empty GP.
+// one wave.  src [n_gp] -> cfg->gp[0 .. n_gp); a record that fails the check is replaced by the empty GP (gp_fit_dev.h has the body).
 __global__ __launch_bounds__(WAVE) void admpc_quad_gp_install_kernel(AdmpcQuadConfig* cfg, int n_gp, const AdmpcGp* src, int32_t* installed)
 {
-    const int lane = lane_id();
-    for (int g = 0; g < n_gp; ++g) {
-        const AdmpcGp* s = src + g;
-        const int nf = s->n_feat, n = s->n_points, out = s->out;
-        bool head = nf >= 1 && nf <= ADMPC_GP_MAX_FEAT && out >= 7 && out <= 9 && n >= 0 && n <= NPT;
-        head = head && isfinite(s->sigma_f) && isfinite(s->ymean);
-#pragma unroll
-        for (int d = 0; d < ADMPC_GP_MAX_FEAT; ++d)
-            if (d < nf) head = head && s->feat[d] >= 7 && s->feat[d] < ADMPC_QUAD_NY && isfinite(s->inv_l2[d]);
-        bool bad = false;
-        if (head && lane < n) {
-            bad = !isfinite(s->alpha[lane]);
-#pragma unroll
-            for (int d = 0; d < ADMPC_GP_MAX_FEAT; ++d)
-                if (d < nf) bad = bad || !isfinite(s->Z[d][lane]);
-        }
-        const bool take = head && __ballot(bad) == 0ull;
-        const uint64_t* sw = (const uint64_t*)s;
-        uint64_t* dw = (uint64_t*)&cfg->gp[g];
-        for (int w = lane; w < (int)GP_WORDS; w += WAVE) {
-            // the empty GP: n_feat 1, feat 7 0 0, out 7, n_points 0, every double zero (the six int32 of the head are words 0 .. 2)
-            const uint64_t empty = w == 0 ? (1ull | (7ull << 32)) : (w == 2 ? 7ull : 0ull);
-            dw[w] = take ? sw[w] : empty;
-        }
-        if (lane == 0) installed[g] = take ? 1 : 0;
-    }
+    gp_install_body<QUAD_LEARN.feat_lo, QUAD_LEARN.feat_hi, QUAD_LEARN.out_lo, QUAD_LEARN.out_hi>(cfg->gp, n_gp, src, installed);
 }
 
 namespace {
 
-// The refusals of the observe parameters, for the entry points that take them (`who` leads the message): admpc_learn.hip's, with the
-// quadrotor's ranges and without the speed band.
+// The refusals of the observe parameters, for the entry points that take them (`who` leads the message): the quadrotor's head, which
+// has no speed band, in front of the regressors' refusals of admpc_learn.hip.
 int quad_observe_params_check(const char* who, const AdmpcQuadObserveParams* obs)
 {
-    char msg[200], what[120];
-    what[0] = 0;
-    if (!obs) snprintf(what, sizeof what, "the observe parameters are not set");
-    else if (!(obs->dt > 0) || !isfinite(obs->dt)) snprintf(what, sizeof what, "dt must be positive and finite");
-    else if (obs->substeps < 1 || obs->substeps > 64) snprintf(what, sizeof what, "substeps must be in [1, 64]");
-    else if (obs->n_gp < 1 || obs->n_gp > ADMPC_QUAD_GP_MAX) snprintf(what, sizeof what, "n_gp must be in [1, %d]", ADMPC_QUAD_GP_MAX);
-    for (int g = 0; !what[0] && g < obs->n_gp; ++g) {
-        const AdmpcGpBins& b = obs->gp[g];
-        const int nf = b.n_feat;
-        const char* bad = nullptr;
-        if (nf < 1 || nf > ADMPC_GP_MAX_FEAT) bad = "n_feat must be in [1, 3]";
-        for (int d = 0; !bad && d < nf; ++d) if (b.feat[d] < 7 || b.feat[d] >= ADMPC_QUAD_NY) bad = "feat must be in [7, 16]";
-        if (!bad && (b.out < 7 || b.out > 9)) bad = "out must be in [7, 9]";
-        long prod = 1;
-        for (int d = 0; !bad && d < 3; ++d) {
-            if (b.nb[d] < 1 || (d >= nf && b.nb[d] != 1)) bad = "nb must be >= 1, and 1 for an unused feature";
-            else if ((prod *= b.nb[d]) > NPT) bad = "the product of nb must not exceed 32";
-        }
-        for (int d = 0; !bad && d < nf; ++d) if (!isfinite(b.lo[d]) || !isfinite(b.hi[d]) || !(b.hi[d] > b.lo[d])) bad = "lo and hi must be finite, hi > lo";
-        if (!bad && (!(b.sigma_f > 0) || !isfinite(b.sigma_f))) bad = "sigma_f must be positive and finite";
-        for (int d = 0; !bad && d < nf; ++d) if (!(b.length[d] > 0) || !isfinite(b.length[d])) bad = "length must be positive and finite";
-        if (!bad && (!(b.noise > 0) || !isfinite(b.noise))) bad = "noise must be positive and finite";
-        if (!bad && (!(b.count_noise >= 0) || !isfinite(b.count_noise))) bad = "count_noise must not be negative";
-        if (bad) snprintf(what, sizeof what, "regressor %d: %s", g, bad);
-    }
-    if (!what[0]) return ADMPC_OK;
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return admpc_set_error(ADMPC_EINVAL, msg);
-}
-
-// a regressor as the bin kernel and the fit read it (admpc_learn.hip: fill_learn, on the quadrotor's parameter block)
-void quad_fill_learn(LearnArgs& a, const AdmpcQuadObserveParams* obs)
-{
-    a.n_gp = obs->n_gp;
-    for (int g = 0; g < ADMPC_GP_MAX; ++g) {
-        LearnGp& G = a.gp[g];
-        G = LearnGp();
-        if (g >= obs->n_gp) continue;
-        const AdmpcGpBins& b = obs->gp[g];
-        G.n_feat = b.n_feat; G.out = b.out; G.nbins = 1;
-        for (int d = 0; d < 3; ++d) {
-            const bool used = d < b.n_feat;
-            G.feat[d] = used ? b.feat[d] : 7; G.nb[d] = used ? b.nb[d] : 1; G.nbins *= G.nb[d];
-            G.lo[d] = used ? b.lo[d] : 0.0;
-            G.scale[d] = used ? (double)b.nb[d] / (b.hi[d] - b.lo[d]) : 0.0;
-            G.inv_l2[d] = used ? 1.0 / (b.length[d] * b.length[d]) : 0.0;
-        }
-        G.sigma_f = b.sigma_f; G.noise = b.noise; G.count_noise = b.count_noise;
-    }
+    if (!obs) return admpc_learn_refuse(who, "the observe parameters are not set");
+    if (!(obs->dt > 0) || !isfinite(obs->dt)) return admpc_learn_refuse(who, "dt must be positive and finite");
+    if (obs->substeps < 1 || obs->substeps > 64) return admpc_learn_refuse(who, "substeps must be in [1, 64]");
+    return admpc_learn_regressors_check(who, obs->n_gp, obs->gp, QUAD_LEARN);
 }
 
 // The two launches of an observation for checked arguments, B > 0, on the model's device (the caller holds it).
@@ -252,7 +170,7 @@ int quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams
                        admpc_quad_solver_config_device(model, nullptr), a);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_quad_observe_kernel: launch failed");
     LearnArgs l = LearnArgs();
-    quad_fill_learn(l, obs);
+    admpc_learn_fill(l, obs->n_gp, obs->gp, QUAD_LEARN.feat_lo);
     l.B = B; l.samples = samples; l.bins = bins; l.dropped = dropped;
     hipLaunchKernelGGL(admpc_quad_bin_kernel, dim3((unsigned)(obs->n_gp * NPT)), dim3(WAVE), 0, (hipStream_t)stream, l);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_quad_bin_kernel: launch failed");
@@ -305,17 +223,7 @@ int admpc_quad_gp_fit(int device, const AdmpcQuadObserveParams* obs, int min_cou
                       void* stream)
 {
     const int rc = quad_observe_params_check("admpc_quad_gp_fit", obs);
-    if (rc) return rc;
-    if (min_count < 1) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_gp_fit: min_count must be at least 1");
-    if (!bins || !gp_out || !info) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_gp_fit: null array argument");
-    DeviceGuard guard(device);
-    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    LearnArgs l = LearnArgs();
-    quad_fill_learn(l, obs);
-    l.min_count = (double)min_count; l.bins = const_cast<double*>(bins); l.out = gp_out; l.info = info;
-    hipLaunchKernelGGL(admpc_quad_gp_fit_kernel, dim3((unsigned)obs->n_gp), dim3(WAVE), 0, (hipStream_t)stream, l);
-    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_quad_gp_fit_kernel: launch failed");
-    return ADMPC_OK;
+    return rc ? rc : admpc_learn_fit("admpc_quad_gp_fit", device, obs->n_gp, obs->gp, QUAD_LEARN.feat_lo, min_count, bins, gp_out, info, stream);
 }
 
 int admpc_quad_gp_install(AdmpcQuadSolver* s, int n_gp, const AdmpcGp* gp_dev, int32_t* installed, void* stream)
@@ -344,12 +252,12 @@ int admpc_quad_rollout_observe_batch(AdmpcQuadSolver* s, const AdmpcQuadTrajBank
                                      const AdmpcQuadSolver* model, const AdmpcQuadObserveParams* obs,
                                      double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
 {
+    const QuadRolloutArgs a = { s, bank, plant, over, B, traj_of, idx, x, xbar, ubar, yref, yref_e, cost, status, iters, tally, counts };
     int rc = quad_observe_params_check("admpc_quad_rollout_observe_batch", obs);
     if (rc) return rc;
     if (!model) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_observe_batch: null model");
-    // the rollout's own refusals but those of its arrays, which are among the ones below: an empty batch reaches them and launches nothing
-    rc = admpc_quad_rollout_batch(s, bank, plant, over, B < 0 ? B : 0, T, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    // the rollout's own refusals but those of its arrays, which are among the ones below
+    rc = admpc_quad_rollout_check(a, T);
     if (rc) return rc;
     int device = 0, model_device = 0, N = 0;
     (void)admpc_quad_solver_info(s, &device, &N, nullptr);
@@ -362,10 +270,10 @@ int admpc_quad_rollout_observe_batch(AdmpcQuadSolver* s, const AdmpcQuadTrajBank
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     rc = quad_latch_launch(B, x, prev, stream);
     const size_t slot = (size_t)B * QX;
-    // slot t of traj_out is written by step t (slot 0 by the first), slot t + 1 too: every step writes the state it leaves
+    // slot 0 of traj_out is written by the first period; every period writes the state it leaves into the next slot
     for (int t = 0; t < T && !rc; ++t) {
-        rc = admpc_quad_rollout_batch(s, bank, plant, over, B, 1, traj_of, idx, x, xbar, ubar, yref, yref_e, cost, status, iters, tally, counts,
-                                      traj_out ? traj_out + (size_t)t * slot : nullptr, u_out ? u_out + (size_t)t * B * QU : nullptr, stream);
+        rc = admpc_quad_rollout_enqueue(a, t == 0 ? traj_out : nullptr, traj_out ? traj_out + (size_t)(t + 1) * slot : nullptr,
+                                        u_out ? u_out + (size_t)t * B * QU : nullptr, stream);
         if (!rc) rc = quad_observe_launch(model, plant, obs, B, ubar, (long long)N * QU, x, prev, samples, bins, dropped, stream);
     }
     return rc;

@@ -1,18 +1,24 @@
 // gp_fit_dev.h -- the body of the GP fit (include/admpc_learn.h: admpc_gp_fit), shared by the kernel that fits at the hyperparameters
 // GIVEN to it (admpc_learn.hip) and the one that fits at the hyperparameters a search has found (admpc_hyper.hip: admpc_gp_refit), and
-// the formation of a regressor's points from its bins, which the search's NLL kernel shares with both.
-// Include at file scope; the translation unit includes model_dev.h in its anonymous namespace (exp_nonpos, declared below).  NPT, ACC
-// and WAVE are defined here.
+// the formation of a regressor's points from its bins, which the search's NLL kernel shares with both; the bodies of the bin kernel and
+// of the install kernel, which the car (admpc_learn.hip) and the quadrotor (admpc_quad_learn.hip) share; and the declarations of the
+// learning host side that admpc_learn.hip defines for the quadrotor and the search (they speak of LearnArgs, which admpc_host.h does
+// not know).  Include at file scope behind admpc_host.h; the translation unit includes model_dev.h in its anonymous namespace
+// (exp_nonpos, declared below).  NPT, ACC and WAVE are defined here.
 #pragma once
 #include "../../include/admpc_hyper.h"
+#include "../../include/admpc_quad.h"
 
 namespace { __device__ __forceinline__ double exp_nonpos(const double x); }      // model_dev.h
 
 #define WAVE 64
 #define NPT ADMPC_GP_MAX_POINTS
 #define ACC 5            // doubles per bin
+#define GP_WORDS (sizeof(AdmpcGp) / 8)
 
 static_assert(NPT == 32, "the fit maps one row to each lane of half a wave");
+static_assert(sizeof(AdmpcGp) % 8 == 0 && offsetof(AdmpcConfig, gp) % 8 == 0 && offsetof(AdmpcQuadConfig, gp) % 8 == 0,
+              "the install copies an AdmpcGp in 8-byte words");
 
 // one regressor as the bin kernel and the fit kernel read it
 struct LearnGp {
@@ -31,6 +37,21 @@ struct LearnArgs {
     AdmpcGp* out;                // [n_gp]
     int32_t* info;               // [n_gp]
 };
+
+// what differs between the vehicles in a regressor to learn: how many a handle holds, the feature indices and the output rows it may name
+struct LearnRanges { int n_gp_max, feat_lo, feat_hi, out_lo, out_hi; };
+constexpr LearnRanges CAR_LEARN = { ADMPC_GP_MAX, 3, 8, 3, 5 }, QUAD_LEARN = { ADMPC_QUAD_GP_MAX, 7, ADMPC_QUAD_NY - 1, 7, 9 };
+static_assert(ADMPC_QUAD_GP_MAX <= ADMPC_GP_MAX, "LearnArgs holds the regressors of either vehicle");
+
+// admpc_learn.hip: the host side that the learning of both vehicles shares (`who` leads a message).  A refusal under the caller's name;
+// the refusals of a parameter block's regressors, behind those of its head, which is the vehicle's own; the regressors as the kernels read
+// them (an unused feature slot names `unused_feat`); and the fit entry behind the check of its parameter block, which launches
+// admpc_gp_fit_kernel for either vehicle: a __global__ function is launched from the unit that defines it.
+ADMPC_HIDDEN int admpc_learn_refuse(const char* who, const char* what);
+ADMPC_HIDDEN int admpc_learn_regressors_check(const char* who, int n_gp, const AdmpcGpBins* gp, const LearnRanges& r);
+ADMPC_HIDDEN void admpc_learn_fill(LearnArgs& a, int n_gp, const AdmpcGpBins* gp, int unused_feat);
+ADMPC_HIDDEN int admpc_learn_fit(const char* who, int device, int n_gp, const AdmpcGpBins* gp, int unused_feat, int min_count, const double* bins,
+                                 AdmpcGp* gp_out, int32_t* info, void* stream);
 
 // where a fit takes its hyperparameters from: the regressor's own (given), or the natural values a search left in device memory
 struct GpHyper {
@@ -128,6 +149,39 @@ static __device__ __forceinline__ void gp_bin_body(const LearnArgs& a, const int
             a.dropped[g] = a.dropped[g] + outside;
             if (g == 0) a.dropped[INVALID_] = a.dropped[INVALID_] + invalid;
         }
+    }
+}
+
+// One wave installs src [n_gp] as dst [0 .. n_gp), the GPs of a handle's device configuration; a record that fails the check (the
+// vehicle's ranges of a feature index and of the output row, the counts, every number finite) is replaced by the empty GP.
+template <int FEAT_LO_, int FEAT_HI_, int OUT_LO_, int OUT_HI_>
+static __device__ __forceinline__ void gp_install_body(AdmpcGp* dst, const int n_gp, const AdmpcGp* src, int32_t* installed)
+{
+    const int lane = gp_lane_id();
+    for (int g = 0; g < n_gp; ++g) {
+        const AdmpcGp* s = src + g;
+        const int nf = s->n_feat, n = s->n_points, out = s->out;
+        bool head = nf >= 1 && nf <= ADMPC_GP_MAX_FEAT && out >= OUT_LO_ && out <= OUT_HI_ && n >= 0 && n <= NPT;
+        head = head && isfinite(s->sigma_f) && isfinite(s->ymean);
+#pragma unroll
+        for (int d = 0; d < ADMPC_GP_MAX_FEAT; ++d)
+            if (d < nf) head = head && s->feat[d] >= FEAT_LO_ && s->feat[d] <= FEAT_HI_ && isfinite(s->inv_l2[d]);
+        bool bad = false;
+        if (head && lane < n) {
+            bad = !isfinite(s->alpha[lane]);
+#pragma unroll
+            for (int d = 0; d < ADMPC_GP_MAX_FEAT; ++d)
+                if (d < nf) bad = bad || !isfinite(s->Z[d][lane]);
+        }
+        const bool take = head && __ballot(bad) == 0ull;
+        const uint64_t* sw = (const uint64_t*)s;
+        uint64_t* dw = (uint64_t*)(dst + g);
+        for (int w = lane; w < (int)GP_WORDS; w += WAVE) {
+            // the empty GP: n_feat 1, feat FEAT_LO_ 0 0, out OUT_LO_, n_points 0, every double zero (the six int32 of the head are words 0 .. 2)
+            const uint64_t empty = w == 0 ? (1ull | ((uint64_t)FEAT_LO_ << 32)) : (w == 2 ? (uint64_t)OUT_LO_ : 0ull);
+            dw[w] = take ? sw[w] : empty;
+        }
+        if (lane == 0) installed[g] = take ? 1 : 0;
     }
 }
 

@@ -33,7 +33,8 @@ def test_every_declared_symbol_is_exported(lib):
     for name in qdecl:
         assert getattr(lib, name) is not None
     for hname, table in (("admpc_fleet.h", _lib.FLEET_EXPORTS), ("admpc_lane.h", _lib.LANE_EXPORTS), ("admpc_plant.h", _lib.PLANT_EXPORTS),
-                         ("admpc_learn.h", _lib.LEARN_EXPORTS), ("admpc_hyper.h", _lib.HYPER_EXPORTS)):
+                         ("admpc_learn.h", _lib.LEARN_EXPORTS), ("admpc_hyper.h", _lib.HYPER_EXPORTS),
+                         ("admpc_quad_fleet.h", _lib.QUAD_FLEET_EXPORTS), ("admpc_quad_learn.h", _lib.QUAD_LEARN_EXPORTS)):
         h = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", hname)).read(), flags=re.S)
         decl = set(re.findall(r"\b(admpc_[a-z0-9_]+)\s*\(", h))
         assert decl == set(table), (hname, decl ^ set(table))
