@@ -107,6 +107,9 @@ _QUAD_LEARN = {     # include/admpc_quad_learn.h: observe -> bin -> fit -> insta
     "admpc_quad_rollout_observe_batch": (I, _QUAD_FLEET["admpc_quad_rollout_batch"][1][:-1] + [vp, qop, dp, dp, dp, ip, vp]),
 }
 QUAD_LEARN_EXPORTS = tuple(_QUAD_LEARN)
+# header under include/ -> its table: what load() declares, and what the arity test holds against the headers' own declarations
+TABLES = {"admpc.h": _CAR, "admpc_quad.h": _QUAD, "admpc_fleet.h": _FLEET, "admpc_lane.h": _LANE, "admpc_plant.h": _PLANT,
+          "admpc_learn.h": _LEARN, "admpc_hyper.h": _HYPER, "admpc_quad_fleet.h": _QUAD_FLEET, "admpc_quad_learn.h": _QUAD_LEARN}
 
 _lib = None
 
@@ -124,9 +127,10 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**_CAR, **_QUAD, **_FLEET, **_LANE, **_PLANT, **_LEARN, **_HYPER, **_QUAD_FLEET, **_QUAD_LEARN}.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    for table in TABLES.values():
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

@@ -4,8 +4,8 @@ every group of candidates (include/admpc_fleet.h: admpc_control_step_bank_batch,
 wherever on it the vehicle is (include/admpc_lane.h: admpc_control_step_lane_batch), or closes the loop on the device: a plant step under
 the record just issued, and T steps of controller and plant per call (include/admpc_plant.h: admpc_plant_step_batch,
 admpc_rollout_lane_batch), or learns the residual GP of its model from the steps it has taken, on the device (include/admpc_learn.h:
-observe -> bin -> fit -> install), and searches the hyperparameters of that GP on the device (include/admpc_hyper.h: search -> re-fit ->
-install).
+observe -> bin -> fit -> install; the side it shares with the quadrotor's fleet is learning.py's), and searches the hyperparameters of
+that GP on the device (include/admpc_hyper.h: search -> re-fit -> install).
 
 ``FleetController`` solves the problem of ``ROSGPMPC(point_reference=False)`` (create_ros_ad_mpc.py:41-101: SQP_RTI, Q_DIAG_ROS /
 R_DIAG_ROS) for every vehicle, and does per step what the reference node does per pose message (gp_ad_mpc_node.py:389-438 ->
@@ -29,8 +29,9 @@ from . import _lib
 from . import config as _c
 from .ad_3d import AD3D
 from .ad_3d_optimizer import ocp_config
-from .config import AdmpcGp, AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams, GP_MAX, GP_MAX_POINTS, NX, NU
+from .config import AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams, GP_MAX, NX, NU
 from .engine import BatchSolver, _ptr
+from .learning import FleetLearning, placeholder_gps
 from .ref_traj import RefTrajectory
 
 SAFE_COUNT_THRESHOLD = 10          # consecutive successes before the node issues an MPC command (gp_ad_mpc_node.py:62)
@@ -84,7 +85,9 @@ class FleetRollout(NamedTuple):
     traj: torch.Tensor         # float64 [steps+1,7,B] or None: the poses at the start of every step, and the final ones
 
 
-class FleetController:
+class FleetController(FleetLearning):
+    _FIT, _INSTALL, _GP_CAP, _REC, _EMPTY, _NOUN = "admpc_gp_fit", "admpc_gp_install", GP_MAX, 10, 3, "controller"
+
     def __init__(self, t_horizon, n_mpc_nodes, opt_dt, B, device=0, resample=True, threshold=SAFE_COUNT_THRESHOLD, blend_min=None,
                  blend_max=None, learn=None):
         """``blend_min`` / ``blend_max`` (None: the vehicle's, ad_3d.py) are the ends of the speed band of vel_switch.  ``learn``: a list
@@ -106,8 +109,7 @@ class FleetController:
             learn = [dict(d) for d in learn]
             bins, n_gp = _c.learn_bins(learn)                            # ValueError on bad bins, before anything is created
             self._nominal = BatchSolver(cfg, device=device)
-            cfg = _c.set_gp(cfg.copy(), [dict(feat=d["feat"], out=d["out"], Z=[], alpha=[], length_scale=d["length_scale"],
-                                              sigma_f=d.get("sigma_f", 1.0)) for d in learn])
+            cfg = _c.set_gp(cfg.copy(), placeholder_gps(learn))
         self._eng = eng = BatchSolver(cfg, device=device)
         self.lib, self.device = eng.lib, eng.device
         self.N, self.B, self.opt_dt = N, B, opt_dt
@@ -134,13 +136,8 @@ class FleetController:
         self._plant_model = None
         self.set_plant()
         if learn is not None:
-            self._learn, self.n_learn = learn, n_gp
-            self._obs = AdmpcObserveParams(dt=0.0, blend_min=ad.blend_min, blend_max=ad.blend_max, substeps=1, n_gp=n_gp, gp=bins)
-            self._observer = self._nominal
-            self._prev, self.samples = z(NX, B), z(B, 10)
-            self.bins, self.dropped = z(GP_MAX, GP_MAX_POINTS, 5), z(GP_MAX + 1, dtype=torch.int32)
-            self._gp_dev = z(GP_MAX * C.sizeof(AdmpcGp), dtype=torch.uint8)
-            self.fit_info, self.installed = z(GP_MAX, dtype=torch.int32), z(GP_MAX, dtype=torch.int32)
+            obs = AdmpcObserveParams(dt=0.0, blend_min=ad.blend_min, blend_max=ad.blend_max, substeps=1, n_gp=n_gp, gp=bins)
+            self._alloc_learning(learn, n_gp, obs, (NX, B))
             # the hyperparameter search (search_gp): its state, a scratch of one NLL per candidate, and what the last round picked
             self.hyper, self._nll = z(GP_MAX, _c.GP_HYPER), z(GP_MAX, _c.GP_SEARCH_MAX)
             self.search_info = z(GP_MAX, 2, dtype=torch.int32)
@@ -171,15 +168,28 @@ class FleetController:
         p.M = int(self._ref.trajectory.shape[0])
         p.vel, p.x, p.y, p.psi, p.psi_unwrapped, p.cdist, p.curv = [c.data_ptr() for c in cols]
 
-    def step(self, x, y, yaw, vx, vy, yaw_rate, steer):
-        """One control step for every vehicle: float64 [B] device tensors in.  Asynchronous on the current stream; returns FleetStep."""
-        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
+    def _poses(self, *ins):
+        """The seven pose tensors of a call, checked (float64 [B] on the device), as the pointers the library takes."""
         for t in ins:
             self._eng._chk(t, (self.B,))
-        _lib.check(self.lib.admpc_control_step_batch(
-            self._eng._h, C.byref(self._path), C.byref(self._prm), self.B, *[_ptr(t) for t in ins],
-            _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
-            _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), self._eng._stream()))
+        return [_ptr(t) for t in ins]
+
+    def _outs(self):
+        """The iterate, the state carried from step to step, the workspace and the record: the ten pointers every step entry takes."""
+        return (_ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
+                _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status))
+
+    def _lane(self, who, lane, back, ahead):
+        prm = AdmpcLaneParams(L=int(lane), back=int(back), ahead=int(ahead))
+        if not 34 <= prm.L <= 256 or prm.back < 0 or prm.ahead < 0:
+            raise ValueError("%s: lane must be in [34, 256], back and ahead must not be negative" % who)
+        return prm
+
+    def step(self, x, y, yaw, vx, vy, yaw_rate, steer):
+        """One control step for every vehicle: float64 [B] device tensors in.  Asynchronous on the current stream; returns FleetStep."""
+        poses = self._poses(x, y, yaw, vx, vy, yaw_rate, steer)
+        _lib.check(self.lib.admpc_control_step_batch(self._eng._h, C.byref(self._path), C.byref(self._prm), self.B, *poses, *self._outs(),
+                                                     self._eng._stream()))
         return FleetStep(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt)
 
     def set_paths(self, paths):
@@ -206,14 +216,10 @@ class FleetController:
         is outside the bank ends the step as one whose solve failed (status 4, brake record, cost +inf).  Returns FleetPathStep."""
         if self._bank is None:
             raise ValueError("step_paths: no bank of paths, call set_paths first")
-        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
         self._eng._chk(path_of, (self.B,), torch.int32)
-        for t in ins:
-            self._eng._chk(t, (self.B,))
-        _lib.check(self.lib.admpc_control_step_bank_batch(
-            self._eng._h, self._bank, C.byref(self._prm), self.B, _ptr(path_of), *[_ptr(t) for t in ins],
-            _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
-            _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), _ptr(self.cost), self._eng._stream()))
+        poses = self._poses(x, y, yaw, vx, vy, yaw_rate, steer)
+        _lib.check(self.lib.admpc_control_step_bank_batch(self._eng._h, self._bank, C.byref(self._prm), self.B, _ptr(path_of), *poses,
+                                                          *self._outs(), _ptr(self.cost), self._eng._stream()))
         self._stepped_paths = True
         return FleetPathStep(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt, self.cost)
 
@@ -225,17 +231,11 @@ class FleetController:
         afterwards.  Returns FleetLaneStep; best_of works as after step_paths."""
         if self._bank is None:
             raise ValueError("step_route: no bank of paths, call set_paths first")
-        prm = AdmpcLaneParams(L=int(lane), back=int(back), ahead=int(ahead))
-        if not 34 <= prm.L <= 256 or prm.back < 0 or prm.ahead < 0:
-            raise ValueError("step_route: lane must be in [34, 256], back and ahead must not be negative")
-        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
+        prm = self._lane("step_route", lane, back, ahead)
         self._eng._chk(path_of, (self.B,), torch.int32)
-        for t in ins:
-            self._eng._chk(t, (self.B,))
-        _lib.check(self.lib.admpc_control_step_lane_batch(
-            self._eng._h, self._bank, C.byref(prm), C.byref(self._prm), self.B, _ptr(path_of), _ptr(self.lane_idx), *[_ptr(t) for t in ins],
-            _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
-            _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), _ptr(self.cost), self._eng._stream()))
+        poses = self._poses(x, y, yaw, vx, vy, yaw_rate, steer)
+        _lib.check(self.lib.admpc_control_step_lane_batch(self._eng._h, self._bank, C.byref(prm), C.byref(self._prm), self.B, _ptr(path_of),
+                                                          _ptr(self.lane_idx), *poses, *self._outs(), _ptr(self.cost), self._eng._stream()))
         self._stepped_paths = True
         return FleetLaneStep(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt, self.cost, self.lane_idx)
 
@@ -260,12 +260,10 @@ class FleetController:
     def plant_step(self, x, y, yaw, vx, vy, yaw_rate, steer):
         """Advances the seven float64 [B] device tensors in place by one period of the plant (set_plant) under the controller's last
         ack and mode.  Asynchronous on the current stream."""
-        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
-        for t in ins:
-            self._eng._chk(t, (self.B,))
+        poses = self._poses(x, y, yaw, vx, vy, yaw_rate, steer)
         model = self._plant_model if self._plant_model is not None else self._eng
-        _lib.check(self.lib.admpc_plant_step_batch(model._h, C.byref(self._plant), self.B, _ptr(self.ack), _ptr(self.mode),
-                                                   *[_ptr(t) for t in ins], self._eng._stream()))
+        _lib.check(self.lib.admpc_plant_step_batch(model._h, C.byref(self._plant), self.B, _ptr(self.ack), _ptr(self.mode), *poses,
+                                                   self._eng._stream()))
 
     def rollout_route(self, path_of, x, y, yaw, vx, vy, yaw_rate, steer, steps, lane=64, back=8, ahead=64, record=False, accumulate=False,
                       observe=False):
@@ -276,29 +274,23 @@ class FleetController:
         as after step_route."""
         if self._bank is None:
             raise ValueError("rollout_route: no bank of paths, call set_paths first")
-        prm = AdmpcLaneParams(L=int(lane), back=int(back), ahead=int(ahead))
-        if not 34 <= prm.L <= 256 or prm.back < 0 or prm.ahead < 0:
-            raise ValueError("rollout_route: lane must be in [34, 256], back and ahead must not be negative")
+        prm = self._lane("rollout_route", lane, back, ahead)
         T = int(steps)
         if not 0 <= T <= 4096:
             raise ValueError("rollout_route: steps must be in [0, 4096]")
-        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
         self._eng._chk(path_of, (self.B,), torch.int32)
-        for t in ins:
-            self._eng._chk(t, (self.B,))
+        poses = self._poses(x, y, yaw, vx, vy, yaw_rate, steer)
         if not accumulate:
             self.tally.zero_()
             self.counts.zero_()
         traj = torch.empty((T + 1, NX, self.B), dtype=torch.float64, device=self.device) if record else None
         if record and T == 0:
-            for i, t in enumerate(ins):
+            for i, t in enumerate((x, y, yaw, vx, vy, yaw_rate, steer)):
                 traj[0, i].copy_(t)
         model = self._plant_model._h if self._plant_model is not None else None
         args = (self._eng._h, self._bank, C.byref(prm), C.byref(self._prm), model, C.byref(self._plant), self.B, T,
-                _ptr(path_of), _ptr(self.lane_idx), *[_ptr(t) for t in ins],
-                _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.safe_count), _ptr(self.prev_u), _ptr(self.has_valid), _ptr(self._work),
-                _ptr(self.ack), _ptr(self.mode), _ptr(self.valid), _ptr(self.status), _ptr(self.cost),
-                _ptr(self.tally), _ptr(self.counts), _ptr(traj) if record else None)
+                _ptr(path_of), _ptr(self.lane_idx), *poses, *self._outs(), _ptr(self.cost), _ptr(self.tally), _ptr(self.counts),
+                _ptr(traj) if record else None)
         if observe:
             obs = self._observe_params("rollout_route")
             _lib.check(self.lib.admpc_rollout_observe_lane_batch(*args, self._observer._h, C.byref(obs), _ptr(self._prev), _ptr(self.samples),
@@ -309,11 +301,7 @@ class FleetController:
         return FleetRollout(self.ack, self.mode, self.status, self.valid, self.x_opt, self.w_opt, self.cost, self.lane_idx, self.tally,
                             self.counts, traj)
 
-    # -- learning the residual GP (include/admpc_learn.h) ------------------------------------------------------------------------------
-    def _learns(self, who):
-        if self._learn is None:
-            raise ValueError("%s: this controller does not learn, create it with learn=[...]" % who)
-
+    # -- learning the residual GP (include/admpc_learn.h): what the car adds to learning.py's FleetLearning -------------------------------
     def _observe_params(self, who, observing=True):
         """The parameters of an observation as things stand: the plant's period and sub-steps, the controller's own speed band.  A call
         that observes is refused when the plant model's input bounds are not the controller's."""
@@ -326,52 +314,31 @@ class FleetController:
         o.dt, o.substeps, o.blend_min, o.blend_max = self._plant.dt, self._plant.substeps, self._prm.blend_min, self._prm.blend_max
         return o
 
-    def set_observer(self, learned=False):
-        """Which model predicts in observe: the nominal one (default; its residual is what fit_gp has to learn) or the controller's own
-        handle with whatever GP is installed (what is left of the residual after learning)."""
-        self._learns("set_observer")
-        self._observer = self._eng if learned else self._nominal
+    def _fitted(self):
+        self._searched = False
 
-    def observe_reset(self):
-        """Forgets every sample: bins and dropped are zeroed on the current stream."""
-        self._learns("observe_reset")
-        self.bins.zero_()
-        self.dropped.zero_()
+    def _head(self, g, d):
+        """After a search_gp the length scales and sigma_f it found (the device's own doubles), not those given to ``learn``."""
+        if not self._searched:
+            return d
+        h = self.hyper[g].tolist()
+        return dict(d, length_scale=h[10:10 + int(self._obs.gp[g].n_feat)], sigma_f=h[13])
 
     def observe_latch(self, x, y, yaw, vx, vy, yaw_rate, steer):
         """Takes the poses the next observe will predict from.  Asynchronous on the current stream."""
         self._observe_params("observe_latch")
-        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
-        for t in ins:
-            self._eng._chk(t, (self.B,))
-        _lib.check(self.lib.admpc_observe_latch_batch(self.device.index, self.B, *[_ptr(t) for t in ins], _ptr(self._prev), self._eng._stream()))
+        poses = self._poses(x, y, yaw, vx, vy, yaw_rate, steer)
+        _lib.check(self.lib.admpc_observe_latch_batch(self.device.index, self.B, *poses, _ptr(self._prev), self._eng._stream()))
 
     def observe(self, x, y, yaw, vx, vy, yaw_rate, steer):
         """The poses one plant period after the latched ones, under the controller's last ack and mode: what the observer's model did not
         predict of v_x, v_y and the yaw rate, per second, goes into ``samples`` [B,10] and from there into ``bins`` [4,32,5] (count, feature
         sums, target sum per bin) and ``dropped`` [5]; the poses are latched for the next call.  Asynchronous on the current stream."""
         obs = self._observe_params("observe")
-        ins = (x, y, yaw, vx, vy, yaw_rate, steer)
-        for t in ins:
-            self._eng._chk(t, (self.B,))
+        poses = self._poses(x, y, yaw, vx, vy, yaw_rate, steer)
         _lib.check(self.lib.admpc_observe_batch(self._observer._h, C.byref(self._plant), C.byref(obs), self.B, _ptr(self.ack), _ptr(self.mode),
-                                                *[_ptr(t) for t in ins], _ptr(self._prev), _ptr(self.samples), _ptr(self.bins),
-                                                _ptr(self.dropped), self._eng._stream()))
-
-    def fit_gp(self, min_count=1, install=True):
-        """Fits every regressor to the means of its bins with at least `min_count` samples, at the hyperparameters given to ``learn``, and
-        (`install`) overwrites the GPs of the controller's handle on the device.  Asynchronous on the current stream; returns the device
-        tensors (info int32 [n], installed int32 [n] or None): info[g] is the number of points, or -(k + 1) where pivot k failed and the
-        GP is empty; installed[g] is 1 where the record passed the install's check."""
-        obs = self._observe_params("fit_gp", observing=False)
-        n = self.n_learn
-        _lib.check(self.lib.admpc_gp_fit(self.device.index, C.byref(obs), int(min_count), _ptr(self.bins), _ptr(self._gp_dev), _ptr(self.fit_info),
-                                         self._eng._stream()))
-        self._searched = False
-        if not install:
-            return self.fit_info[:n], None
-        _lib.check(self.lib.admpc_gp_install(self._eng._h, n, _ptr(self._gp_dev), _ptr(self.installed), self._eng._stream()))
-        return self.fit_info[:n], self.installed[:n]
+                                                *poses, _ptr(self._prev), _ptr(self.samples), _ptr(self.bins), _ptr(self.dropped),
+                                                self._eng._stream()))
 
     def search_gp(self, min_count=1, grid=5, rounds=10, shrink=0.5, bounds=None, resume=False, install=True):
         """Searches the length scales, sigma_f and the noise of every regressor for the smallest negative log marginal likelihood of its
@@ -412,35 +379,6 @@ class FleetController:
             else:
                 out.append(dict(length_scale=[float(hy[g, 10 + k]) for k in range(nf)], sigma_f=float(hy[g, 13]), noise=float(hy[g, 14]),
                                 nll=float(hy[g, 15])))
-        return out
-
-    def learned_gps(self):
-        """The GPs of the last fit_gp or search_gp as the list of dicts config.set_gp takes (synchronises): to save the model, or to
-        create another handle with it.  length_scale is the one given to ``learn`` after a fit_gp, and the one found after a search_gp:
-        the device's own double, from which set_gp forms the inv_l2 that was installed.  A record the install refuses (a number that is
-        not finite) is returned as the install leaves it in the handle: the empty GP, feature 3, row 3, no points, mean 0."""
-        self._learns("learned_gps")
-        torch.cuda.current_stream(self.device).synchronize()
-        raw = self._gp_dev.cpu().numpy().tobytes()
-        hy = self.hyper.cpu().numpy()
-        out = []
-        for g, d in enumerate(self._learn):
-            if self._searched:
-                d = dict(d, length_scale=[float(hy[g, 10 + k]) for k in range(int(self._obs.gp[g].n_feat))], sigma_f=float(hy[g, 13]))
-            gp = AdmpcGp.from_buffer_copy(raw, g * C.sizeof(AdmpcGp))
-            nf, n = int(gp.n_feat), int(gp.n_points)
-            if nf == 0:                                                  # no fit yet: the placeholder
-                out.append(dict(feat=d["feat"], out=d["out"], Z=[], alpha=[], length_scale=d["length_scale"], sigma_f=d.get("sigma_f", 1.0), ymean=0.0))
-                continue
-            nums = [gp.sigma_f, gp.ymean] + [gp.inv_l2[k] for k in range(nf)] + [gp.alpha[i] for i in range(n)] + \
-                [gp.Z[k][i] for k in range(nf) for i in range(n)]
-            if not np.isfinite(np.array(nums, dtype=np.float64)).all():      # (the fit writes no other head than the one given to learn)
-                out.append(dict(feat=3, out=3, Z=[], alpha=[], length_scale=1.0, sigma_f=0.0, ymean=0.0))
-                continue
-            out.append(dict(feat=[int(gp.feat[k]) for k in range(nf)], out=int(gp.out),
-                            Z=np.array([[gp.Z[k][i] for k in range(nf)] for i in range(n)], dtype=np.float64).reshape(n, nf),
-                            alpha=np.array([gp.alpha[i] for i in range(n)], dtype=np.float64), length_scale=d["length_scale"],
-                            sigma_f=float(gp.sigma_f), ymean=float(gp.ymean)))
         return out
 
     def best_of(self, group, cost=None):

@@ -3,7 +3,8 @@
 simplified simulator for ``control_period / simulation_dt`` sub-steps -- for B vehicles, T steps per call, with a tally of the tracking
 error.  Built on ``QuadBatchSolver``; the OCP is shaped as ``Quad3DOptimizer`` shapes it (weight expansion for the quaternion, the
 vehicle's constants, the linear drag, one cluster of residual GPs).  With ``learn`` the fleet fits those GPs itself, on the device, from
-the steps it has flown (include/admpc_quad_learn.h: observe -> bin -> fit -> install)."""
+the steps it has flown (include/admpc_quad_learn.h: observe -> bin -> fit -> install; the side it shares with the car's fleet is
+learning.py's)."""
 import ctypes as C
 from collections import namedtuple
 
@@ -12,7 +13,7 @@ import torch
 
 from . import _lib
 from .engine import QuadBatchSolver, _ptr
-from .config import AdmpcGp, GP_MAX_POINTS
+from .learning import FleetLearning, placeholder_gps
 from .quad_config import (QNX, QNU, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, default_quad_config, quad_learn_bins, quad_plant_params,
                           set_quad_gp)
 
@@ -58,7 +59,7 @@ def fleet_quad_config(quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=
     return cfg
 
 
-class QuadFleet:
+class QuadFleet(FleetLearning):
     """B quadrotors, each on one of K reference trajectories.  State on the device: ``x`` [B,13], ``idx`` [B] int32 (the sliding index),
     ``traj_of`` [B] int32, the persistent never-shifted iterate ``x_opt`` [B,N+1,13] / ``w_opt`` [B,N,4], the window ``yref`` / ``yref_e``,
     ``cost`` / ``status`` / ``iters`` of the last step, ``tally`` [B,3] (sum |e|, sum |e|^2, max |e|) and ``counts`` [B,3] int32 (steps,
@@ -69,6 +70,7 @@ class QuadFleet:
     on the device; a second, nominal handle (no GP, same vehicle, same rdrv) predicts for observe; the observation's period is the
     control period, predicted in ``observe_substeps`` RK4 steps.  ``samples`` [B,14], ``bins`` [3,32,5] and ``dropped`` [4] are the
     record, the statistics and the counts of include/admpc_quad_learn.h."""
+    _FIT, _INSTALL, _GP_CAP, _REC, _EMPTY, _NOUN = "admpc_quad_gp_fit", "admpc_quad_gp_install", QUAD_GP_MAX, QUAD_REC, 7, "fleet"
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
                  gp_regressors=None, rdrv_d_mat=None, device=0, learn=None, observe_substeps=1):
@@ -88,8 +90,7 @@ class QuadFleet:
         cfg = fleet_quad_config(quad, t_horizon, n_nodes, q_cost, r_cost, gp_regressors, rdrv_d_mat)
         if learn is not None:
             self._nominal = QuadBatchSolver(cfg, device=device)
-            cfg = set_quad_gp(cfg.copy(), [dict(feat=d["feat"], out=d["out"], Z=[], alpha=[], length_scale=d["length_scale"],
-                                                sigma_f=d.get("sigma_f", 1.0)) for d in learn])
+            cfg = set_quad_gp(cfg.copy(), placeholder_gps(learn))
         self._eng = QuadBatchSolver(cfg, device=device)
         self.lib, self.device, self.device_index, self.cfg = self._eng.lib, self._eng.device, self._eng.device_index, self._eng.cfg
         self._bank, self._M = None, None
@@ -107,13 +108,8 @@ class QuadFleet:
         self._eng.solve(self.x, self.yref, self.yref_e, f64(B, N + 1, QNX), f64(B, N, QNU))
         torch.cuda.synchronize(dev)
         if learn is not None:
-            self._learn, self.n_learn = learn, n_gp
-            self._obs = AdmpcQuadObserveParams(dt=self.control_period, substeps=int(observe_substeps), n_gp=n_gp, gp=bins)
-            self._observer = self._nominal
-            self._prev, self.samples = f64(B, QNX), f64(B, QUAD_REC)
-            self.bins, self.dropped = f64(QUAD_GP_MAX, GP_MAX_POINTS, 5), i32(QUAD_GP_MAX + 1)
-            self._gp_dev = torch.zeros(QUAD_GP_MAX * C.sizeof(AdmpcGp), dtype=torch.uint8, device=dev)
-            self.fit_info, self.installed = i32(QUAD_GP_MAX), i32(QUAD_GP_MAX)
+            obs = AdmpcQuadObserveParams(dt=self.control_period, substeps=int(observe_substeps), n_gp=n_gp, gp=bins)
+            self._alloc_learning(learn, n_gp, obs, (B, QNX))
 
     # -- lifetime ---------------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -186,15 +182,19 @@ class QuadFleet:
                                                        _ptr(self.yref_e), _ptr(pos_ref), self._stream()))
 
     # -- the plant --------------------------------------------------------------------------------------------------------------------
+    def _u_stride(self, who, u, B):
+        """The row stride of the activations u, a float64 [B,4] view with unit inner stride; a single row has no stride to speak of."""
+        if u.dtype != torch.float64 or u.device != self.device or tuple(u.shape) != (B, QNU) or u.stride(1) != 1 or (B > 1 and u.stride(0) < QNU):
+            raise ValueError("%s: u must be float64 [B,4] on the fleet's device with unit inner stride" % who)
+        return u.stride(0) if B > 1 else QNU
+
     def plant_step(self, u, x=None):
         """One control period of the simulator under u [B,4] (or any float64 view with rows of 4 and a row stride, such as
         ``w_opt[:, 0, :]``), in place on x (default: the fleet's state)."""
         x = self.x if x is None else x
         self._eng._chk(x, (x.shape[0], QNX))
         Bx = x.shape[0]
-        if u.dtype != torch.float64 or u.device != self.device or tuple(u.shape) != (Bx, QNU) or u.stride(1) != 1 or (Bx > 1 and u.stride(0) < QNU):
-            raise ValueError("plant_step: u must be float64 [B,4] on the fleet's device with unit inner stride")
-        stride = u.stride(0) if Bx > 1 else QNU
+        stride = self._u_stride("plant_step", u, Bx)
         _lib.check(self.lib.admpc_quad_plant_step_batch(C.byref(self._plant), self.device_index, Bx, C.c_void_p(u.data_ptr()), stride, _ptr(x),
                                                         self._stream()))
 
@@ -235,23 +235,7 @@ class QuadFleet:
         NaN for a vehicle that has taken no step.  A device tensor [B]."""
         return self.tally[:, 0] / self.counts[:, 0].to(torch.float64)
 
-    # -- learning the body-frame residual GPs (include/admpc_quad_learn.h) --------------------------------------------------------------
-    def _learns(self, who):
-        if self._learn is None:
-            raise ValueError("%s: this fleet does not learn, create it with learn=[...]" % who)
-
-    def set_observer(self, learned=False):
-        """Which handle predicts in observe: the nominal one (default; its residual is what fit_gp has to learn) or the controller's own
-        with whatever GPs are installed (what is left of the residual after learning)."""
-        self._learns("set_observer")
-        self._observer = self._eng if learned else self._nominal
-
-    def observe_reset(self):
-        """Forgets every sample: bins and dropped are zeroed on the current stream."""
-        self._learns("observe_reset")
-        self.bins.zero_()
-        self.dropped.zero_()
-
+    # -- learning the body-frame residual GPs (include/admpc_quad_learn.h): what the quadrotor adds to learning.py's FleetLearning ------
     def observe_latch(self):
         """Takes the fleet's state as the one the next observe will predict from.  Asynchronous on the current stream."""
         self._learns("observe_latch")
@@ -264,48 +248,7 @@ class QuadFleet:
         next call.  Asynchronous on the current stream."""
         self._learns("observe")
         u = self.w_opt[:, 0, :] if u is None else u
-        if u.dtype != torch.float64 or u.device != self.device or tuple(u.shape) != (self.B, QNU) or u.stride(1) != 1 or (self.B > 1 and u.stride(0) < QNU):
-            raise ValueError("observe: u must be float64 [B,4] on the fleet's device with unit inner stride")
-        stride = u.stride(0) if self.B > 1 else QNU
+        stride = self._u_stride("observe", u, self.B)
         _lib.check(self.lib.admpc_quad_observe_batch(self._observer._h, C.byref(self._plant), C.byref(self._obs), self.B, C.c_void_p(u.data_ptr()),
                                                      stride, _ptr(self.x), _ptr(self._prev), _ptr(self.samples), _ptr(self.bins),
                                                      _ptr(self.dropped), self._stream()))
-
-    def fit_gp(self, min_count=1, install=True):
-        """Fits every regressor to the means of its bins with at least `min_count` samples, at the hyperparameters given to ``learn``, and
-        (`install`) overwrites the GPs of the controller's handle on the device.  Asynchronous on the current stream; returns the device
-        tensors (info int32 [n], installed int32 [n] or None): info[g] is the number of points, or -(k + 1) where pivot k failed and the
-        GP is empty; installed[g] is 1 where the record passed the install's check."""
-        self._learns("fit_gp")
-        n = self.n_learn
-        _lib.check(self.lib.admpc_quad_gp_fit(self.device_index, C.byref(self._obs), int(min_count), _ptr(self.bins), _ptr(self._gp_dev),
-                                              _ptr(self.fit_info), self._stream()))
-        if not install:
-            return self.fit_info[:n], None
-        _lib.check(self.lib.admpc_quad_gp_install(self._eng._h, n, _ptr(self._gp_dev), _ptr(self.installed), self._stream()))
-        return self.fit_info[:n], self.installed[:n]
-
-    def learned_gps(self):
-        """The GPs of the last fit_gp as the list of dicts ``set_quad_gp`` / ``gp_regressors=`` take (synchronises): to save the model, or
-        to create another handle with what was learned.  A record the install refuses (a number that is not finite) is returned as the
-        install leaves it in the handle: the empty GP, feature 7, row 7, no points, mean 0."""
-        self._learns("learned_gps")
-        torch.cuda.current_stream(self.device).synchronize()
-        raw = self._gp_dev.cpu().numpy().tobytes()
-        out = []
-        for g, d in enumerate(self._learn):
-            gp = AdmpcGp.from_buffer_copy(raw, g * C.sizeof(AdmpcGp))
-            nf, n = int(gp.n_feat), int(gp.n_points)
-            if nf == 0:                                                  # no fit yet: the placeholder
-                out.append(dict(feat=d["feat"], out=d["out"], Z=[], alpha=[], length_scale=d["length_scale"], sigma_f=d.get("sigma_f", 1.0), ymean=0.0))
-                continue
-            nums = [gp.sigma_f, gp.ymean] + [gp.inv_l2[k] for k in range(nf)] + [gp.alpha[i] for i in range(n)] + \
-                [gp.Z[k][i] for k in range(nf) for i in range(n)]
-            if not np.isfinite(np.array(nums, dtype=np.float64)).all():      # (the fit writes no other head than the one given to learn)
-                out.append(dict(feat=7, out=7, Z=[], alpha=[], length_scale=1.0, sigma_f=0.0, ymean=0.0))
-                continue
-            out.append(dict(feat=[int(gp.feat[k]) for k in range(nf)], out=int(gp.out),
-                            Z=np.array([[gp.Z[k][i] for k in range(nf)] for i in range(n)], dtype=np.float64).reshape(n, nf),
-                            alpha=np.array([gp.alpha[i] for i in range(n)], dtype=np.float64), length_scale=d["length_scale"],
-                            sigma_f=float(gp.sigma_f), ymean=float(gp.ymean)))
-        return out

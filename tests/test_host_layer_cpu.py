@@ -1,5 +1,5 @@
 """The Python host layer without a GPU: the layout of the staging buffer (engine.packed_layout) and the prototype table of
-ad_mpc_amd/_lib.py against the declarations of include/admpc.h and include/admpc_quad.h."""
+ad_mpc_amd/_lib.py against the declarations of the nine headers under include/."""
 import ctypes as C
 import os
 import re
@@ -55,29 +55,34 @@ def lib():
     return _lib.load()
 
 
-def _declared_arity():
-    """name -> number of parameters, from the two public headers: comments stripped, the parameter list split on commas, (void) is zero."""
-    arity = {}
-    for h in ("admpc.h", "admpc_quad.h"):
-        txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
-        for name, params in re.findall(r"\b(admpc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
-            arity[name] = 0 if params.strip() in ("", "void") else len(params.split(","))
-    return arity
+def _declared_arity(header):
+    """name -> number of parameters, from one header under include/: both kinds of comment stripped, the parameter list split on commas,
+    (void) is zero."""
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    txt = re.sub(r"//[^\n]*", "", txt)
+    return {name: 0 if params.strip() in ("", "void") else len(params.split(","))
+            for name, params in re.findall(r"\b(admpc_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt)}
 
 
 def test_every_export_has_a_prototype_of_the_declared_arity(lib):
     names = _lib.EXPORTS + _lib.QUAD_EXPORTS
     assert len(set(names)) == len(names) == 34
-    arity = _declared_arity()
-    assert set(arity) == set(names), set(arity) ^ set(names)
-    no_result = {"admpc_destroy", "admpc_quad_destroy", "admpc_quad_default_config"}
+    assert len(_lib.TABLES) == 9 and list(_lib.TABLES)[:2] == ["admpc.h", "admpc_quad.h"]
+    assert tuple(_lib.TABLES["admpc.h"]) == _lib.EXPORTS and tuple(_lib.TABLES["admpc_quad.h"]) == _lib.QUAD_EXPORTS
+    no_result = {"admpc_destroy", "admpc_quad_destroy", "admpc_quad_default_config", "admpc_path_bank_destroy", "admpc_quad_traj_bank_destroy"}
     strings = {"admpc_last_error", "admpc_version"}
-    for name in names:
-        fn = getattr(lib, name)
-        assert fn.argtypes is not None, "%s: no prototype applied" % name
-        want = None if name in no_result else C.c_char_p if name in strings else C.c_int
-        assert fn.restype is want, "%s: restype %r" % (name, fn.restype)
-        assert len(fn.argtypes) == arity[name], "%s: %d argtypes, %d declared parameters" % (name, len(fn.argtypes), arity[name])
+    seen = []
+    for header, table in _lib.TABLES.items():
+        arity = _declared_arity(header)
+        assert set(arity) == set(table), "%s: %s" % (header, set(arity) ^ set(table))
+        for name in table:
+            fn = getattr(lib, name)
+            assert fn.argtypes is not None, "%s: no prototype applied" % name
+            want = None if name in no_result else C.c_char_p if name in strings else C.c_int
+            assert fn.restype is want, "%s: restype %r" % (name, fn.restype)
+            assert len(fn.argtypes) == arity[name], "%s: %d argtypes, %d declared parameters" % (name, len(fn.argtypes), arity[name])
+        seen += list(table)
+    assert len(set(seen)) == len(seen) == 61                 # no name is declared by two headers
 
 
 def test_exports_are_the_two_parts_of_the_table():
