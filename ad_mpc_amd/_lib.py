@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 from .config import AdmpcConfig, AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
-from .quad_config import AdmpcQuadConfig, AdmpcQuadObserveParams, AdmpcQuadPlantParams
+from .quad_config import AdmpcQuadConfig, AdmpcQuadNoiseParams, AdmpcQuadObserveParams, AdmpcQuadPlantParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libadmpc.so")
@@ -110,6 +110,15 @@ QUAD_LEARN_EXPORTS = tuple(_QUAD_LEARN)
 # header under include/ -> its table: what load() declares, and what the arity test holds against the headers' own declarations
 TABLES = {"admpc.h": _CAR, "admpc_quad.h": _QUAD, "admpc_fleet.h": _FLEET, "admpc_lane.h": _LANE, "admpc_plant.h": _PLANT,
           "admpc_learn.h": _LEARN, "admpc_hyper.h": _HYPER, "admpc_quad_fleet.h": _QUAD_FLEET, "admpc_quad_learn.h": _QUAD_LEARN}
+# the headers behind the nine of TABLES, declared by load() in the same way
+np_ = C.POINTER(AdmpcQuadNoiseParams)
+_QUAD_NOISE = {     # include/admpc_quad_noise.h: the simulator's random disturbances: the draws, the noisy plant step, the noisy rollout
+    "admpc_quad_noise_draw_batch": (I, [np_, I, I, I, ip, dp, ip, vp]),
+    "admpc_quad_plant_step_noise_batch": (I, [pp, np_, I, I, dp, C.c_int64, dp, ip, vp]),
+    "admpc_quad_rollout_noise_batch": (I, _QUAD_LEARN["admpc_quad_rollout_observe_batch"][1][:-1] + [np_, ip, vp]),
+}
+QUAD_NOISE_EXPORTS = tuple(_QUAD_NOISE)
+MORE_TABLES = {"admpc_quad_noise.h": _QUAD_NOISE}
 
 _lib = None
 
@@ -119,7 +128,7 @@ class AdmpcError(RuntimeError):
 
 
 def load():
-    """dlopen libadmpc.so and declare the prototypes of the nine headers under include/ (no GPU needed for this)."""
+    """dlopen libadmpc.so and declare the prototypes of the headers under include/ (no GPU needed for this)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -127,7 +136,7 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for table in TABLES.values():
+    for table in list(TABLES.values()) + list(MORE_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -15,6 +15,7 @@
 #include "../../include/admpc_quad.h"
 #include "../../include/admpc_quad_fleet.h"
 #include "../../include/admpc_quad_learn.h"
+#include "../../include/admpc_quad_noise.h"
 
 // Every entry point runs on the solver's device and restores the caller's current device on return (a host with several GPUs
 // keeps its own current device: torch allocations and default-stream work of the caller are not redirected).
@@ -51,7 +52,8 @@ struct RolloutArgs {
     double* tally; int32_t* counts;
 };
 
-// admpc_quad_rollout_batch's arguments but T, the records (traj_out, u_out) and the stream
+// admpc_quad_rollout_batch's arguments but T, the records (traj_out, u_out) and the stream; noise: null, or the disturbances of
+// admpc_quad_rollout_noise_batch (checked by it) with the vehicles' period counters
 struct QuadRolloutArgs {
     AdmpcQuadSolver* s; const AdmpcQuadTrajBank* bank; const AdmpcQuadPlantParams* plant;
     int over, B;
@@ -59,7 +61,10 @@ struct QuadRolloutArgs {
     double *x, *xbar, *ubar, *yref, *yref_e, *cost;
     int32_t *status, *iters;
     double* tally; int32_t* counts;
+    const AdmpcQuadNoiseParams* noise; uint64_t* noise_step;
 };
+
+struct QuadPlantArgs;       // quad_sim_dev.h: what one launch of a quadrotor plant kernel works on
 
 #define ADMPC_HIDDEN extern "C" __attribute__((visibility("hidden")))
 
@@ -91,3 +96,11 @@ ADMPC_HIDDEN int admpc_quad_plant_params_check(const char* who, const AdmpcQuadP
 // admpc_quad_fleet.hip: the refusals of a rollout up to those of its arrays (under admpc_quad_rollout_batch's name), and one checked period
 ADMPC_HIDDEN int admpc_quad_rollout_check(const QuadRolloutArgs& a, int T);
 ADMPC_HIDDEN int admpc_quad_rollout_enqueue(const QuadRolloutArgs& a, double* traj_pre, double* traj_post, double* u_out, void* stream);
+// admpc_quad_fleet.hip, admpc_quad_learn.hip: a whole rollout and a whole observed rollout behind their arguments' block, refusals and
+// no-ops included (under the names of admpc_quad_rollout_batch and admpc_quad_rollout_observe_batch)
+ADMPC_HIDDEN int admpc_quad_rollout_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, void* stream);
+ADMPC_HIDDEN int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, const AdmpcQuadSolver* model,
+                                                const AdmpcQuadObserveParams* obs, double* prev, double* samples, double* bins, int32_t* dropped,
+                                                void* stream);
+// admpc_quad_noise.hip: one launch of the noisy plant kernel for filled arguments and checked disturbances, B > 0
+ADMPC_HIDDEN int admpc_quad_plant_noise_launch(const QuadPlantArgs& a, const AdmpcQuadNoiseParams* noise, uint64_t* noise_step, void* stream);

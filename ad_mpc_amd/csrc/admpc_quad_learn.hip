@@ -245,14 +245,12 @@ int admpc_quad_gp_install(AdmpcQuadSolver* s, int n_gp, const AdmpcGp* gp_dev, i
     return ADMPC_OK;
 }
 
-int admpc_quad_rollout_observe_batch(AdmpcQuadSolver* s, const AdmpcQuadTrajBank* bank, const AdmpcQuadPlantParams* plant, int over, int B,
-                                     int T, const int32_t* traj_of, int32_t* idx, double* x, double* xbar, double* ubar,
-                                     double* yref, double* yref_e, double* cost, int32_t* status, int32_t* iters,
-                                     double* tally, int32_t* counts, double* traj_out, double* u_out,
-                                     const AdmpcQuadSolver* model, const AdmpcQuadObserveParams* obs,
-                                     double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
+// admpc_quad_rollout_observe_batch behind its arguments' block: the refusals, the no-ops, the latch and the T observed periods; with
+// a.noise the plant of every period is the noisy one (admpc_quad_noise.hip), whose counter array is refused last
+int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, const AdmpcQuadSolver* model,
+                                   const AdmpcQuadObserveParams* obs, double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
 {
-    const QuadRolloutArgs a = { s, bank, plant, over, B, traj_of, idx, x, xbar, ubar, yref, yref_e, cost, status, iters, tally, counts };
+    const int B = a.B;
     int rc = quad_observe_params_check("admpc_quad_rollout_observe_batch", obs);
     if (rc) return rc;
     if (!model) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_observe_batch: null model");
@@ -260,23 +258,35 @@ int admpc_quad_rollout_observe_batch(AdmpcQuadSolver* s, const AdmpcQuadTrajBank
     rc = admpc_quad_rollout_check(a, T);
     if (rc) return rc;
     int device = 0, model_device = 0, N = 0;
-    (void)admpc_quad_solver_info(s, &device, &N, nullptr);
+    (void)admpc_quad_solver_info(a.s, &device, &N, nullptr);
     (void)admpc_quad_solver_info(model, &model_device, nullptr, nullptr);
     if (model_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_observe_batch: the model lives on another device than the solver");
     if (B == 0 || T == 0) return ADMPC_OK;
-    if (!traj_of || !idx || !x || !xbar || !ubar || !yref || !yref_e || !status || !tally || !counts || !prev || !samples || !bins || !dropped)
+    if (!a.traj_of || !a.idx || !a.x || !a.xbar || !a.ubar || !a.yref || !a.yref_e || !a.status || !a.tally || !a.counts || !prev || !samples || !bins || !dropped)
         return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_observe_batch: null array argument");
+    if (a.noise && !a.noise_step) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_noise_batch: null noise_step");
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    rc = quad_latch_launch(B, x, prev, stream);
+    rc = quad_latch_launch(B, a.x, prev, stream);
     const size_t slot = (size_t)B * QX;
     // slot 0 of traj_out is written by the first period; every period writes the state it leaves into the next slot
     for (int t = 0; t < T && !rc; ++t) {
         rc = admpc_quad_rollout_enqueue(a, t == 0 ? traj_out : nullptr, traj_out ? traj_out + (size_t)(t + 1) * slot : nullptr,
                                         u_out ? u_out + (size_t)t * B * QU : nullptr, stream);
-        if (!rc) rc = quad_observe_launch(model, plant, obs, B, ubar, (long long)N * QU, x, prev, samples, bins, dropped, stream);
+        if (!rc) rc = quad_observe_launch(model, a.plant, obs, B, a.ubar, (long long)N * QU, a.x, prev, samples, bins, dropped, stream);
     }
     return rc;
+}
+
+int admpc_quad_rollout_observe_batch(AdmpcQuadSolver* s, const AdmpcQuadTrajBank* bank, const AdmpcQuadPlantParams* plant, int over, int B,
+                                     int T, const int32_t* traj_of, int32_t* idx, double* x, double* xbar, double* ubar,
+                                     double* yref, double* yref_e, double* cost, int32_t* status, int32_t* iters,
+                                     double* tally, int32_t* counts, double* traj_out, double* u_out,
+                                     const AdmpcQuadSolver* model, const AdmpcQuadObserveParams* obs,
+                                     double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
+{
+    const QuadRolloutArgs a = { s, bank, plant, over, B, traj_of, idx, x, xbar, ubar, yref, yref_e, cost, status, iters, tally, counts, nullptr, nullptr };
+    return admpc_quad_rollout_observe_run(a, T, traj_out, u_out, model, obs, prev, samples, bins, dropped, stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 """ctypes mirror of include/admpc_quad.h (AdmpcQuadConfig) and the shipped quadrotor problem
 (acados_models/my_quad_acados_ocp.json, src/quad_mpc/quad_3d.py:40-74); of include/admpc_quad_fleet.h (AdmpcQuadPlantParams), the
 simulator's vehicle (src/quad_mpc/quad_3d.py:22-95); of include/admpc_quad_learn.h (AdmpcQuadObserveParams), the regressors a fleet
-learns on the device."""
+learns on the device; of include/admpc_quad_noise.h (AdmpcQuadNoiseParams), the simulator's random disturbances."""
 import ctypes as C
 import math
 
@@ -98,6 +98,12 @@ class AdmpcQuadPlantParams(C.Structure):
         return c
 
 
+class AdmpcQuadNoiseParams(C.Structure):
+    """include/admpc_quad_noise.h: the key of the generator, the two switches, the scales of the reference's distributions."""
+    _fields_ = [("seed", C.c_uint64), ("noisy", C.c_int32), ("motor_noise", C.c_int32), ("force_std", C.c_double), ("torque_std", C.c_double),
+                ("motor_bias", C.c_double), ("motor_ref", C.c_double), ("motor_std", C.c_double)]
+
+
 class AdmpcQuadObserveParams(C.Structure):
     """include/admpc_quad_learn.h: the period between two states, the RK4 sub-steps of the prediction, the regressors to learn."""
     _fields_ = [("dt", C.c_double), ("substeps", C.c_int32), ("n_gp", C.c_int32), ("gp", AdmpcGpBins * QUAD_GP_MAX)]
@@ -116,7 +122,7 @@ class SimQuad:
     """The attributes of the reference's ``Quadrotor3D`` (quad_3d.py:22-95) that the plant reads, with its values: the vehicle of
     ``quad_plant_params(None, ...)`` and of the tests."""
 
-    def __init__(self, drag=False, payload=False):
+    def __init__(self, drag=False, payload=False, noisy=False, motor_noise=False):
         self.max_thrust = 20
         self.max_input_value, self.min_input_value = 1, 0
         self.J = np.array([.03, .03, .06])
@@ -130,7 +136,7 @@ class SimQuad:
         self.g = np.array([[0], [0], [9.81]])
         self.rotor_drag_xy, self.rotor_drag_z = 0.3, 0.0
         self.aero_drag = 0.08
-        self.drag, self.noisy, self.motor_noise = drag, False, False
+        self.drag, self.noisy, self.motor_noise = drag, noisy, motor_noise
         self.payload_mass = 0.3 * payload
 
 
@@ -151,14 +157,34 @@ def quad_substeps(simulation_dt, control_period):
     return n
 
 
-def quad_plant_params(quad, simulation_dt, control_period):
+def quad_is_noisy(quad):
+    return quad is not None and bool(getattr(quad, "noisy", False) or getattr(quad, "motor_noise", False))
+
+
+def quad_noise_params(quad, simulation_dt, seed):
+    """AdmpcQuadNoiseParams of a ``Quadrotor3D``-shaped object: its switches ``noisy`` and ``motor_noise``, the reference's constants
+    (quad_3d.py:190-199: f_d and t_d with std 10 * dt per sub-step; a rotor's error with mean 0.1 * (u / 1.3)^2 and std 0.02 * sqrt(u))
+    and the generator's key ``seed`` (0 .. 2^64 - 1)."""
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("quad_noise_params: seed must be in [0, 2^64)")
+    n = AdmpcQuadNoiseParams()
+    n.seed = int(seed)
+    n.noisy, n.motor_noise = int(bool(getattr(quad, "noisy", False))), int(bool(getattr(quad, "motor_noise", False)))
+    n.force_std = n.torque_std = 10 * float(simulation_dt)
+    n.motor_bias, n.motor_ref, n.motor_std = 0.1, 1.3, 0.02
+    return n
+
+
+def quad_plant_params(quad, simulation_dt, control_period, allow_noise=False):
     """AdmpcQuadPlantParams of a ``Quadrotor3D``-shaped object (None: ``SimQuad()``): mass, J, max_thrust, x_f, y_f, z_l_tau, g (a scalar
     or the reference's 3 x 1 vector), drag, rotor_drag_xy / rotor_drag_z, aero_drag, payload_mass, min_input_value / max_input_value.
-    The random disturbances of the simulator are not offered: ``noisy`` or ``motor_noise`` set raises NotImplementedError."""
+    The random disturbances are not the plant parameters' business: ``noisy`` or ``motor_noise`` set raises NotImplementedError unless
+    the caller says with ``allow_noise`` that it flies them through ``quad_noise_params`` and the entries of include/admpc_quad_noise.h."""
     if quad is None:
         quad = SimQuad()
-    if getattr(quad, "noisy", False) or getattr(quad, "motor_noise", False):
-        raise NotImplementedError("the simulator's random disturbances (noisy, motor_noise: np.random per sub-step) are not offered by the plant on the device")
+    if quad_is_noisy(quad) and not allow_noise:
+        raise NotImplementedError("the simulator's random disturbances (noisy, motor_noise: np.random per sub-step) are not offered by the deterministic "
+                                  "plant on the device: give QuadFleet a noise_seed (include/admpc_quad_noise.h)")
     p = AdmpcQuadPlantParams()
     p.dt, p.substeps = float(simulation_dt), quad_substeps(simulation_dt, control_period)
     p.mass, p.max_thrust = float(quad.mass), float(quad.max_thrust)

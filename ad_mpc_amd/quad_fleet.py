@@ -4,7 +4,8 @@ simplified simulator for ``control_period / simulation_dt`` sub-steps -- for B v
 error.  Built on ``QuadBatchSolver``; the OCP is shaped as ``Quad3DOptimizer`` shapes it (weight expansion for the quaternion, the
 vehicle's constants, the linear drag, one cluster of residual GPs).  With ``learn`` the fleet fits those GPs itself, on the device, from
 the steps it has flown (include/admpc_quad_learn.h: observe -> bin -> fit -> install; the side it shares with the car's fleet is
-learning.py's)."""
+learning.py's).  With ``noise_seed`` and a vehicle whose ``noisy`` or ``motor_noise`` is set, the plant is the simulator under its random
+disturbances (include/admpc_quad_noise.h)."""
 import ctypes as C
 from collections import namedtuple
 
@@ -14,8 +15,8 @@ import torch
 from . import _lib
 from .engine import QuadBatchSolver, _ptr
 from .learning import FleetLearning, placeholder_gps
-from .quad_config import (QNX, QNU, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, default_quad_config, quad_learn_bins, quad_plant_params,
-                          set_quad_gp)
+from .quad_config import (QNX, QNU, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, default_quad_config, quad_is_noisy, quad_learn_bins,
+                          quad_noise_params, quad_plant_params, set_quad_gp)
 
 QuadRollout = namedtuple("QuadRollout", ("x", "idx", "tally", "counts", "traj", "u"))
 T_MAX = 4096
@@ -69,16 +70,24 @@ class QuadFleet(FleetLearning):
     sigma_f, noise, count_noise).  With it the controller's handle is created with placeholder GPs of no points, which fit_gp overwrites
     on the device; a second, nominal handle (no GP, same vehicle, same rdrv) predicts for observe; the observation's period is the
     control period, predicted in ``observe_substeps`` RK4 steps.  ``samples`` [B,14], ``bins`` [3,32,5] and ``dropped`` [4] are the
-    record, the statistics and the counts of include/admpc_quad_learn.h."""
+    record, the statistics and the counts of include/admpc_quad_learn.h.
+
+    ``noise_seed``: the key of the disturbances' generator.  With it and a quad whose ``noisy`` or ``motor_noise`` is set, ``plant_step``
+    and ``rollout``, observed or not, go through the entries of include/admpc_quad_noise.h, and ``noise_step`` [B] int64 holds every
+    vehicle's period counter (zeros at first; the 64 bits are the header's uint64).  A quad without disturbances ignores the seed; a quad
+    with them and no seed is refused."""
     _FIT, _INSTALL, _GP_CAP, _REC, _EMPTY, _NOUN = "admpc_quad_gp_fit", "admpc_quad_gp_install", QUAD_GP_MAX, QUAD_REC, 7, "fleet"
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
-                 gp_regressors=None, rdrv_d_mat=None, device=0, learn=None, observe_substeps=1):
+                 gp_regressors=None, rdrv_d_mat=None, device=0, learn=None, observe_substeps=1, noise_seed=None):
         self.B, self.N, self.over = int(B), int(n_nodes), int(reference_over_sampling)
         if self.B < 1 or self.over < 1:
             raise ValueError("QuadFleet: B and reference_over_sampling must be at least 1")
         self.control_period = float(t_horizon) / (self.N * self.over)                      # trajectory_test.py: t_horizon / (n_mpc_nodes * over)
-        self._plant = quad_plant_params(quad, simulation_dt, self.control_period)          # refuses noisy / motor_noise before a handle exists
+        flies_noise = quad_is_noisy(quad) and noise_seed is not None
+        self._plant = quad_plant_params(quad, simulation_dt, self.control_period, allow_noise=flies_noise)    # refuses noisy / motor_noise without a seed before a handle exists
+        self._noise = quad_noise_params(quad, simulation_dt, noise_seed) if flies_noise else None
+        self.noise_step = None
         self._learn = self._nominal = None
         if learn is not None:                                                              # every refusal before a handle exists
             learn = [dict(d) for d in learn]
@@ -102,6 +111,8 @@ class QuadFleet(FleetLearning):
         self.cost, self.status, self.iters = f64(B), i32(B), i32(B)
         self.tally, self.counts = f64(B, 3), i32(B, 3)
         self.traj_of, self.idx = i32(B), i32(B)
+        if self._noise is not None:
+            self.noise_step = torch.zeros(B, dtype=torch.int64, device=dev)
         # one eager solve: the N = 20 handle allocates its slot buffer at its first solve, so a later graph capture of rollout() is legal
         self.x[:, 3] = 1.0
         self.yref[:, :, 3] = 1.0; self.yref_e[:, 3] = 1.0
@@ -156,7 +167,8 @@ class QuadFleet(FleetLearning):
 
     def reset(self, traj_of, idx0=0, x0=None):
         """Vehicle b follows trajectory traj_of[b] from row idx0 (a number or [B]); it starts at x0 [B,13] or, as the reference does, at
-        that row of its trajectory.  The iterate, the tally and the counts are zeroed."""
+        that row of its trajectory.  The iterate, the tally and the counts are zeroed.  ``noise_step`` is NOT touched: a fleet that is reset
+        goes on drawing fresh disturbances; ``reseed`` starts the stream over."""
         self._need_bank("reset")
         tk = np.broadcast_to(np.asarray(traj_of, dtype=np.int64), (self.B,))
         i0 = np.broadcast_to(np.asarray(idx0, dtype=np.int64), (self.B,))
@@ -195,6 +207,12 @@ class QuadFleet(FleetLearning):
         self._eng._chk(x, (x.shape[0], QNX))
         Bx = x.shape[0]
         stride = self._u_stride("plant_step", u, Bx)
+        if self._noise is not None:
+            if Bx > self.B:
+                raise ValueError("plant_step: under the disturbances x has at most the fleet's B rows (row b draws with noise_step[b])")
+            _lib.check(self.lib.admpc_quad_plant_step_noise_batch(C.byref(self._plant), C.byref(self._noise), self.device_index, Bx,
+                                                                  C.c_void_p(u.data_ptr()), stride, _ptr(x), _ptr(self.noise_step), self._stream()))
+            return
         _lib.check(self.lib.admpc_quad_plant_step_batch(C.byref(self._plant), self.device_index, Bx, C.c_void_p(u.data_ptr()), stride, _ptr(x),
                                                         self._stream()))
 
@@ -203,7 +221,7 @@ class QuadFleet(FleetLearning):
         """T closed-loop steps (admpc_quad_rollout_batch): no host synchronisation.  Returns QuadRollout(x, idx, tally, counts, traj, u):
         the fleet's own tensors, and with record traj [T+1,B,13] (slot t: the state at the start of step t) and u [T,B,4].  `observe`:
         every step is observed, as observe_latch before the first and observe behind each would (admpc_quad_rollout_observe_batch;
-        needs ``learn``)."""
+        needs ``learn``).  Under the disturbances both forms are admpc_quad_rollout_noise_batch, and noise_step advances by T."""
         self._need_bank("rollout")
         if observe:
             self._learns("rollout")
@@ -219,7 +237,11 @@ class QuadFleet(FleetLearning):
         args = (self._eng._h, self._bank, C.byref(self._plant), self.over, self.B, T, _ptr(self.traj_of), _ptr(self.idx), _ptr(self.x),
                 _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.yref), _ptr(self.yref_e), _ptr(self.cost), _ptr(self.status), _ptr(self.iters),
                 _ptr(self.tally), _ptr(self.counts), _ptr(traj), _ptr(u))
-        if observe:
+        if self._noise is not None:
+            watch = (self._observer._h, C.byref(self._obs), _ptr(self._prev), _ptr(self.samples), _ptr(self.bins), _ptr(self.dropped)) if observe \
+                else (None,) * 6
+            _lib.check(self.lib.admpc_quad_rollout_noise_batch(*args, *watch, C.byref(self._noise), _ptr(self.noise_step), self._stream()))
+        elif observe:
             _lib.check(self.lib.admpc_quad_rollout_observe_batch(*args, self._observer._h, C.byref(self._obs), _ptr(self._prev), _ptr(self.samples),
                                                                  _ptr(self.bins), _ptr(self.dropped), self._stream()))
         else:
@@ -229,6 +251,34 @@ class QuadFleet(FleetLearning):
     def step(self):
         """One closed-loop step."""
         return self.rollout(1)
+
+    # -- the disturbances (include/admpc_quad_noise.h) ---------------------------------------------------------------------------------
+    def _noisy(self, who):
+        if self._noise is None:
+            raise ValueError("%s: this fleet flies the deterministic simulator (a quad with noisy or motor_noise and a noise_seed make it noisy)" % who)
+
+    def reseed(self, seed=None, step=0):
+        """Sets the generator's key (None: keeps it) and fills ``noise_step`` with ``step`` (a number or [B]): the same call sequence
+        after the same reseed draws the same numbers.  The fill is asynchronous on the current stream; the key is read at each call, so a
+        captured graph keeps the key it was captured with."""
+        self._noisy("reseed")
+        if seed is not None:
+            if not 0 <= int(seed) < 2 ** 64:
+                raise ValueError("reseed: seed must be in [0, 2^64)")
+            self._noise.seed = int(seed)
+        self.noise_step.copy_(torch.as_tensor(np.broadcast_to(np.asarray(step, dtype=np.int64), (self.B,)).copy()))
+
+    def noise_draws(self, substeps=None):
+        """z [B, substeps, 10] on the host: the ten standard normals of every sub-step of the period the fleet flies NEXT
+        (admpc_quad_noise_draw_batch; ``substeps`` defaults to the plant's).  ``noise_step`` is not advanced.  Synchronises."""
+        self._noisy("noise_draws")
+        S = int(self._plant.substeps if substeps is None else substeps)
+        if not 1 <= S <= 1024:
+            raise ValueError("noise_draws: substeps must be in [1, 1024]")
+        z = torch.empty((self.B, S, 10), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.admpc_quad_noise_draw_batch(C.byref(self._noise), self.device_index, self.B, S, _ptr(self.noise_step), _ptr(z), None,
+                                                        self._stream()))
+        return z.cpu().numpy()
 
     def tracking_rmse(self):
         """trajectory_test.py:137's figure per vehicle: the mean of the position error norms over the steps taken (tally[:, 0] / steps);

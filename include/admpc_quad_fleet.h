@@ -18,8 +18,10 @@
  *   experiments/trajectory_test.py:137      mean of the position error norms (the "RMSE")   tally[b][0] / counts[b][0]
  *   quad_mpc/quad_3d_optimizer.py:29-207    (the horizon and device of a built solver)      admpc_quad_solver_info
  *
- * NOT offered: the simulator's random disturbances (`noisy`: a normal force and torque per sub-step; `motor_noise`: a normal error per
- * rotor and sub-step, both drawn from np.random, quad_3d.py:187-202).  The plant here is the deterministic simulator.
+ * The plant here is the deterministic simulator.  The simulator's random disturbances (`noisy`: a normal force and torque per sub-step;
+ * `motor_noise`: a normal error per rotor and sub-step, quad_3d.py:187-202) are flown by the entries of admpc_quad_noise.h, which has
+ * their distributions at the same places of the update.  NOT offered: np.random's own stream; the numbers come from a counter-based
+ * generator that the contract there spells out.
  */
 #ifndef ADMPC_QUAD_FLEET_H
 #define ADMPC_QUAD_FLEET_H

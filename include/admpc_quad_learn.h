@@ -21,7 +21,8 @@
  *     AdmpcQuadObserveParams holds AdmpcGpBins as AdmpcObserveParams does, so that a later change can route it; until then the length
  *     scales, sigma_f and the noise are GIVEN, as in admpc_learn.h;
  *   - clustered GP ensembles (one handle drives the whole fleet, as in admpc_quad_fleet.h);
- *   - the simulator's random disturbances (admpc_quad_fleet.h);
+ *   - np.random's own stream for the simulator's random disturbances: their distributions are flown by admpc_quad_rollout_noise_batch
+ *     (admpc_quad_noise.h), observed or not, from a counter-based generator;
  *   - handles in SQP mode (the rollout is the RTI loop);
  *   - pruning by a velocity cap (gp_common.py:101-104) beyond what the box of the bins does: a sample outside the box is dropped and counted.
  *

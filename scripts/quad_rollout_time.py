@@ -11,7 +11,13 @@ times: the median per STEP and the 10th and 90th percentile of the R windows, in
   host          the only route without this module: solve on the device, u[0] to the host, a vectorised numpy plant, the next window built
                 on the host and uploaded -- host clock around three steps ending in a synchronise, a few repeats
 
-    python scripts/quad_rollout_time.py [--steps 10] [--replays 10] [--windows 20] [--out FILE]
+With --noise the simulator's random disturbances (include/admpc_quad_noise.h; noisy and motor_noise both on, the reference's
+simulation_disturbances) are measured against the deterministic simulator instead: per horizon two fleets, the same but for the
+switches, their `rollout` and `plant` graphs captured once and then measured ALTERNATING, calm, noisy, calm, noisy, ..., three times
+each; every figure is the median of the three window medians, with the smallest and the largest of them.  The kernels' own times come from
+running the same command under `rocprofv3 --kernel-trace --stats`, in a run of its own.
+
+    python scripts/quad_rollout_time.py [--steps 10] [--replays 10] [--windows 20] [--out FILE] [--noise]
 """
 import argparse
 import json
@@ -34,8 +40,8 @@ from ad_mpc_amd.quad_scenarios import circle_reference  # noqa: E402
 B, OVER, ROWS = 4096, 5, 6000
 
 
-def graph_time(fn, steps, replays, windows):
-    """(median, p10, p90) microseconds per step of fn (which enqueues `steps` steps), captured once and replayed."""
+def graph_capture(fn, replays):
+    """fn (which enqueues some steps) run once, captured, and replayed `replays` times as a warm-up: the graph."""
     fn()
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
@@ -44,6 +50,15 @@ def graph_time(fn, steps, replays, windows):
     for _ in range(replays):
         g.replay()
     torch.cuda.synchronize()
+    return g
+
+
+def graph_time(fn, steps, replays, windows):
+    """(median, p10, p90) microseconds per step of fn (which enqueues `steps` steps), captured once and replayed."""
+    return graph_measure(graph_capture(fn, replays), steps, replays, windows)
+
+
+def graph_measure(g, steps, replays, windows):
     out = []
     for _ in range(windows):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -82,6 +97,52 @@ def host_route(fl, traj, u, steps):
     return (time.perf_counter() - t0) / steps
 
 
+def noise_against_calm(a):
+    """--noise: the closed-loop step and the plant launch of a fleet under both disturbances against the deterministic fleet."""
+    res = {"case": "B = %d, t_horizon 1 s, over-sampling %d, simulation_dt 5e-4, drag on, circle 5 m at 3 m/s; noisy and motor_noise on against both off" % (B, OVER),
+           "steps_per_graph": a.steps, "replays_per_window": a.replays, "windows": a.windows, "alternations": 3,
+           "microseconds": "per closed-loop step: median, smallest, largest of the three window medians", "device": torch.cuda.get_device_name(0)}
+    rows = 2000 + 2 * a.steps * a.replays * (1 + 3 * a.windows) + 200
+    for N in (10, 20):
+        rng = np.random.default_rng(0)
+        fleets = {"calm": QuadFleet(B, quad=SimQuad(drag=True), n_nodes=N, reference_over_sampling=OVER),
+                  "noisy": QuadFleet(B, quad=SimQuad(drag=True, noisy=True, motor_noise=True), n_nodes=N, reference_over_sampling=OVER, noise_seed=1)}
+        traj, u = circle_reference(rows, fleets["calm"].control_period, 5.0, 3.0)
+        idx0 = rng.integers(0, 2000, B)
+        x0 = traj[idx0].copy()
+        x0[:, 0:3] += rng.uniform(-0.2, 0.2, (B, 3))
+        graphs = {}
+        for name, fl in fleets.items():
+            fl.set_trajectories([(traj, u)])
+            fl.reset(0, idx0, x0)
+            graphs[name, "rollout"] = graph_capture(lambda fl=fl: fl.rollout(a.steps), a.replays)
+
+            def plant(fl=fl):
+                for _ in range(a.steps):
+                    fl.plant_step(fl.w_opt[:, 0, :], fl.scratch_x)
+
+            fl.scratch_x = fl.x.clone()                                            # the plant alone moves a copy, not the fleet
+            graphs[name, "plant"] = graph_capture(plant, a.replays)
+        r = {"substeps": int(fleets["calm"]._plant.substeps)}
+        for what in ("rollout", "plant"):
+            meds = {"calm": [], "noisy": []}
+            for _ in range(3):
+                for name in ("calm", "noisy"):
+                    fleets[name].scratch_x.copy_(fleets[name].x)
+                    meds[name].append(graph_measure(graphs[name, what], a.steps, a.replays, a.windows)[0])
+            for name in ("calm", "noisy"):
+                r["%s_%s" % (what, name)] = [float(np.median(meds[name])), min(meds[name]), max(meds[name])]
+            r["%s_noisy_over_calm" % what] = r[what + "_noisy"][0] / r[what + "_calm"][0]
+        for name, fl in fleets.items():
+            torch.cuda.synchronize()
+            assert int(fl.idx.max()) < rows - 1 - (N + 1) * OVER, "the fleet ran into the end of the reference"
+            r["status_nonzero_steps_" + name] = int(fl.counts[:, 1].sum())
+            r["tracking_rmse_mean_" + name] = float(fl.tracking_rmse().mean())
+            fl.close()
+        res["N%d" % N] = r
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
@@ -89,8 +150,12 @@ def main():
     ap.add_argument("--windows", type=int, default=20)
     ap.add_argument("--host-repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--noise", action="store_true", help="the noisy simulator against the deterministic one, alternating")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "quad_rollout_time.py measures on the GPU"
+    if a.noise:
+        emit(noise_against_calm(a), a.out)
+        return
     res = {"case": "B = %d, t_horizon 1 s, over-sampling %d, simulation_dt 5e-4, drag on, circle 5 m at 3 m/s" % (B, OVER),
            "steps_per_graph": a.steps, "replays_per_window": a.replays, "windows": a.windows, "microseconds": "median, 10th, 90th percentile per closed-loop step",
            "device": torch.cuda.get_device_name(0)}
@@ -130,11 +195,15 @@ def main():
         r["host_over_rollout"] = float(np.median(r["host"])) / r["rollout"][0]
         res["N%d" % N] = r
         fl.close()
+    emit(res, a.out)
+
+
+def emit(res, out):
     line = json.dumps(res)
     print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write(line + "\n")
 
 
