@@ -119,6 +119,19 @@ _QUAD_NOISE = {     # include/admpc_quad_noise.h: the simulator's random disturb
 }
 QUAD_NOISE_EXPORTS = tuple(_QUAD_NOISE)
 MORE_TABLES = {"admpc_quad_noise.h": _QUAD_NOISE}
+# the headers of what is built on the two registers above, declared by load() in the same way
+_roll = _QUAD_FLEET["admpc_quad_rollout_batch"][1][:-1]
+_QUAD_ENSEMBLE = {  # include/admpc_quad_ensemble.h: a clustered GP ensemble in the quadrotor's closed loop, flown and learned on the device
+    "admpc_quad_ensemble_create": (I, [hp, I, I, fp, C.POINTER(C.c_double), qop, hp]),
+    "admpc_quad_ensemble_destroy": (None, [vp]),
+    "admpc_quad_ensemble_route_batch": (I, [vp, I, dp, ip, vp]),
+    "admpc_quad_ensemble_observe_batch": (I, [vp, vp, pp, I, dp, C.c_int64, dp, dp, dp, dp, ip, vp]),
+    "admpc_quad_ensemble_fit": (I, [vp, I, dp, vp, ip, vp]),
+    "admpc_quad_ensemble_install": (I, [vp, vp, ip, vp]),
+    "admpc_quad_ensemble_rollout_batch": (I, _roll + [ip, ip] + [vp, dp, dp, dp, ip] + [np_, ip, vp]),
+}
+QUAD_ENSEMBLE_EXPORTS = tuple(_QUAD_ENSEMBLE)
+ENSEMBLE_TABLES = {"admpc_quad_ensemble.h": _QUAD_ENSEMBLE}
 
 _lib = None
 
@@ -136,7 +149,7 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for table in list(TABLES.values()) + list(MORE_TABLES.values()):
+    for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -1,7 +1,8 @@
 // admpc_host.h -- what the host sides of the fleet units share: the device guard, the argument blocks of the two rollouts, and one
 // declaration of every hidden function that one unit defines for another.  The defining unit includes this header too, so that the
 // compiler holds each definition against its declaration.  Included by admpc_kernels.hip, admpc_step.hip, admpc_lane.hip,
-// admpc_plant.hip, admpc_learn.hip, admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip and admpc_quad_learn.hip.  The learning host
+// admpc_plant.hip, admpc_learn.hip, admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip, admpc_quad_learn.hip, admpc_quad_noise.hip and
+// admpc_quad_ensemble.hip.  The learning host
 // side that admpc_learn.hip defines for admpc_quad_learn.hip and admpc_hyper.hip is declared in gp_fit_dev.h, next to the LearnArgs it
 // speaks of.
 #pragma once
@@ -53,7 +54,10 @@ struct RolloutArgs {
 };
 
 // admpc_quad_rollout_batch's arguments but T, the records (traj_out, u_out) and the stream; noise: null, or the disturbances of
-// admpc_quad_rollout_noise_batch (checked by it) with the vehicles' period counters
+// admpc_quad_rollout_noise_batch (checked by it) with the vehicles' period counters; ens: null, or the clustered ensemble of
+// admpc_quad_ensemble_rollout_batch, whose handles solve in place of s (s is its handle 0: the device, the horizon, the RTI mode), with
+// route [B] and route_out (null or [T][B])
+struct AdmpcQuadEnsemble;
 struct QuadRolloutArgs {
     AdmpcQuadSolver* s; const AdmpcQuadTrajBank* bank; const AdmpcQuadPlantParams* plant;
     int over, B;
@@ -62,6 +66,7 @@ struct QuadRolloutArgs {
     int32_t *status, *iters;
     double* tally; int32_t* counts;
     const AdmpcQuadNoiseParams* noise; uint64_t* noise_step;
+    const AdmpcQuadEnsemble* ens; int32_t *route, *route_out;
 };
 
 struct QuadPlantArgs;       // quad_sim_dev.h: what one launch of a quadrotor plant kernel works on
@@ -95,12 +100,25 @@ ADMPC_HIDDEN AdmpcQuadConfig* admpc_quad_solver_config_device(const AdmpcQuadSol
 ADMPC_HIDDEN int admpc_quad_plant_params_check(const char* who, const AdmpcQuadPlantParams* plant);
 // admpc_quad_fleet.hip: the refusals of a rollout up to those of its arrays (under admpc_quad_rollout_batch's name), and one checked period
 ADMPC_HIDDEN int admpc_quad_rollout_check(const QuadRolloutArgs& a, int T);
-ADMPC_HIDDEN int admpc_quad_rollout_enqueue(const QuadRolloutArgs& a, double* traj_pre, double* traj_post, double* u_out, void* stream);
+ADMPC_HIDDEN int admpc_quad_rollout_enqueue(const QuadRolloutArgs& a, double* traj_pre, double* traj_post, double* u_out, int32_t* route_out, void* stream);
 // admpc_quad_fleet.hip, admpc_quad_learn.hip: a whole rollout and a whole observed rollout behind their arguments' block, refusals and
 // no-ops included (under the names of admpc_quad_rollout_batch and admpc_quad_rollout_observe_batch)
 ADMPC_HIDDEN int admpc_quad_rollout_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, void* stream);
 ADMPC_HIDDEN int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, const AdmpcQuadSolver* model,
                                                 const AdmpcQuadObserveParams* obs, double* prev, double* samples, double* bins, int32_t* dropped,
                                                 void* stream);
-// admpc_quad_noise.hip: one launch of the noisy plant kernel for filled arguments and checked disturbances, B > 0
+// admpc_quad_noise.hip: one launch of the noisy plant kernel for filled arguments and checked disturbances, B > 0; the refusals of the
+// disturbances (plant: null, or the plant whose u_min motor_noise is held against)
 ADMPC_HIDDEN int admpc_quad_plant_noise_launch(const QuadPlantArgs& a, const AdmpcQuadNoiseParams* noise, uint64_t* noise_step, void* stream);
+ADMPC_HIDDEN int admpc_quad_noise_params_check(const char* who, const AdmpcQuadNoiseParams* noise, const AdmpcQuadPlantParams* plant);
+// admpc_quad_learn.hip: the refusals of the quadrotor's observe parameters; the two launches of an observation for checked arguments,
+// B > 0, on the model's device -- with ens the bin launch is the ensemble's, all clusters at once
+ADMPC_HIDDEN int admpc_quad_observe_params_check(const char* who, const AdmpcQuadObserveParams* obs);
+ADMPC_HIDDEN int admpc_quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams* plant, const AdmpcQuadObserveParams* obs,
+                                           const AdmpcQuadEnsemble* ens, int B, const double* u, long long u_stride, const double* x, double* prev,
+                                           double* samples, double* bins, int32_t* dropped, void* stream);
+// admpc_quad_ensemble.hip: the handles of an ensemble (returns K); one launch of its route kernel (route_out: null or [B]) and one of its
+// bin kernel, B > 0, on its device
+ADMPC_HIDDEN int admpc_quad_ensemble_handles(const AdmpcQuadEnsemble* e, AdmpcQuadSolver* const** solvers);
+ADMPC_HIDDEN int admpc_quad_ensemble_route_launch(const AdmpcQuadEnsemble* e, int B, const double* yref, int32_t* route, int32_t* route_out, void* stream);
+ADMPC_HIDDEN int admpc_quad_ensemble_bin_launch(const AdmpcQuadEnsemble* e, int B, const double* samples, double* bins, int32_t* dropped, void* stream);

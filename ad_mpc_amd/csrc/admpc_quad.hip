@@ -40,6 +40,7 @@ constexpr int QX = ADMPC_QUAD_NX, QU = ADMPC_QUAD_NU, QY = ADMPC_QUAD_NY;
 typedef AdmpcQuadConfig Cfg;
 
 #include "quad_model_dev.h"      // quad_rot, quad_drot, quad_f_tan: the model, which admpc_quad_learn.hip integrates too
+#include "quad_route_dev.h"      // quad_route_row: the cluster of an instance, which admpc_quad_ensemble.hip takes from a window's row too
 
 // classic RK4, one step of length h: the state and ONE sensitivity column (col < 13: d/dx_col, else d/du_(col-13))
 __device__ __forceinline__ void rk4_col(const Cfg* __restrict__ c, const double* x, const double* u, bool trig, const double* __restrict__ gq, double h, int col, double* phi, double* scol)
@@ -931,32 +932,7 @@ __global__ void admpc_quad_select_cluster_kernel(int B, int d, int f0, int f1, i
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const double* x = xs + (size_t)b * QX;
-    double R[3][3];
-    quad_rot(x[3], x[4], x[5], x[6], R);
-    double zz[QY];
-#pragma unroll
-    for (int i = 0; i < QX; ++i) zz[i] = x[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) zz[7 + i] = R[0][i] * x[7] + R[1][i] * x[8] + R[2][i] * x[9];        // v_b = R' v
-#pragma unroll
-    for (int m = 0; m < QU; ++m) zz[QX + m] = us[(size_t)b * QU + m];
-    const int f[3] = { f0, f1, f2 };
-    double z[3] = { 0, 0, 0 };
-    for (int j = 0; j < d; ++j) {
-        double v = 0;
-#pragma unroll
-        for (int i = 0; i < QY; ++i) v = f[j] == i ? zz[i] : v;
-        z[j] = v;
-    }
-    double best = INFINITY; int bi = 0;
-    for (int c = 0; c < K; ++c) {
-        double acc = 0.0;
-        for (int j = 0; j < d; ++j) { const double e = z[j] - cent[c * d + j]; acc = acc + e * e; }
-        const double dist = __dsqrt_rn(acc);
-        if (dist < best) { best = dist; bi = c; }
-    }
-    route[b] = bi;
+    route[b] = quad_route_row(xs + (size_t)b * QX, us + (size_t)b * QU, d, f0, f1, f2, K, cent);      // quad_route_dev.h: shared with the ensemble's rollout
 }
 // routed solve: an instance whose route names no cluster fails (status 4, infinite cost) with its iterate untouched
 __global__ void admpc_quad_route_invalid_kernel(int B, const int32_t* __restrict__ route, int K, int32_t* __restrict__ status, double* __restrict__ cost,

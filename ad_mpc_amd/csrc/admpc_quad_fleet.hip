@@ -6,7 +6,8 @@
 //                             simulator's model in a serial chain, ONE lane per vehicle (QP_LANES), everything in registers; behind a step
 //                             of the rollout the same launch does the tally, the counts, the records and the index update
 //
-// The rollout (admpc_quad_rollout_batch) is T times chunk -> admpc_quad_solve_batch_ex -> plant on one stream.  The simulator's device
+// The rollout (admpc_quad_rollout_batch) is T times chunk -> admpc_quad_solve_batch_ex -> plant on one stream; with a clustered ensemble in
+// its argument block (admpc_quad_ensemble.hip) the solve is route -> admpc_quad_solve_batch_routed.  The simulator's device
 // text is quad_sim_dev.h, which admpc_quad_noise.hip includes too; a rollout whose argument block carries disturbances launches that
 // unit's plant kernel in every period.
 #include <stdio.h>
@@ -280,12 +281,20 @@ int admpc_quad_rollout_check(const QuadRolloutArgs& a, int T)
 
 // One closed-loop period for checked arguments, B > 0, on the solver's device (the caller holds it): window -> RTI step -> plant.
 // traj_pre / traj_post: null or [B][13], the states before and after the period; u_out: null or [B][4], the input applied in it.
-int admpc_quad_rollout_enqueue(const QuadRolloutArgs& r, double* traj_pre, double* traj_post, double* u_out, void* stream)
+// With r.ens the RTI step is the ensemble's: the cluster of every vehicle from row 0 of its window (route_out: null or [B], the record of
+// it), then admpc_quad_solve_batch_routed over the ensemble's handles on the ONE iterate xbar / ubar.
+int admpc_quad_rollout_enqueue(const QuadRolloutArgs& r, double* traj_pre, double* traj_post, double* u_out, int32_t* route_out, void* stream)
 {
     int N = 0;
     (void)admpc_quad_solver_info(r.s, nullptr, &N, nullptr);
     int rc = chunk_launch(r.bank, r.B, N, r.over, r.traj_of, r.idx, r.yref, r.yref_e, nullptr, (hipStream_t)stream);
-    if (!rc) rc = admpc_quad_solve_batch_ex(r.s, r.B, r.x, r.yref, r.yref_e, nullptr, r.xbar, r.ubar, r.cost, r.status, r.iters, stream);
+    if (!rc && r.ens) {
+        AdmpcQuadSolver* const* handles = nullptr;
+        const int K = admpc_quad_ensemble_handles(r.ens, &handles);
+        rc = admpc_quad_ensemble_route_launch(r.ens, r.B, r.yref, r.route, route_out, stream);
+        if (!rc) rc = admpc_quad_solve_batch_routed(handles, K, r.B, r.route, r.x, r.yref, r.yref_e, nullptr, r.xbar, r.ubar, r.cost, r.status, r.iters, stream);
+    }
+    else if (!rc) rc = admpc_quad_solve_batch_ex(r.s, r.B, r.x, r.yref, r.yref_e, nullptr, r.xbar, r.ubar, r.cost, r.status, r.iters, stream);
     if (rc) return rc;
     QuadPlantArgs a = plant_only(r.plant, r.B, r.ubar, (long long)N * QU, r.x);
     a.K = r.bank->K; a.desc = r.bank->d_desc;
@@ -301,7 +310,7 @@ int admpc_quad_rollout_run(const QuadRolloutArgs& a, int T, double* traj_out, do
 {
     int rc = admpc_quad_rollout_check(a, T);
     if (rc || a.B == 0 || T == 0) return rc;
-    if (!a.traj_of || !a.idx || !a.x || !a.xbar || !a.ubar || !a.yref || !a.yref_e || !a.status)
+    if (!a.traj_of || !a.idx || !a.x || !a.xbar || !a.ubar || !a.yref || !a.yref_e || !a.status || (a.ens && !a.route))
         return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: null array argument");
     if (!a.tally || !a.counts) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: null tally or counts");
     if (a.noise && !a.noise_step) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_noise_batch: null noise_step");
@@ -312,7 +321,7 @@ int admpc_quad_rollout_run(const QuadRolloutArgs& a, int T, double* traj_out, do
     // slot 0 of traj_out is written by the first period; every period writes the state it leaves into the next slot
     for (int t = 0; t < T && !rc; ++t)
         rc = admpc_quad_rollout_enqueue(a, t == 0 ? traj_out : nullptr, traj_out ? traj_out + (size_t)(t + 1) * a.B * QX : nullptr,
-                                        u_out ? u_out + (size_t)t * a.B * QU : nullptr, stream);
+                                        u_out ? u_out + (size_t)t * a.B * QU : nullptr, a.route_out ? a.route_out + (size_t)t * a.B : nullptr, stream);
     return rc;
 }
 

@@ -156,10 +156,11 @@ int quad_observe_params_check(const char* who, const AdmpcQuadObserveParams* obs
     return admpc_learn_regressors_check(who, obs->n_gp, obs->gp, QUAD_LEARN);
 }
 
-// The two launches of an observation for checked arguments, B > 0, on the model's device (the caller holds it).
-int quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams* plant, const AdmpcQuadObserveParams* obs, int B,
-                        const double* u, long long u_stride, const double* x, double* prev, double* samples, double* bins, int32_t* dropped,
-                        void* stream)
+// The two launches of an observation for checked arguments, B > 0, on the model's device (the caller holds it).  With ens the records go
+// to the bins of their clusters: the ensemble's bin launch (admpc_quad_ensemble.hip), all clusters at once, under its own boxes.
+int quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams* plant, const AdmpcQuadObserveParams* obs,
+                        const AdmpcQuadEnsemble* ens, int B, const double* u, long long u_stride, const double* x, double* prev, double* samples,
+                        double* bins, int32_t* dropped, void* stream)
 {
     QuadObserveArgs a;
     a.h = obs->dt / obs->substeps; a.dt = obs->dt; a.u_min = plant->u_min; a.u_max = plant->u_max;
@@ -169,6 +170,7 @@ int quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams
     hipLaunchKernelGGL(admpc_quad_observe_kernel, dim3((unsigned)(nblk < QO_GRID ? nblk : QO_GRID)), dim3(WAVE), 0, (hipStream_t)stream,
                        admpc_quad_solver_config_device(model, nullptr), a);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_quad_observe_kernel: launch failed");
+    if (ens) return admpc_quad_ensemble_bin_launch(ens, B, samples, bins, dropped, stream);
     LearnArgs l = LearnArgs();
     admpc_learn_fill(l, obs->n_gp, obs->gp, QUAD_LEARN.feat_lo);
     l.B = B; l.samples = samples; l.bins = bins; l.dropped = dropped;
@@ -186,6 +188,15 @@ int quad_latch_launch(int B, const double* x, double* prev, void* stream)
 }
 
 }  // namespace
+
+// for admpc_quad_ensemble.hip: the refusals of the observe parameters, and the two launches of an observation
+extern "C" int admpc_quad_observe_params_check(const char* who, const AdmpcQuadObserveParams* obs) { return quad_observe_params_check(who, obs); }
+extern "C" int admpc_quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams* plant, const AdmpcQuadObserveParams* obs,
+                                         const AdmpcQuadEnsemble* ens, int B, const double* u, long long u_stride, const double* x, double* prev,
+                                         double* samples, double* bins, int32_t* dropped, void* stream)
+{
+    return quad_observe_launch(model, plant, obs, ens, B, u, u_stride, x, prev, samples, bins, dropped, stream);
+}
 
 extern "C" {
 
@@ -216,7 +227,7 @@ int admpc_quad_observe_batch(const AdmpcQuadSolver* model, const AdmpcQuadPlantP
     (void)admpc_quad_solver_info(model, &device, nullptr, nullptr);
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    return quad_observe_launch(model, plant, obs, B, u, (long long)u_stride, x, prev, samples, bins, dropped, stream);
+    return quad_observe_launch(model, plant, obs, nullptr, B, u, (long long)u_stride, x, prev, samples, bins, dropped, stream);
 }
 
 int admpc_quad_gp_fit(int device, const AdmpcQuadObserveParams* obs, int min_count, const double* bins, AdmpcGp* gp_out, int32_t* info,
@@ -246,7 +257,8 @@ int admpc_quad_gp_install(AdmpcQuadSolver* s, int n_gp, const AdmpcGp* gp_dev, i
 }
 
 // admpc_quad_rollout_observe_batch behind its arguments' block: the refusals, the no-ops, the latch and the T observed periods; with
-// a.noise the plant of every period is the noisy one (admpc_quad_noise.hip), whose counter array is refused last
+// a.noise the plant of every period is the noisy one (admpc_quad_noise.hip), whose counter array is refused last; with a.ens the solve of
+// every period is the ensemble's routed one and the bin launch the ensemble's (admpc_quad_ensemble.hip), obs being the block its clusters share
 int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, const AdmpcQuadSolver* model,
                                    const AdmpcQuadObserveParams* obs, double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
 {
@@ -262,7 +274,8 @@ int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj
     (void)admpc_quad_solver_info(model, &model_device, nullptr, nullptr);
     if (model_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_observe_batch: the model lives on another device than the solver");
     if (B == 0 || T == 0) return ADMPC_OK;
-    if (!a.traj_of || !a.idx || !a.x || !a.xbar || !a.ubar || !a.yref || !a.yref_e || !a.status || !a.tally || !a.counts || !prev || !samples || !bins || !dropped)
+    if (!a.traj_of || !a.idx || !a.x || !a.xbar || !a.ubar || !a.yref || !a.yref_e || !a.status || !a.tally || !a.counts || !prev || !samples || !bins || !dropped ||
+        (a.ens && !a.route))
         return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_observe_batch: null array argument");
     if (a.noise && !a.noise_step) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_noise_batch: null noise_step");
     DeviceGuard guard(device);
@@ -272,8 +285,8 @@ int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj
     // slot 0 of traj_out is written by the first period; every period writes the state it leaves into the next slot
     for (int t = 0; t < T && !rc; ++t) {
         rc = admpc_quad_rollout_enqueue(a, t == 0 ? traj_out : nullptr, traj_out ? traj_out + (size_t)(t + 1) * slot : nullptr,
-                                        u_out ? u_out + (size_t)t * B * QU : nullptr, stream);
-        if (!rc) rc = quad_observe_launch(model, a.plant, obs, B, a.ubar, (long long)N * QU, a.x, prev, samples, bins, dropped, stream);
+                                        u_out ? u_out + (size_t)t * B * QU : nullptr, a.route_out ? a.route_out + (size_t)t * B : nullptr, stream);
+        if (!rc) rc = quad_observe_launch(model, a.plant, obs, a.ens, B, a.ubar, (long long)N * QU, a.x, prev, samples, bins, dropped, stream);
     }
     return rc;
 }

@@ -211,6 +211,9 @@ int noise_params_check(const char* who, const AdmpcQuadNoiseParams* n, const Adm
 
 }  // namespace
 
+// for admpc_quad_ensemble.hip: the refusals of the disturbances
+extern "C" int admpc_quad_noise_params_check(const char* who, const AdmpcQuadNoiseParams* noise, const AdmpcQuadPlantParams* plant) { return noise_params_check(who, noise, plant); }
+
 // for admpc_quad_fleet.hip's period: one launch of the noisy plant kernel
 extern "C" int admpc_quad_plant_noise_launch(const QuadPlantArgs& a, const AdmpcQuadNoiseParams* noise, uint64_t* noise_step, void* stream)
 {

@@ -98,8 +98,15 @@ static __device__ __forceinline__ double gp_ymean(const double* ts, const int n)
 // acceptance, the bin index, the lane-ordered sums).  The record layout is the caller's: REC_ doubles, the last of them the flag; feature
 // index f reads entry f - FEAT0_, output `out` reads entry Y0_ + out - FEAT0_; the records that are not valid go into dropped[INVALID_].
 // Bin 0 of a regressor also counts what fell outside its box, regressor 0 also what was not valid.
-template <int REC_, int FEAT0_, int Y0_, int INVALID_>
-static __device__ __forceinline__ void gp_bin_body(const LearnArgs& a, const int g, const int bin)
+// `takes` is the routing predicate of a clustered ensemble (admpc_quad_ensemble.hip): a valid record it does not take is absent to this
+// wave -- not added, not counted as dropped -- and keeps its lane; the wave tallies the records that are not valid only if the predicate
+// says so.  The default takes every record, and the kernels that use it are what they were without it.
+struct GpBinTakesAll {
+    __device__ __forceinline__ constexpr bool operator()(const double*) const { return true; }
+    __device__ __forceinline__ constexpr bool tallies_invalid() const { return true; }
+};
+template <int REC_, int FEAT0_, int Y0_, int INVALID_, class Takes_ = GpBinTakesAll>
+static __device__ __forceinline__ void gp_bin_body(const LearnArgs& a, const int g, const int bin, const Takes_ takes = Takes_())
 {
 #pragma clang fp contract(off)
     const LearnGp& G = a.gp[g];
@@ -110,6 +117,7 @@ static __device__ __forceinline__ void gp_bin_body(const LearnArgs& a, const int
     for (long b = lane; b < a.B; b += WAVE) {
         const double* r = a.samples + b * REC_;
         if (!(r[REC_ - 1] == 1.0)) { ++invalid; continue; }
+        if (!takes(r)) continue;
         double z[3] = { 0.0, 0.0, 0.0 };
         bool in = true;
         int k = 0;
@@ -147,7 +155,7 @@ static __device__ __forceinline__ void gp_bin_body(const LearnArgs& a, const int
         for (int w = WAVE / 2; w > 0; w >>= 1) { outside += __shfl_xor(outside, w); invalid += __shfl_xor(invalid, w); }
         if (lane == 0) {
             a.dropped[g] = a.dropped[g] + outside;
-            if (g == 0) a.dropped[INVALID_] = a.dropped[INVALID_] + invalid;
+            if (g == 0 && takes.tallies_invalid()) a.dropped[INVALID_] = a.dropped[INVALID_] + invalid;
         }
     }
 }

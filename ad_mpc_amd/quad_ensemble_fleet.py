@@ -1,0 +1,198 @@
+"""A fleet of quadrotors that flies -- and learns -- a clustered GP ensemble in closed loop on the device
+(include/admpc_quad_ensemble.h): the reference keeps one solver per cluster of its GP ensemble (quad_3d_optimizer.py:207) and picks one
+per solve from the first row of the reference chunk (:485-491, gp.py:738-770); here one handle per cluster solves the vehicles whose
+window routes to it, in every period of a rollout, and the steps flown go to the bins of the cluster they were flown in.  The plant,
+the bank, reset, the disturbances and the tally are ``QuadFleet``'s."""
+import ctypes as C
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .config import AdmpcGp, GP_MAX_POINTS
+from .engine import QuadBatchSolver, _ptr
+from .learning import decode_gps, placeholder_gps
+from .quad_3d_optimizer import QuadGPEnsemble
+from .quad_config import QNX, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, quad_learn_bins
+from .quad_fleet import QuadFleet, fleet_quad_config
+
+QuadEnsembleRollout = namedtuple("QuadEnsembleRollout", ("x", "idx", "tally", "counts", "traj", "u", "routes"))
+CLUSTERS_MAX = 8
+
+
+def ensemble_layout(centroids, feats, learn=None):
+    """The centroids as float64 [K, n_feat] and the features as a list, checked as admpc_quad_ensemble_create checks them, and with
+    ``learn`` (K lists of quad_learn_bins dicts) the K blocks of regressors: (centroids, feats, [(AdmpcGpBins array, n_gp)] or None).
+    Raises ValueError; needs no GPU."""
+    feats = [int(f) for f in np.atleast_1d(feats).reshape(-1)]
+    if not 1 <= len(feats) <= 3 or any(not 0 <= f < QNY for f in feats):
+        raise ValueError("QuadEnsembleFleet: 1 to 3 clustering features in 0 .. 16")
+    cent = np.asarray(centroids, dtype=np.float64)
+    if cent.ndim == 1:
+        cent = cent.reshape(-1, len(feats))
+    K = cent.shape[0]
+    if not 1 <= K <= CLUSTERS_MAX:
+        raise ValueError("QuadEnsembleFleet: 1 to %d clusters, got %d" % (CLUSTERS_MAX, K))
+    if cent.shape != (K, len(feats)):
+        raise ValueError("QuadEnsembleFleet: centroids must be K x len(feats)")
+    if not np.isfinite(cent).all():
+        raise ValueError("QuadEnsembleFleet: a centroid is not finite")
+    if learn is None:
+        return np.ascontiguousarray(cent), feats, None
+    learn = [[dict(d) for d in cluster] for cluster in learn]
+    if len(learn) != K:
+        raise ValueError("QuadEnsembleFleet: learn needs one list of regressors per cluster (%d), got %d" % (K, len(learn)))
+    blocks = [quad_learn_bins(cluster) for cluster in learn]                               # ValueError on bad bins
+    head = lambda cluster: [([int(f) for f in np.atleast_1d(d["feat"]).reshape(-1)], int(d["out"])) for d in cluster]
+    for c in range(1, K):
+        if head(learn[c]) != head(learn[0]):
+            raise ValueError("QuadEnsembleFleet: the clusters of learn must agree in every regressor's feat and out (cluster %d differs); "
+                             "the box, the bins and the hyperparameters may differ" % c)
+    if min(feats) < 7:
+        raise ValueError("QuadEnsembleFleet: a fleet that learns clusters on features in 7 .. 16 (the sample record holds no others)")
+    return np.ascontiguousarray(cent), feats, blocks
+
+
+class QuadEnsembleFleet(QuadFleet):
+    """``QuadFleet`` with one handle per cluster.  Either ``ensemble`` (a ``QuadGPEnsemble``: the fleet flies given clusters) or
+    ``centroids`` [K, n_feat], ``feats`` and ``learn`` -- K lists of ``quad_learn_bins`` dicts, one list per cluster, which agree in feat
+    and out and are free in the box, the bins and the hyperparameters -- for a fleet that learns them: every cluster's handle is created
+    with placeholder GPs, one nominal handle predicts for observe.
+
+    State besides QuadFleet's: ``route`` int32 [B] (the clusters of the last period), and with ``learn`` ``bins`` [K,3,32,5],
+    ``dropped`` [K,4] ([c][g]: valid records of cluster c outside regressor g's box; [0][3]: records that are not valid), ``fit_info``
+    and ``installed`` [K,3].  There is ONE iterate per vehicle: a vehicle that changes cluster is warm-started from the other cluster's
+    solution (the reference keeps an iterate per solver)."""
+
+    def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
+                 ensemble=None, centroids=None, feats=None, learn=None, rdrv_d_mat=None, device=0, observe_substeps=1, noise_seed=None):
+        self._ens = None
+        self._solvers = []
+        self._init_plant(B, quad, t_horizon, n_nodes, simulation_dt, reference_over_sampling, noise_seed)
+        # every refusal that needs no GPU, before a handle exists
+        if (ensemble is None) == (learn is None):
+            raise ValueError("QuadEnsembleFleet: give either ensemble=QuadGPEnsemble(...) or centroids, feats and learn")
+        if ensemble is not None:
+            if centroids is not None or feats is not None:
+                raise ValueError("QuadEnsembleFleet: centroids and feats come with the ensemble")
+            cent, feats, blocks = ensemble_layout(ensemble.centroids, ensemble.feats)
+            clusters = [list(c) for c in ensemble.clusters]
+            if len(clusters) != cent.shape[0]:
+                raise ValueError("QuadEnsembleFleet: the ensemble needs one centroid per cluster")
+        else:
+            if centroids is None or feats is None:
+                raise ValueError("QuadEnsembleFleet: learn needs centroids and feats")
+            cent, feats, blocks = ensemble_layout(centroids, feats, learn)
+            learn = [[dict(d) for d in cluster] for cluster in learn]
+            if not 1 <= int(observe_substeps) <= 64:
+                raise ValueError("QuadEnsembleFleet: observe_substeps must be in [1, 64]")
+            clusters = [placeholder_gps(cluster) for cluster in learn]
+        self.K, self.feats, self.centroids = cent.shape[0], feats, cent
+        cfgs = [fleet_quad_config(quad, t_horizon, n_nodes, q_cost, r_cost, gps, rdrv_d_mat) for gps in clusters]      # one configuration per cluster
+        if learn is not None:
+            self._nominal = QuadBatchSolver(fleet_quad_config(quad, t_horizon, n_nodes, q_cost, r_cost, None, rdrv_d_mat), device=device)
+        self._solvers = [QuadBatchSolver(c, device=device) for c in cfgs]
+        self._eng = self._solvers[0]                                                       # the stream, the device and the checks of the fleet
+        self._handles = (C.c_void_p * self.K)(*[s._h for s in self._solvers])
+        obs = None
+        if learn is not None:
+            obs = (AdmpcQuadObserveParams * self.K)()
+            for c, (bins, n_gp) in enumerate(blocks):
+                obs[c] = AdmpcQuadObserveParams(dt=self.control_period, substeps=int(observe_substeps), n_gp=n_gp, gp=bins)
+        h = C.c_void_p(0)
+        _lib.check(_lib.load().admpc_quad_ensemble_create(self._handles, self.K, len(feats), (C.c_int32 * len(feats))(*feats),
+                                                          cent.ctypes.data_as(C.POINTER(C.c_double)), obs, C.byref(h)))
+        self._ens = h
+        self._alloc_state(self._solvers)
+        self.route = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        if learn is not None:
+            z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=self.device)
+            self._learn, self.n_learn, self._obs, self._observer = learn, blocks[0][1], obs, self._nominal
+            self._prev, self.samples = z(self.B, QNX), z(self.B, QUAD_REC)
+            self.bins, self.dropped = z(self.K, QUAD_GP_MAX, GP_MAX_POINTS, 5), z(self.K, QUAD_GP_MAX + 1, dtype=torch.int32)
+            self._gp_dev = z(self.K * QUAD_GP_MAX * C.sizeof(AdmpcGp), dtype=torch.uint8)
+            self.fit_info, self.installed = z(self.K, QUAD_GP_MAX, dtype=torch.int32), z(self.K, QUAD_GP_MAX, dtype=torch.int32)
+
+    # -- lifetime ---------------------------------------------------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_ens", None):
+            self.lib.admpc_quad_ensemble_destroy(self._ens)
+            self._ens = None
+        for s in getattr(self, "_solvers", [])[1:]:
+            s.close()
+        super().close()                                                                    # the bank, handle 0 and the nominal handle
+
+    # -- routing and the routed solve, for a loop driven from the host ------------------------------------------------------------------
+    def route_window(self, route=None):
+        """The cluster of every vehicle from row 0 of its window ``yref`` as it stands (admpc_quad_ensemble_route_batch), into ``route``
+        (default: the fleet's).  Asynchronous."""
+        route = self.route if route is None else route
+        self._eng._chk(route, (self.B,), torch.int32)
+        _lib.check(self.lib.admpc_quad_ensemble_route_batch(self._ens, self.B, _ptr(self.yref), _ptr(route), self._stream()))
+        return route
+
+    def solve_routed(self, route=None):
+        """One RTI step of every vehicle by the handle of its cluster, in place on the fleet's iterate
+        (admpc_quad_solve_batch_routed under ``route``, default the fleet's).  Asynchronous."""
+        route = self.route if route is None else route
+        self._eng._chk(route, (self.B,), torch.int32)
+        _lib.check(self.lib.admpc_quad_solve_batch_routed(self._handles, self.K, self.B, _ptr(route), _ptr(self.x), _ptr(self.yref), _ptr(self.yref_e),
+                                                          None, _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.cost), _ptr(self.status),
+                                                          _ptr(self.iters), self._stream()))
+
+    # -- the closed loop --------------------------------------------------------------------------------------------------------------
+    def rollout(self, T, record=False, observe=False):
+        """T closed-loop steps (admpc_quad_ensemble_rollout_batch): window -> routing from the window -> routed solve -> plant, and with
+        `observe` the ensemble's observation behind every plant step.  Returns QuadEnsembleRollout(x, idx, tally, counts, traj, u,
+        routes): QuadRollout's fields, and with record routes int32 [T,B], the cluster that solved every vehicle in every step."""
+        self._need_bank("rollout")
+        if observe:
+            self._learns("rollout")
+        T, traj, u = self._records("rollout", T, record)
+        routes = torch.empty((T, self.B), dtype=torch.int32, device=self.device) if record else None
+        watch = (self._observer._h, _ptr(self._prev), _ptr(self.samples), _ptr(self.bins), _ptr(self.dropped)) if observe else (None,) * 5
+        noise = (C.byref(self._noise), _ptr(self.noise_step)) if self._noise is not None else (None, None)
+        _lib.check(self.lib.admpc_quad_ensemble_rollout_batch(*self._rollout_args(self._ens, T, traj, u), _ptr(self.route), _ptr(routes), *watch,
+                                                              *noise, self._stream()))
+        return QuadEnsembleRollout(self.x, self.idx, self.tally, self.counts, traj, u, routes)
+
+    # -- learning, per cluster ----------------------------------------------------------------------------------------------------------
+    def set_observer(self, learned=False, cluster=0):
+        """Which handle predicts in observe: the nominal one (default) or, with `learned`, the handle of ``cluster`` with whatever GPs
+        are installed in it."""
+        self._learns("set_observer")
+        if learned and not 0 <= int(cluster) < self.K:
+            raise ValueError("set_observer: cluster must be in 0 .. %d" % (self.K - 1))
+        self._observer = self._solvers[int(cluster)] if learned else self._nominal
+
+    def observe(self, u=None):
+        """QuadFleet.observe with every record going to the bins of ITS cluster, the centroid nearest to the record's own features
+        (admpc_quad_ensemble_observe_batch).  Asynchronous."""
+        self._learns("observe")
+        u = self.w_opt[:, 0, :] if u is None else u
+        stride = self._u_stride("observe", u, self.B)
+        _lib.check(self.lib.admpc_quad_ensemble_observe_batch(self._ens, self._observer._h, C.byref(self._plant), self.B, C.c_void_p(u.data_ptr()),
+                                                              stride, _ptr(self.x), _ptr(self._prev), _ptr(self.samples), _ptr(self.bins),
+                                                              _ptr(self.dropped), self._stream()))
+
+    def fit_gp(self, min_count=1, install=True):
+        """Fits every regressor of every cluster to the means of its bins with at least `min_count` samples, at that cluster's
+        hyperparameters, and (`install`) overwrites the GPs of the K handles on the device.  Asynchronous; returns the device tensors
+        (info int32 [K,n], installed int32 [K,n] or None) as QuadFleet.fit_gp explains them."""
+        self._learns("fit_gp")
+        n, s = self.n_learn, self._stream()
+        _lib.check(self.lib.admpc_quad_ensemble_fit(self._ens, int(min_count), _ptr(self.bins), _ptr(self._gp_dev), _ptr(self.fit_info), s))
+        if not install:
+            return self.fit_info[:, :n], None
+        _lib.check(self.lib.admpc_quad_ensemble_install(self._ens, _ptr(self._gp_dev), _ptr(self.installed), s))
+        return self.fit_info[:, :n], self.installed[:, :n]
+
+    def learned_gps(self):
+        """The GPs of the last fit_gp as a ``QuadGPEnsemble`` with the fleet's centroids and features (synchronises): what
+        ``QuadEnsembleFleet(ensemble=...)`` takes.  Every cluster is decoded as QuadFleet.learned_gps decodes its one."""
+        self._learns("learned_gps")
+        torch.cuda.current_stream(self.device).synchronize()
+        raw = self._gp_dev.cpu().numpy().tobytes()
+        per = QUAD_GP_MAX * C.sizeof(AdmpcGp)
+        return QuadGPEnsemble([decode_gps(raw[c * per:(c + 1) * per], self._learn[c], self._EMPTY) for c in range(self.K)], self.centroids, self.feats)

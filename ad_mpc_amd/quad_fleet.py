@@ -54,7 +54,8 @@ def fleet_quad_config(quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=
     if gp_regressors is not None:
         if isinstance(gp_regressors, QuadGPEnsemble):
             if gp_regressors.n_models > 1:
-                raise NotImplementedError("clustered GP ensembles are not served by the rollout (one handle drives the whole fleet)")
+                raise NotImplementedError("clustered GP ensembles are not served by this rollout (one handle drives the whole fleet): "
+                                          "QuadEnsembleFleet (quad_ensemble_fleet.py) flies and learns them")
             gp_regressors = gp_regressors.clusters[0]
         set_quad_gp(cfg, list(gp_regressors))
     return cfg
@@ -80,15 +81,7 @@ class QuadFleet(FleetLearning):
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
                  gp_regressors=None, rdrv_d_mat=None, device=0, learn=None, observe_substeps=1, noise_seed=None):
-        self.B, self.N, self.over = int(B), int(n_nodes), int(reference_over_sampling)
-        if self.B < 1 or self.over < 1:
-            raise ValueError("QuadFleet: B and reference_over_sampling must be at least 1")
-        self.control_period = float(t_horizon) / (self.N * self.over)                      # trajectory_test.py: t_horizon / (n_mpc_nodes * over)
-        flies_noise = quad_is_noisy(quad) and noise_seed is not None
-        self._plant = quad_plant_params(quad, simulation_dt, self.control_period, allow_noise=flies_noise)    # refuses noisy / motor_noise without a seed before a handle exists
-        self._noise = quad_noise_params(quad, simulation_dt, noise_seed) if flies_noise else None
-        self.noise_step = None
-        self._learn = self._nominal = None
+        self._init_plant(B, quad, t_horizon, n_nodes, simulation_dt, reference_over_sampling, noise_seed)
         if learn is not None:                                                              # every refusal before a handle exists
             learn = [dict(d) for d in learn]
             bins, n_gp = quad_learn_bins(learn)                                            # ValueError on bad bins
@@ -101,6 +94,25 @@ class QuadFleet(FleetLearning):
             self._nominal = QuadBatchSolver(cfg, device=device)
             cfg = set_quad_gp(cfg.copy(), placeholder_gps(learn))
         self._eng = QuadBatchSolver(cfg, device=device)
+        self._alloc_state([self._eng])
+        if learn is not None:
+            obs = AdmpcQuadObserveParams(dt=self.control_period, substeps=int(observe_substeps), n_gp=n_gp, gp=bins)
+            self._alloc_learning(learn, n_gp, obs, (self.B, QNX))
+
+    def _init_plant(self, B, quad, t_horizon, n_nodes, simulation_dt, reference_over_sampling, noise_seed):
+        """The sizes, the simulator's vehicle and its disturbances: everything here is refused before a handle exists."""
+        self.B, self.N, self.over = int(B), int(n_nodes), int(reference_over_sampling)
+        if self.B < 1 or self.over < 1:
+            raise ValueError("QuadFleet: B and reference_over_sampling must be at least 1")
+        self.control_period = float(t_horizon) / (self.N * self.over)                      # trajectory_test.py: t_horizon / (n_mpc_nodes * over)
+        flies_noise = quad_is_noisy(quad) and noise_seed is not None
+        self._plant = quad_plant_params(quad, simulation_dt, self.control_period, allow_noise=flies_noise)    # refuses noisy / motor_noise without a seed before a handle exists
+        self._noise = quad_noise_params(quad, simulation_dt, noise_seed) if flies_noise else None
+        self.noise_step = None
+        self._learn = self._nominal = None
+
+    def _alloc_state(self, engines):
+        """The fleet's tensors on the device of ``_eng``, and one eager solve on every handle that will solve in the loop."""
         self.lib, self.device, self.device_index, self.cfg = self._eng.lib, self._eng.device, self._eng.device_index, self._eng.cfg
         self._bank, self._M = None, None
         B, N, dev = self.B, self.N, self.device
@@ -116,11 +128,9 @@ class QuadFleet(FleetLearning):
         # one eager solve: the N = 20 handle allocates its slot buffer at its first solve, so a later graph capture of rollout() is legal
         self.x[:, 3] = 1.0
         self.yref[:, :, 3] = 1.0; self.yref_e[:, 3] = 1.0
-        self._eng.solve(self.x, self.yref, self.yref_e, f64(B, N + 1, QNX), f64(B, N, QNU))
+        for eng in engines:
+            eng.solve(self.x, self.yref, self.yref_e, f64(B, N + 1, QNX), f64(B, N, QNU))
         torch.cuda.synchronize(dev)
-        if learn is not None:
-            obs = AdmpcQuadObserveParams(dt=self.control_period, substeps=int(observe_substeps), n_gp=n_gp, gp=bins)
-            self._alloc_learning(learn, n_gp, obs, (B, QNX))
 
     # -- lifetime ---------------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -225,18 +235,8 @@ class QuadFleet(FleetLearning):
         self._need_bank("rollout")
         if observe:
             self._learns("rollout")
-        T = int(T)
-        if T < 0 or T > T_MAX:
-            raise ValueError("rollout: T must be in [0, %d]" % T_MAX)
-        traj = u = None
-        if record:
-            traj = torch.empty((T + 1, self.B, QNX), dtype=torch.float64, device=self.device)
-            u = torch.empty((T, self.B, QNU), dtype=torch.float64, device=self.device)
-            if T == 0:
-                traj[0].copy_(self.x)
-        args = (self._eng._h, self._bank, C.byref(self._plant), self.over, self.B, T, _ptr(self.traj_of), _ptr(self.idx), _ptr(self.x),
-                _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.yref), _ptr(self.yref_e), _ptr(self.cost), _ptr(self.status), _ptr(self.iters),
-                _ptr(self.tally), _ptr(self.counts), _ptr(traj), _ptr(u))
+        T, traj, u = self._records("rollout", T, record)
+        args = self._rollout_args(self._eng._h, T, traj, u)
         if self._noise is not None:
             watch = (self._observer._h, C.byref(self._obs), _ptr(self._prev), _ptr(self.samples), _ptr(self.bins), _ptr(self.dropped)) if observe \
                 else (None,) * 6
@@ -247,6 +247,25 @@ class QuadFleet(FleetLearning):
         else:
             _lib.check(self.lib.admpc_quad_rollout_batch(*args, self._stream()))
         return QuadRollout(self.x, self.idx, self.tally, self.counts, traj, u)
+
+    def _rollout_args(self, solver, T, traj, u):
+        """The arguments every rollout entry shares, admpc_quad_rollout_batch's up to u_out."""
+        return (solver, self._bank, C.byref(self._plant), self.over, self.B, T, _ptr(self.traj_of), _ptr(self.idx), _ptr(self.x),
+                _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.yref), _ptr(self.yref_e), _ptr(self.cost), _ptr(self.status), _ptr(self.iters),
+                _ptr(self.tally), _ptr(self.counts), _ptr(traj), _ptr(u))
+
+    def _records(self, who, T, record):
+        """T checked, and with record the tensors traj [T+1,B,13] and u [T,B,4] (else None, None)."""
+        T = int(T)
+        if T < 0 or T > T_MAX:
+            raise ValueError("%s: T must be in [0, %d]" % (who, T_MAX))
+        traj = u = None
+        if record:
+            traj = torch.empty((T + 1, self.B, QNX), dtype=torch.float64, device=self.device)
+            u = torch.empty((T, self.B, QNU), dtype=torch.float64, device=self.device)
+            if T == 0:
+                traj[0].copy_(self.x)
+        return T, traj, u
 
     def step(self):
         """One closed-loop step."""

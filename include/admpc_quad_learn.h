@@ -20,7 +20,8 @@
  *   - the search of the hyperparameters for the quadrotor: admpc_gp_search (admpc_hyper.h) checks the car's feature and output ranges.
  *     AdmpcQuadObserveParams holds AdmpcGpBins as AdmpcObserveParams does, so that a later change can route it; until then the length
  *     scales, sigma_f and the noise are GIVEN, as in admpc_learn.h;
- *   - clustered GP ensembles (one handle drives the whole fleet, as in admpc_quad_fleet.h);
+ *   - clustered GP ensembles by THESE entries (one handle and one block of regressors, as in admpc_quad_fleet.h): admpc_quad_ensemble.h
+ *     has observe -> bin -> fit -> install per cluster, and the rollout that flies them;
  *   - np.random's own stream for the simulator's random disturbances: their distributions are flown by admpc_quad_rollout_noise_batch
  *     (admpc_quad_noise.h), observed or not, from a counter-based generator;
  *   - handles in SQP mode (the rollout is the RTI loop);
