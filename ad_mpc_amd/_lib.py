@@ -132,6 +132,17 @@ _QUAD_ENSEMBLE = {  # include/admpc_quad_ensemble.h: a clustered GP ensemble in 
 }
 QUAD_ENSEMBLE_EXPORTS = tuple(_QUAD_ENSEMBLE)
 ENSEMBLE_TABLES = {"admpc_quad_ensemble.h": _QUAD_ENSEMBLE}
+# what finds the centroids of such an ensemble, declared by load() in the same way
+_QUAD_CLUSTERS = {  # include/admpc_quad_clusters.h: the logged rollout, the Gaussian-mixture EM, the install of its means, the re-bin
+    "admpc_quad_ensemble_rollout_log_batch": (I, _QUAD_ENSEMBLE["admpc_quad_ensemble_rollout_batch"][1][:-1] + [dp, vp]),
+    "admpc_quad_clusters_fit": (I, [vp, I, D, D, I, C.c_int64, dp, dp, dp, dp, dp, ip, vp]),
+    "admpc_quad_clusters_install": (I, [vp, dp, ip, ip, ip, vp]),
+    "admpc_quad_ensemble_centroids_set": (I, [vp, dp, ip, vp]),
+    "admpc_quad_ensemble_centroids_get": (I, [vp, dp, vp]),
+    "admpc_quad_clusters_rebin": (I, [vp, I, I, dp, dp, ip, vp]),
+}
+QUAD_CLUSTERS_EXPORTS = tuple(_QUAD_CLUSTERS)
+CLUSTER_TABLES = {"admpc_quad_clusters.h": _QUAD_CLUSTERS}
 
 _lib = None
 
@@ -149,7 +160,7 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()):
+    for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -1,8 +1,8 @@
 // admpc_host.h -- what the host sides of the fleet units share: the device guard, the argument blocks of the two rollouts, and one
 // declaration of every hidden function that one unit defines for another.  The defining unit includes this header too, so that the
 // compiler holds each definition against its declaration.  Included by admpc_kernels.hip, admpc_step.hip, admpc_lane.hip,
-// admpc_plant.hip, admpc_learn.hip, admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip, admpc_quad_learn.hip, admpc_quad_noise.hip and
-// admpc_quad_ensemble.hip.  The learning host
+// admpc_plant.hip, admpc_learn.hip, admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip, admpc_quad_learn.hip, admpc_quad_noise.hip,
+// admpc_quad_ensemble.hip and admpc_quad_clusters.hip.  The learning host
 // side that admpc_learn.hip defines for admpc_quad_learn.hip and admpc_hyper.hip is declared in gp_fit_dev.h, next to the LearnArgs it
 // speaks of.
 #pragma once
@@ -102,11 +102,15 @@ ADMPC_HIDDEN int admpc_quad_plant_params_check(const char* who, const AdmpcQuadP
 ADMPC_HIDDEN int admpc_quad_rollout_check(const QuadRolloutArgs& a, int T);
 ADMPC_HIDDEN int admpc_quad_rollout_enqueue(const QuadRolloutArgs& a, double* traj_pre, double* traj_post, double* u_out, int32_t* route_out, void* stream);
 // admpc_quad_fleet.hip, admpc_quad_learn.hip: a whole rollout and a whole observed rollout behind their arguments' block, refusals and
-// no-ops included (under the names of admpc_quad_rollout_batch and admpc_quad_rollout_observe_batch)
+// no-ops included (under the names of admpc_quad_rollout_batch and admpc_quad_rollout_observe_batch).  samples_step: what the samples
+// pointer advances by per period, 0 for every entry but the logged rollout of admpc_quad_clusters.hip ([T][B][14]: B * 14).  The
+// observed run's refusals alone, for that entry, which has one more behind them: 0 also where B == 0 or T == 0
 ADMPC_HIDDEN int admpc_quad_rollout_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, void* stream);
+ADMPC_HIDDEN int admpc_quad_rollout_observe_check(const QuadRolloutArgs& a, int T, const AdmpcQuadSolver* model, const AdmpcQuadObserveParams* obs,
+                                                  const double* prev, const double* samples, const double* bins, const int32_t* dropped);
 ADMPC_HIDDEN int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, const AdmpcQuadSolver* model,
-                                                const AdmpcQuadObserveParams* obs, double* prev, double* samples, double* bins, int32_t* dropped,
-                                                void* stream);
+                                                const AdmpcQuadObserveParams* obs, double* prev, double* samples, long long samples_step,
+                                                double* bins, int32_t* dropped, void* stream);
 // admpc_quad_noise.hip: one launch of the noisy plant kernel for filled arguments and checked disturbances, B > 0; the refusals of the
 // disturbances (plant: null, or the plant whose u_min motor_noise is held against)
 ADMPC_HIDDEN int admpc_quad_plant_noise_launch(const QuadPlantArgs& a, const AdmpcQuadNoiseParams* noise, uint64_t* noise_step, void* stream);
@@ -117,8 +121,15 @@ ADMPC_HIDDEN int admpc_quad_observe_params_check(const char* who, const AdmpcQua
 ADMPC_HIDDEN int admpc_quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams* plant, const AdmpcQuadObserveParams* obs,
                                            const AdmpcQuadEnsemble* ens, int B, const double* u, long long u_stride, const double* x, double* prev,
                                            double* samples, double* bins, int32_t* dropped, void* stream);
-// admpc_quad_ensemble.hip: the handles of an ensemble (returns K); one launch of its route kernel (route_out: null or [B]) and one of its
-// bin kernel, B > 0, on its device
+// admpc_quad_ensemble.hip: the handles of an ensemble (returns K); what admpc_quad_clusters.hip needs of one (its device centroids to be
+// written, its features, whether it learns and under which blocks; the regressors reach it through the bin launch); one launch of its
+// route kernel (route_out: null or [B]) and one of its bin kernel, B > 0, on its device
+struct QuadEnsembleView {
+    int device, K, n_feat, feat[3], learns;
+    double* cent;                               // device [K][n_feat]
+    const AdmpcQuadObserveParams* obs;          // host [K] (learns)
+};
 ADMPC_HIDDEN int admpc_quad_ensemble_handles(const AdmpcQuadEnsemble* e, AdmpcQuadSolver* const** solvers);
+ADMPC_HIDDEN void admpc_quad_ensemble_view(const AdmpcQuadEnsemble* e, QuadEnsembleView* v);
 ADMPC_HIDDEN int admpc_quad_ensemble_route_launch(const AdmpcQuadEnsemble* e, int B, const double* yref, int32_t* route, int32_t* route_out, void* stream);
 ADMPC_HIDDEN int admpc_quad_ensemble_bin_launch(const AdmpcQuadEnsemble* e, int B, const double* samples, double* bins, int32_t* dropped, void* stream);

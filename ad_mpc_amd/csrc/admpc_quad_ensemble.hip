@@ -31,7 +31,7 @@ struct AdmpcQuadEnsemble {
     AdmpcQuadSolver* solvers[KMAX];
     AdmpcQuadObserveParams obs[KMAX];         // the host copies (learns)
     void* d_mem;                              // the one allocation: centroids [K][n_feat], then LearnGp [K][GMAX]
-    const double* d_cent;
+    double* d_cent;                           // written by admpc_quad_clusters.hip's install and set kernels
     const LearnGp* d_gp;
 };
 
@@ -126,6 +126,14 @@ extern "C" int admpc_quad_ensemble_handles(const AdmpcQuadEnsemble* e, AdmpcQuad
     return e->K;
 }
 
+// for admpc_quad_clusters.hip: the device centroids, the features and the blocks of an ensemble
+extern "C" void admpc_quad_ensemble_view(const AdmpcQuadEnsemble* e, QuadEnsembleView* v)
+{
+    v->device = e->device; v->K = e->K; v->n_feat = e->n_feat; v->learns = e->learns;
+    for (int j = 0; j < 3; ++j) v->feat[j] = e->feat[j];
+    v->cent = e->d_cent; v->obs = e->obs;
+}
+
 // one launch of the route kernel for a checked ensemble, B > 0, on its device (the caller holds it); route_out: null or [B]
 extern "C" int admpc_quad_ensemble_route_launch(const AdmpcQuadEnsemble* e, int B, const double* yref, int32_t* route, int32_t* route_out, void* stream)
 {
@@ -211,7 +219,7 @@ int admpc_quad_ensemble_create(AdmpcQuadSolver* const* solvers, int K, int n_fea
         delete e;
         return admpc_set_error(ADMPC_EHIP, "admpc_quad_ensemble_create: device allocation or copy failed");
     }
-    e->d_cent = (const double*)e->d_mem; e->d_gp = (const LearnGp*)((char*)e->d_mem + nc);
+    e->d_cent = (double*)e->d_mem; e->d_gp = (const LearnGp*)((char*)e->d_mem + nc);
     *out = e;
     return ADMPC_OK;
 }
@@ -306,7 +314,7 @@ int admpc_quad_ensemble_rollout_batch(AdmpcQuadEnsemble* e, const AdmpcQuadTrajB
     // the chain of the plain, observed and noisy rollouts: handle 0 stands for the device, the horizon and the RTI mode of all
     const QuadRolloutArgs a = { e->solvers[0], bank, plant, over, B, traj_of, idx, x, xbar, ubar, yref, yref_e, cost, status, iters, tally, counts,
                                 noise, noise ? noise_step : nullptr, e, route, route_out };
-    return model ? admpc_quad_rollout_observe_run(a, T, traj_out, u_out, model, &e->obs[0], prev, samples, bins, dropped, stream)
+    return model ? admpc_quad_rollout_observe_run(a, T, traj_out, u_out, model, &e->obs[0], prev, samples, 0, bins, dropped, stream)
                  : admpc_quad_rollout_run(a, T, traj_out, u_out, stream);
 }
 

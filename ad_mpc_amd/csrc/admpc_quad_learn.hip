@@ -256,28 +256,42 @@ int admpc_quad_gp_install(AdmpcQuadSolver* s, int n_gp, const AdmpcGp* gp_dev, i
     return ADMPC_OK;
 }
 
-// admpc_quad_rollout_observe_batch behind its arguments' block: the refusals, the no-ops, the latch and the T observed periods; with
-// a.noise the plant of every period is the noisy one (admpc_quad_noise.hip), whose counter array is refused last; with a.ens the solve of
-// every period is the ensemble's routed one and the bin launch the ensemble's (admpc_quad_ensemble.hip), obs being the block its clusters share
-int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, const AdmpcQuadSolver* model,
-                                   const AdmpcQuadObserveParams* obs, double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
+// The refusals of admpc_quad_rollout_observe_batch behind its arguments' block, in its order; 0 also where B == 0 or T == 0, whose arrays are
+// not looked at.  The logged rollout of admpc_quad_clusters.hip has one refusal more behind these.
+int admpc_quad_rollout_observe_check(const QuadRolloutArgs& a, int T, const AdmpcQuadSolver* model, const AdmpcQuadObserveParams* obs,
+                                     const double* prev, const double* samples, const double* bins, const int32_t* dropped)
 {
-    const int B = a.B;
     int rc = quad_observe_params_check("admpc_quad_rollout_observe_batch", obs);
     if (rc) return rc;
     if (!model) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_observe_batch: null model");
     // the rollout's own refusals but those of its arrays, which are among the ones below
     rc = admpc_quad_rollout_check(a, T);
     if (rc) return rc;
-    int device = 0, model_device = 0, N = 0;
-    (void)admpc_quad_solver_info(a.s, &device, &N, nullptr);
+    int device = 0, model_device = 0;
+    (void)admpc_quad_solver_info(a.s, &device, nullptr, nullptr);
     (void)admpc_quad_solver_info(model, &model_device, nullptr, nullptr);
     if (model_device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_observe_batch: the model lives on another device than the solver");
-    if (B == 0 || T == 0) return ADMPC_OK;
+    if (a.B == 0 || T == 0) return ADMPC_OK;
     if (!a.traj_of || !a.idx || !a.x || !a.xbar || !a.ubar || !a.yref || !a.yref_e || !a.status || !a.tally || !a.counts || !prev || !samples || !bins || !dropped ||
         (a.ens && !a.route))
         return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_observe_batch: null array argument");
     if (a.noise && !a.noise_step) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_noise_batch: null noise_step");
+    return ADMPC_OK;
+}
+
+// admpc_quad_rollout_observe_batch behind its arguments' block: the refusals, the no-ops, the latch and the T observed periods; with
+// a.noise the plant of every period is the noisy one (admpc_quad_noise.hip), whose counter array is refused last; with a.ens the solve of
+// every period is the ensemble's routed one and the bin launch the ensemble's (admpc_quad_ensemble.hip), obs being the block its clusters
+// share.  Period t writes and bins the records at samples + t * samples_step: 0 for one [B][14] that every period overwrites.
+int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, const AdmpcQuadSolver* model,
+                                   const AdmpcQuadObserveParams* obs, double* prev, double* samples, long long samples_step, double* bins,
+                                   int32_t* dropped, void* stream)
+{
+    const int B = a.B;
+    int rc = admpc_quad_rollout_observe_check(a, T, model, obs, prev, samples, bins, dropped);
+    if (rc || B == 0 || T == 0) return rc;
+    int device = 0, N = 0;
+    (void)admpc_quad_solver_info(a.s, &device, &N, nullptr);
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     rc = quad_latch_launch(B, a.x, prev, stream);
@@ -286,7 +300,7 @@ int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj
     for (int t = 0; t < T && !rc; ++t) {
         rc = admpc_quad_rollout_enqueue(a, t == 0 ? traj_out : nullptr, traj_out ? traj_out + (size_t)(t + 1) * slot : nullptr,
                                         u_out ? u_out + (size_t)t * B * QU : nullptr, a.route_out ? a.route_out + (size_t)t * B : nullptr, stream);
-        if (!rc) rc = quad_observe_launch(model, a.plant, obs, a.ens, B, a.ubar, (long long)N * QU, a.x, prev, samples, bins, dropped, stream);
+        if (!rc) rc = quad_observe_launch(model, a.plant, obs, a.ens, B, a.ubar, (long long)N * QU, a.x, prev, samples + (long long)t * samples_step, bins, dropped, stream);
     }
     return rc;
 }
@@ -299,7 +313,7 @@ int admpc_quad_rollout_observe_batch(AdmpcQuadSolver* s, const AdmpcQuadTrajBank
                                      double* prev, double* samples, double* bins, int32_t* dropped, void* stream)
 {
     const QuadRolloutArgs a = { s, bank, plant, over, B, traj_of, idx, x, xbar, ubar, yref, yref_e, cost, status, iters, tally, counts, nullptr, nullptr };
-    return admpc_quad_rollout_observe_run(a, T, traj_out, u_out, model, obs, prev, samples, bins, dropped, stream);
+    return admpc_quad_rollout_observe_run(a, T, traj_out, u_out, model, obs, prev, samples, 0, bins, dropped, stream);
 }
 
 }  // extern "C"

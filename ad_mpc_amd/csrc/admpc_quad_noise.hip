@@ -291,7 +291,7 @@ int admpc_quad_rollout_noise_batch(AdmpcQuadSolver* s, const AdmpcQuadTrajBank* 
     if (!rc) rc = noise_params_check(who, noise, plant);
     if (rc) return rc;
     const QuadRolloutArgs a = { s, bank, plant, over, B, traj_of, idx, x, xbar, ubar, yref, yref_e, cost, status, iters, tally, counts, noise, noise_step };
-    return model ? admpc_quad_rollout_observe_run(a, T, traj_out, u_out, model, obs, prev, samples, bins, dropped, stream)
+    return model ? admpc_quad_rollout_observe_run(a, T, traj_out, u_out, model, obs, prev, samples, 0, bins, dropped, stream)
                  : admpc_quad_rollout_run(a, T, traj_out, u_out, stream);
 }
 

@@ -18,7 +18,9 @@ from .quad_config import QNX, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams
 from .quad_fleet import QuadFleet, fleet_quad_config
 
 QuadEnsembleRollout = namedtuple("QuadEnsembleRollout", ("x", "idx", "tally", "counts", "traj", "u", "routes"))
+QuadClusters = namedtuple("QuadClusters", ("weights", "means", "covariances", "n_iter", "converged", "status", "perm"))
 CLUSTERS_MAX = 8
+GMM_BLOCKS_MAX, GMM_ROW, GMM_PARTIAL, GMM_ENOVALID = 256, 18, 81, -100                  # include/admpc_quad_clusters.h
 
 
 def ensemble_layout(centroids, feats, learn=None):
@@ -54,6 +56,48 @@ def ensemble_layout(centroids, feats, learn=None):
     return np.ascontiguousarray(cent), feats, blocks
 
 
+def log_layout(log_steps, learns):
+    """``log_steps`` of the constructor, checked: 0, or the steps the sample log holds in a fleet that learns.  Raises ValueError; needs
+    no GPU."""
+    steps = int(log_steps)
+    if steps < 0 or steps != log_steps:
+        raise ValueError("QuadEnsembleFleet: log_steps must be a whole number and not negative")
+    if steps and not learns:
+        raise ValueError("QuadEnsembleFleet: a sample log (log_steps) needs a fleet that learns: give centroids, feats and learn")
+    return steps
+
+
+def clusters_request(K, feats, steps, max_iter=100, tol=1e-3, reg_covar=1e-6, init=None):
+    """The arguments of ``fit_clusters`` checked as admpc_quad_clusters_fit checks them, for K clusters on ``feats`` and a log that holds
+    ``steps`` steps: (max_iter, tol, reg_covar, init as float64 [K, len(feats)] or None).  Raises ValueError; needs no GPU."""
+    if min(feats) < 7:
+        raise ValueError("fit_clusters: the clustering features must lie in 7 .. 16 (the sample record holds no others)")
+    if int(steps) < 1:
+        raise ValueError("fit_clusters: the log is empty: fly rollout(T, observe=True, log=True) first")
+    if int(max_iter) != max_iter or not 1 <= int(max_iter) <= 1000:
+        raise ValueError("fit_clusters: max_iter must be in 1 .. 1000")
+    tol, reg_covar = float(tol), float(reg_covar)
+    if not tol >= 0.0:
+        raise ValueError("fit_clusters: tol must not be negative")
+    if not (reg_covar >= 0.0 and np.isfinite(reg_covar)):
+        raise ValueError("fit_clusters: reg_covar must be finite and not negative")
+    if init is not None:
+        init = centroid_block("fit_clusters: init", init, K, len(feats))
+    return int(max_iter), tol, reg_covar, init
+
+
+def centroid_block(who, c, K, d):
+    """c as float64 [K, d], finite.  Raises ValueError; needs no GPU."""
+    c = np.asarray(c, dtype=np.float64)
+    if c.ndim == 1 and d == 1:
+        c = c.reshape(-1, 1)
+    if c.shape != (K, d):
+        raise ValueError("%s must be K x len(feats) = %d x %d" % (who, K, d))
+    if not np.isfinite(c).all():
+        raise ValueError("%s: a centroid is not finite" % who)
+    return np.ascontiguousarray(c)
+
+
 class QuadEnsembleFleet(QuadFleet):
     """``QuadFleet`` with one handle per cluster.  Either ``ensemble`` (a ``QuadGPEnsemble``: the fleet flies given clusters) or
     ``centroids`` [K, n_feat], ``feats`` and ``learn`` -- K lists of ``quad_learn_bins`` dicts, one list per cluster, which agree in feat
@@ -63,10 +107,15 @@ class QuadEnsembleFleet(QuadFleet):
     State besides QuadFleet's: ``route`` int32 [B] (the clusters of the last period), and with ``learn`` ``bins`` [K,3,32,5],
     ``dropped`` [K,4] ([c][g]: valid records of cluster c outside regressor g's box; [0][3]: records that are not valid), ``fit_info``
     and ``installed`` [K,3].  There is ONE iterate per vehicle: a vehicle that changes cluster is warm-started from the other cluster's
-    solution (the reference keeps an iterate per solver)."""
+    solution (the reference keeps an iterate per solver).
+
+    With ``log_steps`` a fleet that learns also keeps the records it flies, ``log`` [log_steps,B,14] on the device with a cursor
+    ``log_count`` on the host, and finds its centroids from them (include/admpc_quad_clusters.h): ``rollout(T, observe=True, log=True)``
+    -> ``fit_clusters()`` -> ``fit_gp()`` -> ``rollout(...)``.  Cluster c keeps the box and the hyperparameters of ``learn[c]``."""
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
-                 ensemble=None, centroids=None, feats=None, learn=None, rdrv_d_mat=None, device=0, observe_substeps=1, noise_seed=None):
+                 ensemble=None, centroids=None, feats=None, learn=None, rdrv_d_mat=None, device=0, observe_substeps=1, noise_seed=None,
+                 log_steps=0):
         self._ens = None
         self._solvers = []
         self._init_plant(B, quad, t_horizon, n_nodes, simulation_dt, reference_over_sampling, noise_seed)
@@ -88,7 +137,9 @@ class QuadEnsembleFleet(QuadFleet):
             if not 1 <= int(observe_substeps) <= 64:
                 raise ValueError("QuadEnsembleFleet: observe_substeps must be in [1, 64]")
             clusters = [placeholder_gps(cluster) for cluster in learn]
+        self.log_steps, self.log_count, self.log = log_layout(log_steps, learn is not None), 0, None
         self.K, self.feats, self.centroids = cent.shape[0], feats, cent
+        self._moved = False                                                                # the device's centroids are no longer self.centroids
         cfgs = [fleet_quad_config(quad, t_horizon, n_nodes, q_cost, r_cost, gps, rdrv_d_mat) for gps in clusters]      # one configuration per cluster
         if learn is not None:
             self._nominal = QuadBatchSolver(fleet_quad_config(quad, t_horizon, n_nodes, q_cost, r_cost, None, rdrv_d_mat), device=device)
@@ -113,6 +164,14 @@ class QuadEnsembleFleet(QuadFleet):
             self.bins, self.dropped = z(self.K, QUAD_GP_MAX, GP_MAX_POINTS, 5), z(self.K, QUAD_GP_MAX + 1, dtype=torch.int32)
             self._gp_dev = z(self.K * QUAD_GP_MAX * C.sizeof(AdmpcGp), dtype=torch.uint8)
             self.fit_info, self.installed = z(self.K, QUAD_GP_MAX, dtype=torch.int32), z(self.K, QUAD_GP_MAX, dtype=torch.int32)
+        # the centroids on their way to and from the object, and what the clustering works in
+        self._cent_dev = torch.as_tensor(cent).to(self.device)
+        self.centroids_installed = torch.ones(1, dtype=torch.int32, device=self.device)
+        if self.log_steps:
+            self.log = z(self.log_steps, self.B, QUAD_REC)
+            self._packed, self._partial = z(self.log_steps * self.B, 4), z(GMM_BLOCKS_MAX, GMM_PARTIAL)
+            self.gmm, self.gmm_info = z(1 + self.K, GMM_ROW), z(4, dtype=torch.int32)
+            self.perm = torch.arange(self.K, dtype=torch.int32, device=self.device)
 
     # -- lifetime ---------------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -142,20 +201,105 @@ class QuadEnsembleFleet(QuadFleet):
                                                           _ptr(self.iters), self._stream()))
 
     # -- the closed loop --------------------------------------------------------------------------------------------------------------
-    def rollout(self, T, record=False, observe=False):
+    def rollout(self, T, record=False, observe=False, log=False):
         """T closed-loop steps (admpc_quad_ensemble_rollout_batch): window -> routing from the window -> routed solve -> plant, and with
-        `observe` the ensemble's observation behind every plant step.  Returns QuadEnsembleRollout(x, idx, tally, counts, traj, u,
-        routes): QuadRollout's fields, and with record routes int32 [T,B], the cluster that solved every vehicle in every step."""
+        `observe` the ensemble's observation behind every plant step.  With `log` (which needs `observe`) the records of the T steps are
+        appended to ``log`` (admpc_quad_ensemble_rollout_log_batch; ValueError if they do not fit).  Returns QuadEnsembleRollout(x, idx,
+        tally, counts, traj, u, routes): QuadRollout's fields, and with record routes int32 [T,B], the cluster that solved every vehicle
+        in every step."""
         self._need_bank("rollout")
         if observe:
             self._learns("rollout")
+        if log:
+            if not observe:
+                raise ValueError("rollout: log=True needs observe=True (logging implies observing)")
+            if int(T) > self.log_steps - self.log_count:
+                raise ValueError("rollout: %d steps do not fit into the log (log_steps = %d, %d of them taken); log_reset() empties it"
+                                 % (int(T), self.log_steps, self.log_count))
         T, traj, u = self._records("rollout", T, record)
         routes = torch.empty((T, self.B), dtype=torch.int32, device=self.device) if record else None
         watch = (self._observer._h, _ptr(self._prev), _ptr(self.samples), _ptr(self.bins), _ptr(self.dropped)) if observe else (None,) * 5
         noise = (C.byref(self._noise), _ptr(self.noise_step)) if self._noise is not None else (None, None)
-        _lib.check(self.lib.admpc_quad_ensemble_rollout_batch(*self._rollout_args(self._ens, T, traj, u), _ptr(self.route), _ptr(routes), *watch,
-                                                              *noise, self._stream()))
+        if log and T > 0:
+            at = C.c_void_p(self.log.data_ptr() + self.log_count * self.B * QUAD_REC * 8)
+            _lib.check(self.lib.admpc_quad_ensemble_rollout_log_batch(*self._rollout_args(self._ens, T, traj, u), _ptr(self.route), _ptr(routes),
+                                                                      *watch, *noise, at, self._stream()))
+            self.log_count += T
+        else:
+            _lib.check(self.lib.admpc_quad_ensemble_rollout_batch(*self._rollout_args(self._ens, T, traj, u), _ptr(self.route), _ptr(routes),
+                                                                  *watch, *noise, self._stream()))
         return QuadEnsembleRollout(self.x, self.idx, self.tally, self.counts, traj, u, routes)
+
+    # -- the centroids: given, or found from the log -----------------------------------------------------------------------------------------
+    def log_reset(self):
+        """Empties the sample log (the cursor; the tensor is not touched)."""
+        self.log_count = 0
+
+    def set_centroids(self, c):
+        """c [K, n_feat] into the ensemble's device centroids, on the stream (admpc_quad_ensemble_centroids_set): routing and the bin
+        kernel use them from the next launch on, a captured rollout at its next replay.  Asynchronous; returns the device tensor
+        ``centroids_installed`` int32 [1].  Bins filled under the old centroids are the caller's to zero (or ``rebin``)."""
+        self._cent_dev.copy_(torch.as_tensor(centroid_block("set_centroids: c", c, self.K, len(self.feats))))
+        _lib.check(self.lib.admpc_quad_ensemble_centroids_set(self._ens, _ptr(self._cent_dev), _ptr(self.centroids_installed), self._stream()))
+        self._moved = True
+        return self.centroids_installed
+
+    def _device_centroids(self):
+        """self.centroids refreshed from the device once an install or set_centroids has moved them (synchronises)."""
+        if self._moved:
+            _lib.check(self.lib.admpc_quad_ensemble_centroids_get(self._ens, _ptr(self._cent_dev), self._stream()))
+            torch.cuda.current_stream(self.device).synchronize()
+            self.centroids = self._cent_dev.cpu().numpy().copy()
+        return self.centroids
+
+    def rebin(self):
+        """bins and dropped zeroed, then the logged steps binned under the present centroids (admpc_quad_clusters_rebin).  Asynchronous."""
+        self._learns("rebin")
+        self.bins.zero_()
+        self.dropped.zero_()
+        if self.log_count:
+            _lib.check(self.lib.admpc_quad_clusters_rebin(self._ens, self.log_count, self.B, _ptr(self.log), _ptr(self.bins), _ptr(self.dropped),
+                                                          self._stream()))
+
+    def fit_clusters(self, max_iter=100, tol=1e-3, reg_covar=1e-6, init=None, install=True, rebin=True, resume=False):
+        """The centroids from the log: sklearn's Gaussian-mixture EM (full covariances; max_iter, tol and reg_covar are its defaults) from
+        the means ``init`` [K, n_feat] (default: the present centroids; a float64 tensor on the fleet's device is taken as it is, which
+        keeps the call free of copies for a graph) over the logged records (admpc_quad_clusters_fit), then
+        (`install`) its means, sorted along the first feature, as the ensemble's centroids, and (`rebin`) the log binned again under
+        them.  One chain of launches on the stream, asynchronous; returns the device tensors (info int32 [4]: iterations, converged,
+        status, n_valid; perm int32 [K]; installed int32 [1]), the last two None without `install`."""
+        self._learns("fit_clusters")
+        start = None
+        if torch.is_tensor(init):
+            self._eng._chk(init, (self.K, len(self.feats)))
+            start, init = init, None
+        max_iter, tol, reg_covar, init = clusters_request(self.K, self.feats, self.log_count, max_iter, tol, reg_covar, init)
+        s = self._stream()
+        if init is not None:
+            start = torch.as_tensor(init).to(self.device)
+        _lib.check(self.lib.admpc_quad_clusters_fit(self._ens, max_iter, tol, reg_covar, 1 if resume else 0, self.log_count * self.B, _ptr(self.log),
+                                                    _ptr(start), _ptr(self._packed), _ptr(self._partial), _ptr(self.gmm), _ptr(self.gmm_info), s))
+        if install:
+            _lib.check(self.lib.admpc_quad_clusters_install(self._ens, _ptr(self.gmm), _ptr(self.gmm_info), _ptr(self.perm),
+                                                            _ptr(self.centroids_installed), s))
+            self._moved = True
+        if rebin:
+            self.rebin()
+        return (self.gmm_info, self.perm, self.centroids_installed) if install else (self.gmm_info, None, None)
+
+    def learned_clusters(self):
+        """The mixture of the last fit_clusters as numpy (synchronises): QuadClusters(weights [K], means [K,n_feat], covariances
+        [K,n_feat,n_feat], n_iter, converged, status, perm [K]), the components in the order of the fit -- cluster c is component
+        perm[c].  ``self.centroids`` is refreshed from the device."""
+        self._learns("learned_clusters")
+        if not self.log_steps:
+            raise ValueError("learned_clusters: this fleet keeps no log, create it with log_steps")
+        self._device_centroids()
+        torch.cuda.current_stream(self.device).synchronize()
+        g, info, d = self.gmm.cpu().numpy(), self.gmm_info.cpu().numpy(), len(self.feats)
+        tri = np.array([[4, 5, 6], [5, 7, 8], [6, 8, 9]])
+        return QuadClusters(g[1:, 0].copy(), g[1:, 1:1 + d].copy(), g[1:][:, tri][:, :d, :d].copy(), int(info[0]), bool(info[1]), int(info[2]),
+                            self.perm.cpu().numpy().copy())
 
     # -- learning, per cluster ----------------------------------------------------------------------------------------------------------
     def set_observer(self, learned=False, cluster=0):
@@ -189,10 +333,11 @@ class QuadEnsembleFleet(QuadFleet):
         return self.fit_info[:, :n], self.installed[:, :n]
 
     def learned_gps(self):
-        """The GPs of the last fit_gp as a ``QuadGPEnsemble`` with the fleet's centroids and features (synchronises): what
+        """The GPs of the last fit_gp as a ``QuadGPEnsemble`` with the centroids the device holds and the fleet's features (synchronises): what
         ``QuadEnsembleFleet(ensemble=...)`` takes.  Every cluster is decoded as QuadFleet.learned_gps decodes its one."""
         self._learns("learned_gps")
         torch.cuda.current_stream(self.device).synchronize()
         raw = self._gp_dev.cpu().numpy().tobytes()
         per = QUAD_GP_MAX * C.sizeof(AdmpcGp)
-        return QuadGPEnsemble([decode_gps(raw[c * per:(c + 1) * per], self._learn[c], self._EMPTY) for c in range(self.K)], self.centroids, self.feats)
+        return QuadGPEnsemble([decode_gps(raw[c * per:(c + 1) * per], self._learn[c], self._EMPTY) for c in range(self.K)], self._device_centroids(),
+                              self.feats)

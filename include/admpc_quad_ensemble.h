@@ -20,7 +20,8 @@
  *   quad_mpc/quad_3d_optimizer.py:289-327  where the GPs enter the model of the MPC            admpc_quad_ensemble_install
  *
  * NOT offered:
- *   - the GMM that finds the centroids (gp_fitting.py): the centroids are GIVEN;
+ *   - the GMM that finds the centroids (gp_fitting.py): to THESE entries the centroids are GIVEN; admpc_quad_clusters.h finds them from a
+ *     log of the records flown, and installs them in the object's device copy;
  *   - the search of the hyperparameters (admpc_hyper.h is not routed: the length scales, sigma_f and the noise of every cluster are given);
  *   - SQP mode (a handle with sqp_iters > 1 is refused: the rollout is the RTI loop).
  *
