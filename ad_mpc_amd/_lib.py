@@ -143,6 +143,17 @@ _QUAD_CLUSTERS = {  # include/admpc_quad_clusters.h: the logged rollout, the Gau
 }
 QUAD_CLUSTERS_EXPORTS = tuple(_QUAD_CLUSTERS)
 CLUSTER_TABLES = {"admpc_quad_clusters.h": _QUAD_CLUSTERS}
+# the search of the quadrotor's hyperparameters, one handle or a whole ensemble, declared by load() in the same way
+sp_ = C.POINTER(AdmpcGpSearchParams)
+_QUAD_HYPER = {     # include/admpc_quad_hyper.h: admpc_hyper.h's search and re-fit with the quadrotor's ranges, and for all clusters of an ensemble at once
+    "admpc_quad_gp_search": (I, [I, qop, sp_, I, I, dp, dp, dp, ip, vp]),
+    "admpc_quad_gp_refit": (I, [I, qop, I, dp, dp, vp, ip, vp]),
+    "admpc_quad_ensemble_set_search": (I, [vp, sp_]),
+    "admpc_quad_ensemble_search": (I, [vp, I, I, dp, dp, dp, ip, vp]),
+    "admpc_quad_ensemble_refit": (I, [vp, I, dp, dp, vp, ip, vp]),
+}
+QUAD_HYPER_EXPORTS = tuple(_QUAD_HYPER)
+HYPER_TABLES = {"admpc_quad_hyper.h": _QUAD_HYPER}
 
 _lib = None
 
@@ -160,7 +171,8 @@ def load():
         raise AdmpcError("%s not found: build it with `make -C ad_mpc_amd/csrc` (or __graft_entry__.build()); "
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()):
+    for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()) + \
+            list(HYPER_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

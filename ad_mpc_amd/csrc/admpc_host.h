@@ -2,9 +2,9 @@
 // declaration of every hidden function that one unit defines for another.  The defining unit includes this header too, so that the
 // compiler holds each definition against its declaration.  Included by admpc_kernels.hip, admpc_step.hip, admpc_lane.hip,
 // admpc_plant.hip, admpc_learn.hip, admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip, admpc_quad_learn.hip, admpc_quad_noise.hip,
-// admpc_quad_ensemble.hip and admpc_quad_clusters.hip.  The learning host
+// admpc_quad_ensemble.hip, admpc_quad_clusters.hip and admpc_quad_hyper.hip.  The learning host
 // side that admpc_learn.hip defines for admpc_quad_learn.hip and admpc_hyper.hip is declared in gp_fit_dev.h, next to the LearnArgs it
-// speaks of.
+// speaks of; the search's host side that admpc_hyper.hip defines for admpc_quad_hyper.hip in gp_search_dev.h, next to its SearchGp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -121,13 +121,23 @@ ADMPC_HIDDEN int admpc_quad_observe_params_check(const char* who, const AdmpcQua
 ADMPC_HIDDEN int admpc_quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams* plant, const AdmpcQuadObserveParams* obs,
                                            const AdmpcQuadEnsemble* ens, int B, const double* u, long long u_stride, const double* x, double* prev,
                                            double* samples, double* bins, int32_t* dropped, void* stream);
-// admpc_quad_ensemble.hip: the handles of an ensemble (returns K); what admpc_quad_clusters.hip needs of one (its device centroids to be
-// written, its features, whether it learns and under which blocks; the regressors reach it through the bin launch); one launch of its
-// route kernel (route_out: null or [B]) and one of its bin kernel, B > 0, on its device
+// admpc_quad_ensemble.hip: the handles of an ensemble (returns K); what admpc_quad_clusters.hip and admpc_quad_hyper.hip need of one (its
+// device centroids to be written, its features, whether it learns and under which blocks, the device copy of its regressors, its search
+// slot); one launch of its route kernel (route_out: null or [B]) and one of its bin kernel, B > 0, on its device
+struct LearnGp;                                 // gp_fit_dev.h: one regressor as the learning kernels read it
+// what admpc_quad_hyper.hip keeps in an ensemble: the device copy of the search descriptors (null until the first
+// admpc_quad_ensemble_set_search; the object frees it), and what the K blocks of the last one agree in, with their largest candidate count
+struct QuadEnsembleSearch {
+    void* d_desc;
+    int set, grid, rounds, cmax;
+    double shrink;
+};
 struct QuadEnsembleView {
-    int device, K, n_feat, feat[3], learns;
+    int device, K, n_feat, feat[3], learns, n_gp;
     double* cent;                               // device [K][n_feat]
     const AdmpcQuadObserveParams* obs;          // host [K] (learns)
+    const LearnGp* gp;                          // device [K][ADMPC_QUAD_GP_MAX] (learns)
+    QuadEnsembleSearch* search;                 // the object's own, to be written by admpc_quad_ensemble_set_search
 };
 ADMPC_HIDDEN int admpc_quad_ensemble_handles(const AdmpcQuadEnsemble* e, AdmpcQuadSolver* const** solvers);
 ADMPC_HIDDEN void admpc_quad_ensemble_view(const AdmpcQuadEnsemble* e, QuadEnsembleView* v);

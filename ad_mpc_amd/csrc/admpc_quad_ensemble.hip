@@ -10,7 +10,8 @@
 //
 // The period of the routed rollout (window -> route -> routed solve -> plant) is admpc_quad_fleet.hip's, the observed run
 // admpc_quad_learn.hip's: their argument block carries the ensemble, and they call the two launches below.  The observe kernel, the fit and
-// the install are those units' own, per cluster.
+// the install are those units' own, per cluster.  The search of the hyperparameters of all clusters is admpc_quad_hyper.hip's, which
+// reaches the object through admpc_quad_ensemble_view and keeps its search descriptors in the object's `search` slot.
 #include <stdio.h>
 #include <math.h>
 #include <new>
@@ -33,6 +34,7 @@ struct AdmpcQuadEnsemble {
     void* d_mem;                              // the one allocation: centroids [K][n_feat], then LearnGp [K][GMAX]
     double* d_cent;                           // written by admpc_quad_clusters.hip's install and set kernels
     const LearnGp* d_gp;
+    QuadEnsembleSearch search;                // admpc_quad_hyper.hip's: the search descriptors of admpc_quad_ensemble_set_search
 };
 
 // what one launch of the bin kernel works on (passed by value; the regressors and the centroids by pointer into the object's device copy)
@@ -126,12 +128,14 @@ extern "C" int admpc_quad_ensemble_handles(const AdmpcQuadEnsemble* e, AdmpcQuad
     return e->K;
 }
 
-// for admpc_quad_clusters.hip: the device centroids, the features and the blocks of an ensemble
+// for admpc_quad_clusters.hip and admpc_quad_hyper.hip: the device centroids, the features, the blocks, the device regressors and the
+// search slot of an ensemble (the slot is the object's own state, which a set_search writes whoever holds the object)
 extern "C" void admpc_quad_ensemble_view(const AdmpcQuadEnsemble* e, QuadEnsembleView* v)
 {
-    v->device = e->device; v->K = e->K; v->n_feat = e->n_feat; v->learns = e->learns;
+    v->device = e->device; v->K = e->K; v->n_feat = e->n_feat; v->learns = e->learns; v->n_gp = e->n_gp;
     for (int j = 0; j < 3; ++j) v->feat[j] = e->feat[j];
-    v->cent = e->d_cent; v->obs = e->obs;
+    v->cent = e->d_cent; v->obs = e->obs; v->gp = e->d_gp;
+    v->search = const_cast<QuadEnsembleSearch*>(&e->search);
 }
 
 // one launch of the route kernel for a checked ensemble, B > 0, on its device (the caller holds it); route_out: null or [B]
@@ -229,6 +233,7 @@ void admpc_quad_ensemble_destroy(AdmpcQuadEnsemble* e)
     if (!e) return;
     DeviceGuard guard(e->device);
     if (e->d_mem) (void)hipFree(e->d_mem);
+    if (e->search.d_desc) (void)hipFree(e->search.d_desc);
     delete e;
 }
 

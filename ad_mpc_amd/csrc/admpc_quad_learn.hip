@@ -11,7 +11,7 @@
 //   install  admpc_quad_gp_install_kernel  one wave: checks each record and copies it into the handle's device configuration; the body
 //                                          of the car's (gp_fit_dev.h) with the quadrotor's ranges
 //
-// The hyperparameters are given (admpc_quad_learn.h: what is not offered).  The refusals of the regressors, their form for the kernels
+// To this unit's fit the hyperparameters are given (admpc_quad_learn.h: what is not offered); admpc_quad_hyper.hip searches them.  The refusals of the regressors, their form for the kernels
 // and the fit entry are admpc_learn.hip's (declared in gp_fit_dev.h).  The rollout with observation is at the end of the file.
 #include <stdio.h>
 #include <math.h>

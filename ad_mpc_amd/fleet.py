@@ -5,7 +5,7 @@ wherever on it the vehicle is (include/admpc_lane.h: admpc_control_step_lane_bat
 the record just issued, and T steps of controller and plant per call (include/admpc_plant.h: admpc_plant_step_batch,
 admpc_rollout_lane_batch), or learns the residual GP of its model from the steps it has taken, on the device (include/admpc_learn.h:
 observe -> bin -> fit -> install; the side it shares with the quadrotor's fleet is learning.py's), and searches the hyperparameters of
-that GP on the device (include/admpc_hyper.h: search -> re-fit -> install).
+that GP on the device (include/admpc_hyper.h: search -> re-fit -> install; search_gp and learned_hyper are learning.py's too).
 
 ``FleetController`` solves the problem of ``ROSGPMPC(point_reference=False)`` (create_ros_ad_mpc.py:41-101: SQP_RTI, Q_DIAG_ROS /
 R_DIAG_ROS) for every vehicle, and does per step what the reference node does per pose message (gp_ad_mpc_node.py:389-438 ->
@@ -29,9 +29,9 @@ from . import _lib
 from . import config as _c
 from .ad_3d import AD3D
 from .ad_3d_optimizer import ocp_config
-from .config import AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams, GP_MAX, NX, NU
+from .config import AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams, GP_MAX, NX, NU
 from .engine import BatchSolver, _ptr
-from .learning import FleetLearning, placeholder_gps
+from .learning import FleetSearch, placeholder_gps
 from .ref_traj import RefTrajectory
 
 SAFE_COUNT_THRESHOLD = 10          # consecutive successes before the node issues an MPC command (gp_ad_mpc_node.py:62)
@@ -85,8 +85,9 @@ class FleetRollout(NamedTuple):
     traj: torch.Tensor         # float64 [steps+1,7,B] or None: the poses at the start of every step, and the final ones
 
 
-class FleetController(FleetLearning):
+class FleetController(FleetSearch):
     _FIT, _INSTALL, _GP_CAP, _REC, _EMPTY, _NOUN = "admpc_gp_fit", "admpc_gp_install", GP_MAX, 10, 3, "controller"
+    _SEARCH, _REFIT = "admpc_gp_search", "admpc_gp_refit"
 
     def __init__(self, t_horizon, n_mpc_nodes, opt_dt, B, device=0, resample=True, threshold=SAFE_COUNT_THRESHOLD, blend_min=None,
                  blend_max=None, learn=None):
@@ -138,10 +139,6 @@ class FleetController(FleetLearning):
         if learn is not None:
             obs = AdmpcObserveParams(dt=0.0, blend_min=ad.blend_min, blend_max=ad.blend_max, substeps=1, n_gp=n_gp, gp=bins)
             self._alloc_learning(learn, n_gp, obs, (NX, B))
-            # the hyperparameter search (search_gp): its state, a scratch of one NLL per candidate, and what the last round picked
-            self.hyper, self._nll = z(GP_MAX, _c.GP_HYPER), z(GP_MAX, _c.GP_SEARCH_MAX)
-            self.search_info = z(GP_MAX, 2, dtype=torch.int32)
-            self._has_hyper = self._searched = False                      # a search has run; _gp_dev holds a re-fit at searched values
 
     def _drop_bank(self):
         if getattr(self, "_bank", None):
@@ -314,16 +311,6 @@ class FleetController(FleetLearning):
         o.dt, o.substeps, o.blend_min, o.blend_max = self._plant.dt, self._plant.substeps, self._prm.blend_min, self._prm.blend_max
         return o
 
-    def _fitted(self):
-        self._searched = False
-
-    def _head(self, g, d):
-        """After a search_gp the length scales and sigma_f it found (the device's own doubles), not those given to ``learn``."""
-        if not self._searched:
-            return d
-        h = self.hyper[g].tolist()
-        return dict(d, length_scale=h[10:10 + int(self._obs.gp[g].n_feat)], sigma_f=h[13])
-
     def observe_latch(self, x, y, yaw, vx, vy, yaw_rate, steer):
         """Takes the poses the next observe will predict from.  Asynchronous on the current stream."""
         self._observe_params("observe_latch")
@@ -339,47 +326,6 @@ class FleetController(FleetLearning):
         _lib.check(self.lib.admpc_observe_batch(self._observer._h, C.byref(self._plant), C.byref(obs), self.B, _ptr(self.ack), _ptr(self.mode),
                                                 *poses, _ptr(self._prev), _ptr(self.samples), _ptr(self.bins), _ptr(self.dropped),
                                                 self._eng._stream()))
-
-    def search_gp(self, min_count=1, grid=5, rounds=10, shrink=0.5, bounds=None, resume=False, install=True):
-        """Searches the length scales, sigma_f and the noise of every regressor for the smallest negative log marginal likelihood of its
-        points (the bins with at least `min_count` samples), fits at what it found and (`install`) overwrites the GPs of the controller's
-        handle on the device: 2 * rounds + 2 launches on the current stream (one more where the search starts), no synchronisation, no allocation.  Every round evaluates
-        a regular grid of `grid` points per free slot in the logarithm of the slots, around the best candidate so far, and multiplies
-        the grid's step by `shrink`; the first round spans the box.  ``bounds``: config.search_boxes (None: the reference's box;
-        lo == hi keeps a slot at that value).  ``resume`` continues the last search on the same statistics with the steps where they
-        stand.  Returns the device tensors (info int32 [n] as fit_gp's, or -33 where no candidate had a finite NLL; installed int32
-        [n] or None; hyper float64 [n, 16]: the centre's logarithms, the steps, the natural values and the best NLL)."""
-        obs = self._observe_params("search_gp", observing=False)
-        n = self.n_learn
-        sp = AdmpcGpSearchParams(grid=int(grid), rounds=int(rounds), shrink=float(shrink), box=_c.search_boxes(self._learn, bounds))
-        s = self._eng._stream()
-        _lib.check(self.lib.admpc_gp_search(self.device.index, C.byref(obs), C.byref(sp), int(min_count), 1 if resume else 0, _ptr(self.bins),
-                                            _ptr(self.hyper), _ptr(self._nll), _ptr(self.search_info), s))
-        _lib.check(self.lib.admpc_gp_refit(self.device.index, C.byref(obs), int(min_count), _ptr(self.bins), _ptr(self.hyper), _ptr(self._gp_dev),
-                                           _ptr(self.fit_info), s))
-        self._has_hyper = self._searched = True
-        if not install:
-            return self.fit_info[:n], None, self.hyper[:n]
-        _lib.check(self.lib.admpc_gp_install(self._eng._h, n, _ptr(self._gp_dev), _ptr(self.installed), s))
-        return self.fit_info[:n], self.installed[:n], self.hyper[:n]
-
-    def learned_hyper(self):
-        """The hyperparameters of every regressor as the last search_gp left them (synchronises): a list of dicts with length_scale (one
-        per feature), sigma_f, noise and nll, the negative log marginal likelihood there.  Before any search: the values given to
-        ``learn`` and nll = inf."""
-        self._learns("learned_hyper")
-        torch.cuda.current_stream(self.device).synchronize()
-        hy = self.hyper.cpu().numpy()
-        out = []
-        for g, d in enumerate(self._learn):
-            b = self._obs.gp[g]
-            nf = int(b.n_feat)
-            if not self._has_hyper:
-                out.append(dict(length_scale=[float(b.length[k]) for k in range(nf)], sigma_f=float(b.sigma_f), noise=float(b.noise), nll=float("inf")))
-            else:
-                out.append(dict(length_scale=[float(hy[g, 10 + k]) for k in range(nf)], sigma_f=float(hy[g, 13]), noise=float(hy[g, 14]),
-                                nll=float(hy[g, 15])))
-        return out
 
     def best_of(self, group, cost=None):
         """The cheapest usable candidate of every group of `group` consecutive instances of the last step_paths or step_route (instance b = v * group + c

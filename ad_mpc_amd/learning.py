@@ -1,14 +1,16 @@
-"""The learning side both fleets share (include/admpc_learn.h, include/admpc_quad_learn.h: observe -> bin -> fit -> install): the
-placeholder GPs a fleet that learns is created with, the tensors of the record and the statistics, the fit, and the decode of the
+"""The learning side both fleets share (include/admpc_learn.h, include/admpc_quad_learn.h: observe -> bin -> fit -> install; include/admpc_hyper.h,
+include/admpc_quad_hyper.h: search -> re-fit -> install): the
+placeholder GPs a fleet that learns is created with, the tensors of the record and the statistics, the fit, the search, and the decode of the
 fitted ``AdmpcGp`` records into the dicts ``config.set_gp`` / ``quad_config.set_quad_gp`` take.  ``FleetController`` (fleet.py) and
-``QuadFleet`` (quad_fleet.py) derive from ``FleetLearning`` and supply what differs between the vehicles."""
+``QuadFleet`` (quad_fleet.py) derive from ``FleetLearning`` and supply what differs between the vehicles; the search is ``FleetSearch``,
+a class of its own on top of it, which ``FleetController`` and ``QuadLearningFleet`` -- what ``QuadFleet(learn=...)`` creates -- derive from."""
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib
-from .config import AdmpcGp, GP_MAX_POINTS
+from .config import AdmpcGp, AdmpcGpSearchParams, GP_HYPER, GP_MAX_POINTS, GP_SEARCH_MAX, search_boxes
 from .engine import _ptr
 
 
@@ -101,7 +103,7 @@ class FleetLearning:
         return self.fit_info[:n], self.installed[:n]
 
     def learned_gps(self):
-        """The GPs of the last fit_gp (or search_gp, where the vehicle has one) as the list of dicts ``set_gp`` / ``set_quad_gp`` /
+        """The GPs of the last fit_gp (or search_gp, where the fleet has one) as the list of dicts ``set_gp`` / ``set_quad_gp`` /
         ``gp_regressors=`` take (synchronises): to save the model, or to create another handle with what was learned.  length_scale is
         the one given to ``learn`` after a fit_gp, and the one found after a search_gp: the device's own double, from which set_gp forms
         the inv_l2 that was installed.  A record the install refuses (a number that is not finite) is returned as the install leaves it
@@ -110,3 +112,73 @@ class FleetLearning:
         torch.cuda.current_stream(self.device).synchronize()
         raw = self._gp_dev.cpu().numpy().tobytes()
         return decode_gps(raw, [self._head(g, d) for g, d in enumerate(self._learn)], self._EMPTY)
+
+
+def hyper_dicts(hy, bins, n, has_hyper):
+    """learned_hyper's list for one block of n regressors: from hy [n, 16] after a search, from the block's given values before."""
+    out = []
+    for g in range(n):
+        b = bins[g]
+        nf = int(b.n_feat)
+        if not has_hyper:
+            out.append(dict(length_scale=[float(b.length[k]) for k in range(nf)], sigma_f=float(b.sigma_f), noise=float(b.noise), nll=float("inf")))
+        else:
+            out.append(dict(length_scale=[float(hy[g, 10 + k]) for k in range(nf)], sigma_f=float(hy[g, 13]), noise=float(hy[g, 14]),
+                            nll=float(hy[g, 15])))
+    return out
+
+
+class FleetSearch(FleetLearning):
+    """FleetLearning with the search of the hyperparameters on the device (include/admpc_hyper.h, include/admpc_quad_hyper.h: search ->
+    re-fit -> install): what ``FleetController`` (fleet.py) and a ``QuadFleet`` that learns (quad_fleet.py: ``QuadLearningFleet``) share."""
+    _SEARCH = _REFIT = None        # the names of the vehicle's search and re-fit entries
+
+    def _alloc_learning(self, learn, n_gp, obs, prev_shape):
+        """FleetLearning's state, and the search's: its state per regressor, a scratch of one NLL per candidate, what the last round picked."""
+        super()._alloc_learning(learn, n_gp, obs, prev_shape)
+        z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=self.device)
+        cap = self._GP_CAP
+        self.hyper, self._nll = z(cap, GP_HYPER), z(cap, GP_SEARCH_MAX)
+        self.search_info = z(cap, 2, dtype=torch.int32)
+        self._has_hyper = self._searched = False                          # a search has run; _gp_dev holds a re-fit at searched values
+
+    def _fitted(self):
+        self._searched = False
+
+    def _head(self, g, d):
+        """After a search_gp the length scales and sigma_f it found (the device's own doubles), not those given to ``learn``."""
+        if not self._searched:
+            return d
+        h = self.hyper[g].tolist()
+        return dict(d, length_scale=h[10:10 + int(self._obs.gp[g].n_feat)], sigma_f=h[13])
+
+    def search_gp(self, min_count=1, grid=5, rounds=10, shrink=0.5, bounds=None, resume=False, install=True):
+        """Searches the length scales, sigma_f and the noise of every regressor for the smallest negative log marginal likelihood of its
+        points (the bins with at least `min_count` samples), fits at what it found and (`install`) overwrites the GPs of the controller's
+        handle on the device: 2 * rounds + 2 launches on the current stream (one more where the search starts), no synchronisation, no allocation.  Every round evaluates
+        a regular grid of `grid` points per free slot in the logarithm of the slots, around the best candidate so far, and multiplies
+        the grid's step by `shrink`; the first round spans the box.  ``bounds``: config.search_boxes (None: the reference's box;
+        lo == hi keeps a slot at that value).  ``resume`` continues the last search on the same statistics with the steps where they
+        stand.  Returns the device tensors (info int32 [n] as fit_gp's, or -33 where no candidate had a finite NLL; installed int32
+        [n] or None; hyper float64 [n, 16]: the centre's logarithms, the steps, the natural values and the best NLL)."""
+        obs = self._observe_params("search_gp", observing=False)
+        n, dev = self.n_learn, self._eng.device_index
+        sp = AdmpcGpSearchParams(grid=int(grid), rounds=int(rounds), shrink=float(shrink), box=search_boxes(self._learn, bounds))
+        s = self._eng._stream()
+        _lib.check(getattr(self.lib, self._SEARCH)(dev, C.byref(obs), C.byref(sp), int(min_count), 1 if resume else 0, _ptr(self.bins),
+                                                  _ptr(self.hyper), _ptr(self._nll), _ptr(self.search_info), s))
+        _lib.check(getattr(self.lib, self._REFIT)(dev, C.byref(obs), int(min_count), _ptr(self.bins), _ptr(self.hyper), _ptr(self._gp_dev),
+                                                 _ptr(self.fit_info), s))
+        self._has_hyper = self._searched = True
+        if not install:
+            return self.fit_info[:n], None, self.hyper[:n]
+        _lib.check(getattr(self.lib, self._INSTALL)(self._eng._h, n, _ptr(self._gp_dev), _ptr(self.installed), s))
+        return self.fit_info[:n], self.installed[:n], self.hyper[:n]
+
+    def learned_hyper(self):
+        """The hyperparameters of every regressor as the last search_gp left them (synchronises): a list of dicts with length_scale (one
+        per feature), sigma_f, noise and nll, the negative log marginal likelihood there.  Before any search: the values given to
+        ``learn`` and nll = inf."""
+        self._learns("learned_hyper")
+        torch.cuda.current_stream(self.device).synchronize()
+        return hyper_dicts(self.hyper.cpu().numpy(), self._obs.gp, self.n_learn, self._has_hyper)

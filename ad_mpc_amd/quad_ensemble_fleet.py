@@ -10,9 +10,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import AdmpcGp, GP_MAX_POINTS
+from .config import AdmpcGp, AdmpcGpSearchParams, GP_HYPER, GP_MAX_POINTS, GP_SEARCH_MAX, search_boxes
 from .engine import QuadBatchSolver, _ptr
-from .learning import decode_gps, placeholder_gps
+from .learning import decode_gps, hyper_dicts, placeholder_gps
 from .quad_3d_optimizer import QuadGPEnsemble
 from .quad_config import QNX, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, quad_learn_bins
 from .quad_fleet import QuadFleet, fleet_quad_config
@@ -111,7 +111,9 @@ class QuadEnsembleFleet(QuadFleet):
 
     With ``log_steps`` a fleet that learns also keeps the records it flies, ``log`` [log_steps,B,14] on the device with a cursor
     ``log_count`` on the host, and finds its centroids from them (include/admpc_quad_clusters.h): ``rollout(T, observe=True, log=True)``
-    -> ``fit_clusters()`` -> ``fit_gp()`` -> ``rollout(...)``.  Cluster c keeps the box and the hyperparameters of ``learn[c]``."""
+    -> ``fit_clusters()`` -> ``fit_gp()`` -> ``rollout(...)``.  Cluster c keeps the box and the hyperparameters of ``learn[c]``; ``search_gp()``
+    in place of ``fit_gp()`` finds the length scales, sigma_f and the noise of every cluster from the data it holds now
+    (include/admpc_quad_hyper.h), all on the same stream.  ``hyper`` [K,3,16] and ``search_info`` [K,3,2] are the state of that search."""
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
                  ensemble=None, centroids=None, feats=None, learn=None, rdrv_d_mat=None, device=0, observe_substeps=1, noise_seed=None,
@@ -164,6 +166,12 @@ class QuadEnsembleFleet(QuadFleet):
             self.bins, self.dropped = z(self.K, QUAD_GP_MAX, GP_MAX_POINTS, 5), z(self.K, QUAD_GP_MAX + 1, dtype=torch.int32)
             self._gp_dev = z(self.K * QUAD_GP_MAX * C.sizeof(AdmpcGp), dtype=torch.uint8)
             self.fit_info, self.installed = z(self.K, QUAD_GP_MAX, dtype=torch.int32), z(self.K, QUAD_GP_MAX, dtype=torch.int32)
+            # the hyperparameter search of all clusters (search_gp): its state, the scratch, the last round's picks, and the parameters
+            # the object holds (set_search is synchronous, so it is called only when they change)
+            self.hyper, self._nll = z(self.K, QUAD_GP_MAX, GP_HYPER), z(self.K, QUAD_GP_MAX, GP_SEARCH_MAX)
+            self.search_info = z(self.K, QUAD_GP_MAX, 2, dtype=torch.int32)
+            self._has_hyper = self._searched = False
+            self._search_set = None
         # the centroids on their way to and from the object, and what the clustering works in
         self._cent_dev = torch.as_tensor(cent).to(self.device)
         self.centroids_installed = torch.ones(1, dtype=torch.int32, device=self.device)
@@ -327,17 +335,71 @@ class QuadEnsembleFleet(QuadFleet):
         self._learns("fit_gp")
         n, s = self.n_learn, self._stream()
         _lib.check(self.lib.admpc_quad_ensemble_fit(self._ens, int(min_count), _ptr(self.bins), _ptr(self._gp_dev), _ptr(self.fit_info), s))
+        self._searched = False                                                             # the records hold the given hyperparameters again
         if not install:
             return self.fit_info[:, :n], None
         _lib.check(self.lib.admpc_quad_ensemble_install(self._ens, _ptr(self._gp_dev), _ptr(self.installed), s))
         return self.fit_info[:, :n], self.installed[:, :n]
 
+    def search_gp(self, min_count=1, grid=5, rounds=10, shrink=0.5, bounds=None, resume=False, install=True):
+        """QuadFleet.search_gp for every regressor of every cluster in one chain of launches (include/admpc_quad_hyper.h:
+        admpc_quad_ensemble_search -> admpc_quad_ensemble_refit -> admpc_quad_ensemble_install): 2 * rounds + 1 + K launches on the
+        fleet's stream, one more where the search starts.  ``bounds``: None (the reference's box everywhere), one list of
+        config.search_boxes dicts per regressor (every cluster searches that box), or K such lists.  grid, rounds and shrink serve all
+        clusters.  The parameters go to the object by admpc_quad_ensemble_set_search, which synchronises, only when they differ from the
+        last call's: a second call with the same ones has no host synchronisation and no allocation.  After ``fit_clusters()`` call
+        with resume=False: the clusters hold other data.  Returns the device tensors (info int32 [K,n], installed int32 [K,n] or None,
+        hyper float64 [K,n,16])."""
+        self._learns("search_gp")
+        n = self.n_learn
+        sp = (AdmpcGpSearchParams * self.K)()
+        for c, b in enumerate(self._cluster_bounds(bounds)):
+            sp[c] = AdmpcGpSearchParams(grid=int(grid), rounds=int(rounds), shrink=float(shrink), box=search_boxes(self._learn[c], b))
+        key = bytes(sp)
+        if key != self._search_set:
+            _lib.check(self.lib.admpc_quad_ensemble_set_search(self._ens, sp))
+            self._search_set = key
+        s = self._stream()
+        _lib.check(self.lib.admpc_quad_ensemble_search(self._ens, int(min_count), 1 if resume else 0, _ptr(self.bins), _ptr(self.hyper),
+                                                       _ptr(self._nll), _ptr(self.search_info), s))
+        _lib.check(self.lib.admpc_quad_ensemble_refit(self._ens, int(min_count), _ptr(self.bins), _ptr(self.hyper), _ptr(self._gp_dev),
+                                                      _ptr(self.fit_info), s))
+        self._has_hyper = self._searched = True
+        if not install:
+            return self.fit_info[:, :n], None, self.hyper[:, :n]
+        _lib.check(self.lib.admpc_quad_ensemble_install(self._ens, _ptr(self._gp_dev), _ptr(self.installed), s))
+        return self.fit_info[:, :n], self.installed[:, :n], self.hyper[:, :n]
+
+    def _cluster_bounds(self, bounds):
+        """``bounds`` of search_gp as K entries for config.search_boxes: None, one list per regressor for every cluster, or K lists."""
+        if bounds is None:
+            return [None] * self.K
+        bounds = list(bounds)
+        if bounds and all(b is None or isinstance(b, dict) for b in bounds):
+            return [bounds] * self.K
+        if len(bounds) != self.K or any(isinstance(b, dict) or not isinstance(b, (list, tuple, type(None))) for b in bounds):
+            raise ValueError("bounds: None, one list of dicts per regressor, or one such list per cluster (%d)" % self.K)
+        return bounds
+
+    def learned_hyper(self):
+        """QuadFleet.learned_hyper per cluster (synchronises): K lists of dicts."""
+        self._learns("learned_hyper")
+        torch.cuda.current_stream(self.device).synchronize()
+        hy = self.hyper.cpu().numpy()
+        return [hyper_dicts(hy[c], self._obs[c].gp, self.n_learn, self._has_hyper) for c in range(self.K)]
+
     def learned_gps(self):
-        """The GPs of the last fit_gp as a ``QuadGPEnsemble`` with the centroids the device holds and the fleet's features (synchronises): what
-        ``QuadEnsembleFleet(ensemble=...)`` takes.  Every cluster is decoded as QuadFleet.learned_gps decodes its one."""
+        """The GPs of the last fit_gp or search_gp as a ``QuadGPEnsemble`` with the centroids the device holds and the fleet's features
+        (synchronises): what ``QuadEnsembleFleet(ensemble=...)`` takes.  Every cluster is decoded as QuadFleet.learned_gps decodes its one:
+        after a search_gp with the length scales and sigma_f it found for that cluster."""
         self._learns("learned_gps")
         torch.cuda.current_stream(self.device).synchronize()
         raw = self._gp_dev.cpu().numpy().tobytes()
         per = QUAD_GP_MAX * C.sizeof(AdmpcGp)
-        return QuadGPEnsemble([decode_gps(raw[c * per:(c + 1) * per], self._learn[c], self._EMPTY) for c in range(self.K)], self._device_centroids(),
+        heads = [list(cluster) for cluster in self._learn]
+        if self._searched:
+            hy = self.hyper.cpu().numpy()
+            heads = [[dict(d, length_scale=hy[c, g, 10:10 + int(self._obs[c].gp[g].n_feat)].tolist(), sigma_f=float(hy[c, g, 13]))
+                      for g, d in enumerate(cluster)] for c, cluster in enumerate(heads)]
+        return QuadGPEnsemble([decode_gps(raw[c * per:(c + 1) * per], heads[c], self._EMPTY) for c in range(self.K)], self._device_centroids(),
                               self.feats)

@@ -4,7 +4,8 @@ simplified simulator for ``control_period / simulation_dt`` sub-steps -- for B v
 error.  Built on ``QuadBatchSolver``; the OCP is shaped as ``Quad3DOptimizer`` shapes it (weight expansion for the quaternion, the
 vehicle's constants, the linear drag, one cluster of residual GPs).  With ``learn`` the fleet fits those GPs itself, on the device, from
 the steps it has flown (include/admpc_quad_learn.h: observe -> bin -> fit -> install; the side it shares with the car's fleet is
-learning.py's).  With ``noise_seed`` and a vehicle whose ``noisy`` or ``motor_noise`` is set, the plant is the simulator under its random
+learning.py's), and searches their hyperparameters there (include/admpc_quad_hyper.h: ``search_gp`` -> re-fit -> install, ``learned_hyper``; learning.py's
+as well).  With ``noise_seed`` and a vehicle whose ``noisy`` or ``motor_noise`` is set, the plant is the simulator under its random
 disturbances (include/admpc_quad_noise.h)."""
 import ctypes as C
 from collections import namedtuple
@@ -14,7 +15,7 @@ import torch
 
 from . import _lib
 from .engine import QuadBatchSolver, _ptr
-from .learning import FleetLearning, placeholder_gps
+from .learning import FleetLearning, FleetSearch, placeholder_gps
 from .quad_config import (QNX, QNU, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, default_quad_config, quad_is_noisy, quad_learn_bins,
                           quad_noise_params, quad_plant_params, set_quad_gp)
 
@@ -71,13 +72,20 @@ class QuadFleet(FleetLearning):
     sigma_f, noise, count_noise).  With it the controller's handle is created with placeholder GPs of no points, which fit_gp overwrites
     on the device; a second, nominal handle (no GP, same vehicle, same rdrv) predicts for observe; the observation's period is the
     control period, predicted in ``observe_substeps`` RK4 steps.  ``samples`` [B,14], ``bins`` [3,32,5] and ``dropped`` [4] are the
-    record, the statistics and the counts of include/admpc_quad_learn.h.
+    record, the statistics and the counts of include/admpc_quad_learn.h.  Such a fleet is created as a ``QuadLearningFleet`` (below),
+    which adds ``search_gp`` and ``learned_hyper`` (include/admpc_quad_hyper.h).
 
     ``noise_seed``: the key of the disturbances' generator.  With it and a quad whose ``noisy`` or ``motor_noise`` is set, ``plant_step``
     and ``rollout``, observed or not, go through the entries of include/admpc_quad_noise.h, and ``noise_step`` [B] int64 holds every
     vehicle's period counter (zeros at first; the 64 bits are the header's uint64).  A quad without disturbances ignores the seed; a quad
     with them and no seed is refused."""
     _FIT, _INSTALL, _GP_CAP, _REC, _EMPTY, _NOUN = "admpc_quad_gp_fit", "admpc_quad_gp_install", QUAD_GP_MAX, QUAD_REC, 7, "fleet"
+
+    def __new__(cls, *args, **kw):
+        """``QuadFleet(..., learn=[...])`` creates a ``QuadLearningFleet``, the fleet with ``search_gp`` and ``learned_hyper``; every
+        other class is created as it is asked for."""
+        learn = kw.get("learn", args[11] if len(args) > 11 else None)
+        return object.__new__(QuadLearningFleet if cls is QuadFleet and learn is not None else cls)
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
                  gp_regressors=None, rdrv_d_mat=None, device=0, learn=None, observe_substeps=1, noise_seed=None):
@@ -321,3 +329,12 @@ class QuadFleet(FleetLearning):
         _lib.check(self.lib.admpc_quad_observe_batch(self._observer._h, C.byref(self._plant), C.byref(self._obs), self.B, C.c_void_p(u.data_ptr()),
                                                      stride, _ptr(self.x), _ptr(self._prev), _ptr(self.samples), _ptr(self.bins),
                                                      _ptr(self.dropped), self._stream()))
+
+
+class QuadLearningFleet(FleetSearch, QuadFleet):
+    """What ``QuadFleet(..., learn=[...])`` creates: the fleet that learns, with the search of the hyperparameters of its residual GPs
+    on the device (include/admpc_quad_hyper.h; learning.py's ``FleetSearch``, which the car's controller shares): ``search_gp(min_count,
+    grid, rounds, shrink, bounds, resume, install)`` -> re-fit -> install and ``learned_hyper()``, with the car's signatures and return
+    values; ``hyper`` [3,16] and ``search_info`` [3,2] are the search's state.  ``learned_gps()`` reports the found length scales and
+    sigma_f after a search, the given ones again after a later ``fit_gp``."""
+    _SEARCH, _REFIT = "admpc_quad_gp_search", "admpc_quad_gp_refit"

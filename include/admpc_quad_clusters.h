@@ -24,7 +24,9 @@
  *   - covariance types other than "full"; choosing K: K is the ensemble's;
  *   - the soft top-2 membership of gp_common.py:253-262: a record trains only its nearest cluster, as admpc_quad_ensemble.h bins it;
  *   - the PCA point selection of gp_fitting.py:237-240;
- *   - the search of the hyperparameters for the quadrotor, and SQP mode (admpc_quad_ensemble.h).
+ *   - the search of the hyperparameters by THESE entries: admpc_quad_hyper.h has it, for all clusters at once, and after an install of new
+ *     centroids and a re-bin it is what finds each cluster's length scales from the data the cluster holds now; SQP mode
+ *     (admpc_quad_ensemble.h).
  *
  * CLUSTER c KEEPS BLOCK c.  The install moves centroids only: cluster c, the c-th along the first feature, goes on binning under the box
  * and fitting at the hyperparameters of the c-th AdmpcQuadObserveParams the ensemble was created with, and flies handle c.

@@ -22,7 +22,8 @@
  * NOT offered:
  *   - the GMM that finds the centroids (gp_fitting.py): to THESE entries the centroids are GIVEN; admpc_quad_clusters.h finds them from a
  *     log of the records flown, and installs them in the object's device copy;
- *   - the search of the hyperparameters (admpc_hyper.h is not routed: the length scales, sigma_f and the noise of every cluster are given);
+ *   - the search of the hyperparameters by THESE entries: to admpc_quad_ensemble_fit the length scales, sigma_f and the noise of every
+ *     cluster are GIVEN; admpc_quad_hyper.h searches them for all clusters in one chain of launches (admpc_quad_ensemble_search, _refit);
  *   - SQP mode (a handle with sqp_iters > 1 is refused: the rollout is the RTI loop).
  *
  * ONE ITERATE PER VEHICLE.  xbar / ubar of vehicle b are used by whichever cluster solves it: a vehicle that changes cluster is

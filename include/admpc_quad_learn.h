@@ -17,9 +17,9 @@
  *   quad_mpc/quad_3d_optimizer.py:289-327  where the GP enters the model of the MPC            admpc_quad_gp_install (no host in between)
  *
  * NOT offered:
- *   - the search of the hyperparameters for the quadrotor: admpc_gp_search (admpc_hyper.h) checks the car's feature and output ranges.
- *     AdmpcQuadObserveParams holds AdmpcGpBins as AdmpcObserveParams does, so that a later change can route it; until then the length
- *     scales, sigma_f and the noise are GIVEN, as in admpc_learn.h;
+ *   - the search of the hyperparameters by THESE entries: to admpc_quad_gp_fit the length scales, sigma_f and the noise are GIVEN, as in
+ *     admpc_learn.h; admpc_quad_hyper.h has the search (admpc_quad_gp_search, admpc_quad_gp_refit), routed to the kernels of
+ *     admpc_hyper.h through the AdmpcGpBins that AdmpcQuadObserveParams holds as AdmpcObserveParams does;
  *   - clustered GP ensembles by THESE entries (one handle and one block of regressors, as in admpc_quad_fleet.h): admpc_quad_ensemble.h
  *     has observe -> bin -> fit -> install per cluster, and the rollout that flies them;
  *   - np.random's own stream for the simulator's random disturbances: their distributions are flown by admpc_quad_rollout_noise_batch
