@@ -42,6 +42,10 @@ LAUNCH_LINES = (
     ("admpc_step.hip", "step_tail", "hipLaunchKernelGGL(admpc_step_command_kernel, dim3(B < 65536 ? B : 65536), dim3(WAVE)"),
     ("admpc_step.hip", "admpc_step_command_kernel", "for (int b = blockIdx.x; b < B; b += gridDim.x) {"),
     ("admpc_step.hip", "step_tail", "const long nP = (long)B * (N + 1);"),
+    # the dispatch of quad_solve that quad_routed_spec.quad_kernel mirrors
+    ("admpc_quad.hip", "quad_solve", "const bool seg20 = s->cfg.N == 20 && !s->wide20;"),
+    ("admpc_quad.hip", "quad_solve", "else if (s->cfg.N * QU > 64)"),
+    ("admpc_quad.hip", "quad_solve", "else if (s->cfg.N * QU == 40 && !s->generic)"),
 )
 
 

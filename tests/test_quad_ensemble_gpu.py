@@ -146,19 +146,26 @@ def _python_loop(fl, trajs, T):
     return np.stack(traj), np.stack(us), np.stack(routes)
 
 
-@pytest.mark.parametrize("noisy", [False, True])
-def test_routed_rollout_equals_the_loop_it_replaces(noisy):
+# Centroids on the body-frame v_x for the circles of TQ._circles(N, 3.0): the rows are 1 / (5 N) s apart, so the span the vehicles' start
+# rows cover shrinks with N (0 .. -2.9 m/s at N = 10 and, wrapping, at N = 5; 0 .. -2.1 at N = 17; 0 .. -1.9 at N = 20, -1.7 at B = 33).
+# N = 20: the cell boundaries -0.59 and -1.19 lie between start rows, and the vehicle at -1.174 passes -1.19 within two steps (-1.207).
+VX_CENT = {5: [[-0.5], [-1.5], [-2.5]], 10: [[-0.5], [-1.5], [-2.5]], 17: [[-0.35], [-1.05], [-1.75]], 20: [[-0.29], [-0.89], [-1.49]]}
+
+
+@pytest.mark.parametrize("N,B,T,noisy", [pytest.param(10, 65, 6, False, id="False"), pytest.param(10, 65, 6, True, id="True"),
+                                         pytest.param(20, 33, 3, False, id="N20-False")])
+def test_routed_rollout_equals_the_loop_it_replaces(N, B, T, noisy):
     """T = 6, B = 65, K = 3 clusters with distinct GPs on the body-frame v_x, which falls from 0 to -2.9 m/s along the circle the vehicles
     are spread over: every cluster solves, and vehicles cross a boundary within the run.  Once with the deterministic plant, once under
-    both disturbances with drag, from the same reseed."""
+    both disturbances with drag, from the same reseed.  N = 20 (the two-wave kernel) at the sizes test_quad_fleet_gpu.py uses there,
+    B = 33 and T = 3, with the deterministic plant and the centroids of VX_CENT."""
     from ad_mpc_amd.quad_3d_optimizer import QuadGPEnsemble
     from ad_mpc_amd.quad_config import SimQuad
-    N, B, T = 10, 65, 6
     trajs = TQ._circles(N, 3.0)
     traj_of = (np.arange(B) % 2).astype(np.int32)
     idx0 = np.where(traj_of == 1, 3, (np.arange(B) * 3) % 110).astype(np.int32)
     x0 = TQ._start(trajs, traj_of, idx0, seed=12)
-    ens = QuadGPEnsemble([_gps(1), _gps(2), _gps(3)], [[-0.5], [-1.5], [-2.5]], [7])
+    ens = QuadGPEnsemble([_gps(1), _gps(2), _gps(3)], VX_CENT[N], [7])
     quad = SimQuad(drag=True, noisy=True, motor_noise=True) if noisy else None
     kw = dict(ensemble=ens, quad=quad, noise_seed=5 if noisy else None)
     whole, loop = (_fleet(B, N, trajs, traj_of, idx0, x0, **kw) for _ in range(2))
@@ -190,11 +197,14 @@ def test_routed_rollout_equals_the_loop_it_replaces(noisy):
 
 # ---- 3. one cluster, identical clusters, and the cluster binning ----------------------------------------------------------------------
 
-def test_one_cluster_and_identical_clusters_fly_what_the_single_handle_flies():
+@pytest.mark.parametrize("N,T", [(10, 4), (20, 3), (17, 3), (5, 3)])
+def test_one_cluster_and_identical_clusters_fly_what_the_single_handle_flies(N, T):
+    """B = 65.  N = 10 on the one-wave dense kernel, 20 on the two-wave kernel, 17 on the wide and 5 on the generic path: an ensemble of
+    K = 1 and one of K = 3 identical clusters (centroids VX_CENT[N]: all three routes occur) fly the bits of the QuadFleet with those GPs."""
     from ad_mpc_amd.quad_3d_optimizer import QuadGPEnsemble
     from ad_mpc_amd.quad_config import SimQuad
     from ad_mpc_amd.quad_fleet import QuadFleet
-    N, B, T = 10, 65, 4
+    B = 65
     trajs = TQ._circles(N, 3.0)
     traj_of = (np.arange(B) % 2).astype(np.int32)
     idx0 = np.where(traj_of == 1, 3, (np.arange(B) * 3) % 110).astype(np.int32)
@@ -203,7 +213,7 @@ def test_one_cluster_and_identical_clusters_fly_what_the_single_handle_flies():
     plain = QuadFleet(B, quad=SimQuad(drag=True), n_nodes=N, gp_regressors=gps)
     plain.set_trajectories(trajs); plain.reset(traj_of, idx0, x0)
     one = _fleet(B, N, trajs, traj_of, idx0, x0, ensemble=QuadGPEnsemble([gps], [[0.0]], [7]))
-    three = _fleet(B, N, trajs, traj_of, idx0, x0, ensemble=QuadGPEnsemble([gps, gps, gps], [[-0.5], [-1.5], [-2.5]], [7]))
+    three = _fleet(B, N, trajs, traj_of, idx0, x0, ensemble=QuadGPEnsemble([gps, gps, gps], VX_CENT[N], [7]))
     try:
         ref = plain.rollout(T, record=True)
         want = TQ._state(plain)
