@@ -5,7 +5,12 @@ The state is the header's: gmm float64 [1 + K, 18] and info int32 [4].  The form
 nearest initial mean at the start, sklearn's full-covariance log-density through the precision's Cholesky factor, the moments taken about
 the CURRENT mean and shifted in the M step, the 3 x 3 Cholesky written out -- but the sums over the records are numpy's, whose order is
 its own: the order inside the sums is not part of the contract.  tests/test_quad_clusters_cpu.py pins this file to
-sklearn.mixture.GaussianMixture, the class the reference calls."""
+sklearn.mixture.GaussianMixture, the class the reference calls.
+
+pack, start, iterate, fit and their helpers take the arithmetic as `dtype` (float64 by default), as learn_spec.fit does, so that the same
+lines run in float64 and in numpy.longdouble; the gap between the two is the yardstick of the GPU tests on data where a tolerance argued
+by hand would not hold (the fixtures of hard() below).  What the device holds as doubles stays those doubles in both: the records, the
+initial means, tol, reg_covar, LOG_2PI and TINY.  So does the start's nearest-mean rule, which is a decision, not an approximation."""
 import numpy as np
 
 import quad_ensemble_spec as ES
@@ -17,11 +22,11 @@ LOG_2PI = float(np.log(2.0 * np.pi))
 TRI = np.array([[0, 1, 2], [1, 3, 4], [2, 4, 5]])          # where entry (i, j) of a symmetric 3 x 3 sits among its six stored values
 
 
-def pack(records, feats):
+def pack(records, feats, dtype=np.float64):
     """packed float64 [M, 4]: (z_0, z_1, z_2, flag), the features past d at 0; a record counts (flag 1) if its own flag is 1.0 and its d
     features are finite, and its row is zero otherwise."""
     S = np.asarray(records, dtype=np.float64).reshape(-1, REC)
-    out = np.zeros((S.shape[0], 4))
+    out = np.zeros((S.shape[0], 4), dtype=dtype)
     z = S[:, [f - QL.FEAT0 for f in feats]]
     ok = (S[:, REC - 1] == 1.0) & np.isfinite(z).all(axis=1)
     out[ok, :len(feats)] = z[ok]
@@ -46,7 +51,7 @@ def nearest_rows(x, init):
 def _moments(x, r, means):
     """The sums the E kernel's blocks write: S [K, 10] = sum r_k, sum r_k D [3], sum r_k D D' [6], D = x - means[k]."""
     K = means.shape[0]
-    S = np.zeros((K, 10))
+    S = np.zeros((K, 10), dtype=x.dtype)
     for k in range(K):
         D = x - means[k]
         rD = r[:, k, None] * D
@@ -56,9 +61,9 @@ def _moments(x, r, means):
 
 
 def _m_step(gmm, info, S, lse_sum, means, d, n_valid, tol, reg, start):
-    """The M kernel, in place; returns False where it failed (the state then stays)."""
-    K = S.shape[0]
-    rows, bad = np.zeros((K, ROW)), []
+    """The M kernel, in place, in the arithmetic of S; returns False where it failed (the state then stays)."""
+    K, dt = S.shape[0], S.dtype.type
+    rows, bad, reg = np.zeros((K, ROW), dtype=dt), [], dt(reg)
     with np.errstate(all="ignore"):
         for k in range(K):
             N = S[k, 0] + TINY
@@ -100,46 +105,47 @@ def _m_step(gmm, info, S, lse_sum, means, d, n_valid, tol, reg, start):
 
 
 def start(packed, init, d, reg_covar, gmm, info):
-    """The start step, in place: hard responsibilities from the nearest initial mean (quad_ensemble_spec.nearest's rule: ties to the
-    lower index), one M step."""
+    """The start step, in place, in the arithmetic of packed: hard responsibilities from the nearest initial mean
+    (quad_ensemble_spec.nearest's rule: ties to the lower index; in float64 whatever the arithmetic), one M step."""
     init = np.asarray(init, dtype=np.float64).reshape(-1, d)
     K = init.shape[0]
     x = packed[packed[:, 3] == 1.0, :3]
     if x.shape[0] == 0:
         info[:] = 0, 0, ENOVALID, 0
         return False
-    means = np.zeros((K, 3)); means[:, :d] = init
-    r = np.zeros((x.shape[0], K))
-    r[np.arange(x.shape[0]), nearest_rows(x[:, :d], init)[0]] = 1.0
+    means = np.zeros((K, 3), dtype=packed.dtype); means[:, :d] = init
+    r = np.zeros((x.shape[0], K), dtype=packed.dtype)
+    r[np.arange(x.shape[0]), nearest_rows(x[:, :d].astype(np.float64), init)[0]] = 1.0
     return _m_step(gmm, info, _moments(x, r, means), 0.0, means, d, float(x.shape[0]), 0.0, reg_covar, True)
 
 
 def iterate(packed, d, tol, reg_covar, gmm, info):
-    """One EM iteration, in place; nothing once converged or a status is set."""
+    """One EM iteration, in place, in the arithmetic of packed (gmm is of that type); nothing once converged or a status is set."""
     if info[1] or info[2]:
         return False
     x = packed[packed[:, 3] == 1.0, :3]
     K = gmm.shape[0] - 1
     means = gmm[1:, 1:4].copy()
-    lp = np.zeros((x.shape[0], K))
+    dt = packed.dtype.type
+    lp = np.zeros((x.shape[0], K), dtype=dt)
     with np.errstate(all="ignore"):
         for k in range(K):
             P = gmm[1 + k, 10:16][TRI] * np.triu(np.ones((3, 3)))
             y = (x - means[k]) @ P
-            lp[:, k] = (np.log(gmm[1 + k, 0]) + gmm[1 + k, 16] - 0.5 * d * LOG_2PI) - 0.5 * (y * y).sum(axis=1)
+            lp[:, k] = (np.log(gmm[1 + k, 0]) + gmm[1 + k, 16] - dt(0.5 * d) * dt(LOG_2PI)) - 0.5 * (y * y).sum(axis=1)
         mx = lp.max(axis=1)
         lse = mx + np.log(np.exp(lp - mx[:, None]).sum(axis=1))
         r = np.exp(lp - lse[:, None])
     return _m_step(gmm, info, _moments(x, r, means), lse.sum(), means, d, gmm[0, 2], tol, reg_covar, False)
 
 
-def fit(records, feats, init, max_iter=100, tol=1e-3, reg_covar=1e-6, gmm=None, info=None, resume=False):
-    """admpc_quad_clusters_fit: (gmm [1 + K, 18], info int32 [4])."""
+def fit(records, feats, init, max_iter=100, tol=1e-3, reg_covar=1e-6, gmm=None, info=None, resume=False, dtype=np.float64):
+    """admpc_quad_clusters_fit: (gmm [1 + K, 18] of `dtype`, info int32 [4]).  A gmm that is given is of `dtype`."""
     d = len(feats)
-    packed = pack(records, feats)
+    packed = pack(records, feats, dtype)
     if not resume:
         K = np.asarray(init).reshape(-1, d).shape[0]
-        gmm = np.zeros((1 + K, ROW)) if gmm is None else gmm
+        gmm = np.zeros((1 + K, ROW), dtype=dtype) if gmm is None else gmm
         info = np.zeros(4, dtype=np.int32) if info is None else info
         start(packed, init, d, reg_covar, gmm, info)
     for _ in range(int(max_iter)):
@@ -184,6 +190,97 @@ def blobs(d, K, n=400, sigma=0.4, gap=2.5, seed=0):
     rec[:, REC - 1] = 1.0
     init = centres + 0.6 * rng.normal(size=centres.shape)
     return rec, init
+
+
+def _records_of(pts, rng):
+    """pts [M, d] shuffled into valid records [M, 14], the entries the clustering does not read random."""
+    pts = pts[rng.permutation(pts.shape[0])]
+    rec = rng.normal(size=(pts.shape[0], REC))
+    rec[:, :pts.shape[1]] = pts
+    rec[:, REC - 1] = 1.0
+    return rec
+
+
+# name: (d, K, the reg_covar values the fixture is fitted at)
+HARD = {"overlap": (2, 3, (1e-6,)), "hover": (3, 3, (1e-6, 1e-9)), "hover_offset": (3, 3, (1e-9,)), "anisotropic": (3, 2, (1e-9, 0.0)),
+        "mixed_scales": (2, 4, (1e-6,)), "outliers": (1, 2, (1e-6,)), "starved": (1, 3, (1e-6,))}
+HARD_CASES = tuple((name, reg) for name, (_, _, regs) in HARD.items() for reg in regs)
+HARD_FAILS = ("starved", 0.0)                             # the start fails with info[2] = -3: the third component has no record and no regulariser
+HARD_MAX_ITER = 200
+ANISO = np.array([[1.0, 0.0, 0.0], [0.999, 0.03, 0.0], [0.5, 0.5, 1e-3]])
+
+
+def hard(name, n=400, seed=0):
+    """The fixtures that are not easy, as (records [M, 14], initial means [K, d]): what a closed loop logs and blobs() does not look like.
+    overlap       unit-variance blobs 1.5 apart, poor initial means
+    hover         rotor activations near the hover value: centres 0.245 + 0.004 k on the diagonal, sigma 1e-3 (variance 1e-6 = reg_covar)
+    hover_offset  the same 1e3 away from the origin: the shifted moments against the one-pass ones
+    anisotropic   points A n about centres 4 apart, n standard normal: strongly correlated features, the smallest pivot 1e-6
+    mixed_scales  sigma 1 with centres 5 apart in the first feature, sigma 1e-3 about 0.25 + 0.01 k in the second
+    outliers      two blobs, one record at 500 and one at -800
+    starved       two blobs and a third initial mean at 40, which takes no record at the start"""
+    d, K, _ = HARD[name]
+    rng = np.random.default_rng(seed + 1000 * sorted(HARD).index(name))
+    if name == "overlap":
+        centres = np.stack([1.5 * np.arange(K), np.array([0.0, 0.6, -0.3])], axis=1)
+        pts = np.concatenate([c + rng.normal(size=(n, d)) for c in centres])
+        init = centres + 0.8 * rng.normal(size=centres.shape)
+    elif name in ("hover", "hover_offset"):
+        centres = np.repeat((0.245 + 0.004 * np.arange(K))[:, None], d, axis=1)
+        pts = np.concatenate([c + 1e-3 * rng.normal(size=(n, d)) for c in centres])
+        init = centres + 1.5e-3 * rng.normal(size=centres.shape)
+        if name == "hover_offset":
+            pts, init = pts + 1e3, init + 1e3
+    elif name == "anisotropic":
+        centres = np.array([[0.0, 0.0, 0.0], [4.0, 0.0, 0.0]])
+        pts = np.concatenate([c + rng.normal(size=(n, d)) @ ANISO.T for c in centres])
+        init = centres + 0.5 * rng.normal(size=centres.shape)
+    elif name == "mixed_scales":
+        centres = np.stack([5.0 * np.arange(K), 0.25 + 0.01 * np.arange(K)], axis=1)
+        pts = np.concatenate([c + rng.normal(size=(n, d)) * [1.0, 1e-3] for c in centres])
+        init = centres + rng.normal(size=centres.shape) * [1.0, 2e-3]
+    elif name == "outliers":
+        pts = np.concatenate([rng.normal(size=(n, 1)), 6.0 + rng.normal(size=(n, 1)), [[500.0], [-800.0]]])
+        init = np.array([[-1.0], [7.5]])
+    else:
+        pts = np.concatenate([0.5 * rng.normal(size=(n, 1)), 3.0 + 0.5 * rng.normal(size=(n, 1))])
+        init = np.array([[0.4], [2.2], [40.0]])
+    return _records_of(pts, rng), init
+
+
+def hard_run(name, reg_covar, dtype=np.float64, tol=1e-3, max_iter=HARD_MAX_ITER):
+    """A hard fixture through the spec in `dtype`, as a dict: rec, init, d, K, feats, span (the range of every feature), margin (the
+    smallest nearest-mean margin at the start), given (the state the FLOAT64 start leaves, which the device can be handed), one (that
+    state after one iteration in `dtype`), whole (the fit from `dtype`'s own start) and changes (the change of the bound of every
+    iteration of the fit that ran, the first, which is infinite, left out).  A state is (gmm, info); one is None where the start fails."""
+    d, K, _ = HARD[name]
+    rec, init = hard(name)
+    feats = FIXTURE_FEATS[d]
+    packed = pack(rec, feats, dtype)
+    out = dict(rec=rec, init=init, d=d, K=K, feats=feats, span=np.ptp(rec[:, :d], axis=0), one=None, changes=[],
+               margin=nearest_rows(pack(rec, feats)[:, :d], init)[1].min())
+    given = np.zeros((1 + K, ROW)), np.zeros(4, dtype=np.int32)
+    if start(pack(rec, feats), init, d, reg_covar, *given):
+        out["one"] = given[0].astype(dtype), given[1].copy()
+        assert iterate(packed, d, 0.0, reg_covar, *out["one"])
+    gmm, info = np.zeros((1 + K, ROW), dtype=dtype), np.zeros(4, dtype=np.int32)
+    start(packed, init, d, reg_covar, gmm, info)
+    for _ in range(max_iter):
+        if iterate(packed, d, tol, reg_covar, gmm, info) and info[0] > 1:
+            out["changes"].append(gmm[0, 1])
+    out["given"], out["whole"] = given, (gmm, info)
+    return out
+
+
+def scaled_gap(got, want, d, span):
+    """The distance of two states in the scaling of the GPU tests, formed in want's arithmetic: (means / the feature's range,
+    covariances / range^2, weights, the bound / (1 + |bound|)), each the largest over its entries."""
+    dt = want.dtype.type
+    gw, gm, gc, _ = unpack(got.astype(dt), d)
+    ww, wm, wc, _ = unpack(want, d)
+    span = np.asarray(span, dtype=dt)
+    bound = abs(dt(got[0, 0]) - want[0, 0]) / (1.0 + abs(want[0, 0])) if np.isfinite(want[0, 0]) else dt(got[0, 0] != want[0, 0])
+    return np.array([(np.abs(gm - wm) / span).max(), (np.abs(gc - wc) / np.outer(span, span)).max(), np.abs(gw - ww).max(), bound], dtype=np.float64)
 
 
 FIXTURES = ((1, 2), (2, 3), (3, 4))                       # (d, K) of the fits the CPU test pins to sklearn and the GPU tests reuse

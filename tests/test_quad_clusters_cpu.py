@@ -1,7 +1,9 @@
 """The centroids of a clustered GP ensemble found on the device (include/admpc_quad_clusters.h; ad_mpc_amd/quad_ensemble_fleet.py) without
 a GPU: the header, the prototype table and the library agree; the refusals that need no handle come back in their order; the Python layer
 refuses before a handle is asked for; and the numpy spec (tests/quad_clusters_spec.py), which the GPU tests hold the kernels against, is
-pinned to sklearn.mixture.GaussianMixture -- the class the reference calls (gp_common.py:224-271).  The refusals behind a live handle are
+pinned to sklearn.mixture.GaussianMixture -- the class the reference calls (gp_common.py:224-271).  The spec runs in float64 and in
+numpy.longdouble: its float64 path is held to the bits it returned before it took the arithmetic as an argument, and the fixtures that
+are not easy (quad_clusters_spec.hard) are held to the conditions the GPU tests rely on, in both.  The refusals behind a live handle are
 in tests/test_quad_clusters_gpu.py."""
 import ctypes as C
 import os
@@ -174,6 +176,208 @@ def test_spec_is_sklearns_em(d, K):
     # what the fit is for: the means find the blobs, 2.5 apart on the first feature, whatever the poor start
     cent, perm, installed = CS.install(gmm, info, init)
     assert installed == 1 and np.abs(cent[:, 0] - 2.5 * np.arange(K)).max() < 0.15 and sorted(perm.tolist()) == list(range(K))
+
+
+# ---- 5. the spec in two precisions ----------------------------------------------------------------------------------------------------------
+
+class Was:
+    """The spec as it stood before it took the arithmetic as an argument: float64 throughout, formulas unchanged.  Kept to hold the
+    float64 path of tests/quad_clusters_spec.py to the bits it returned then; nothing else may use it."""
+
+    @staticmethod
+    def pack(records, feats):
+        S = np.asarray(records, dtype=np.float64).reshape(-1, CS.REC)
+        out = np.zeros((S.shape[0], 4))
+        z = S[:, [f - CS.QL.FEAT0 for f in feats]]
+        ok = (S[:, CS.REC - 1] == 1.0) & np.isfinite(z).all(axis=1)
+        out[ok, :len(feats)] = z[ok]
+        out[ok, 3] = 1.0
+        return out
+
+    @staticmethod
+    def moments(x, r, means):
+        K = means.shape[0]
+        S = np.zeros((K, 10))
+        for k in range(K):
+            D = x - means[k]
+            rD = r[:, k, None] * D
+            S[k, 0], S[k, 1:4] = r[:, k].sum(), rD.sum(axis=0)
+            S[k, 4:10] = [(rD[:, i] * D[:, j]).sum() for i, j in ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))]
+        return S
+
+    @staticmethod
+    def m_step(gmm, info, S, lse_sum, means, d, n_valid, tol, reg, start):
+        K = S.shape[0]
+        rows, bad = np.zeros((K, CS.ROW)), []
+        with np.errstate(all="ignore"):
+            for k in range(K):
+                N = S[k, 0] + CS.TINY
+                s = S[k, 1:4] / N
+                m = means[k] + s
+                c = S[k, 4:10] / N - np.array([s[0] * s[0], s[0] * s[1], s[0] * s[2], s[1] * s[1], s[1] * s[2], s[2] * s[2]])
+                c[[0, 3, 5]] += reg
+                if d < 2:
+                    m[1], c[1], c[3], c[4] = 0.0, 0.0, 1.0, 0.0
+                if d < 3:
+                    m[2], c[2], c[4], c[5] = 0.0, 0.0, 0.0, 1.0
+                p0 = c[0]; l00 = np.sqrt(p0); l10 = c[1] / l00; l20 = c[2] / l00
+                p1 = c[3] - l10 * l10; l11 = np.sqrt(p1); l21 = (c[4] - l20 * l10) / l11
+                p2 = c[5] - l20 * l20 - l21 * l21; l22 = np.sqrt(p2)
+                if not all(p > 0.0 and np.isfinite(p) for p in (p0, p1, p2)):
+                    bad.append(k)
+                    continue
+                P00, P11, P22 = 1.0 / l00, 1.0 / l11, 1.0 / l22
+                P01 = -(l10 * P00) / l11; P12 = -(l21 * P11) / l22; P02 = -(l20 * P00 + l21 * P01) / l22
+                rows[k, 0], rows[k, 1:4], rows[k, 4:10] = N / n_valid, m, c
+                rows[k, 10:16] = [P00, P01, P02, P11, P12, P22]
+                rows[k, 16], rows[k, 17] = np.log(P00) + np.log(P11) + np.log(P22), N
+        if bad:
+            info[2] = -(bad[0] + 1)
+            if start:
+                info[0], info[1], info[3] = 0, 0, int(n_valid)
+            return False
+        lb, change = -np.inf, np.inf
+        if not start:
+            lb = lse_sum / n_valid
+            change = lb - gmm[0, 0]
+        gmm[1:] = rows
+        gmm[0] = 0.0
+        gmm[0, :3] = lb, change, n_valid
+        info[0] = 0 if start else info[0] + 1
+        info[1] = int((not start) and abs(change) < tol)
+        info[2], info[3] = 0, int(n_valid)
+        return True
+
+    @staticmethod
+    def start(packed, init, d, reg_covar, gmm, info):
+        init = np.asarray(init, dtype=np.float64).reshape(-1, d)
+        K = init.shape[0]
+        x = packed[packed[:, 3] == 1.0, :3]
+        if x.shape[0] == 0:
+            info[:] = 0, 0, CS.ENOVALID, 0
+            return False
+        means = np.zeros((K, 3)); means[:, :d] = init
+        r = np.zeros((x.shape[0], K))
+        r[np.arange(x.shape[0]), CS.nearest_rows(x[:, :d], init)[0]] = 1.0
+        return Was.m_step(gmm, info, Was.moments(x, r, means), 0.0, means, d, float(x.shape[0]), 0.0, reg_covar, True)
+
+    @staticmethod
+    def iterate(packed, d, tol, reg_covar, gmm, info):
+        if info[1] or info[2]:
+            return False
+        x = packed[packed[:, 3] == 1.0, :3]
+        K = gmm.shape[0] - 1
+        means = gmm[1:, 1:4].copy()
+        lp = np.zeros((x.shape[0], K))
+        with np.errstate(all="ignore"):
+            for k in range(K):
+                P = gmm[1 + k, 10:16][CS.TRI] * np.triu(np.ones((3, 3)))
+                y = (x - means[k]) @ P
+                lp[:, k] = (np.log(gmm[1 + k, 0]) + gmm[1 + k, 16] - 0.5 * d * CS.LOG_2PI) - 0.5 * (y * y).sum(axis=1)
+            mx = lp.max(axis=1)
+            lse = mx + np.log(np.exp(lp - mx[:, None]).sum(axis=1))
+            r = np.exp(lp - lse[:, None])
+        return Was.m_step(gmm, info, Was.moments(x, r, means), lse.sum(), means, d, gmm[0, 2], tol, reg_covar, False)
+
+    @staticmethod
+    def fit(records, feats, init, max_iter, tol, reg_covar):
+        d = len(feats)
+        packed = Was.pack(records, feats)
+        gmm, info = np.zeros((1 + np.asarray(init).reshape(-1, d).shape[0], CS.ROW)), np.zeros(4, dtype=np.int32)
+        Was.start(packed, init, d, reg_covar, gmm, info)
+        for _ in range(int(max_iter)):
+            Was.iterate(packed, d, tol, reg_covar, gmm, info)
+        return gmm, info
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+@pytest.mark.parametrize("d,K", CS.FIXTURES)
+def test_float64_path_returns_the_bits_it_returned_and_longdouble_agrees(d, K):
+    """The float64 path against the formulas as they stood (class Was), bit for bit: the packed records, the start, every one of 30
+    iterations at tol = 0, and the fit at the defaults.  The longdouble path returns arrays of that type and lies within the sklearn
+    pin's own figure, 1e-12, of the float64 path (measured when this was written: below 1e-14); same iteration count at the default tol."""
+    LD = np.longdouble
+    rec, init = CS.blobs(d, K)
+    feats = CS.FIXTURE_FEATS[d]
+    assert _same_bits(CS.pack(rec, feats), Was.pack(rec, feats))
+    packed = CS.pack(rec, feats)
+    now, was = (np.zeros((1 + K, CS.ROW)), np.zeros(4, dtype=np.int32)), (np.zeros((1 + K, CS.ROW)), np.zeros(4, dtype=np.int32))
+    assert CS.start(packed, init, d, 1e-6, *now) and Was.start(packed, init, d, 1e-6, *was)
+    for it in range(31):
+        assert _same_bits(now[0], was[0]) and now[1].tolist() == was[1].tolist(), it
+        assert CS.iterate(packed, d, 0.0, 1e-6, *now) and Was.iterate(packed, d, 0.0, 1e-6, *was)
+    whole, old = CS.fit(rec, feats, init), Was.fit(rec, feats, init, 100, 1e-3, 1e-6)
+    assert _same_bits(whole[0], old[0]) and whole[1].tolist() == old[1].tolist() and whole[1][1] == 1
+    # the same lines in 80-bit arithmetic
+    assert CS.pack(rec, feats, LD).dtype == LD and np.array_equal(CS.pack(rec, feats, LD), packed)
+    for kw in (dict(max_iter=30, tol=0.0), dict()):
+        lo, hi = CS.fit(rec, feats, init, **kw), CS.fit(rec, feats, init, dtype=LD, **kw)
+        assert hi[0].dtype == LD and lo[0].dtype == np.float64 and hi[1].dtype == np.int32 and hi[1].tolist() == lo[1].tolist()
+        (lw, lm, lc, _), (hw, hm, hc, _) = CS.unpack(lo[0], d), CS.unpack(hi[0], d)
+        assert hm.dtype == LD and hc.dtype == LD and hw.dtype == LD
+        gaps = [float(np.abs(a - b).max()) for a, b in ((lm, hm), (lc, hc), (lw, hw))] + [float(abs(lo[0][0, 0] - hi[0][0, 0]))]
+        print("d %d K %d %s: float64 against longdouble |means| %.2e |cov| %.2e |weights| %.2e |bound| %.2e" % ((d, K, kw) + tuple(gaps)))
+        assert max(gaps) <= 1e-12
+        assert np.abs(hi[0] - hi[0].astype(np.float64)).max() > 0.0                              # it is not float64 carried in a wider type
+
+
+# ---- 6. the hard fixtures keep the conditions the GPU tests rely on -------------------------------------------------------------------------
+
+@pytest.mark.parametrize("name,reg", CS.HARD_CASES + (CS.HARD_FAILS,))
+def test_hard_fixtures_hold_what_the_gpu_tests_rely_on(name, reg):
+    """For every hard fixture, in float64 and in longdouble, at tol = 1e-3: the fit does not fail (but `starved` at reg_covar = 0, whose
+    start fails with info[2] = -3 and leaves the state as it was); both arithmetics converge, in the same number of iterations; no
+    iteration's |change| lies within 1e-6 of tol, nor within 100 x the largest gap in `change` between the two arithmetics, so the
+    device's iteration count cannot differ for a correct kernel; at the start every record's nearest-mean margin is at least 1e-9.  The
+    gap between the two arithmetics, which the GPU tests scale their tolerance with, is printed in their scaling."""
+    tol, LD = 1e-3, np.longdouble
+    d, K, regs = CS.HARD[name]
+    lo, hi = CS.hard_run(name, reg, np.float64, tol), CS.hard_run(name, reg, LD, tol)
+    assert lo["rec"].shape[0] <= 4000 and lo["init"].shape == (K, d) and hi["whole"][0].dtype == LD
+    assert lo["margin"] >= 1e-9 and np.isfinite(lo["rec"][:, :d]).all()
+    if (name, reg) == CS.HARD_FAILS:
+        keep = np.full((1 + K, CS.ROW), 7.0)
+        for dtype in (np.float64, LD):
+            gmm, info = CS.fit(lo["rec"], lo["feats"], lo["init"], max_iter=3, reg_covar=reg, gmm=keep.astype(dtype), info=np.full(4, 9, dtype=np.int32),
+                               dtype=dtype)
+            assert info.tolist() == [0, 0, -3, lo["rec"].shape[0]] and np.array_equal(gmm, keep)
+        assert lo["one"] is None and hi["one"] is None and CS.install(gmm, info, lo["init"])[2] == 0
+        assert reg not in regs and any(n == name for n, _ in CS.HARD_CASES)                      # the same data is fitted at the default
+        return
+    n = lo["rec"].shape[0]
+    for run in (lo, hi):
+        assert run["one"][1].tolist() == [1, 0, 0, n] and run["whole"][1][1:].tolist() == [1, 0, n], (name, reg, run["whole"][1])
+        assert 2 <= run["whole"][1][0] < CS.HARD_MAX_ITER and len(run["changes"]) == run["whole"][1][0] - 1
+    near = min(abs(abs(float(ch)) - tol) for run in (lo, hi) for ch in run["changes"])
+    assert near >= 1e-6, (lo["changes"], hi["changes"])
+    assert lo["whole"][1].tolist() == hi["whole"][1].tolist()
+    dch = max(abs(float(a - b)) for a, b in zip(lo["changes"], hi["changes"]))
+    one, whole = CS.scaled_gap(lo["one"][0], hi["one"][0], d, lo["span"]), CS.scaled_gap(lo["whole"][0], hi["whole"][0], d, lo["span"])
+    print("%s reg %g: %d iterations; float64 against longdouble (means, covariances, weights, bound) one iteration %s, whole fit %s; change %.1e"
+          % (name, reg, lo["whole"][1][0], ["%.1e" % g for g in one], ["%.1e" % g for g in whole], dch))
+    # the device's change may differ from the float64 spec's by twice the tolerance of the bound, 10 x the gap each: the nearest change
+    # of this fixture keeps five times that from tol
+    assert near >= 100.0 * dch, (near, dch)
+    if name == "starved":
+        assert lo["given"][0][3, 17] == CS.TINY and lo["whole"][0][3, 17] == CS.TINY            # the third component has no record, then and later
+
+
+@pytest.mark.parametrize("name", ["anisotropic", "overlap"])
+def test_without_a_regulariser_the_bound_of_the_spec_does_not_decrease(name):
+    """EM's bound is monotone; at reg_covar = 0 the M step is the exact maximiser, so what decrease there is is rounding.  40 iterations at
+    tol = 0: the longdouble run's change is never below -1e-15 (1 + |bound|).  The float64 run's lies within the gap between the two,
+    which is what the GPU test allows the device ten times of."""
+    lo, hi = CS.hard_run(name, 0.0, np.float64, 0.0, 40), CS.hard_run(name, 0.0, np.longdouble, 0.0, 40)
+    assert lo["whole"][1].tolist() == hi["whole"][1].tolist() == [40, 0, 0, lo["rec"].shape[0]] and len(hi["changes"]) == 39
+    bound = float(hi["whole"][0][0, 0])
+    gap = max(abs(float(a - b)) for a, b in zip(lo["changes"], hi["changes"]))
+    print("%s: bound %.6f, smallest change longdouble %.2e float64 %.2e, largest gap in change %.2e" % (name, bound, float(min(hi["changes"])), min(lo["changes"]), gap))
+    floor = -1e-15 * (1.0 + abs(bound))
+    assert float(min(hi["changes"])) >= floor
+    assert min(lo["changes"]) >= floor - gap and 0.0 < gap < 1e-12
 
 
 def test_spec_resume_failures_and_install():

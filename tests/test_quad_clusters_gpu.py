@@ -1,8 +1,15 @@
 """The centroids of a clustered GP ensemble found on the device (include/admpc_quad_clusters.h; ad_mpc_amd/quad_ensemble_fleet.py) on the
 GPU, against the numpy spec of tests/quad_clusters_spec.py, which tests/test_quad_clusters_cpu.py pins to sklearn's GaussianMixture: one EM
 iteration and whole fits, determinism, the failures, the install, the log and the re-bin, the refusals, and a short closed loop that
-learns its clusters and their GPs from its own flight."""
+learns its clusters and their GPs from its own flight.
+
+One iteration runs on every instantiation of the E kernel (K = 1 .. 8) and on every shape of the M kernel's row reduction; the fixtures
+that are not easy (quad_clusters_spec.hard) are held to the spec in numpy.longdouble, within ten times the gap between that and the spec
+in float64; and after every such fit the device's own state is asked what needs no spec (_statements)."""
 import ctypes as C
+import functools
+import os
+import re
 
 import numpy as np
 import pytest
@@ -18,6 +25,13 @@ pytestmark = pytest.mark.gpu
 _dev, _p, _host, _bits, _stream = TQ._dev, TQ._p, TQ._host, TQ._bits, TQ._stream
 VX = TE.VX
 SIZES = (1, 63, 64, 65, 256, 257, CS.BLOCKS_MAX * 256 + 1)         # the last is past the grid, into the stride loop
+LD = np.longdouble
+E_KERNEL_K = (1, 2, 3, 4, 5, 6, 7, 8)                               # the instantiations of admpc_quad_gmm_e_kernel<K, START>, each run at d = 3
+ONE_ITERATION = [(d, K) for d in (1, 2) for K in (1, 2, 3, 8)] + [(3, K) for K in E_KERNEL_K]
+# the M kernel adds the rows of partial sixteen at a time, then a tail: no full group; one and no tail; one and a tail of 1; a tail of 15;
+# two and a tail of 1; fifteen and a tail of 15.  M = 256 nblk - 3: the last block is not full
+ROW_COUNTS = (15, 16, 17, 31, 33, 255)
+PAD = 8                                                             # rows of packed behind the records, which no kernel may touch
 
 
 @pytest.fixture(autouse=True)
@@ -52,7 +66,7 @@ class Ens:
                                                cent.ctypes.data_as(C.POINTER(C.c_double)), None, C.byref(self.h))
         assert rc == 0, self.L.admpc_last_error()
         z = lambda *s, dtype=torch.float64: torch.zeros(s, dtype=dtype, device="cuda:0")
-        self.packed, self.partial = z(max(M, 1), 4), z(CS.BLOCKS_MAX, CS.PARTIAL)
+        self.packed, self.partial = z(max(M, 1) + PAD, 4), z(CS.BLOCKS_MAX, CS.PARTIAL)
         self.gmm, self.info = z(1 + K, CS.ROW), z(4, dtype=torch.int32)
         self.perm, self.installed, self.cent = z(K, dtype=torch.int32), z(1, dtype=torch.int32), z(K, self.d)
 
@@ -74,15 +88,32 @@ class Ens:
     def state(self):
         return _host(self.gmm).copy(), _host(self.info).copy()
 
+    def poison(self, M):
+        """NaN wherever a fit of M records has nothing to read: all of partial, which the E kernel writes before the M kernel reads, and
+        packed behind row M."""
+        self.partial.fill_(float("nan")); self.packed[M:].fill_(float("nan"))
+
+    def untouched(self, M, what):
+        """After a fit that ran its E kernel: the first nblk rows of partial hold 10 K + 1 sums each and nothing else was written."""
+        nblk, ne = min(-(-M // 256), CS.BLOCKS_MAX), 10 * self.K + 1
+        partial, packed = _host(self.partial), _host(self.packed)
+        assert np.isfinite(partial[:nblk, :ne]).all() and np.isnan(partial[:nblk, ne:]).all() and np.isnan(partial[nblk:]).all(), what
+        assert np.isnan(packed[M:]).all() and packed[M:].shape[0] >= PAD and np.isfinite(packed[:M]).all(), what
+
     def close(self):
         self.L.admpc_quad_ensemble_destroy(self.h)
+
+
+@functools.lru_cache(maxsize=None)
+def _blobs(d, nb, n, seed):
+    return CS.blobs(d, nb, n=n, seed=seed)                          # drawn once; _records copies what it changes
 
 
 def _records(d, K, M, seed=0):
     """The first M records of a fixture of max(K, 2) blobs, with a cleared flag, a NaN and an infinite feature sprinkled in (M >= 63);
     poor initial means; the range of every feature over the WHOLE fixture, which the tolerances scale with."""
     nb = max(K, 2)
-    rec, init = CS.blobs(d, nb, n=-(-SIZES[-1] // nb), seed=seed)
+    rec, init = _blobs(d, nb, -(-SIZES[-1] // nb), seed)
     span = np.ptp(rec[:, :d], axis=0)
     rec = rec[:M].copy()
     if M >= 63:
@@ -109,7 +140,93 @@ def _close(got, want, d, span, scale, what, bound=True):
 
 # ---- 1. one iteration from a given state -------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("d,K", [(d, K) for d in (1, 2, 3) for K in (1, 2, 3, 8)])
+def _held(got, lo, hi, d, span, present, what):
+    """The device's state against the spec in longdouble (hi), each of means, covariances, weights and the bound within
+    max(present, 10 x the gap between the spec in float64 (lo) and hi) in the scaling of _close; info and n_valid the float64 spec's,
+    exactly.  The factor 10 is hyper_spec's and tests/test_learn_gpu.py's: two correct orders of evaluation differ by a small multiple of
+    that gap.  Prints, and returns, (gap, distance, ratio) per quantity."""
+    (gg, gi), (wg, wi) = got, lo
+    assert gi.tolist() == wi.tolist() == hi[1].tolist(), (what, gi, wi, hi[1])
+    gap, dist = CS.scaled_gap(wg, hi[0], d, span), CS.scaled_gap(gg, hi[0], d, span)
+    allowed = np.maximum(present, 10.0 * gap)
+    for q, g, e, a in zip(("means", "covariances", "weights", "bound"), gap, dist, allowed):
+        print("%s: %-11s gap %.2e device %.2e ratio %s allowed %.2e" % (what, q, g, e, "%.2f" % (e / g) if g > 0.0 else "-", a))
+    assert (dist <= allowed).all(), (what, dist, allowed)
+    assert gg[0, 2] == wg[0, 2] == wi[3], what
+    return gap, dist
+
+
+def _product(gmm):
+    """max |P' Sigma P - I| over the components of a float64 state, the product formed in longdouble: what is left is the rounding of the
+    stored state and whatever the factor does not owe to its covariance."""
+    worst = 0.0
+    for g in np.asarray(gmm, dtype=np.float64)[1:].astype(LD):
+        P, S = g[10:16][CS.TRI] * np.triu(np.ones((3, 3))), g[4:10][CS.TRI]
+        worst = max(worst, float(np.abs(P.T @ S @ P - np.eye(3)).max()))
+    return worst
+
+
+def _statements(got, hi, d, what):
+    """What a state the device left says about itself, whatever the spec: the N_k add up to the records that count (plus the K guards of
+    10 eps) within K units in the last place of n_valid, the weights to that sum over n_valid to the same figure; g[16] is the sum of the
+    logs of the stored factor's diagonal, bit for bit in numpy's order or within 3 units in the last place of its largest term (each
+    log is good to one); P' Sigma P is the identity within 10 x what the state of the longdouble spec, rounded to float64, leaves of it
+    -- that reference taken as no less than 2^-52, below which a state stored in float64 falls by chance alone (one component in one
+    feature has a single entry); the rows of a feature that is not there are the identity's."""
+    gg, gi = got
+    K, n_valid = gg.shape[0] - 1, gg[0, 2]
+    assert gi[2] == 0 and n_valid == gi[3] > 0, what
+    N = gg[1:, 17].astype(LD).sum()
+    assert abs(float(N - (LD(n_valid) + K * LD(CS.TINY)))) <= K * np.spacing(n_valid), (what, N, n_valid)
+    assert abs(float(gg[1:, 0].astype(LD).sum() - N / LD(n_valid))) <= K * np.spacing(1.0), (what, gg[1:, 0])
+    logs = np.log(gg[1:, [10, 13, 15]])
+    ulp = np.spacing(np.maximum(np.abs(logs).max(axis=1), np.abs(gg[1:, 16])))
+    assert (np.abs(gg[1:, 16] - ((logs[:, 0] + logs[:, 1]) + logs[:, 2])) <= 3.0 * ulp).all(), (what, gg[1:, 16], logs)
+    dev, ref = _product(gg), max(_product(hi[0]), 2.0 ** -52)
+    print("%s: |P' Sigma P - I| device %.2e, the longdouble spec's state in float64 %.2e" % (what, dev, ref))
+    assert dev <= 10.0 * ref, (what, dev, ref)
+    g = gg[1:]
+    if d < 3:
+        assert (g[:, 3] == 0.0).all() and (g[:, [6, 8, 12, 14]] == 0.0).all() and (g[:, [9, 15]] == 1.0).all(), what
+    if d < 2:
+        assert (g[:, 2] == 0.0).all() and (g[:, [5, 11]] == 0.0).all() and (g[:, [7, 13]] == 1.0).all(), what
+
+
+def _one_iteration(e, d, K, M):
+    """The body of the two tests below at M records: the device's own start plus one iteration, and one iteration from the spec's state
+    with resume = 1, both from scratch filled with NaN, both against the float64 spec at the tolerances of the first test's docstring
+    and asked _statements against the longdouble spec's iteration of the same state."""
+    feats = CS.FIXTURE_FEATS[d]
+    rec, init, span = _records(d, K, M)
+    packed = CS.pack(rec, feats)
+    if K > 1:
+        assert CS.nearest_rows(packed[packed[:, 3] == 1.0, :d], init)[1].min() >= 1e-9
+    gmm, info = np.zeros((1 + K, CS.ROW)), np.zeros(4, dtype=np.int32)
+    assert CS.start(packed, init, d, 1e-6, gmm, info) and info[3] == packed[:, 3].sum() and (M < 63 or info[3] < M)
+    drec = _dev(rec)
+    # the device's own start, max_iter = 1: start + one iteration
+    e.gmm.fill_(3.0); e.info.fill_(5); e.poison(M)
+    e.fit(drec, _dev(init), max_iter=1, tol=0.0)
+    _bits(_host(e.packed)[:M], packed, "packed, M = %d" % M)
+    e.untouched(M, "M %d: the start and one iteration" % M)
+    own = e.state()
+    # one iteration from the spec's state
+    given = gmm.copy()
+    e.gmm.copy_(_dev(gmm)); e.info.copy_(_dev(info)); e.poison(M)
+    e.fit(drec, None, max_iter=1, tol=0.0, resume=1)
+    e.untouched(M, "M %d: one iteration" % M)
+    hi = (gmm.astype(LD), info.copy())
+    assert CS.iterate(packed.astype(LD), d, 0.0, 1e-6, *hi)
+    want = (gmm, info)
+    assert CS.iterate(packed, d, 0.0, 1e-6, gmm, info) and info.tolist() == [1, 0, 0, int(packed[:, 3].sum())]
+    _close(e.state(), want, d, span, 1e-12, "d %d K %d M %d: one iteration" % (d, K, M))
+    _close(own, want, d, span, 1e-12, "d %d K %d M %d: the start and one iteration" % (d, K, M), bound=M > 1)
+    _statements(e.state(), hi, d, "d %d K %d M %d: one iteration" % (d, K, M))
+    _statements(own, hi, d, "d %d K %d M %d: the start and one iteration" % (d, K, M))
+    assert M < 63 or not np.array_equal(given[1:], gmm[1:])                                    # the iteration moved the state
+
+
+@pytest.mark.parametrize("d,K", ONE_ITERATION)
 def test_one_iteration_from_a_given_state_equals_the_spec(handle, d, K):
     """The state the spec's start step leaves is given to the device, which runs one iteration of it with resume = 1; and the start step
     itself.  Tolerance, derived: a responsibility that matters has a log-ratio above -40, so exp gives it to a few tens of units in the
@@ -118,34 +235,41 @@ def test_one_iteration_from_a_given_state_equals_the_spec(handle, d, K):
     the fixture whose first M records are used.  n_valid exact.  The device's own start followed by one iteration is held to the same
     figures, but for the bound at M = 1: the covariance of a single point is the regulariser alone, 1e-6, to which the start adds the
     rounding of D D' - s s', about 1e-16 x range^2, and the log-determinant in the bound divides that by the regulariser: an error of
-    1e-10 x range^2 there says nothing about the kernel (the means, covariances and weights are held at M = 1 too)."""
-    feats = CS.FIXTURE_FEATS[d]
-    e = Ens(handle, K, feats, np.zeros((K, d)), SIZES[-1])
+    1e-10 x range^2 there says nothing about the kernel (the means, covariances and weights are held at M = 1 too).
+    Every K of e_launch's switch runs at d = 3, in both START flavours (test_every_instantiation_of_the_e_kernel_is_run holds the list
+    to the switch); d = 1 and 2 at K = 1, 2, 3 and 8.  The derivation does not depend on K <= 8."""
+    e = Ens(handle, K, CS.FIXTURE_FEATS[d], np.zeros((K, d)), SIZES[-1])
     try:
         for M in SIZES:
-            rec, init, span = _records(d, K, M)
-            packed = CS.pack(rec, feats)
-            if K > 1:
-                assert CS.nearest_rows(packed[packed[:, 3] == 1.0, :d], init)[1].min() >= 1e-9
-            gmm, info = np.zeros((1 + K, CS.ROW)), np.zeros(4, dtype=np.int32)
-            assert CS.start(packed, init, d, 1e-6, gmm, info) and info[3] == packed[:, 3].sum() and (M < 63 or info[3] < M)
-            drec = _dev(rec)
-            # the device's own start, max_iter = 1: start + one iteration
-            e.gmm.fill_(3.0); e.info.fill_(5)
-            e.fit(drec, _dev(init), max_iter=1, tol=0.0)
-            _bits(_host(e.packed)[:M], packed, "packed, M = %d" % M)
-            own = e.state()
-            # one iteration from the spec's state
-            given = gmm.copy()
-            e.gmm.copy_(_dev(gmm)); e.info.copy_(_dev(info))
-            e.fit(drec, None, max_iter=1, tol=0.0, resume=1)
-            want = (gmm, info)
-            assert CS.iterate(packed, d, 0.0, 1e-6, gmm, info) and info.tolist() == [1, 0, 0, int(packed[:, 3].sum())]
-            _close(e.state(), want, d, span, 1e-12, "d %d K %d M %d: one iteration" % (d, K, M))
-            _close(own, want, d, span, 1e-12, "d %d K %d M %d: the start and one iteration" % (d, K, M), bound=M > 1)
-            assert M < 63 or not np.array_equal(given[1:], gmm[1:])                                # the iteration moved the state
+            _one_iteration(e, d, K, M)
     finally:
         e.close()
+
+
+@pytest.mark.parametrize("nblk", ROW_COUNTS)
+@pytest.mark.parametrize("K", [1, 5, 8])
+def test_one_iteration_at_every_shape_of_the_row_reduction(handle, K, nblk):
+    """The M kernel's sum over the rows of partial in its general shape -- full groups of sixteen and a tail -- and at the edges of it
+    (ROW_COUNTS), at the narrowest, a middle and the widest row (10 K + 1 columns: 11, 51, 81; the last takes a second pass of the
+    wave).  SIZES reaches 1, 2 and 256 rows only.  The same checks and tolerances as the test above: its derivation covers M <= 65 537."""
+    M = 256 * nblk - 3
+    assert min(-(-M // 256), CS.BLOCKS_MAX) == nblk and M <= SIZES[-1]
+    e = Ens(handle, K, CS.FIXTURE_FEATS[3], np.zeros((K, 3)), M)
+    try:
+        _one_iteration(e, 3, K, M)
+    finally:
+        e.close()
+
+
+def test_every_instantiation_of_the_e_kernel_is_run():
+    """The K the one-iteration test runs at d = 3 are exactly the cases of e_launch's switch; the row counts hold a full group with a tail."""
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ad_mpc_amd", "csrc", "admpc_quad_clusters.hip")).read()
+    switch = re.search(r"switch \(K\) \{([^}]*)\}", src).group(1)
+    cases = [int(k) for k in re.findall(r"E_CASE\((\d+)\)", switch)]
+    assert cases == list(E_KERNEL_K) == list(range(1, CS.PARTIAL // 10 + 1)) and re.sub(r"E_CASE\(\d+\)|\s", "", switch) == ""
+    assert sorted(K for d, K in ONE_ITERATION if d == 3) == cases and len(set(ONE_ITERATION)) == len(ONE_ITERATION)
+    assert re.search(r"for \(; r \+ 15 < nblk; r \+= 16\)", src)
+    assert any(n > 16 and n % 16 for n in ROW_COUNTS) and all(256 * n - 3 <= SIZES[-1] for n in ROW_COUNTS)
 
 
 # ---- 2. whole fits ---------------------------------------------------------------------------------------------------------------------------
@@ -167,6 +291,100 @@ def test_full_fits_equal_the_spec(handle, d, K):
         wc, wp, wi = CS.install(want[0], want[1], init)
         assert installed == wi == 1 and perm == wp.tolist() and np.abs(cent - wc).max() <= 1e-10 * span.max()
         assert np.abs(cent[:, 0] - 2.5 * np.arange(K)).max() < 0.15
+    finally:
+        e.close()
+
+
+# ---- 2b. the fixtures that are not easy ---------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def _hard(name, reg, tol=1e-3, max_iter=CS.HARD_MAX_ITER):
+    """The fixture through the spec in float64 and in longdouble, once per module."""
+    return CS.hard_run(name, reg, np.float64, tol, max_iter), CS.hard_run(name, reg, LD, tol, max_iter)
+
+
+@pytest.mark.parametrize("name,reg", CS.HARD_CASES)
+def test_hard_fixtures_equal_the_longdouble_spec_within_ten_gaps(handle, name, reg):
+    """What a closed loop logs (quad_clusters_spec.hard: overlapping clusters, a spread of the size of reg_covar, an offset 1e6 spreads
+    away, nearly dependent features, scales 1e3 apart, outliers, a component without a record): one iteration from the float64 spec's
+    start (resume = 1) and the whole fit from the device's own start (tol = 1e-3).  The tolerances of the easy fixtures (1e-12 and
+    1e-10 of the scale) are argued for well-conditioned data and do not carry here; each quantity is held to
+    max(that, 10 x the gap between the spec in float64 and in longdouble), the distance taken to the longdouble spec (_held).  The gap is
+    computed here, from the spec alone.  info equals the float64 spec's: tests/test_quad_clusters_cpu.py holds every change of the
+    bound away from tol by 100 gaps.
+    Measured on the MI355X: see the table of DESIGN.md's section on the centroids."""
+    lo, hi = _hard(name, reg)
+    d, K, M, span = lo["d"], lo["K"], lo["rec"].shape[0], lo["span"]
+    e = Ens(handle, K, lo["feats"], np.zeros((K, d)), M)
+    try:
+        drec, what = _dev(lo["rec"]), "%s reg %g" % (name, reg)
+        e.gmm.copy_(_dev(lo["given"][0])); e.info.copy_(_dev(lo["given"][1])); e.poison(M)
+        e.fit(drec, None, max_iter=1, tol=0.0, reg=reg, resume=1)
+        e.untouched(M, what)
+        _held(e.state(), lo["one"], hi["one"], d, span, 1e-12, what + ", one iteration")
+        _statements(e.state(), hi["one"], d, what + ", one iteration")
+        e.gmm.fill_(3.0); e.info.fill_(5); e.poison(M)
+        e.fit(drec, _dev(lo["init"]), max_iter=CS.HARD_MAX_ITER, tol=1e-3, reg=reg)
+        e.untouched(M, what)
+        assert lo["whole"][1][1] == 1 and lo["whole"][1][0] >= 2
+        _held(e.state(), lo["whole"], hi["whole"], d, span, 1e-10, what + ", whole fit of %d iterations" % lo["whole"][1][0])
+        _statements(e.state(), hi["whole"], d, what + ", whole fit")
+        if name == "starved":
+            assert e.state()[0][3, 17] == CS.TINY and e.state()[0][3, 1] == 40.0                  # no record, the mean where it was put
+    finally:
+        e.close()
+
+
+def test_a_component_without_a_record_and_without_a_regulariser_fails_the_start(handle):
+    """`starved` at reg_covar = 0: the third initial mean takes no record, its covariance is zero and its first pivot fails."""
+    name, reg = CS.HARD_FAILS
+    rec, init = CS.hard(name)
+    M = rec.shape[0]
+    e = Ens(handle, 3, [7], init, M)
+    try:
+        e.gmm.fill_(7.0); e.info.fill_(9); e.poison(M)
+        e.fit(_dev(rec), None, max_iter=3, reg=reg)
+        gmm, info = e.state()
+        assert info.tolist() == [0, 0, -3, M] and (gmm == 7.0).all()
+        e.untouched(M, "the failed start")
+        perm, installed, cent = e.install()
+        assert installed == 0 and perm == [0, 1, 2] and np.array_equal(cent, init)
+        want = CS.fit(rec, [7], init, max_iter=3, reg_covar=reg, gmm=np.full((4, CS.ROW), 7.0), info=np.full(4, 9, dtype=np.int32))
+        assert want[1].tolist() == info.tolist() and np.array_equal(want[0], gmm)
+    finally:
+        e.close()
+
+
+@pytest.mark.parametrize("name", ["anisotropic", "overlap"])
+def test_without_a_regulariser_the_bound_does_not_decrease(handle, name):
+    """EM's bound is monotone, and at reg_covar = 0 the M step maximises exactly: a decrease is rounding.  40 iterations at tol = 0,
+    one per resumed call: no change of the bound lies below -10 x the largest gap in `change` between the spec in float64 and in
+    longdouble on this fixture (the CPU test: that spec's own never decreases by more than 1e-15 (1 + |bound|)).  One call of 40
+    leaves the same bits; the state is held as a whole fit's."""
+    lo, hi = _hard(name, 0.0, 0.0, 40)
+    d, K, M = lo["d"], lo["K"], lo["rec"].shape[0]
+    gap = max(abs(float(a - b)) for a, b in zip(lo["changes"], hi["changes"]))
+    assert len(lo["changes"]) == 39 and gap > 0.0
+    e = Ens(handle, K, lo["feats"], lo["init"], M)
+    try:
+        drec, changes = _dev(lo["rec"]), []
+        e.gmm.fill_(3.0); e.info.fill_(5); e.poison(M)
+        e.fit(drec, None, max_iter=1, tol=0.0, reg=0.0)
+        for _ in range(39):
+            changes.append(e.state()[0][0, 1])
+            e.fit(drec, None, max_iter=1, tol=0.0, reg=0.0, resume=1)
+        changes.append(e.state()[0][0, 1])
+        stepped = e.state()
+        print("%s: smallest change of the bound %.3e on the device, %.3e in float64, %.3e in longdouble; largest gap in change %.3e"
+              % (name, min(changes), min(lo["changes"]), float(min(hi["changes"])), gap))
+        assert changes[0] == np.inf and stepped[1].tolist() == [40, 0, 0, M]
+        assert min(changes[1:]) >= -10.0 * gap, (changes, gap)
+        e.gmm.fill_(3.0); e.info.fill_(5); e.poison(M)
+        e.fit(drec, None, max_iter=40, tol=0.0, reg=0.0)
+        _bits(e.state()[0], stepped[0], "one call of 40 against 40 calls of one"); _bits(e.state()[1], stepped[1], "info")
+        e.untouched(M, name)
+        _held(stepped, lo["whole"], hi["whole"], d, lo["span"], 1e-10, "%s reg 0, 40 iterations" % name)
+        _statements(stepped, hi["whole"], d, "%s reg 0, 40 iterations" % name)
     finally:
         e.close()
 
