@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 from .config import AdmpcConfig, AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
-from .quad_config import AdmpcQuadConfig, AdmpcQuadNoiseParams, AdmpcQuadObserveParams, AdmpcQuadPlantParams
+from .quad_config import AdmpcQuadConfig, AdmpcQuadNoiseParams, AdmpcQuadObserveParams, AdmpcQuadPlantParams, AdmpcQuadTargetParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libadmpc.so")
@@ -154,6 +154,19 @@ _QUAD_HYPER = {     # include/admpc_quad_hyper.h: admpc_hyper.h's search and re-
 }
 QUAD_HYPER_EXPORTS = tuple(_QUAD_HYPER)
 HYPER_TABLES = {"admpc_quad_hyper.h": _QUAD_HYPER}
+# flying to random targets and recording, declared by load() in the same way
+tp_ = C.POINTER(AdmpcQuadTargetParams)
+_QUAD_TARGETS = {   # include/admpc_quad_targets.h: the draw of a target, the reset, the window with the recovery, the plant step with the reach test, the observation with a period per vehicle, the rollout
+    "admpc_quad_target_draw_batch": (I, [tp_, I, I, dp, C.c_int64, ip, dp, ip, vp]),
+    "admpc_quad_targets_reset_batch": (I, [tp_, I, I, dp, dp, dp, ip, ip, ip, ip, vp]),
+    "admpc_quad_target_window_batch": (I, [tp_, I, I, I, dp, dp, ip, ip, ip, ip, dp, dp, dp, vp]),
+    "admpc_quad_plant_target_step_batch": (I, [pp, tp_, np_, I, I, dp, C.c_int64, dp, ip, dp, dp, ip, ip, ip, ip, ip, ip, vp]),
+    "admpc_quad_observe_var_batch": (I, [vp, pp, qop, I, dp, C.c_int64, dp, dp, ip, dp, dp, ip, vp]),
+    "admpc_quad_rollout_targets_batch": (I, [vp, pp, tp_, I, I] + [dp] * 6 + [ip, ip] + [dp, dp, ip, ip, ip, ip, ip] + [dp, dp, ip, dp] +
+                                         [vp, qop, dp, dp, dp, ip] + [np_, ip, vp]),
+}
+QUAD_TARGETS_EXPORTS = tuple(_QUAD_TARGETS)
+TARGET_TABLES = {"admpc_quad_targets.h": _QUAD_TARGETS}
 
 _lib = None
 
@@ -172,7 +185,7 @@ def load():
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
     for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()) + \
-            list(HYPER_TABLES.values()):
+            list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -2,7 +2,7 @@
 // declaration of every hidden function that one unit defines for another.  The defining unit includes this header too, so that the
 // compiler holds each definition against its declaration.  Included by admpc_kernels.hip, admpc_step.hip, admpc_lane.hip,
 // admpc_plant.hip, admpc_learn.hip, admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip, admpc_quad_learn.hip, admpc_quad_noise.hip,
-// admpc_quad_ensemble.hip, admpc_quad_clusters.hip and admpc_quad_hyper.hip.  The learning host
+// admpc_quad_ensemble.hip, admpc_quad_clusters.hip, admpc_quad_hyper.hip and admpc_quad_targets.hip.  The learning host
 // side that admpc_learn.hip defines for admpc_quad_learn.hip and admpc_hyper.hip is declared in gp_fit_dev.h, next to the LearnArgs it
 // speaks of; the search's host side that admpc_hyper.hip defines for admpc_quad_hyper.hip in gp_search_dev.h, next to its SearchGp.
 #pragma once
@@ -121,6 +121,10 @@ ADMPC_HIDDEN int admpc_quad_observe_params_check(const char* who, const AdmpcQua
 ADMPC_HIDDEN int admpc_quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams* plant, const AdmpcQuadObserveParams* obs,
                                            const AdmpcQuadEnsemble* ens, int B, const double* u, long long u_stride, const double* x, double* prev,
                                            double* samples, double* bins, int32_t* dropped, void* stream);
+// admpc_quad_learn.hip, for admpc_quad_targets.hip: the bin launch of an observation alone (the second of the two above, without an
+// ensemble), and the latch, both for checked arguments, B > 0, on the current device
+ADMPC_HIDDEN int admpc_quad_bin_launch(const AdmpcQuadObserveParams* obs, int B, const double* samples, double* bins, int32_t* dropped, void* stream);
+ADMPC_HIDDEN int admpc_quad_latch_launch(int B, const double* x, double* prev, void* stream);
 // admpc_quad_ensemble.hip: the handles of an ensemble (returns K); what admpc_quad_clusters.hip and admpc_quad_hyper.hip need of one (its
 // device centroids to be written, its features, whether it learns and under which blocks, the device copy of its regressors, its search
 // slot); one launch of its route kernel (route_out: null or [B]) and one of its bin kernel, B > 0, on its device

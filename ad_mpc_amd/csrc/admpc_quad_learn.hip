@@ -44,43 +44,7 @@ constexpr int QX = ADMPC_QUAD_NX, QU = ADMPC_QUAD_NU;
 typedef AdmpcQuadConfig Cfg;
 
 #include "quad_model_dev.h"
-
-// one classic RK4 step of length h of the model's state alone: quad_f_tan with zero tangents, the GP features from the integrated state
-__device__ __forceinline__ void quad_rk4_state(const Cfg* __restrict__ c, double (&x)[QX], const double (&u)[QU], const double h)
-{
-    const double sx[QX] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, su[QU] = { 0, 0, 0, 0 };
-    double kx[QX], ax[QX];
-#pragma unroll
-    for (int i = 0; i < QX; ++i) { kx[i] = 0; ax[i] = 0; }
-    // ONE copy of the model in the kernel: with the four stages unrolled the constants of all four copies were held in scalar registers
-    // at once (4 SGPR spills, 256 VGPRs); the stage's node and weight are selects, not table reads, which would live in scratch
-#pragma unroll 1
-    for (int s = 0; s < 4; ++s) {
-        const double cs = s == 0 ? 0.0 : (s == 3 ? 1.0 : 0.5), ws = (s == 0 || s == 3) ? 1.0 / 6 : 2.0 / 6;
-        double X[QX], f[QX], df[QX];
-#pragma unroll
-        for (int i = 0; i < QX; ++i) X[i] = x[i] + cs * h * kx[i];
-        quad_f_tan(c, X, u, sx, su, false, X, f, df);
-#pragma unroll
-        for (int i = 0; i < QX; ++i) { kx[i] = f[i]; ax[i] += ws * f[i]; }
-    }
-#pragma unroll
-    for (int i = 0; i < QX; ++i) x[i] = x[i] + h * ax[i];
-}
-
-// The velocity of state s in the body frame of s's own attitude: the expressions of quad_rot, every operation rounded on its own, so
-// that numpy reproduces the features bit for bit (quad_rot itself is compiled with contraction, as the solve wants it).
-__device__ __forceinline__ void body_velocity(const double (&s)[QX], double (&vb)[3])
-{
-#pragma clang fp contract(off)
-    const double qw = s[3], qx = s[4], qy = s[5], qz = s[6];
-    double R[3][3];
-    R[0][0] = 1 - 2 * (qy * qy + qz * qz); R[0][1] = 2 * (qx * qy - qw * qz); R[0][2] = 2 * (qx * qz + qw * qy);
-    R[1][0] = 2 * (qx * qy + qw * qz); R[1][1] = 1 - 2 * (qx * qx + qz * qz); R[1][2] = 2 * (qy * qz - qw * qx);
-    R[2][0] = 2 * (qx * qz - qw * qy); R[2][1] = 2 * (qy * qz + qw * qx); R[2][2] = 1 - 2 * (qx * qx + qy * qy);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) vb[i] = (R[0][i] * s[7] + R[1][i] * s[8]) + R[2][i] * s[9];
-}
+#include "quad_observe_dev.h"  // quad_rk4_state, body_velocity: shared with the observe kernel of admpc_quad_targets.hip
 
 }  // namespace
 
@@ -171,6 +135,12 @@ int quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams
                        admpc_quad_solver_config_device(model, nullptr), a);
     if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_quad_observe_kernel: launch failed");
     if (ens) return admpc_quad_ensemble_bin_launch(ens, B, samples, bins, dropped, stream);
+    return admpc_quad_bin_launch(obs, B, samples, bins, dropped, stream);
+}
+
+// the bin launch of an observation alone, for checked arguments, B > 0, on the current device
+int quad_bin_launch(const AdmpcQuadObserveParams* obs, int B, const double* samples, double* bins, int32_t* dropped, void* stream)
+{
     LearnArgs l = LearnArgs();
     admpc_learn_fill(l, obs->n_gp, obs->gp, QUAD_LEARN.feat_lo);
     l.B = B; l.samples = samples; l.bins = bins; l.dropped = dropped;
@@ -191,6 +161,11 @@ int quad_latch_launch(int B, const double* x, double* prev, void* stream)
 
 // for admpc_quad_ensemble.hip: the refusals of the observe parameters, and the two launches of an observation
 extern "C" int admpc_quad_observe_params_check(const char* who, const AdmpcQuadObserveParams* obs) { return quad_observe_params_check(who, obs); }
+extern "C" int admpc_quad_latch_launch(int B, const double* x, double* prev, void* stream) { return quad_latch_launch(B, x, prev, stream); }
+extern "C" int admpc_quad_bin_launch(const AdmpcQuadObserveParams* obs, int B, const double* samples, double* bins, int32_t* dropped, void* stream)
+{
+    return quad_bin_launch(obs, B, samples, bins, dropped, stream);
+}
 extern "C" int admpc_quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams* plant, const AdmpcQuadObserveParams* obs,
                                          const AdmpcQuadEnsemble* ens, int B, const double* u, long long u_stride, const double* x, double* prev,
                                          double* samples, double* bins, int32_t* dropped, void* stream)

@@ -1,5 +1,5 @@
 // quad_model_dev.h -- device code of the quadrotor model shared by the solve kernels (admpc_quad.hip) and the observe kernel
-// (admpc_quad_learn.hip): the rotation matrix of a quaternion, its directional derivative, and f(x, u) with its forward-mode tangent,
+// (admpc_quad_learn.hip; with a period per vehicle: admpc_quad_targets.hip): the rotation matrix of a quaternion, its directional derivative, and f(x, u) with its forward-mode tangent,
 // the GP residual and the linear rotor drag included.  Include INSIDE the translation unit's anonymous namespace, after QX, QU and
 // Cfg (AdmpcQuadConfig) are defined; every function is __forceinline__.
 #pragma once

@@ -1,7 +1,8 @@
 """ctypes mirror of include/admpc_quad.h (AdmpcQuadConfig) and the shipped quadrotor problem
 (acados_models/my_quad_acados_ocp.json, src/quad_mpc/quad_3d.py:40-74); of include/admpc_quad_fleet.h (AdmpcQuadPlantParams), the
 simulator's vehicle (src/quad_mpc/quad_3d.py:22-95); of include/admpc_quad_learn.h (AdmpcQuadObserveParams), the regressors a fleet
-learns on the device; of include/admpc_quad_noise.h (AdmpcQuadNoiseParams), the simulator's random disturbances."""
+learns on the device; of include/admpc_quad_noise.h (AdmpcQuadNoiseParams), the simulator's random disturbances; of
+include/admpc_quad_targets.h (AdmpcQuadTargetParams), the targets a fleet chases."""
 import ctypes as C
 import math
 
@@ -102,6 +103,44 @@ class AdmpcQuadNoiseParams(C.Structure):
     """include/admpc_quad_noise.h: the key of the generator, the two switches, the scales of the reference's distributions."""
     _fields_ = [("seed", C.c_uint64), ("noisy", C.c_int32), ("motor_noise", C.c_int32), ("force_std", C.c_double), ("torque_std", C.c_double),
                 ("motor_bias", C.c_double), ("motor_ref", C.c_double), ("motor_std", C.c_double)]
+
+
+class AdmpcQuadTargetParams(C.Structure):
+    """include/admpc_quad_targets.h: the key of the targets' generator, how the next target is found, when one counts as reached and
+    when a vehicle is recovered."""
+    _fields_ = [("seed", C.c_uint64), ("mode", C.c_int32), ("n_preset", C.c_int32), ("world_radius", C.c_double), ("thresh", C.c_double),
+                ("v_max", C.c_double), ("max_iters", C.c_int32), ("pad", C.c_int32)]
+
+
+TARGET_MODES = {"preset": 0, "aggressive": 1, "uniform": 2}
+
+
+def quad_target_params(mode="aggressive", world_radius=3.0, thresh=0.05, v_max=14.0, max_iters=100, seed=None, n_preset=0):
+    """AdmpcQuadTargetParams with the reference's constants (point_tracking_and_record.py:112, :204, :255); every refusal of the header
+    is a ValueError here.  ``seed`` (0 .. 2^64 - 1) is needed by the two random modes."""
+    if mode not in TARGET_MODES:
+        raise ValueError("quad_target_params: mode must be one of %s" % sorted(TARGET_MODES))
+    world_radius, thresh, v_max = float(world_radius), float(thresh), float(v_max)
+    if not (world_radius > 0 and math.isfinite(world_radius)):
+        raise ValueError("quad_target_params: world_radius must be positive and finite")
+    if not (thresh > 0 and math.isfinite(thresh)):
+        raise ValueError("quad_target_params: thresh must be positive and finite")
+    if math.isnan(v_max):
+        raise ValueError("quad_target_params: v_max must not be NaN")
+    if int(max_iters) != max_iters or not 0 <= int(max_iters) < 2 ** 31:
+        raise ValueError("quad_target_params: max_iters must be an integer in [0, 2^31)")
+    t = AdmpcQuadTargetParams()
+    t.mode = TARGET_MODES[mode]
+    if t.mode == 0:
+        if not 1 <= int(n_preset) < 2 ** 31:
+            raise ValueError("quad_target_params: mode 'preset' needs at least one preset target per vehicle")
+        t.n_preset, seed = int(n_preset), 0 if seed is None else seed
+    elif seed is None:
+        raise ValueError("quad_target_params: mode '%s' needs a seed" % mode)
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("quad_target_params: seed must be in [0, 2^64)")
+    t.seed, t.world_radius, t.thresh, t.v_max, t.max_iters = int(seed), world_radius, thresh, v_max, int(max_iters)
+    return t
 
 
 class AdmpcQuadObserveParams(C.Structure):

@@ -190,6 +190,9 @@ class QuadEnsembleFleet(QuadFleet):
             s.close()
         super().close()                                                                    # the bank, handle 0 and the nominal handle
 
+    def _targets_offered(self, who):
+        raise ValueError("%s: clustered ensembles do not chase targets (include/admpc_quad_targets.h: not offered); QuadFleet does" % who)
+
     # -- routing and the routed solve, for a loop driven from the host ------------------------------------------------------------------
     def route_window(self, route=None):
         """The cluster of every vehicle from row 0 of its window ``yref`` as it stands (admpc_quad_ensemble_route_batch), into ``route``

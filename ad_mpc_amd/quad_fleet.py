@@ -6,7 +6,9 @@ vehicle's constants, the linear drag, one cluster of residual GPs).  With ``lear
 the steps it has flown (include/admpc_quad_learn.h: observe -> bin -> fit -> install; the side it shares with the car's fleet is
 learning.py's), and searches their hyperparameters there (include/admpc_quad_hyper.h: ``search_gp`` -> re-fit -> install, ``learned_hyper``; learning.py's
 as well).  With ``noise_seed`` and a vehicle whose ``noisy`` or ``motor_noise`` is set, the plant is the simulator under its random
-disturbances (include/admpc_quad_noise.h)."""
+disturbances (include/admpc_quad_noise.h).  With ``set_targets`` the fleet flies the reference's other experiment,
+``experiments/point_tracking_and_record.py``: every vehicle chases random target points, reached within a threshold that is tested after
+every simulator sub-step, and is recorded over the time it really flew (include/admpc_quad_targets.h)."""
 import ctypes as C
 from collections import namedtuple
 
@@ -17,9 +19,11 @@ from . import _lib
 from .engine import QuadBatchSolver, _ptr
 from .learning import FleetLearning, FleetSearch, placeholder_gps
 from .quad_config import (QNX, QNU, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, default_quad_config, quad_is_noisy, quad_learn_bins,
-                          quad_noise_params, quad_plant_params, set_quad_gp)
+                          quad_noise_params, quad_plant_params, quad_target_params, set_quad_gp)
 
 QuadRollout = namedtuple("QuadRollout", ("x", "idx", "tally", "counts", "traj", "u"))
+QuadTargetRollout = namedtuple("QuadTargetRollout", ("x", "target", "target_no", "tcounts", "traj", "u", "nsub", "targets"))
+START_STATE = (0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)      # point_tracking_and_record.py:115
 T_MAX = 4096
 
 
@@ -118,6 +122,7 @@ class QuadFleet(FleetLearning):
         self._noise = quad_noise_params(quad, simulation_dt, noise_seed) if flies_noise else None
         self.noise_step = None
         self._learn = self._nominal = None
+        self._tp, self._targets_started = None, False
 
     def _alloc_state(self, engines):
         """The fleet's tensors on the device of ``_eng``, and one eager solve on every handle that will solve in the loop."""
@@ -278,6 +283,119 @@ class QuadFleet(FleetLearning):
     def step(self):
         """One closed-loop step."""
         return self.rollout(1)
+
+    # -- flying to targets (include/admpc_quad_targets.h) --------------------------------------------------------------------------------
+    def _targets_offered(self, who):
+        """A fleet that cannot chase targets says so here."""
+
+    def _chases(self, who, started=True):
+        self._targets_offered(who)
+        if self._tp is None:
+            raise ValueError("%s: call set_targets first" % who)
+        if started and not self._targets_started:
+            raise ValueError("%s: call reset_targets first" % who)
+
+    def set_targets(self, mode="aggressive", world_radius=3.0, thresh=0.05, v_max=14.0, max_iters=100, seed=None, presets=None):
+        """How the fleet chases targets (point_tracking_and_record.py; the defaults are the reference's): ``mode`` "aggressive" (the next
+        target is sampled away from where the vehicle stands), "uniform" (in the world box) or "preset" (``presets`` [n,3] for all
+        vehicles or [B,n,3]); a target counts as reached within ``thresh``; a vehicle with a velocity component above ``v_max`` or more
+        than ``max_iters`` periods on one target is put back on its target.  ``seed`` is the key of the targets' generator, needed by
+        the two random modes.  Every refusal is a ValueError, raised before any device call.  State: ``target`` [B,3], ``target_no`` [B]
+        int64 (the 64 bits are the header's uint64), ``n_iter`` [B], ``fast`` [B], ``tcounts`` [B,5] (targets reached, recoveries,
+        periods flown, periods with status != 0, periods with a replaced activation) and ``nsub`` [B] (the sub-steps of the last
+        period).  ``reset_targets`` starts the flight."""
+        self._targets_offered("set_targets")
+        pre, n_preset = None, 0
+        if mode == "preset":
+            if presets is None:
+                raise ValueError("set_targets: mode 'preset' needs presets [n,3] or [B,n,3]")
+            pre = np.asarray(presets, dtype=np.float64)
+            if pre.ndim == 2:
+                pre = np.broadcast_to(pre, (self.B,) + pre.shape)
+            if pre.ndim != 3 or pre.shape[0] != self.B or pre.shape[1] < 1 or pre.shape[2] != 3:
+                raise ValueError("set_targets: presets must be [n,3] or [B,n,3] with n >= 1")
+            pre, n_preset = np.ascontiguousarray(pre), pre.shape[1]
+        elif presets is not None:
+            raise ValueError("set_targets: presets come with mode 'preset'")
+        tp = quad_target_params(mode, world_radius, thresh, v_max, max_iters, seed, n_preset)
+        z = lambda *shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=self.device)
+        self.target, self.target_no = z(self.B, 3, dtype=torch.float64), z(self.B, dtype=torch.int64)
+        self.n_iter, self.fast, self.tcounts, self.nsub = z(self.B), z(self.B), z(self.B, 5), z(self.B)
+        self._presets = None if pre is None else torch.as_tensor(pre).to(self.device)
+        self._tp, self._targets_started = tp, False
+
+    def reset_targets(self, x0=None):
+        """The fleet starts at x0 [B,13] or [13] (default: the reference's start state, level at the origin); the iterate and the
+        targets' counters are zeroed, ``fast`` is taken from x0 and target number 0 is installed (admpc_quad_targets_reset_batch).
+        ``noise_step`` is NOT touched, as in ``reset``."""
+        self._chases("reset_targets", started=False)
+        x0 = np.asarray(START_STATE if x0 is None else x0, dtype=np.float64)
+        if x0.shape not in ((QNX,), (self.B, QNX)):
+            raise ValueError("reset_targets: x0 must be [13] or [B,13]")
+        self.x.copy_(torch.as_tensor(np.broadcast_to(x0, (self.B, QNX)).copy()))
+        for t in (self.x_opt, self.w_opt, self.cost, self.status, self.iters):
+            t.zero_()
+        _lib.check(self.lib.admpc_quad_targets_reset_batch(C.byref(self._tp), self.device_index, self.B, _ptr(self.x), _ptr(self._presets),
+                                                           _ptr(self.target), _ptr(self.target_no), _ptr(self.n_iter), _ptr(self.fast),
+                                                           _ptr(self.tcounts), self._stream()))
+        self._targets_started = True
+
+    def target_window(self):
+        """The recovery of every vehicle that has run away, then the point reference of every vehicle into yref / yref_e
+        (admpc_quad_target_window_batch).  A fleet that learns has the recovered state latched for its next observation."""
+        self._chases("target_window")
+        prev = self._prev if self._learn is not None else None
+        _lib.check(self.lib.admpc_quad_target_window_batch(C.byref(self._tp), self.device_index, self.B, self.N, _ptr(self.x), _ptr(self.target),
+                                                           _ptr(self.target_no), _ptr(self.n_iter), _ptr(self.fast), _ptr(self.tcounts),
+                                                           _ptr(prev), _ptr(self.yref), _ptr(self.yref_e), self._stream()))
+
+    def plant_step_targets(self, u=None):
+        """One control period of the simulator towards the targets, stopped for a vehicle at the sub-step at which it reaches
+        (admpc_quad_plant_target_step_batch): ``nsub``, the counters, ``fast`` and, at a reach, the next target in the same launch.
+        u [B,4] (a float64 view with rows of 4 and a row stride); default ``w_opt[:, 0, :]``, and then ``status`` of the solve that left
+        it is counted in ``tcounts``.  Under the disturbances ``noise_step`` advances by 1."""
+        self._chases("plant_step_targets")
+        status = self.status if u is None else None
+        u = self.w_opt[:, 0, :] if u is None else u
+        stride = self._u_stride("plant_step_targets", u, self.B)
+        noise = None if self._noise is None else C.byref(self._noise)
+        _lib.check(self.lib.admpc_quad_plant_target_step_batch(C.byref(self._plant), C.byref(self._tp), noise, self.device_index, self.B,
+                                                               C.c_void_p(u.data_ptr()), stride, _ptr(self.x), _ptr(status), _ptr(self._presets),
+                                                               _ptr(self.target), _ptr(self.target_no), _ptr(self.n_iter), _ptr(self.fast),
+                                                               _ptr(self.tcounts), _ptr(self.nsub), _ptr(self.noise_step), self._stream()))
+
+    def observe_targets(self, u=None):
+        """``observe`` over the time every vehicle really flew in the last period, ``nsub`` sub-steps (admpc_quad_observe_var_batch)."""
+        self._chases("observe_targets")
+        self._learns("observe_targets")
+        u = self.w_opt[:, 0, :] if u is None else u
+        stride = self._u_stride("observe_targets", u, self.B)
+        _lib.check(self.lib.admpc_quad_observe_var_batch(self._observer._h, C.byref(self._plant), C.byref(self._obs), self.B, C.c_void_p(u.data_ptr()),
+                                                         stride, _ptr(self.x), _ptr(self._prev), _ptr(self.nsub), _ptr(self.samples),
+                                                         _ptr(self.bins), _ptr(self.dropped), self._stream()))
+
+    def rollout_targets(self, T, record=False, observe=False):
+        """T periods of the target flight (admpc_quad_rollout_targets_batch): recovery and window -> RTI step -> plant with the reach test,
+        and with `observe` (needs ``learn``) a latch first and the observation of the flown time behind every period.  No host
+        synchronisation.  Returns QuadTargetRollout(x, target, target_no, tcounts, traj, u, nsub, targets): the fleet's own tensors, and
+        with record traj [T+1,B,13], u [T,B,4], nsub [T,B] int32 and targets [T,B,3] (the target in force during the period)."""
+        self._chases("rollout_targets")
+        if observe:
+            self._learns("rollout_targets")
+        T, traj, u = self._records("rollout_targets", T, record)
+        nsub = targets = None
+        if record:
+            nsub = torch.empty((T, self.B), dtype=torch.int32, device=self.device)
+            targets = torch.empty((T, self.B, 3), dtype=torch.float64, device=self.device)
+        watch = (self._observer._h, C.byref(self._obs), _ptr(self._prev), _ptr(self.samples), _ptr(self.bins), _ptr(self.dropped)) if observe \
+            else (None,) * 6
+        noise = None if self._noise is None else C.byref(self._noise)
+        _lib.check(self.lib.admpc_quad_rollout_targets_batch(
+            self._eng._h, C.byref(self._plant), C.byref(self._tp), self.B, T, _ptr(self.x), _ptr(self.x_opt), _ptr(self.w_opt), _ptr(self.yref),
+            _ptr(self.yref_e), _ptr(self.cost), _ptr(self.status), _ptr(self.iters), _ptr(self._presets), _ptr(self.target), _ptr(self.target_no),
+            _ptr(self.n_iter), _ptr(self.fast), _ptr(self.tcounts), _ptr(self.nsub), _ptr(traj), _ptr(u), _ptr(nsub), _ptr(targets), *watch,
+            noise, _ptr(self.noise_step), self._stream()))
+        return QuadTargetRollout(self.x, self.target, self.target_no, self.tcounts, traj, u, nsub, targets)
 
     # -- the disturbances (include/admpc_quad_noise.h) ---------------------------------------------------------------------------------
     def _noisy(self, who):

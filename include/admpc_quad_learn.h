@@ -12,8 +12,11 @@
  *                                      to the body frame, y_err = (x_out - x_pred) / dt
  *   model_fitting/gp_common.py:101-112 prune_dataset: the data set cut into bins               admpc_quad_observe_batch: bins
  *   model_fitting/gp.py:81-138, 325-345  the kernel (sigma_f not squared); fit: y_mean, K^-1 y admpc_quad_gp_fit
- *   experiments/point_tracking_and_record.py:215-265  the recording loop: optimize, simulate,  admpc_quad_rollout_observe_batch
- *                                      predict with the nominal model, store the three states
+ *   experiments/point_tracking_and_record.py:215-265  of the recording loop the RECORD of a    admpc_quad_rollout_observe_batch (along the
+ *                                      flown period (:215, :230-234, :261-265): predict with    trajectories of a bank); the FLIGHT of that loop
+ *                                      the nominal model, store state_in, input_in, state_out   -- random targets, the reach test per sub-step,
+ *                                      and state_pred                                           the recovery, the period a vehicle really flew
+ *                                                                                               -- is admpc_quad_targets.h's
  *   quad_mpc/quad_3d_optimizer.py:289-327  where the GP enters the model of the MPC            admpc_quad_gp_install (no host in between)
  *
  * NOT offered:
