@@ -1,8 +1,8 @@
 // admpc_host.h -- what the host sides of the fleet units share: the device guard, the argument blocks of the two rollouts, and one
 // declaration of every hidden function that one unit defines for another.  The defining unit includes this header too, so that the
 // compiler holds each definition against its declaration.  Included by admpc_kernels.hip, admpc_step.hip, admpc_lane.hip,
-// admpc_plant.hip, admpc_learn.hip, admpc_hyper.hip, admpc_quad.hip, admpc_quad_fleet.hip, admpc_quad_learn.hip, admpc_quad_noise.hip,
-// admpc_quad_ensemble.hip, admpc_quad_clusters.hip, admpc_quad_hyper.hip and admpc_quad_targets.hip.  The learning host
+// admpc_plant.hip, admpc_learn.hip, admpc_hyper.hip, admpc_quad.hip, admpc_quad_plant.hip, admpc_quad_fleet.hip, admpc_quad_learn.hip,
+// admpc_quad_noise.hip, admpc_quad_ensemble.hip, admpc_quad_clusters.hip, admpc_quad_hyper.hip and admpc_quad_targets.hip.  The learning host
 // side that admpc_learn.hip defines for admpc_quad_learn.hip and admpc_hyper.hip is declared in gp_fit_dev.h, next to the LearnArgs it
 // speaks of; the search's host side that admpc_hyper.hip defines for admpc_quad_hyper.hip in gp_search_dev.h, next to its SearchGp.
 #pragma once
@@ -17,6 +17,7 @@
 #include "../../include/admpc_quad_fleet.h"
 #include "../../include/admpc_quad_learn.h"
 #include "../../include/admpc_quad_noise.h"
+#include "../../include/admpc_quad_targets.h"
 
 // Every entry point runs on the solver's device and restores the caller's current device on return (a host with several GPUs
 // keeps its own current device: torch allocations and default-stream work of the caller are not redirected).
@@ -70,12 +71,25 @@ struct QuadRolloutArgs {
 };
 
 struct QuadPlantArgs;       // quad_sim_dev.h: what one launch of a quadrotor plant kernel works on
+struct QuadTargetArgs;      // quad_target_dev.h: the target state of such a launch
+
+// the record slots of period t of a quadrotor rollout of B vehicles (traj_out: null or [T + 1][B][13], u_out: null or [T][B][4]): slot 0
+// of traj_out is written by the first period; every period writes the state it leaves into the next slot
+struct QuadRecordSlots { double *traj_pre, *traj_post, *u_out; };
+inline QuadRecordSlots admpc_quad_record_slots(double* traj_out, double* u_out, int B, int t)
+{
+    const size_t slot = (size_t)B * ADMPC_QUAD_NX;
+    return { t == 0 ? traj_out : nullptr, traj_out ? traj_out + (size_t)(t + 1) * slot : nullptr, u_out ? u_out + (size_t)t * B * ADMPC_QUAD_NU : nullptr };
+}
 
 #define ADMPC_HIDDEN extern "C" __attribute__((visibility("hidden")))
 
-// admpc_kernels.hip: the thread-local message behind admpc_last_error(); the problem a handle solves and the device it lives on; the
-// device copy of that problem, to be read and to be written; the horizon of a bank and its device; a bank's table (returns H)
+// admpc_kernels.hip: the thread-local message behind admpc_last_error(); a refusal (ADMPC_EINVAL, "who: what"); ADMPC_ENODEV unless
+// `device` is one of the host's; the problem a handle solves and the device it lives on; the device copy of that problem, to be read and
+// to be written; the horizon of a bank and its device; a bank's table (returns H)
 ADMPC_HIDDEN int admpc_set_error(int code, const char* msg);
+ADMPC_HIDDEN int admpc_refuse(const char* who, const char* what);
+ADMPC_HIDDEN int admpc_device_check(int device);
 ADMPC_HIDDEN const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device);
 ADMPC_HIDDEN const AdmpcConfig* admpc_solver_config_device(const AdmpcSolver* s);
 ADMPC_HIDDEN AdmpcConfig* admpc_solver_config_device_rw(AdmpcSolver* s);
@@ -96,8 +110,12 @@ ADMPC_HIDDEN int admpc_rollout_enqueue(const RolloutArgs& a, double* traj_pre, d
 // admpc_quad.hip: the device copy of a quadrotor handle's problem, which admpc_quad_learn.hip reads (observe) and writes (install), and
 // the n_gp the handle was created with (n_gp may be NULL); next to admpc_quad_solver_info of include/admpc_quad_fleet.h
 ADMPC_HIDDEN AdmpcQuadConfig* admpc_quad_solver_config_device(const AdmpcQuadSolver* s, int* n_gp);
-// admpc_quad_fleet.hip: the refusals of the quadrotor's plant parameters
+// admpc_quad_plant.hip: the refusals of the quadrotor's plant parameters; the arguments of a plant-only step (a period of a rollout
+// sets its own pointers behind it); one launch of a plant kernel for filled arguments, B > 0, on the current device -- noise: null, or
+// checked disturbances with the period counters; g: null, or the target state of admpc_quad_targets.hip
 ADMPC_HIDDEN int admpc_quad_plant_params_check(const char* who, const AdmpcQuadPlantParams* plant);
+ADMPC_HIDDEN void admpc_quad_plant_fill(QuadPlantArgs& a, const AdmpcQuadPlantParams* plant, int B, const double* u, long long u_stride, double* x);
+ADMPC_HIDDEN int admpc_quad_plant_launch(const QuadPlantArgs& a, const AdmpcQuadNoiseParams* noise, uint64_t* noise_step, const QuadTargetArgs* g, void* stream);
 // admpc_quad_fleet.hip: the refusals of a rollout up to those of its arrays (under admpc_quad_rollout_batch's name), and one checked period
 ADMPC_HIDDEN int admpc_quad_rollout_check(const QuadRolloutArgs& a, int T);
 ADMPC_HIDDEN int admpc_quad_rollout_enqueue(const QuadRolloutArgs& a, double* traj_pre, double* traj_post, double* u_out, int32_t* route_out, void* stream);
@@ -111,18 +129,19 @@ ADMPC_HIDDEN int admpc_quad_rollout_observe_check(const QuadRolloutArgs& a, int 
 ADMPC_HIDDEN int admpc_quad_rollout_observe_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, const AdmpcQuadSolver* model,
                                                 const AdmpcQuadObserveParams* obs, double* prev, double* samples, long long samples_step,
                                                 double* bins, int32_t* dropped, void* stream);
-// admpc_quad_noise.hip: one launch of the noisy plant kernel for filled arguments and checked disturbances, B > 0; the refusals of the
-// disturbances (plant: null, or the plant whose u_min motor_noise is held against)
-ADMPC_HIDDEN int admpc_quad_plant_noise_launch(const QuadPlantArgs& a, const AdmpcQuadNoiseParams* noise, uint64_t* noise_step, void* stream);
+// admpc_quad_noise.hip: the refusals of the disturbances (plant: null, or the plant whose u_min motor_noise is held against)
 ADMPC_HIDDEN int admpc_quad_noise_params_check(const char* who, const AdmpcQuadNoiseParams* noise, const AdmpcQuadPlantParams* plant);
+// admpc_quad_targets.hip: the refusals of the target parameters
+ADMPC_HIDDEN int admpc_quad_target_params_check(const char* who, const AdmpcQuadTargetParams* t);
 // admpc_quad_learn.hip: the refusals of the quadrotor's observe parameters; the two launches of an observation for checked arguments,
-// B > 0, on the model's device -- with ens the bin launch is the ensemble's, all clusters at once
+// B > 0, on the model's device -- with ens the bin launch is the ensemble's, all clusters at once; nsub: null, or the sub-steps every
+// vehicle flew of its period ([B]: the observation over the flown time of include/admpc_quad_targets.h)
 ADMPC_HIDDEN int admpc_quad_observe_params_check(const char* who, const AdmpcQuadObserveParams* obs);
 ADMPC_HIDDEN int admpc_quad_observe_launch(const AdmpcQuadSolver* model, const AdmpcQuadPlantParams* plant, const AdmpcQuadObserveParams* obs,
                                            const AdmpcQuadEnsemble* ens, int B, const double* u, long long u_stride, const double* x, double* prev,
-                                           double* samples, double* bins, int32_t* dropped, void* stream);
-// admpc_quad_learn.hip, for admpc_quad_targets.hip: the bin launch of an observation alone (the second of the two above, without an
-// ensemble), and the latch, both for checked arguments, B > 0, on the current device
+                                           const int32_t* nsub, double* samples, double* bins, int32_t* dropped, void* stream);
+// admpc_quad_learn.hip: the bin launch of an observation alone (the second of the two above, without an ensemble), and the latch, which
+// admpc_quad_targets.hip launches too, both for checked arguments, B > 0, on the current device
 ADMPC_HIDDEN int admpc_quad_bin_launch(const AdmpcQuadObserveParams* obs, int B, const double* samples, double* bins, int32_t* dropped, void* stream);
 ADMPC_HIDDEN int admpc_quad_latch_launch(int B, const double* x, double* prev, void* stream);
 // admpc_quad_ensemble.hip: the handles of an ensemble (returns K); what admpc_quad_clusters.hip and admpc_quad_hyper.hip need of one (its

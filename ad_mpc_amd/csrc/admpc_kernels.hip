@@ -545,6 +545,20 @@ extern "C" {
 const char* admpc_last_error(void) { return g_err.c_str(); }
 // for the other translation units of the library (admpc_quad.hip)
 int admpc_set_error(int code, const char* msg) { return fail(code, msg ? msg : ""); }
+// a refusal of the entry point `who`
+int admpc_refuse(const char* who, const char* what)
+{
+    char msg[220];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return fail(ADMPC_EINVAL, msg);
+}
+// for the entry points that take a device and no handle
+int admpc_device_check(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(ADMPC_ENODEV, "no such device");
+    return ADMPC_OK;
+}
 const char* admpc_version(void) { return "admpc-mi355x 0.1 (gfx950)"; }
 // for the control step (admpc_step.hip): the problem a handle solves and the device it lives on
 const AdmpcConfig* admpc_solver_config(const AdmpcSolver* s, int* device)

@@ -267,13 +267,6 @@ __global__ __launch_bounds__(64) void admpc_quad_centroids_set_kernel(int n, con
 
 namespace {
 
-int refuse(const char* who, const char* what)
-{
-    char msg[220];
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return admpc_set_error(ADMPC_EINVAL, msg);
-}
-
 int launched(const char* kernel)
 {
     if (hipGetLastError() == hipSuccess) return ADMPC_OK;
@@ -311,10 +304,10 @@ int admpc_quad_ensemble_rollout_log_batch(AdmpcQuadEnsemble* e, const AdmpcQuadT
 {
     const char* who = "admpc_quad_ensemble_rollout_batch";                  // the refusals it shares are under that entry's name
     (void)samples;
-    if (!e) return refuse(who, "null ensemble");
+    if (!e) return admpc_refuse(who, "null ensemble");
     QuadEnsembleView v;
     admpc_quad_ensemble_view(e, &v);
-    if (model && !v.learns) return refuse(who, "the ensemble was created without observe parameters");
+    if (model && !v.learns) return admpc_refuse(who, "the ensemble was created without observe parameters");
     if (noise) {
         int rc = admpc_quad_plant_params_check("admpc_quad_rollout_noise_batch", plant);
         if (!rc) rc = admpc_quad_noise_params_check("admpc_quad_rollout_noise_batch", noise, plant);
@@ -326,12 +319,12 @@ int admpc_quad_ensemble_rollout_log_batch(AdmpcQuadEnsemble* e, const AdmpcQuadT
                                 noise, noise ? noise_step : nullptr, e, route, route_out };
     if (!model) {
         const int rc = admpc_quad_rollout_check(a, T);
-        return rc ? rc : refuse("admpc_quad_ensemble_rollout_log_batch", "null model: logging implies observing");
+        return rc ? rc : admpc_refuse("admpc_quad_ensemble_rollout_log_batch", "null model: logging implies observing");
     }
     // the observed run's refusals with prev standing in for a log that is not there, which is refused behind them
     const int rc = admpc_quad_rollout_observe_check(a, T, model, v.obs, prev, log ? log : prev, bins, dropped);
     if (rc || B == 0 || T == 0) return rc;
-    if (!log) return refuse("admpc_quad_ensemble_rollout_log_batch", "null log");
+    if (!log) return admpc_refuse("admpc_quad_ensemble_rollout_log_batch", "null log");
     return admpc_quad_rollout_observe_run(a, T, traj_out, u_out, model, v.obs, prev, log, (long long)B * QREC, bins, dropped, stream);
 }
 
@@ -340,18 +333,18 @@ int admpc_quad_clusters_fit(const AdmpcQuadEnsemble* e, int max_iter, double tol
                             void* stream)
 {
     const char* who = "admpc_quad_clusters_fit";
-    if (!e) return refuse(who, "null ensemble");
+    if (!e) return admpc_refuse(who, "null ensemble");
     QuadEnsembleView v;
     admpc_quad_ensemble_view(e, &v);
     for (int j = 0; j < v.n_feat; ++j)
-        if (v.feat[j] < FEAT_LO) return refuse(who, "the clustering features must lie in [7, 16]: the sample record holds no others");
-    if (max_iter < 1 || max_iter > 1000) return refuse(who, "max_iter must be in [1, 1000]");
-    if (!(tol >= 0.0)) return refuse(who, "tol must not be negative");
-    if (!(reg_covar >= 0.0) || !isfinite(reg_covar)) return refuse(who, "reg_covar must be finite and not negative");
-    if (resume != 0 && resume != 1) return refuse(who, "resume must be 0 or 1");
-    if (M < 0) return refuse(who, "negative number of records");
+        if (v.feat[j] < FEAT_LO) return admpc_refuse(who, "the clustering features must lie in [7, 16]: the sample record holds no others");
+    if (max_iter < 1 || max_iter > 1000) return admpc_refuse(who, "max_iter must be in [1, 1000]");
+    if (!(tol >= 0.0)) return admpc_refuse(who, "tol must not be negative");
+    if (!(reg_covar >= 0.0) || !isfinite(reg_covar)) return admpc_refuse(who, "reg_covar must be finite and not negative");
+    if (resume != 0 && resume != 1) return admpc_refuse(who, "resume must be 0 or 1");
+    if (M < 0) return admpc_refuse(who, "negative number of records");
     if (M == 0) return ADMPC_OK;
-    if (!records || !packed || !partial || !gmm || !info) return refuse(who, "null array argument");
+    if (!records || !packed || !partial || !gmm || !info) return admpc_refuse(who, "null array argument");
     DeviceGuard guard(v.device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
@@ -382,8 +375,8 @@ int admpc_quad_clusters_fit(const AdmpcQuadEnsemble* e, int max_iter, double tol
 int admpc_quad_clusters_install(AdmpcQuadEnsemble* e, const double* gmm, const int32_t* info, int32_t* perm, int32_t* installed, void* stream)
 {
     const char* who = "admpc_quad_clusters_install";
-    if (!e) return refuse(who, "null ensemble");
-    if (!gmm || !info || !perm || !installed) return refuse(who, "null array argument");
+    if (!e) return admpc_refuse(who, "null ensemble");
+    if (!gmm || !info || !perm || !installed) return admpc_refuse(who, "null array argument");
     QuadEnsembleView v;
     admpc_quad_ensemble_view(e, &v);
     DeviceGuard guard(v.device);
@@ -395,8 +388,8 @@ int admpc_quad_clusters_install(AdmpcQuadEnsemble* e, const double* gmm, const i
 int admpc_quad_ensemble_centroids_set(AdmpcQuadEnsemble* e, const double* centroids, int32_t* installed, void* stream)
 {
     const char* who = "admpc_quad_ensemble_centroids_set";
-    if (!e) return refuse(who, "null ensemble");
-    if (!centroids || !installed) return refuse(who, "null array argument");
+    if (!e) return admpc_refuse(who, "null ensemble");
+    if (!centroids || !installed) return admpc_refuse(who, "null array argument");
     QuadEnsembleView v;
     admpc_quad_ensemble_view(e, &v);
     DeviceGuard guard(v.device);
@@ -408,8 +401,8 @@ int admpc_quad_ensemble_centroids_set(AdmpcQuadEnsemble* e, const double* centro
 int admpc_quad_ensemble_centroids_get(const AdmpcQuadEnsemble* e, double* centroids, void* stream)
 {
     const char* who = "admpc_quad_ensemble_centroids_get";
-    if (!e) return refuse(who, "null ensemble");
-    if (!centroids) return refuse(who, "null array argument");
+    if (!e) return admpc_refuse(who, "null ensemble");
+    if (!centroids) return admpc_refuse(who, "null array argument");
     QuadEnsembleView v;
     admpc_quad_ensemble_view(e, &v);
     DeviceGuard guard(v.device);
@@ -422,13 +415,13 @@ int admpc_quad_ensemble_centroids_get(const AdmpcQuadEnsemble* e, double* centro
 int admpc_quad_clusters_rebin(const AdmpcQuadEnsemble* e, int steps, int B, const double* log, double* bins, int32_t* dropped, void* stream)
 {
     const char* who = "admpc_quad_clusters_rebin";
-    if (!e) return refuse(who, "null ensemble");
+    if (!e) return admpc_refuse(who, "null ensemble");
     QuadEnsembleView v;
     admpc_quad_ensemble_view(e, &v);
-    if (!v.learns) return refuse(who, "the ensemble was created without observe parameters");
-    if (steps < 0 || B < 0) return refuse(who, "negative steps or batch");
+    if (!v.learns) return admpc_refuse(who, "the ensemble was created without observe parameters");
+    if (steps < 0 || B < 0) return admpc_refuse(who, "negative steps or batch");
     if (steps == 0 || B == 0) return ADMPC_OK;
-    if (!log || !bins || !dropped) return refuse(who, "null array argument");
+    if (!log || !bins || !dropped) return admpc_refuse(who, "null array argument");
     DeviceGuard guard(v.device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     int rc = ADMPC_OK;

@@ -12,7 +12,6 @@
 // admpc_quad_learn.hip's: their argument block carries the ensemble, and they call the two launches below.  The observe kernel, the fit and
 // the install are those units' own, per cluster.  The search of the hyperparameters of all clusters is admpc_quad_hyper.hip's, which
 // reaches the object through admpc_quad_ensemble_view and keeps its search descriptors in the object's `search` slot.
-#include <stdio.h>
 #include <math.h>
 #include <new>
 #include "admpc_host.h"
@@ -102,13 +101,6 @@ __global__ __launch_bounds__(WAVE) void admpc_quad_ensemble_bin_kernel(const Ens
 
 namespace {
 
-int refuse(const char* who, const char* what)
-{
-    char msg[220];
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return admpc_set_error(ADMPC_EINVAL, msg);
-}
-
 bool same_structure(const AdmpcQuadObserveParams& a, const AdmpcQuadObserveParams& b)
 {
     if (a.dt != b.dt || a.substeps != b.substeps || a.n_gp != b.n_gp) return false;
@@ -165,37 +157,37 @@ int admpc_quad_ensemble_create(AdmpcQuadSolver* const* solvers, int K, int n_fea
                                const AdmpcQuadObserveParams* obs, AdmpcQuadEnsemble** out)
 {
     const char* who = "admpc_quad_ensemble_create";
-    if (!solvers || !feats || !centroids || !out) return refuse(who, "null argument");
-    if (K < 1 || K > KMAX) return refuse(who, "K must be in [1, 8]");
-    for (int c = 0; c < K; ++c) if (!solvers[c]) return refuse(who, "null solver");
+    if (!solvers || !feats || !centroids || !out) return admpc_refuse(who, "null argument");
+    if (K < 1 || K > KMAX) return admpc_refuse(who, "K must be in [1, 8]");
+    for (int c = 0; c < K; ++c) if (!solvers[c]) return admpc_refuse(who, "null solver");
     int device = 0, N = 0;
     (void)admpc_quad_solver_info(solvers[0], &device, &N, nullptr);
     for (int c = 1; c < K; ++c) {
         int dv = 0, n = 0;
         (void)admpc_quad_solver_info(solvers[c], &dv, &n, nullptr);
-        if (dv != device || n != N) return refuse(who, "the cluster solvers must share device and horizon");
+        if (dv != device || n != N) return admpc_refuse(who, "the cluster solvers must share device and horizon");
     }
     for (int c = 0; c < K; ++c) {
         int sqp = 0;
         (void)admpc_quad_solver_info(solvers[c], nullptr, nullptr, &sqp);
-        if (sqp > 1) return refuse(who, "a solver in SQP mode (sqp_iters > 1) is not served: the rollout is the RTI loop");
+        if (sqp > 1) return admpc_refuse(who, "a solver in SQP mode (sqp_iters > 1) is not served: the rollout is the RTI loop");
     }
-    if (n_feat < 1 || n_feat > ADMPC_GP_MAX_FEAT) return refuse(who, "n_feat must be in [1, 3]");
-    for (int j = 0; j < n_feat; ++j) if (feats[j] < 0 || feats[j] >= QY) return refuse(who, "feature index outside z = [x; u]");
-    for (int i = 0; i < K * n_feat; ++i) if (!isfinite(centroids[i])) return refuse(who, "a centroid is not finite");
+    if (n_feat < 1 || n_feat > ADMPC_GP_MAX_FEAT) return admpc_refuse(who, "n_feat must be in [1, 3]");
+    for (int j = 0; j < n_feat; ++j) if (feats[j] < 0 || feats[j] >= QY) return admpc_refuse(who, "feature index outside z = [x; u]");
+    for (int i = 0; i < K * n_feat; ++i) if (!isfinite(centroids[i])) return admpc_refuse(who, "a centroid is not finite");
     if (obs) {
         for (int c = 0; c < K; ++c) {
             const int rc = admpc_quad_observe_params_check(who, obs + c);
             if (rc) return rc;
         }
         for (int c = 1; c < K; ++c)
-            if (!same_structure(obs[0], obs[c])) return refuse(who, "the observe parameters of the clusters must share dt, substeps, n_gp and every regressor's n_feat, feat and out");
+            if (!same_structure(obs[0], obs[c])) return admpc_refuse(who, "the observe parameters of the clusters must share dt, substeps, n_gp and every regressor's n_feat, feat and out");
         for (int j = 0; j < n_feat; ++j)
-            if (feats[j] < QUAD_LEARN.feat_lo) return refuse(who, "an ensemble that learns clusters on features in [7, 16]: the sample record holds no others");
+            if (feats[j] < QUAD_LEARN.feat_lo) return admpc_refuse(who, "an ensemble that learns clusters on features in [7, 16]: the sample record holds no others");
         for (int c = 0; c < K; ++c) {
             int have = 0;
             (void)admpc_quad_solver_config_device(solvers[c], &have);
-            if (have != obs[0].n_gp) return refuse(who, "a handle's n_gp is not the observe parameters' n_gp (create it with placeholder GPs of n_points = 0)");
+            if (have != obs[0].n_gp) return admpc_refuse(who, "a handle's n_gp is not the observe parameters' n_gp (create it with placeholder GPs of n_points = 0)");
         }
     }
     DeviceGuard guard(device);
@@ -240,10 +232,10 @@ void admpc_quad_ensemble_destroy(AdmpcQuadEnsemble* e)
 int admpc_quad_ensemble_route_batch(const AdmpcQuadEnsemble* e, int B, const double* yref, int32_t* route, void* stream)
 {
     const char* who = "admpc_quad_ensemble_route_batch";
-    if (!e) return refuse(who, "null ensemble");
-    if (B < 0) return refuse(who, "negative batch");
+    if (!e) return admpc_refuse(who, "null ensemble");
+    if (B < 0) return admpc_refuse(who, "negative batch");
     if (B == 0) return ADMPC_OK;
-    if (!yref || !route) return refuse(who, "null array argument");
+    if (!yref || !route) return admpc_refuse(who, "null array argument");
     DeviceGuard guard(e->device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     return admpc_quad_ensemble_route_launch(e, B, yref, route, nullptr, stream);
@@ -254,27 +246,27 @@ int admpc_quad_ensemble_observe_batch(const AdmpcQuadEnsemble* e, const AdmpcQua
                                       int32_t* dropped, void* stream)
 {
     const char* who = "admpc_quad_ensemble_observe_batch";
-    if (!e) return refuse(who, "null ensemble");
-    if (!e->learns) return refuse(who, "the ensemble was created without observe parameters");
+    if (!e) return admpc_refuse(who, "null ensemble");
+    if (!e->learns) return admpc_refuse(who, "the ensemble was created without observe parameters");
     const int rc = admpc_quad_plant_params_check(who, plant);
     if (rc) return rc;
-    if (!model) return refuse(who, "null model");
-    if (B < 0) return refuse(who, "negative batch");
+    if (!model) return admpc_refuse(who, "null model");
+    if (B < 0) return admpc_refuse(who, "negative batch");
     if (B == 0) return ADMPC_OK;
-    if (!u || !x || !prev || !samples || !bins || !dropped) return refuse(who, "null array argument");
-    if (u_stride < QU) return refuse(who, "u_stride must be at least 4");
+    if (!u || !x || !prev || !samples || !bins || !dropped) return admpc_refuse(who, "null array argument");
+    if (u_stride < QU) return admpc_refuse(who, "u_stride must be at least 4");
     DeviceGuard guard(e->device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    return admpc_quad_observe_launch(model, plant, &e->obs[0], e, B, u, (long long)u_stride, x, prev, samples, bins, dropped, stream);
+    return admpc_quad_observe_launch(model, plant, &e->obs[0], e, B, u, (long long)u_stride, x, prev, nullptr, samples, bins, dropped, stream);
 }
 
 int admpc_quad_ensemble_fit(const AdmpcQuadEnsemble* e, int min_count, const double* bins, AdmpcGp* gp_out, int32_t* info, void* stream)
 {
     const char* who = "admpc_quad_ensemble_fit";
-    if (!e) return refuse(who, "null ensemble");
-    if (!e->learns) return refuse(who, "the ensemble was created without observe parameters");
-    if (min_count < 1) return refuse(who, "min_count must be at least 1");
-    if (!bins || !gp_out || !info) return refuse(who, "null array argument");
+    if (!e) return admpc_refuse(who, "null ensemble");
+    if (!e->learns) return admpc_refuse(who, "the ensemble was created without observe parameters");
+    if (min_count < 1) return admpc_refuse(who, "min_count must be at least 1");
+    if (!bins || !gp_out || !info) return admpc_refuse(who, "null array argument");
     for (int c = 0; c < e->K; ++c) {
         const int rc = admpc_learn_fit(who, e->device, e->n_gp, e->obs[c].gp, QUAD_LEARN.feat_lo, min_count, bins + (size_t)c * GMAX * NPT * ACC,
                                        gp_out + (size_t)c * GMAX, info + (size_t)c * GMAX, stream);
@@ -286,13 +278,13 @@ int admpc_quad_ensemble_fit(const AdmpcQuadEnsemble* e, int min_count, const dou
 int admpc_quad_ensemble_install(AdmpcQuadEnsemble* e, const AdmpcGp* gp_dev, int32_t* installed, void* stream)
 {
     const char* who = "admpc_quad_ensemble_install";
-    if (!e) return refuse(who, "null ensemble");
+    if (!e) return admpc_refuse(who, "null ensemble");
     int have[KMAX];
     for (int c = 0; c < e->K; ++c) {
         (void)admpc_quad_solver_config_device(e->solvers[c], &have[c]);
-        if (have[c] < 1) return refuse(who, "a handle was created without GPs (create it with placeholder GPs of n_points = 0)");
+        if (have[c] < 1) return admpc_refuse(who, "a handle was created without GPs (create it with placeholder GPs of n_points = 0)");
     }
-    if (!gp_dev || !installed) return refuse(who, "null array argument");
+    if (!gp_dev || !installed) return admpc_refuse(who, "null array argument");
     for (int c = 0; c < e->K; ++c) {
         const int rc = admpc_quad_gp_install(e->solvers[c], have[c], gp_dev + (size_t)c * GMAX, installed + (size_t)c * GMAX, stream);
         if (rc) return rc;
@@ -309,8 +301,8 @@ int admpc_quad_ensemble_rollout_batch(AdmpcQuadEnsemble* e, const AdmpcQuadTrajB
                                       const AdmpcQuadNoiseParams* noise, uint64_t* noise_step, void* stream)
 {
     const char* who = "admpc_quad_ensemble_rollout_batch";
-    if (!e) return refuse(who, "null ensemble");
-    if (model && !e->learns) return refuse(who, "the ensemble was created without observe parameters");
+    if (!e) return admpc_refuse(who, "null ensemble");
+    if (model && !e->learns) return admpc_refuse(who, "the ensemble was created without observe parameters");
     if (noise) {
         int rc = admpc_quad_plant_params_check("admpc_quad_rollout_noise_batch", plant);
         if (!rc) rc = admpc_quad_noise_params_check("admpc_quad_rollout_noise_batch", noise, plant);

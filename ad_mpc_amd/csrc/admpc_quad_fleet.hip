@@ -1,31 +1,23 @@
-// admpc_quad_fleet.hip -- the quadrotor's closed loop on the device (include/admpc_quad_fleet.h): two kernels and their host side.
+// admpc_quad_fleet.hip -- the quadrotor's closed loop on the device (include/admpc_quad_fleet.h): the bank of trajectories, one kernel
+// and the rollout.
 //
 //   admpc_quad_chunk_kernel   the reference window of every vehicle (get_reference_chunk + set_reference_trajectory's padding): a
 //                             gather, one thread per double written, so the 17 doubles of a node row leave contiguous lanes
-//   admpc_quad_plant_kernel   Quadrotor3D.update `substeps` times under one input (quad_3d.py:175-287): substeps x 4 evaluations of the
-//                             simulator's model in a serial chain, ONE lane per vehicle (QP_LANES), everything in registers; behind a step
-//                             of the rollout the same launch does the tally, the counts, the records and the index update
 //
 // The rollout (admpc_quad_rollout_batch) is T times chunk -> admpc_quad_solve_batch_ex -> plant on one stream; with a clustered ensemble in
-// its argument block (admpc_quad_ensemble.hip) the solve is route -> admpc_quad_solve_batch_routed.  The simulator's device
-// text is quad_sim_dev.h, which admpc_quad_noise.hip includes too; a rollout whose argument block carries disturbances launches that
-// unit's plant kernel in every period.
-#include <stdio.h>
+// its argument block (admpc_quad_ensemble.hip) the solve is route -> admpc_quad_solve_batch_routed.  The plant kernels and their launch
+// are admpc_quad_plant.hip's: a rollout whose argument block carries disturbances gets the noisy kernel in every period.
 #include <math.h>
 #include <new>
 #include "admpc_host.h"
 #include "../../include/admpc_quad_fleet.h"
-#include "quad_sim_dev.h"     // QuadTrajDesc, QuadPlantArgs, the simulator's device text
+#include "quad_sim_dev.h"     // QuadTrajDesc, QuadPlantArgs
 
 #define QX ADMPC_QUAD_NX
 #define QU ADMPC_QUAD_NU
 #define QY ADMPC_QUAD_NY
-#define WAVE 64
-#define QP_LANES 1             // lanes per vehicle of the plant kernel; four (a lane per state group) measured 1.40 times slower: profiles/HISTORY.md
-#define QP_GRID 4096           // blocks of the plant kernel at most (the cap of admpc_plant_kernel); more vehicles go round the stride loop
 #define QC_THREADS 256
 #define QC_GRID 4096           // blocks of the chunk kernel at most
-static_assert(QP_LANES == 1, "admpc_quad_plant_kernel maps one lane to one vehicle");
 
 struct AdmpcQuadTrajBank {
     int device, K;
@@ -34,49 +26,6 @@ struct AdmpcQuadTrajBank {
     const QuadTrajDesc* d_desc;
     const double *d_X, *d_U;
 };
-
-__global__ __launch_bounds__(WAVE) void admpc_quad_plant_kernel(const QuadPlantArgs a)
-{
-    const SimConst c = sim_const(a.p);
-    for (long long b = (long long)blockIdx.x * WAVE + threadIdx.x; b < a.B; b += (long long)gridDim.x * WAVE) {
-        double x[QX];
-        double* xb = a.x + b * QX;
-#pragma unroll
-        for (int i = 0; i < QX; ++i) x[i] = xb[i];
-        const double* ub = a.u + b * a.u_stride;
-        double f[QU];
-        bool replaced = false;
-#pragma unroll
-        for (int m = 0; m < QU; ++m) {
-            const double raw = ub[m];
-            if (a.u_out) a.u_out[b * QU + m] = raw;
-            double v = raw < c.u_max ? raw : c.u_max;        // max(min(u, u_max), u_min)
-            v = v > c.u_min ? v : c.u_min;
-            if (!isfinite(raw)) { v = c.u_min; replaced = true; }
-            f[m] = v * c.max_thrust;
-        }
-        if (a.tally) quad_tally(a, b, x, replaced);          // the error at the START of the step
-        if (a.traj_pre) {
-#pragma unroll
-            for (int i = 0; i < QX; ++i) a.traj_pre[b * QX + i] = x[i];
-        }
-        const Thrust th = quad_thrust(c, f);
-        for (int m = 0; m < a.p.substeps; ++m) quad_sim_update<false>(c, th, x);
-#pragma unroll
-        for (int i = 0; i < QX; ++i) xb[i] = x[i];
-        if (a.traj_post) {
-#pragma unroll
-            for (int i = 0; i < QX; ++i) a.traj_post[b * QX + i] = x[i];
-        }
-        if (a.idx) {                                          // idx <- min(idx + 1, M - 1) where the vehicle has a window
-            const int k = a.traj_of[b];
-            if (k >= 0 && k < a.K) {
-                const int M = a.desc[k].M, i = a.idx[b];
-                if (i >= 0 && i < M) a.idx[b] = i + 1 < M ? i + 1 : M - 1;
-            }
-        }
-    }
-}
 
 __global__ __launch_bounds__(QC_THREADS) void admpc_quad_chunk_kernel(const QuadTrajDesc* __restrict__ desc, const double* __restrict__ X,
                                                                        const double* __restrict__ U, int K, int B, int N, int over,
@@ -125,21 +74,6 @@ __global__ __launch_bounds__(QC_THREADS) void admpc_quad_chunk_kernel(const Quad
 
 namespace {
 
-int plant_params_check(const char* who, const AdmpcQuadPlantParams* p)
-{
-    char msg[160];
-    const char* what = nullptr;
-    if (!p) what = "the plant parameters are not set";
-    else if (!(p->dt > 0) || !isfinite(p->dt)) what = "dt must be positive and finite";
-    else if (p->substeps < 1 || p->substeps > 1024) what = "substeps must be in [1, 1024]";
-    else if (!(p->mass > 0) || !(p->J[0] > 0 && p->J[1] > 0 && p->J[2] > 0)) what = "mass and J must be positive";
-    else if (!(p->u_min <= p->u_max) || !isfinite(p->u_min) || !isfinite(p->u_max)) what = "u_min <= u_max, both finite, required";
-    else if (p->drag != 0 && p->drag != 1) what = "drag must be 0 or 1";
-    if (!what) return ADMPC_OK;
-    snprintf(msg, sizeof msg, "%s: %s", who, what);
-    return admpc_set_error(ADMPC_EINVAL, msg);
-}
-
 // one launch of the chunk kernel for checked arguments, B > 0, on the bank's device (the caller holds it)
 int chunk_launch(const AdmpcQuadTrajBank* bank, int B, int N, int over, const int32_t* traj_of, const int32_t* idx, double* yref,
                  double* yref_e, double* pos_ref, hipStream_t st)
@@ -153,48 +87,9 @@ int chunk_launch(const AdmpcQuadTrajBank* bank, int B, int N, int over, const in
     return ADMPC_OK;
 }
 
-// one launch of the plant kernel for filled arguments, B > 0
-int plant_launch(const QuadPlantArgs& a, hipStream_t st)
-{
-    const int nblk = (a.B + WAVE - 1) / WAVE;
-    const int grid = nblk < QP_GRID ? nblk : QP_GRID;
-    hipLaunchKernelGGL(admpc_quad_plant_kernel, dim3((unsigned)grid), dim3(WAVE), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "admpc_quad_plant_kernel: launch failed");
-    return ADMPC_OK;
-}
-
-QuadPlantArgs plant_only(const AdmpcQuadPlantParams* plant, int B, const double* u, long long u_stride, double* x)
-{
-    QuadPlantArgs a;
-    a.p = *plant; a.B = B; a.K = 0;
-    a.u = u; a.u_stride = u_stride; a.x = x;
-    a.yref = nullptr; a.yref_stride = 0; a.status = nullptr; a.tally = nullptr; a.counts = nullptr;
-    a.traj_of = nullptr; a.idx = nullptr; a.desc = nullptr; a.traj_pre = a.traj_post = nullptr; a.u_out = nullptr;
-    return a;
-}
-
 }  // namespace
 
-// for admpc_quad_learn.hip: the refusals of the plant parameters
-extern "C" int admpc_quad_plant_params_check(const char* who, const AdmpcQuadPlantParams* plant) { return plant_params_check(who, plant); }
-
 extern "C" {
-
-int admpc_quad_plant_step_batch(const AdmpcQuadPlantParams* plant, int device, int B, const double* u, int64_t u_stride, double* x,
-                                void* stream)
-{
-    const int rc = plant_params_check("admpc_quad_plant_step_batch", plant);
-    if (rc) return rc;
-    if (B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_plant_step_batch: negative batch");
-    if (B == 0) return ADMPC_OK;
-    if (!u || !x) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_plant_step_batch: null array argument");
-    if (u_stride < QU) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_plant_step_batch: u_stride must be at least 4");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return admpc_set_error(ADMPC_ENODEV, "no such device");
-    DeviceGuard guard(device);
-    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    return plant_launch(plant_only(plant, B, u, (long long)u_stride, x), (hipStream_t)stream);
-}
 
 int admpc_quad_traj_bank_create(int device, int K, const int32_t* M, const double* const* traj, const double* const* u,
                                 AdmpcQuadTrajBank** bank)
@@ -271,7 +166,7 @@ int admpc_quad_rollout_check(const QuadRolloutArgs& a, int T)
     if (sqp > 1) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: a solver in SQP mode (sqp_iters > 1) is not served: the rollout is the RTI loop");
     if (!a.bank) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: null bank");
     if (a.bank->device != device) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: the bank is on another device than the solver");
-    const int rc = plant_params_check("admpc_quad_rollout_batch", a.plant);
+    const int rc = admpc_quad_plant_params_check("admpc_quad_rollout_batch", a.plant);
     if (rc) return rc;
     if (a.over < 1) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: over must be at least 1");
     if (a.B < 0) return admpc_set_error(ADMPC_EINVAL, "admpc_quad_rollout_batch: negative batch");
@@ -296,16 +191,17 @@ int admpc_quad_rollout_enqueue(const QuadRolloutArgs& r, double* traj_pre, doubl
     }
     else if (!rc) rc = admpc_quad_solve_batch_ex(r.s, r.B, r.x, r.yref, r.yref_e, nullptr, r.xbar, r.ubar, r.cost, r.status, r.iters, stream);
     if (rc) return rc;
-    QuadPlantArgs a = plant_only(r.plant, r.B, r.ubar, (long long)N * QU, r.x);
+    QuadPlantArgs a;
+    admpc_quad_plant_fill(a, r.plant, r.B, r.ubar, (long long)N * QU, r.x);
     a.K = r.bank->K; a.desc = r.bank->d_desc;
     a.yref = r.yref; a.yref_stride = (long long)N * QY; a.status = r.status; a.tally = r.tally; a.counts = r.counts;
     a.traj_of = r.traj_of; a.idx = r.idx;
     a.traj_pre = traj_pre; a.traj_post = traj_post; a.u_out = u_out;
-    return r.noise ? admpc_quad_plant_noise_launch(a, r.noise, r.noise_step, stream) : plant_launch(a, (hipStream_t)stream);
+    return admpc_quad_plant_launch(a, r.noise, r.noise_step, nullptr, stream);
 }
 
 // admpc_quad_rollout_batch behind its arguments' block: the refusals, the no-ops and the T periods; with a.noise the plant of every
-// period is the noisy one (admpc_quad_noise.hip), whose counter array is refused last
+// period is the noisy one, whose counter array is refused last
 int admpc_quad_rollout_run(const QuadRolloutArgs& a, int T, double* traj_out, double* u_out, void* stream)
 {
     int rc = admpc_quad_rollout_check(a, T);
@@ -318,10 +214,10 @@ int admpc_quad_rollout_run(const QuadRolloutArgs& a, int T, double* traj_out, do
     (void)admpc_quad_solver_info(a.s, &device, nullptr, nullptr);
     DeviceGuard guard(device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
-    // slot 0 of traj_out is written by the first period; every period writes the state it leaves into the next slot
-    for (int t = 0; t < T && !rc; ++t)
-        rc = admpc_quad_rollout_enqueue(a, t == 0 ? traj_out : nullptr, traj_out ? traj_out + (size_t)(t + 1) * a.B * QX : nullptr,
-                                        u_out ? u_out + (size_t)t * a.B * QU : nullptr, a.route_out ? a.route_out + (size_t)t * a.B : nullptr, stream);
+    for (int t = 0; t < T && !rc; ++t) {
+        const QuadRecordSlots rec = admpc_quad_record_slots(traj_out, u_out, a.B, t);
+        rc = admpc_quad_rollout_enqueue(a, rec.traj_pre, rec.traj_post, rec.u_out, a.route_out ? a.route_out + (size_t)t * a.B : nullptr, stream);
+    }
     return rc;
 }
 

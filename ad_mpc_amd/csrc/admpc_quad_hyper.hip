@@ -19,7 +19,6 @@
 //
 // No atomics, no grid that depends on data.  Regressor (c, g) lives at the flat index c * 3 + g of every array; the entries of a regressor
 // past n_gp are not touched.
-#include <stdio.h>
 #include <math.h>
 #include "admpc_host.h"
 #include "../../include/admpc_quad_hyper.h"
@@ -106,14 +105,12 @@ __global__ __launch_bounds__(WAVE) void admpc_quad_ensemble_refit_kernel(const E
 
 namespace {
 
-int refuse(const char* who, const char* what) { return admpc_learn_refuse(who, what); }
-
 // the first refusals of the three ensemble entries, and the view of a checked ensemble
 int ensemble_check(const char* who, const AdmpcQuadEnsemble* e, QuadEnsembleView& v)
 {
-    if (!e) return refuse(who, "null ensemble");
+    if (!e) return admpc_refuse(who, "null ensemble");
     admpc_quad_ensemble_view(e, &v);
-    if (!v.learns) return refuse(who, "the ensemble was created without observe parameters");
+    if (!v.learns) return admpc_refuse(who, "the ensemble was created without observe parameters");
     return ADMPC_OK;
 }
 
@@ -143,7 +140,7 @@ int admpc_quad_ensemble_set_search(AdmpcQuadEnsemble* e, const AdmpcGpSearchPara
     QuadEnsembleView v;
     int rc = ensemble_check(who, e, v);
     if (rc) return rc;
-    if (!sp) return refuse(who, "the search parameters are not set");
+    if (!sp) return admpc_refuse(who, "the search parameters are not set");
     EnsembleSearchDev host = EnsembleSearchDev();
     int cmax = 1;
     for (int c = 0; c < v.K; ++c) {
@@ -154,7 +151,7 @@ int admpc_quad_ensemble_set_search(AdmpcQuadEnsemble* e, const AdmpcGpSearchPara
     }
     for (int c = 1; c < v.K; ++c)
         if (sp[c].grid != sp[0].grid || sp[c].rounds != sp[0].rounds || sp[c].shrink != sp[0].shrink)
-            return refuse(who, "the search parameters of the clusters must share grid, rounds and shrink (the boxes are free per cluster)");
+            return admpc_refuse(who, "the search parameters of the clusters must share grid, rounds and shrink (the boxes are free per cluster)");
     host.grid = sp[0].grid; host.half = (sp[0].grid - 1) / 2; host.shrink = sp[0].shrink;
     DeviceGuard guard(v.device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
@@ -177,10 +174,10 @@ int admpc_quad_ensemble_search(const AdmpcQuadEnsemble* e, int min_count, int re
     QuadEnsembleView v;
     const int rc = ensemble_check(who, e, v);
     if (rc) return rc;
-    if (!v.search->set) return refuse(who, "no search parameters yet: call admpc_quad_ensemble_set_search first");
-    if (min_count < 1) return refuse(who, "min_count must be at least 1");
-    if (resume != 0 && resume != 1) return refuse(who, "resume must be 0 or 1");
-    if (!bins || !hyper || !nll || !search_info) return refuse(who, "null array argument");
+    if (!v.search->set) return admpc_refuse(who, "no search parameters yet: call admpc_quad_ensemble_set_search first");
+    if (min_count < 1) return admpc_refuse(who, "min_count must be at least 1");
+    if (resume != 0 && resume != 1) return admpc_refuse(who, "resume must be 0 or 1");
+    if (!bins || !hyper || !nll || !search_info) return admpc_refuse(who, "null array argument");
     DeviceGuard guard(v.device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     EnsembleSearchArgs a = EnsembleSearchArgs();
@@ -208,8 +205,8 @@ int admpc_quad_ensemble_refit(const AdmpcQuadEnsemble* e, int min_count, const d
     QuadEnsembleView v;
     const int rc = ensemble_check(who, e, v);
     if (rc) return rc;
-    if (min_count < 1) return refuse(who, "min_count must be at least 1");
-    if (!bins || !hyper || !gp_out || !info) return refuse(who, "null array argument");
+    if (min_count < 1) return admpc_refuse(who, "min_count must be at least 1");
+    if (!bins || !hyper || !gp_out || !info) return admpc_refuse(who, "null array argument");
     DeviceGuard guard(v.device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     EnsembleSearchArgs a = EnsembleSearchArgs();

@@ -1,6 +1,6 @@
-// quad_noise_dev.h -- the counter-based generator of include/admpc_quad_noise.h as device text, for admpc_quad_noise.hip (the
-// disturbances of a sub-step) and admpc_quad_targets.hip (the same disturbances in the target-chasing plant kernel, and the uniforms of a
-// new target, which take the generator's calls at the far end of the fourth counter word).  Include INSIDE the translation unit's
+// quad_noise_dev.h -- the counter-based generator of include/admpc_quad_noise.h as device text, for admpc_quad_plant.hip (the
+// disturbances of a sub-step), admpc_quad_noise.hip (the same draws for the host) and quad_target_dev.h (the uniforms of a new target,
+// which take the generator's calls at the far end of the fourth counter word).  Include INSIDE the translation unit's
 // anonymous namespace; every function is __forceinline__.
 #pragma once
 

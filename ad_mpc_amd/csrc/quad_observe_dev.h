@@ -1,5 +1,5 @@
-// quad_observe_dev.h -- what the observe kernel of admpc_quad_learn.hip and the observe kernel with a period per vehicle of
-// admpc_quad_targets.hip share: the model's prediction of a flown period and the body-frame map.  Include INSIDE the translation unit's
+// quad_observe_dev.h -- what the observe kernel of admpc_quad_learn.hip is made of: the model's prediction of a flown period and the
+// body-frame map.  Include INSIDE the translation unit's
 // anonymous namespace, behind quad_model_dev.h; every function is __forceinline__.
 #pragma once
 

@@ -1,6 +1,6 @@
-// quad_sim_dev.h -- the device text of the quadrotor's simplified simulator (Quadrotor3D.update, quad_3d.py:175-287) that the plant kernel
-// of admpc_quad_fleet.hip, the noisy plant kernel of admpc_quad_noise.hip and the plant-target kernel of admpc_quad_targets.hip share: the argument block of a plant launch, the vehicle's
-// constants in vector registers, the derivative, one RK4 update, and the rollout's tally.  Everything is static and inlined: each unit
+// quad_sim_dev.h -- the device text of the quadrotor's simplified simulator (Quadrotor3D.update, quad_3d.py:175-287) that the two plant
+// kernels of admpc_quad_plant.hip share, and whose argument block the rollouts of admpc_quad_fleet.hip and admpc_quad_targets.hip fill: the
+// argument block of a plant launch, the vehicle's constants in vector registers, the derivative, one RK4 update, and the rollout's tally.  Everything is static and inlined: each unit
 // has its own copy, and the deterministic instantiation (DIST = false) carries no term of the disturbances.
 #pragma once
 #include <math.h>

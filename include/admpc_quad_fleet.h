@@ -1,5 +1,5 @@
 /*
- * admpc_quad_fleet.h -- the quadrotor's closed loop on the device (libadmpc.so; csrc/admpc_quad_fleet.hip): the simplified simulator as a
+ * admpc_quad_fleet.h -- the quadrotor's closed loop on the device (libadmpc.so; csrc/admpc_quad_fleet.hip, the plant step csrc/admpc_quad_plant.hip): the simplified simulator as a
  * PLANT step, a bank of over-sampled reference trajectories, the reference window of every vehicle, and T closed-loop steps of
  * window -> RTI step -> plant per call, with a tally of the tracking error.  An addition to admpc_quad.h, whose conventions hold here:
  * device pointers owned by the caller, instance-major and dense, fp64; `stream` a hipStream_t passed as void*; 0 or a negative ADMPC_E*

@@ -1,5 +1,5 @@
 /*
- * admpc_quad_noise.h -- the simulator's random disturbances on the device (libadmpc.so; csrc/admpc_quad_noise.hip): the plant step and
+ * admpc_quad_noise.h -- the simulator's random disturbances on the device (libadmpc.so; csrc/admpc_quad_noise.hip, the plant step csrc/admpc_quad_plant.hip): the plant step and
  * the closed-loop rollout of admpc_quad_fleet.h / admpc_quad_learn.h under `noisy` (a normal force and torque per sub-step) and
  * `motor_noise` (a normal error per rotor and sub-step), the reference's default data-collection set-up
  * (utils/configuration_parameters.py:47-50).  An addition to admpc_quad_fleet.h, whose conventions hold here: device pointers owned by

@@ -1,5 +1,5 @@
 /*
- * admpc_quad_targets.h -- flying to random target points and recording, on the device (libadmpc.so; csrc/admpc_quad_targets.hip): a
+ * admpc_quad_targets.h -- flying to random target points and recording, on the device (libadmpc.so; csrc/admpc_quad_targets.hip, the plant step csrc/admpc_quad_plant.hip, the observation csrc/admpc_quad_learn.hip): a
  * point reference for every vehicle, the reach test after every simulator sub-step, the sampling of the next target, the recovery of a
  * vehicle that has run away, and an observation whose period is the time a vehicle really flew.  An addition to admpc_quad_fleet.h,
  * admpc_quad_learn.h and admpc_quad_noise.h, whose conventions hold here: device pointers owned by the caller, fp64; `stream` a
@@ -77,8 +77,8 @@
  * n_iter and tcounts changes any more; fast and noise_step are still written.  The reference's loop ends there.
  *
  * Measured on one MI355X at B = 4096, drag on, the target flight and the flight along a circle alternating (scripts/quad_targets_time.py;
- * DESIGN section 7, profiles/HISTORY.md): by kernel trace over the periods of N = 10 and N = 20 the plant-target kernel takes 57.0 us
- * against 52.0 us of admpc_quad_plant_kernel, under the disturbances 120.3 against 113.4 us of admpc_quad_plant_noise_kernel, the window
+ * DESIGN section 7, profiles/HISTORY.md): by kernel trace over the periods of N = 10 and N = 20 the plant kernel towards targets takes 57.0 us
+ * against 52.0 us of admpc_quad_plant_kernel, under the disturbances 120.3 against 113.4 us of the noisy plant kernel, the window
  * kernel 11.1 us against 8.3 us of the chunk kernel.  A closed-loop period of the target flight takes 1217 against 453 us at N = 10 and
  * 2903 against 1442 us at N = 20 (under the disturbances 844 against 533 and 2947 against 1487): the difference is the RTI step's, whose
  * interior point takes 8.9 to 9.3 iterations on average towards a point 1.5 to 4.5 m away, with the inputs at their bounds, and 3.0 along
@@ -135,14 +135,14 @@ int admpc_quad_target_window_batch(const AdmpcQuadTargetParams* tp, int device, 
                                    const uint64_t* target_no, int32_t* n_iter, const int32_t* fast, int32_t* tcounts, double* prev,
                                    double* yref, double* yref_e, void* stream);
 
-/* One period of the simulator towards the targets, one launch (admpc_quad_plant_target_kernel): per vehicle, in this order
+/* One period of the simulator towards the targets, one launch (admpc_quad_plant_period_kernel<NOISY, L, true>): per vehicle, in this order
  *   fast[b] from x[b]; the clip of the activations and `replaced` (rule 1 of admpc_quad_plant_step_batch); up to plant->substeps sub-steps
  *   of admpc_quad_plant_step_batch -- with `noise`, of admpc_quad_plant_step_noise_batch under the numbers that header gives (b,
  *   noise_step[b], sub-step m) -- with the reach test behind each; x[b] and nsub[b] written; then, unless the vehicle is DONE,
  *   tcounts[b][2] += 1, tcounts[b][3] += 1 where status is given and status[b] != 0, tcounts[b][4] += 1 where an activation was replaced,
  *   and at a reach target_no, tcounts[b][0] and the next target; n_iter by its rule; noise_step[b] += 1 whatever nsub[b] is.
  * noise and noise_step may be NULL: the deterministic simulator.  The noisy form gives a vehicle four lanes up to 8192 vehicles, which
- * share out the generator's calls through LDS as admpc_quad_plant_noise_kernel does; a vehicle that has reached keeps meeting the
+ * share out the generator's calls through LDS as the noisy plant step does (the same kernel text without the targets); a vehicle that has reached keeps meeting the
  * barriers and only skips the integration.  The mapping changes no result.
  * u [B] rows of 4, row b at u + b * u_stride; x [B][13] in/out; status NULL or [B]; presets as above; nsub [B] int32 out.
  * ADMPC_EINVAL, in this order: the plant parameters as in admpc_quad_plant_step_batch; the target parameters; with a noise, its refusals
@@ -153,7 +153,7 @@ int admpc_quad_plant_target_step_batch(const AdmpcQuadPlantParams* plant, const 
                                        const double* presets, double* target, uint64_t* target_no, int32_t* n_iter, int32_t* fast,
                                        int32_t* tcounts, int32_t* nsub, uint64_t* noise_step, void* stream);
 
-/* admpc_quad_observe_batch with a period per vehicle: admpc_quad_observe_var_kernel is admpc_quad_observe_kernel with
+/* admpc_quad_observe_batch with a period per vehicle: admpc_quad_observe_kernel<true> is admpc_quad_observe_kernel<false> with
  *     dt_b = obs->dt where nsub[b] == plant->substeps, else (double)nsub[b] * plant->dt;   h_b = dt_b / obs->substeps
  * in the places of obs->dt and h.  A record with nsub[b] < 1 is invalid (flag 0.0: counted in the last entry of dropped); prev is latched
  * all the same.  The bin launch behind it is admpc_quad_observe_batch's.  For a full period (nsub[b] == plant->substeps) this is the

@@ -7,8 +7,8 @@ scripts/quad_rollout_time.py flies it, and `targets`, every vehicle from the ref
 (world radius 3 m, reached within 5 cm, the reference's recovery).  Their graphs of STEPS closed-loop periods are captured once and then
 measured ALTERNATING, circle, targets, circle, targets, ..., three times each; every figure is the median of the three window medians,
 with the smallest and the largest of them, in microseconds per period.  With --noise both fleets fly the simulator's random disturbances
-(noisy and motor_noise on).  The kernels' own times -- admpc_quad_plant_target_kernel against admpc_quad_plant_kernel, or against
-admpc_quad_plant_noise_kernel -- come from running the same command under `rocprofv3 --kernel-trace --stats`, in a run of its own.
+(noisy and motor_noise on).  The kernels' own times -- admpc_quad_plant_period_kernel<NOISY, L, true> against admpc_quad_plant_kernel, or against
+admpc_quad_plant_period_kernel<true, L, false> -- come from running the same command under `rocprofv3 --kernel-trace --stats`, in a run of its own.
 
     python scripts/quad_targets_time.py [--steps 10] [--replays 10] [--windows 20] [--out FILE] [--noise]
 """

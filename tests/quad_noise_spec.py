@@ -6,7 +6,7 @@ import numpy as np
 
 import quad_plant_spec as QS
 
-WIDE_MAX, WIDE_LANES, LDS_DOUBLES = 8192, 4, 1600                    # admpc_quad_noise.hip: QN_WIDE_MAX, QN_LANES, QN_LDS_DOUBLES
+WIDE_MAX, WIDE_LANES, LDS_DOUBLES = 8192, 4, 1600                    # admpc_quad_plant.hip: QN_WIDE_MAX, QN_LANES, QN_LDS_DOUBLES
 M0, M1, W0, W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
 MASK = np.uint64(0xffffffff)
 TWO_PI = 6.283185307179586

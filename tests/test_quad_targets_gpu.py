@@ -14,6 +14,7 @@ import pytest
 import gen_quad_plant_golden as GG
 import gen_quad_targets_golden as TG
 import quad_learn_spec as QL
+import quad_noise_spec as NS
 import quad_plant_spec as QS
 import quad_targets_spec as TS
 import test_quad_fleet_gpu as TQ
@@ -273,6 +274,58 @@ def test_plant_target_kernel_past_the_grid(noisy):
     if noise is not None:
         assert (got[3] == 6).all()
     assert (got[2] >= 1).all() and (got[2] <= 2).all() and (got[1]["tcounts"][:, 2] == 1).all()
+
+
+def _run_plain(L, plant, noise, X, U, noise_step):
+    """admpc_quad_plant_step_batch or, with a noise, admpc_quad_plant_step_noise_batch on copies: (x [B,13], noise_step afterwards or None)."""
+    x, u, ns = _dev(X), _dev(U), None
+    if noise is None:
+        rc = L.admpc_quad_plant_step_batch(C.byref(plant), 0, X.shape[0], _p(u), 4, _p(x), _stream())
+    else:
+        ns = _dev(np.asarray(noise_step, dtype=np.uint64).view(np.int64))
+        rc = L.admpc_quad_plant_step_noise_batch(C.byref(plant), C.byref(noise), 0, X.shape[0], _p(u), 4, _p(x), _p(ns), _stream())
+    assert rc == 0, L.admpc_last_error()
+    return _host(x), (None if ns is None else _host(ns).view(np.uint64))
+
+
+NO_TARGET_CASES = [(n, m, B, 13) for n, m in SWITCHES for B in (1, 67)] + [(True, True, NS.WIDE_MAX, 13), (True, True, NS.WIDE_MAX + 1, 5)]
+
+
+@pytest.mark.parametrize("noisy,motor_noise,B,substeps", NO_TARGET_CASES)
+def test_plant_where_no_target_can_matter_equals_the_plain_plant_bit_for_bit(noisy, motor_noise, B, substeps):
+    """The plant towards targets and the noisy plant are one kernel text (TARGET on and off); the deterministic plant has its own.
+    Where no target can be reached -- every vehicle DONE (mode 0, one preset, target number 1), or a threshold of 1e-300 -- the target
+    step leaves x and noise_step as the plain step of the same inputs does, bit for bit, and nsub == substeps.  Device against device,
+    drag on.  B = 1: vehicle 9 of QS.fleet67 alone, whose NaN activation is replaced; B = 67: five blocks of 16 vehicles with a partial
+    last one under four lanes a vehicle, two waves under one; 13 sub-steps cross the chunk of 10 that four lanes have.  Under the
+    disturbances also the largest fleet with four lanes a vehicle and the smallest with one (5 sub-steps: chunks of 2)."""
+    L = TQ._lib()
+    X67, U67 = QS.fleet67()
+    t = np.array([9]) if B == 1 else np.arange(B) % 67
+    X, U = X67[t].copy(), U67[t].copy()
+    assert np.isnan(U).any()
+    plant, noise, step0 = _plant(True, substeps), _noise(noisy, motor_noise), _numbers(B)
+    wx, wstep = _run_plain(L, plant, noise, X, U, step0)
+    assert not np.isnan(wx).any() and not np.array_equal(wx, X)
+    presets = (X[:, None, :3] + 50.0).copy()
+    done = dict(target=presets[:, 0].copy(), target_no=np.ones(B, dtype=np.uint64), n_iter=(np.arange(B) % 5).astype(np.int32),
+                fast=np.full(B, 7, dtype=np.int32), tcounts=(np.arange(B * 5).reshape(B, 5) % 11).astype(np.int32))
+    far = dict(done, target_no=_numbers(B))
+    for what, tp, st0, pre in (("done", _tp(mode="preset", thresh=THRESH, n_preset=1, seed=None), done, presets),
+                               ("thresh = 1e-300", _tp(mode="aggressive", thresh=1e-300), far, None)):
+        gx, st, nsub, gstep = _run_step(L, plant, tp, noise, X, U, st0, step0, presets=pre)
+        _bits(gx, wx, "x, " + what)
+        assert (nsub == substeps).all()
+        if noise is not None:
+            _bits(gstep, wstep, "noise_step, " + what)
+            _bits(gstep, step0 + np.uint64(1), "noise_step advanced by one, " + what)
+        _bits(st["target"], st0["target"], "target, " + what); _bits(st["target_no"], st0["target_no"], "target_no, " + what)
+        counted = 0 if what == "done" else 1                                                     # a DONE vehicle counts nothing any more
+        want_tc = st0["tcounts"].copy()
+        want_tc[:, 2] += counted
+        want_tc[:, 4] += counted * np.isnan(U).any(axis=1)
+        _bits(st["tcounts"], want_tc, "tcounts, " + what); _bits(st["n_iter"], st0["n_iter"] + np.int32(counted), "n_iter, " + what)
+        assert (st["fast"] == 0).all()
 
 
 def test_presets_the_last_one_reached_then_done():
