@@ -91,7 +91,8 @@ int admpc_observe_batch(const AdmpcSolver* model, const AdmpcPlantParams* plant,
 
 /* One wave per regressor: bins [n_gp][32][5] -> gp_out [n_gp], complete AdmpcGp records in device memory (unused entries zero,
  * inv_l2 = 1 / (length * length) formed on the host), and info [n_gp] int32.
- *   points  the bins with count >= min_count, in ascending bin order: Z_i = sum z / count, t_i = sum y / count
+ *   points  the bins with count >= min_count, in ascending bin order: Z_i = sum z / count, t_i = sum y / count.  Only the rows below the
+ *           product of nb are read: what a larger grid left in the rows behind them is no point
  *   ymean   the serial sum of the t_i, divided by n
  *   K_ij    sigma_f * exp(-0.5 * sum_d (Z_i,d - Z_j,d)^2 * inv_l2_d) + delta_ij * (noise + count_noise / count_i), exp as the
  *           kernels evaluate it (model_dev.h: exp_nonpos); sigma_f is not squared
