@@ -167,6 +167,14 @@ _QUAD_TARGETS = {   # include/admpc_quad_targets.h: the draw of a target, the re
 }
 QUAD_TARGETS_EXPORTS = tuple(_QUAD_TARGETS)
 TARGET_TABLES = {"admpc_quad_targets.h": _QUAD_TARGETS}
+# pruning the log and the RDRv drag fit, declared by load() in the same way
+_QUAD_PRUNE = {     # include/admpc_quad_prune.h: the flags of a log rewritten by the reference's prune_dataset, the linear drag fitted from what is left, its install
+    "admpc_quad_records_prune": (I, [I, C.c_int64, dp, D, I, D, dp, dp, ip, ip, vp]),
+    "admpc_quad_rdrv_fit": (I, [I, C.c_int64, I, dp, dp, dp, dp, ip, vp]),
+    "admpc_quad_rdrv_install": (I, [vp, dp, ip, ip, vp]),
+}
+QUAD_PRUNE_EXPORTS = tuple(_QUAD_PRUNE)
+PRUNE_TABLES = {"admpc_quad_prune.h": _QUAD_PRUNE}
 
 _lib = None
 
@@ -185,7 +193,7 @@ def load():
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
     for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()) + \
-            list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()):
+            list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()) + list(PRUNE_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

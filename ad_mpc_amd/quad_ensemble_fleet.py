@@ -21,6 +21,7 @@ QuadEnsembleRollout = namedtuple("QuadEnsembleRollout", ("x", "idx", "tally", "c
 QuadClusters = namedtuple("QuadClusters", ("weights", "means", "covariances", "n_iter", "converged", "status", "perm"))
 CLUSTERS_MAX = 8
 GMM_BLOCKS_MAX, GMM_ROW, GMM_PARTIAL, GMM_ENOVALID = 256, 18, 81, -100                  # include/admpc_quad_clusters.h
+PRUNE_BINS_MAX, PRUNE_PARTIAL, RDRV_PARTIAL, PRUNE_ENOVALID, REC_PRUNED = 256, 9, 7, -100, 2.0        # include/admpc_quad_prune.h
 
 
 def ensemble_layout(centroids, feats, learn=None):
@@ -86,6 +87,31 @@ def clusters_request(K, feats, steps, max_iter=100, tol=1e-3, reg_covar=1e-6, in
     return int(max_iter), tol, reg_covar, init
 
 
+def prune_request(steps, x_cap=16.0, bins=40, thresh=0.001):
+    """The arguments of ``prune_log`` checked as admpc_quad_records_prune checks them, for a log that holds ``steps`` steps: (x_cap with
+    None as +inf, bins, thresh).  Raises ValueError; needs no GPU."""
+    if int(steps) < 1:
+        raise ValueError("prune_log: the log is empty: fly rollout(T, observe=True, log=True) first")
+    if int(bins) != bins or not 1 <= int(bins) <= PRUNE_BINS_MAX:
+        raise ValueError("prune_log: bins must be in 1 .. %d" % PRUNE_BINS_MAX)
+    thresh = float(thresh)
+    if not 0.0 <= thresh <= 1.0:
+        raise ValueError("prune_log: thresh must be in [0, 1]")
+    x_cap = float("inf") if x_cap is None else float(x_cap)
+    if not x_cap > 0.0:
+        raise ValueError("prune_log: x_cap must be positive, or None for no cap")
+    return x_cap, int(bins), thresh
+
+
+def rdrv_axes(axes):
+    """``axes`` of ``fit_rdrv`` -- the reference's features, a subset of (7, 8, 9) -- as the 3-bit mask of admpc_quad_rdrv_fit.  Raises
+    ValueError; needs no GPU."""
+    axes = [int(a) for a in np.atleast_1d(axes).reshape(-1)]
+    if not axes or any(not 7 <= a <= 9 for a in axes) or len(set(axes)) != len(axes):
+        raise ValueError("fit_rdrv: axes must be a subset of (7, 8, 9) without repeats, and not empty")
+    return sum(1 << (a - 7) for a in axes)
+
+
 def centroid_block(who, c, K, d):
     """c as float64 [K, d], finite.  Raises ValueError; needs no GPU."""
     c = np.asarray(c, dtype=np.float64)
@@ -111,7 +137,9 @@ class QuadEnsembleFleet(QuadFleet):
 
     With ``log_steps`` a fleet that learns also keeps the records it flies, ``log`` [log_steps,B,14] on the device with a cursor
     ``log_count`` on the host, and finds its centroids from them (include/admpc_quad_clusters.h): ``rollout(T, observe=True, log=True)``
-    -> ``fit_clusters()`` -> ``fit_gp()`` -> ``rollout(...)``.  Cluster c keeps the box and the hyperparameters of ``learn[c]``; ``search_gp()``
+    -> ``prune_log()`` -> ``fit_clusters()`` -> ``fit_gp()`` -> ``rollout(...)``.  ``prune_log()`` is the reference's prune_dataset over the
+    log (include/admpc_quad_prune.h): it rewrites flags, which every later stage reads; ``fit_rdrv()`` learns the linear drag from the
+    records that are left, in place of the GPs or under them.  Cluster c keeps the box and the hyperparameters of ``learn[c]``; ``search_gp()``
     in place of ``fit_gp()`` finds the length scales, sigma_f and the noise of every cluster from the data it holds now
     (include/admpc_quad_hyper.h), all on the same stream.  ``hyper`` [K,3,16] and ``search_info`` [K,3,2] are the state of that search."""
 
@@ -142,6 +170,7 @@ class QuadEnsembleFleet(QuadFleet):
         self.log_steps, self.log_count, self.log = log_layout(log_steps, learn is not None), 0, None
         self.K, self.feats, self.centroids = cent.shape[0], feats, cent
         self._moved = False                                                                # the device's centroids are no longer self.centroids
+        self._rdrv_given = rdrv_d_mat is not None and bool(np.any(np.asarray(rdrv_d_mat, dtype=np.float64) != 0.0))
         cfgs = [fleet_quad_config(quad, t_horizon, n_nodes, q_cost, r_cost, gps, rdrv_d_mat) for gps in clusters]      # one configuration per cluster
         if learn is not None:
             self._nominal = QuadBatchSolver(fleet_quad_config(quad, t_horizon, n_nodes, q_cost, r_cost, None, rdrv_d_mat), device=device)
@@ -180,6 +209,12 @@ class QuadEnsembleFleet(QuadFleet):
             self._packed, self._partial = z(self.log_steps * self.B, 4), z(GMM_BLOCKS_MAX, GMM_PARTIAL)
             self.gmm, self.gmm_info = z(1 + self.K, GMM_ROW), z(4, dtype=torch.int32)
             self.perm = torch.arange(self.K, dtype=torch.int32, device=self.device)
+            # the prune and the drag fit (include/admpc_quad_prune.h): scratch, state and results
+            self._prune_partial, self._rdrv_partial = z(GMM_BLOCKS_MAX, PRUNE_PARTIAL), z(GMM_BLOCKS_MAX, RDRV_PARTIAL)
+            self.prune_edges, self.prune_counts = z(4, PRUNE_BINS_MAX + 1), z(4, PRUNE_BINS_MAX, dtype=torch.int32)
+            self.prune_info = z(8, dtype=torch.int32)
+            self.rdrv, self.rdrv_sums, self.rdrv_info = z(3), z(3, 2), z(2, dtype=torch.int32)
+            self.rdrv_installed = z(self.K, dtype=torch.int32)
 
     # -- lifetime ---------------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -271,6 +306,55 @@ class QuadEnsembleFleet(QuadFleet):
         if self.log_count:
             _lib.check(self.lib.admpc_quad_clusters_rebin(self._ens, self.log_count, self.B, _ptr(self.log), _ptr(self.bins), _ptr(self.dropped),
                                                           self._stream()))
+
+    def prune_log(self, x_cap=16.0, bins=40, thresh=0.001, rebin=True):
+        """The reference's prune_dataset over the logged steps (admpc_quad_records_prune; the defaults are its ModelFitConfig, x_cap=None
+        is no cap): a record behind the velocity cap or in a sparse bin of one of the four error histograms leaves with flag 2.0, every
+        other valid one with 1.0, so that ``fit_clusters``, ``rebin``, ``fit_gp`` and ``search_gp`` see what is left; then (`rebin`) the
+        log binned again.  The result depends on the data alone: a second call with other parameters prunes afresh.  Asynchronous;
+        returns the device tensor info int32 [8]: status, n_valid, n_kept, pruned by the cap, by axis 0, 1, 2, by the norm."""
+        self._learns("prune_log")
+        if not self.log_steps:
+            raise ValueError("prune_log: this fleet keeps no log, create it with log_steps")
+        x_cap, bins, thresh = prune_request(self.log_count, x_cap, bins, thresh)
+        _lib.check(self.lib.admpc_quad_records_prune(self.device_index, self.log_count * self.B, _ptr(self.log), x_cap, bins, thresh,
+                                                     _ptr(self._prune_partial), _ptr(self.prune_edges), _ptr(self.prune_counts),
+                                                     _ptr(self.prune_info), self._stream()))
+        if rebin:
+            self.rebin()
+        return self.prune_info
+
+    def fit_rdrv(self, axes=(7, 8, 9), install=True):
+        """Faessler's diagonal linear drag from the logged records with flag 1.0 (admpc_quad_rdrv_fit: D_i = sum v_b,i y_i / sum v_b,i^2
+        for the features in ``axes``, 0 elsewhere), and (`install`) into rdrv of all K cluster handles on the device
+        (admpc_quad_rdrv_install); the nominal handle, which predicts for observe, keeps none.  The values are set, not added, so a
+        fleet created with a non-zero ``rdrv_d_mat`` is refused: its residual was observed against a model that had drag already.
+        Asynchronous; returns the device tensors (d float64 [3], info int32 [2]: n_used and status, installed int32 [K] or None)."""
+        self._learns("fit_rdrv")
+        if not self.log_steps:
+            raise ValueError("fit_rdrv: this fleet keeps no log, create it with log_steps")
+        if self._rdrv_given:
+            raise ValueError("fit_rdrv: the fleet was created with a non-zero rdrv_d_mat; the fit sets the drag, it does not add to it")
+        mask = rdrv_axes(axes)
+        if self.log_count < 1:
+            raise ValueError("fit_rdrv: the log is empty: fly rollout(T, observe=True, log=True) first")
+        s = self._stream()
+        _lib.check(self.lib.admpc_quad_rdrv_fit(self.device_index, self.log_count * self.B, mask, _ptr(self.log), _ptr(self._rdrv_partial),
+                                                _ptr(self.rdrv), _ptr(self.rdrv_sums), _ptr(self.rdrv_info), s))
+        if not install:
+            return self.rdrv, self.rdrv_info, None
+        for c, solver in enumerate(self._solvers):
+            _lib.check(self.lib.admpc_quad_rdrv_install(solver._h, _ptr(self.rdrv), _ptr(self.rdrv_info),
+                                                        C.c_void_p(self.rdrv_installed.data_ptr() + 4 * c), s))
+        return self.rdrv, self.rdrv_info, self.rdrv_installed
+
+    def learned_rdrv(self):
+        """The drag of the last fit_rdrv as a 3 x 3 diagonal numpy matrix, what ``rdrv_d_mat`` takes (synchronises)."""
+        self._learns("learned_rdrv")
+        if not self.log_steps:
+            raise ValueError("learned_rdrv: this fleet keeps no log, create it with log_steps")
+        torch.cuda.current_stream(self.device).synchronize()
+        return np.diag(self.rdrv.cpu().numpy())
 
     def fit_clusters(self, max_iter=100, tol=1e-3, reg_covar=1e-6, init=None, install=True, rebin=True, resume=False):
         """The centroids from the log: sklearn's Gaussian-mixture EM (full covariances; max_iter, tol and reg_covar are its defaults) from

@@ -28,7 +28,9 @@
  *   - np.random's own stream for the simulator's random disturbances: their distributions are flown by admpc_quad_rollout_noise_batch
  *     (admpc_quad_noise.h), observed or not, from a counter-based generator;
  *   - handles in SQP mode (the rollout is the RTI loop);
- *   - pruning by a velocity cap (gp_common.py:101-104) beyond what the box of the bins does: a sample outside the box is dropped and counted.
+ *   - pruning by a velocity cap and by the error histograms (gp_common.py:101-112) by THESE entries, beyond what the box of the bins does (a
+ *     sample outside the box is dropped and counted): admpc_quad_prune.h has the reference's prune over a log of these records, which
+ *     rewrites entry 13 -- a pruned record carries 2.0 there and is taken by no bin -- and the RDRv drag fit from what is left.
  *
  * A handle that is to learn is created with placeholder GPs (n_points = 0, which admpc_quad.h admits): the solve kernels take the GP path
  * from n_gp of the configuration, which an install does not change.  The host copy of a handle's configuration is NOT changed by an
