@@ -175,6 +175,13 @@ _QUAD_PRUNE = {     # include/admpc_quad_prune.h: the flags of a log rewritten b
 }
 QUAD_PRUNE_EXPORTS = tuple(_QUAD_PRUNE)
 PRUNE_TABLES = {"admpc_quad_prune.h": _QUAD_PRUNE}
+# the evaluation of the learned GPs on a log, declared by load() in the same way
+_QUAD_EVAL = {      # include/admpc_quad_eval.h: every regressor of an ensemble factored once (K = L L', alpha, W = L^-1), posterior mean and standard deviation per record of a log, the error statistics per cluster and regressor
+    "admpc_quad_ensemble_factor": (I, [vp, I, dp, dp, dp, ip, vp]),
+    "admpc_quad_ensemble_evaluate": (I, [vp, C.c_int64, dp, I, dp, dp, dp, dp, dp, ip, vp]),
+}
+QUAD_EVAL_EXPORTS = tuple(_QUAD_EVAL)
+EVAL_TABLES = {"admpc_quad_eval.h": _QUAD_EVAL}
 
 _lib = None
 
@@ -193,7 +200,7 @@ def load():
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
     for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()) + \
-            list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()) + list(PRUNE_TABLES.values()):
+            list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()) + list(PRUNE_TABLES.values()) + list(EVAL_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -193,18 +193,15 @@ static __device__ __forceinline__ void gp_install_body(AdmpcGp* dst, const int n
     }
 }
 
-// One wave (a block of its own) fits regressor g at the hyperparameters h.  Lane r < 32 owns point r and row r of K; lanes 32 .. 63
-// mirror lanes 0 .. 31 and store nothing.
-static __device__ __forceinline__ void gp_fit_body(const LearnArgs& a, const int g, const GpHyper& h)
+// K of regressor G at the hyperparameters h over the n points of Zs, cs (gp_points), and its Cholesky factor L in its place, by ONE
+// wave: As (LDS) leaves with L in the lower triangle and on the diagonal.  Returns 0, k + 1 for pivot k that is not positive and finite
+// (or whose target ts[k] is not finite), or -ADMPC_GP_NO_OPTIMUM for a search without an optimum, the same on every lane; then As is
+// not a factor.  The fit (gp_fit_body) and the factor of the evaluation (admpc_quad_eval.hip) share this text: the same bits.
+static __device__ __forceinline__ int gp_chol(const LearnGp& G, const GpHyper& h, const int n, const int lane, const double (*Zs)[NPT], const double* ts,
+                                              const double* cs, double (*As)[NPT + 1])
 {
-    __shared__ double Zs[3][NPT], ts[NPT], cs[NPT], As[NPT][NPT + 1];
-    const LearnGp& G = a.gp[g];
-    const int lane = gp_lane_id(), r = lane & (NPT - 1);
+    const int r = lane & (NPT - 1), nf = G.n_feat;
     const bool act = lane < NPT;
-    const int nf = G.n_feat;
-    const int n = gp_points(a, g, lane, Zs, ts, cs);
-    __syncthreads();
-    const double ymean = gp_ymean(ts, n);
     // row r of K in LDS (lower triangle and diagonal: what the factorisation reads)
     const double il0 = h.inv_l2[0], il1 = nf > 1 ? h.inv_l2[1] : 0.0, il2 = nf > 2 ? h.inv_l2[2] : 0.0;
     const double z0 = Zs[0][r], z1 = Zs[1][r], z2 = Zs[2][r];
@@ -234,6 +231,15 @@ static __device__ __forceinline__ void gp_fit_body(const LearnArgs& a, const int
         if (act && r >= k && r < n) As[r][k] = r == k ? l : s / l;
         __syncthreads();
     }
+    return fail;
+}
+
+// alpha = K^-1 (t - ymean) through the factor gp_chol left in As, by ONE wave: lane r < n returns alpha_r (every lane its right-hand
+// side where `fail` is set)
+static __device__ __forceinline__ double gp_alpha(const int fail, const int n, const int lane, const double* ts, const double ymean,
+                                                  const double (*As)[NPT + 1])
+{
+    const int r = lane & (NPT - 1);
     double bb = r < n ? ts[r] - ymean : 0.0;
     if (!fail) {
 #pragma unroll 1
@@ -249,6 +255,23 @@ static __device__ __forceinline__ void gp_fit_body(const LearnArgs& a, const int
             else if (r < k) bb = bb - As[k][r] * ak;
         }
     }
+    return bb;
+}
+
+// One wave (a block of its own) fits regressor g at the hyperparameters h.  Lane r < 32 owns point r and row r of K; lanes 32 .. 63
+// mirror lanes 0 .. 31 and store nothing.
+static __device__ __forceinline__ void gp_fit_body(const LearnArgs& a, const int g, const GpHyper& h)
+{
+    __shared__ double Zs[3][NPT], ts[NPT], cs[NPT], As[NPT][NPT + 1];
+    const LearnGp& G = a.gp[g];
+    const int lane = gp_lane_id(), r = lane & (NPT - 1);
+    const bool act = lane < NPT;
+    const int nf = G.n_feat;
+    const int n = gp_points(a, g, lane, Zs, ts, cs);
+    __syncthreads();
+    const double ymean = gp_ymean(ts, n);
+    const int fail = gp_chol(G, h, n, lane, Zs, ts, cs, As);
+    const double bb = gp_alpha(fail, n, lane, ts, ymean, As);
     const int np = fail ? 0 : n;
     AdmpcGp* o = a.out + g;
     if (act) {

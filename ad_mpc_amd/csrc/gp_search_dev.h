@@ -198,9 +198,10 @@ static __device__ __forceinline__ void gp_pick_body(const SearchGp& S, const int
 }
 
 // one wave: the fit of regressor g of a at the natural values of the search's centre, hy [HYP]
-static __device__ __forceinline__ void gp_refit_body(const LearnArgs& a, const int g, const double* __restrict__ hy)
+// the natural values a search left in hy [HYP] as the fit takes its hyperparameters (the re-fit and the factor of the evaluation,
+// admpc_quad_eval.hip, read them here)
+static __device__ __forceinline__ GpHyper gp_hyper_natural(const int nf, const double* __restrict__ hy)
 {
-    const int nf = a.gp[g].n_feat;
     GpHyper h;
     {
 #pragma clang fp contract(off)
@@ -213,5 +214,10 @@ static __device__ __forceinline__ void gp_refit_body(const LearnArgs& a, const i
     h.sigma_f = hy[2 * NSLOT + 3];
     h.noise = hy[2 * NSLOT + 4];
     h.no_optimum = isfinite(hy[3 * NSLOT]) ? 0 : 1;
-    gp_fit_body(a, g, h);
+    return h;
+}
+
+static __device__ __forceinline__ void gp_refit_body(const LearnArgs& a, const int g, const double* __restrict__ hy)
+{
+    gp_fit_body(a, g, gp_hyper_natural(a.gp[g].n_feat, hy));
 }

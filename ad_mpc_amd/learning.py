@@ -152,7 +152,7 @@ class FleetSearch(FleetLearning):
         h = self.hyper[g].tolist()
         return dict(d, length_scale=h[10:10 + int(self._obs.gp[g].n_feat)], sigma_f=h[13])
 
-    def search_gp(self, min_count=1, grid=5, rounds=10, shrink=0.5, bounds=None, resume=False, install=True):
+    def search_gp(self, min_count=1, grid=5, rounds=10, shrink=0.5, bounds=None, resume=False, install=True, factor=False):
         """Searches the length scales, sigma_f and the noise of every regressor for the smallest negative log marginal likelihood of its
         points (the bins with at least `min_count` samples), fits at what it found and (`install`) overwrites the GPs of the controller's
         handle on the device: 2 * rounds + 2 launches on the current stream (one more where the search starts), no synchronisation, no allocation.  Every round evaluates
@@ -160,7 +160,10 @@ class FleetSearch(FleetLearning):
         the grid's step by `shrink`; the first round spans the box.  ``bounds``: config.search_boxes (None: the reference's box;
         lo == hi keeps a slot at that value).  ``resume`` continues the last search on the same statistics with the steps where they
         stand.  Returns the device tensors (info int32 [n] as fit_gp's, or -33 where no candidate had a finite NLL; installed int32
-        [n] or None; hyper float64 [n, 16]: the centre's logarithms, the steps, the natural values and the best NLL)."""
+        [n] or None; hyper float64 [n, 16]: the centre's logarithms, the steps, the natural values and the best NLL).  ``factor`` is the
+        clustered ensemble's (include/admpc_quad_eval.h: the factors of an evaluation on a log); a fleet without a log refuses it."""
+        if factor:
+            raise ValueError("search_gp: factor=True needs the clustered ensemble's log (QuadEnsembleFleet, include/admpc_quad_eval.h)")
         obs = self._observe_params("search_gp", observing=False)
         n, dev = self.n_learn, self._eng.device_index
         sp = AdmpcGpSearchParams(grid=int(grid), rounds=int(rounds), shrink=float(shrink), box=search_boxes(self._learn, bounds))

@@ -19,9 +19,12 @@ from .quad_fleet import QuadFleet, fleet_quad_config
 
 QuadEnsembleRollout = namedtuple("QuadEnsembleRollout", ("x", "idx", "tally", "counts", "traj", "u", "routes"))
 QuadClusters = namedtuple("QuadClusters", ("weights", "means", "covariances", "n_iter", "converged", "status", "perm"))
+QuadEvaluation = namedtuple("QuadEvaluation", ("count", "nominal_mae", "augmented_mae", "nominal_rms", "augmented_rms", "mean_std", "within_3std",
+                                               "clipped", "total"))
 CLUSTERS_MAX = 8
 GMM_BLOCKS_MAX, GMM_ROW, GMM_PARTIAL, GMM_ENOVALID = 256, 18, 81, -100                  # include/admpc_quad_clusters.h
 PRUNE_BINS_MAX, PRUNE_PARTIAL, RDRV_PARTIAL, PRUNE_ENOVALID, REC_PRUNED = 256, 9, 7, -100, 2.0        # include/admpc_quad_prune.h
+EVAL_FACTOR, EVAL_STATS, EVAL_ENOVALID = 672, 8, -100                                    # include/admpc_quad_eval.h
 
 
 def ensemble_layout(centroids, feats, learn=None):
@@ -103,6 +106,38 @@ def prune_request(steps, x_cap=16.0, bins=40, thresh=0.001):
     return x_cap, int(bins), thresh
 
 
+def eval_request(log_steps, steps, has_factor, include_pruned=False, drag=False, has_rdrv=False, per_record=False):
+    """The arguments of ``evaluate_log`` checked before any launch, for a fleet whose log holds ``steps`` of ``log_steps`` steps, with
+    (``has_factor``) a factor from fit_gp(factor=True), search_gp(factor=True) or factor_gp(), and (``has_rdrv``) a drag from fit_rdrv:
+    (take_pruned 0 or 1, drag, per_record).  Raises ValueError; needs no GPU."""
+    if int(log_steps) < 1:
+        raise ValueError("evaluate_log: this fleet keeps no log, create it with log_steps")
+    if int(steps) < 1:
+        raise ValueError("evaluate_log: the log is empty: fly rollout(T, observe=True, log=True) first")
+    if not has_factor:
+        raise ValueError("evaluate_log: no factor yet: call fit_gp(factor=True), search_gp(factor=True) or factor_gp() first")
+    for name, v in (("include_pruned", include_pruned), ("drag", drag), ("per_record", per_record)):
+        if not isinstance(v, (bool, np.bool_)):
+            raise ValueError("evaluate_log: %s must be True or False" % name)
+    if drag and not has_rdrv:
+        raise ValueError("evaluate_log: drag=True needs the drag of a fit_rdrv() first")
+    return (1 if include_pruned else 0), bool(drag), bool(per_record)
+
+
+def evaluation_table(stats, n, dt=None):
+    """stats [K, 3, 8] of admpc_quad_ensemble_evaluate as a ``QuadEvaluation`` of [K, n] arrays, whose ``total`` is the same over all
+    clusters per regressor ([n], its own total None); with ``dt`` the errors and the standard deviation are multiplied by it (the
+    reference's velocity units).  A cluster without a record has count 0 and NaN elsewhere.  Needs no GPU."""
+    def table(s):
+        cnt = s[..., 0]
+        scale = 1.0 if dt is None else float(dt)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return (cnt.astype(np.int64), scale * s[..., 1] / cnt, scale * s[..., 3] / cnt, scale * np.sqrt(s[..., 2] / cnt),
+                    scale * np.sqrt(s[..., 4] / cnt), scale * s[..., 5] / cnt, s[..., 6] / cnt, s[..., 7].astype(np.int64))
+    s = np.asarray(stats, dtype=np.float64)[:, :n]
+    return QuadEvaluation(*table(s), QuadEvaluation(*table(s.sum(axis=0)), None))
+
+
 def rdrv_axes(axes):
     """``axes`` of ``fit_rdrv`` -- the reference's features, a subset of (7, 8, 9) -- as the 3-bit mask of admpc_quad_rdrv_fit.  Raises
     ValueError; needs no GPU."""
@@ -141,7 +176,12 @@ class QuadEnsembleFleet(QuadFleet):
     log (include/admpc_quad_prune.h): it rewrites flags, which every later stage reads; ``fit_rdrv()`` learns the linear drag from the
     records that are left, in place of the GPs or under them.  Cluster c keeps the box and the hyperparameters of ``learn[c]``; ``search_gp()``
     in place of ``fit_gp()`` finds the length scales, sigma_f and the noise of every cluster from the data it holds now
-    (include/admpc_quad_hyper.h), all on the same stream.  ``hyper`` [K,3,16] and ``search_info`` [K,3,2] are the state of that search."""
+    (include/admpc_quad_hyper.h), all on the same stream.  ``hyper`` [K,3,16] and ``search_info`` [K,3,2] are the state of that search.
+
+    The chain closes with the evaluation of what was learned (include/admpc_quad_eval.h): ``fit_gp(factor=True)`` or
+    ``search_gp(factor=True)`` -> ``log_reset()`` -> ``rollout(T, observe=True, log=True)`` again -> ``evaluate_log()`` -> ``evaluation()``.
+    ``factor`` [K,3,672] holds every regressor factored once (alpha and W = L^-1), ``eval_stats`` [K,3,8] and ``eval_info`` [4] the sums
+    and the counts of the last evaluation, ``eval_per_record`` the mean and the standard deviation of every record once asked for."""
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
                  ensemble=None, centroids=None, feats=None, learn=None, rdrv_d_mat=None, device=0, observe_substeps=1, noise_seed=None,
@@ -215,6 +255,12 @@ class QuadEnsembleFleet(QuadFleet):
             self.prune_info = z(8, dtype=torch.int32)
             self.rdrv, self.rdrv_sums, self.rdrv_info = z(3), z(3, 2), z(2, dtype=torch.int32)
             self.rdrv_installed = z(self.K, dtype=torch.int32)
+            # the evaluation of the learned GPs on the log (include/admpc_quad_eval.h): the factors, scratch, results; per_record [M,3,2]
+            # is allocated when it is first asked for
+            self.factor, self.factor_info = z(self.K, QUAD_GP_MAX, EVAL_FACTOR), z(self.K, QUAD_GP_MAX, dtype=torch.int32)
+            self._eval_partial, self.eval_stats = z(GMM_BLOCKS_MAX, self.K * QUAD_GP_MAX * EVAL_STATS), z(self.K, QUAD_GP_MAX, EVAL_STATS)
+            self.eval_info, self.eval_per_record = z(4, dtype=torch.int32), None
+            self._has_factor = self._has_rdrv = self._evaluated = False
 
     # -- lifetime ---------------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -339,6 +385,7 @@ class QuadEnsembleFleet(QuadFleet):
         if self.log_count < 1:
             raise ValueError("fit_rdrv: the log is empty: fly rollout(T, observe=True, log=True) first")
         s = self._stream()
+        self._has_rdrv = True
         _lib.check(self.lib.admpc_quad_rdrv_fit(self.device_index, self.log_count * self.B, mask, _ptr(self.log), _ptr(self._rdrv_partial),
                                                 _ptr(self.rdrv), _ptr(self.rdrv_sums), _ptr(self.rdrv_info), s))
         if not install:
@@ -415,29 +462,37 @@ class QuadEnsembleFleet(QuadFleet):
                                                               stride, _ptr(self.x), _ptr(self._prev), _ptr(self.samples), _ptr(self.bins),
                                                               _ptr(self.dropped), self._stream()))
 
-    def fit_gp(self, min_count=1, install=True):
+    def fit_gp(self, min_count=1, install=True, factor=False):
         """Fits every regressor of every cluster to the means of its bins with at least `min_count` samples, at that cluster's
-        hyperparameters, and (`install`) overwrites the GPs of the K handles on the device.  Asynchronous; returns the device tensors
+        hyperparameters, and (`install`) overwrites the GPs of the K handles on the device.  With `factor` the factors of the evaluation
+        (``factor_gp``) follow the fit in the same chain, from the same bins.  Asynchronous; returns the device tensors
         (info int32 [K,n], installed int32 [K,n] or None) as QuadFleet.fit_gp explains them."""
         self._learns("fit_gp")
+        if factor:
+            self._keeps_log("fit_gp: factor=True")
         n, s = self.n_learn, self._stream()
         _lib.check(self.lib.admpc_quad_ensemble_fit(self._ens, int(min_count), _ptr(self.bins), _ptr(self._gp_dev), _ptr(self.fit_info), s))
         self._searched = False                                                             # the records hold the given hyperparameters again
+        if factor:
+            self.factor_gp(min_count)
         if not install:
             return self.fit_info[:, :n], None
         _lib.check(self.lib.admpc_quad_ensemble_install(self._ens, _ptr(self._gp_dev), _ptr(self.installed), s))
         return self.fit_info[:, :n], self.installed[:, :n]
 
-    def search_gp(self, min_count=1, grid=5, rounds=10, shrink=0.5, bounds=None, resume=False, install=True):
+    def search_gp(self, min_count=1, grid=5, rounds=10, shrink=0.5, bounds=None, resume=False, install=True, factor=False):
         """QuadFleet.search_gp for every regressor of every cluster in one chain of launches (include/admpc_quad_hyper.h:
         admpc_quad_ensemble_search -> admpc_quad_ensemble_refit -> admpc_quad_ensemble_install): 2 * rounds + 1 + K launches on the
         fleet's stream, one more where the search starts.  ``bounds``: None (the reference's box everywhere), one list of
         config.search_boxes dicts per regressor (every cluster searches that box), or K such lists.  grid, rounds and shrink serve all
         clusters.  The parameters go to the object by admpc_quad_ensemble_set_search, which synchronises, only when they differ from the
         last call's: a second call with the same ones has no host synchronisation and no allocation.  After ``fit_clusters()`` call
-        with resume=False: the clusters hold other data.  Returns the device tensors (info int32 [K,n], installed int32 [K,n] or None,
+        with resume=False: the clusters hold other data.  With `factor` the factors of the evaluation (``factor_gp``) follow the re-fit in
+        the same chain, from the same bins and the same ``hyper``.  Returns the device tensors (info int32 [K,n], installed int32 [K,n] or None,
         hyper float64 [K,n,16])."""
         self._learns("search_gp")
+        if factor:
+            self._keeps_log("search_gp: factor=True")
         n = self.n_learn
         sp = (AdmpcGpSearchParams * self.K)()
         for c, b in enumerate(self._cluster_bounds(bounds)):
@@ -452,10 +507,65 @@ class QuadEnsembleFleet(QuadFleet):
         _lib.check(self.lib.admpc_quad_ensemble_refit(self._ens, int(min_count), _ptr(self.bins), _ptr(self.hyper), _ptr(self._gp_dev),
                                                       _ptr(self.fit_info), s))
         self._has_hyper = self._searched = True
+        if factor:
+            self.factor_gp(min_count)
         if not install:
             return self.fit_info[:, :n], None, self.hyper[:, :n]
         _lib.check(self.lib.admpc_quad_ensemble_install(self._ens, _ptr(self._gp_dev), _ptr(self.installed), s))
         return self.fit_info[:, :n], self.installed[:, :n], self.hyper[:, :n]
+
+    # -- the evaluation of the learned GPs on the log (include/admpc_quad_eval.h) -----------------------------------------------------------
+    def _keeps_log(self, who):
+        if not self.log_steps:
+            raise ValueError("%s: this fleet keeps no log, create it with log_steps" % who)
+
+    def factor_gp(self, min_count=1):
+        """Every regressor of every cluster factored once from the present bins (admpc_quad_ensemble_factor: the fit's K, its Cholesky
+        factor, alpha, and W = L^-1), at the hyperparameters of the last ``fit_gp`` / ``search_gp``: each cluster's given ones, or what the
+        search left in ``hyper``.  One launch, asynchronous; returns the device tensor factor_info int32 [K,n]: the points, or the fit's
+        failure code.  What a later flight adds to the bins does not reach the factor."""
+        self._learns("factor_gp")
+        self._keeps_log("factor_gp")
+        _lib.check(self.lib.admpc_quad_ensemble_factor(self._ens, int(min_count), _ptr(self.bins), _ptr(self.hyper) if self._searched else None,
+                                                       _ptr(self.factor), _ptr(self.factor_info), self._stream()))
+        self._has_factor = True
+        return self.factor_info[:, :self.n_learn]
+
+    def evaluate_log(self, include_pruned=False, drag=False, per_record=False):
+        """The learned GPs, as the last factor holds them, evaluated over the ``log_count * B`` logged records
+        (admpc_quad_ensemble_evaluate: the reference's gp_evaluate_test_set): per record the posterior mean and standard deviation of
+        every regressor of its cluster, per cluster and regressor the error sums.  `include_pruned` also takes the records a prune took
+        out (the reference's pruned=False); `drag` scores the linear drag of the last ``fit_rdrv`` under the GPs; `per_record` asks for
+        the [log_count * B, 3, 2] tensor of mean and standard deviation (allocated at the first call that asks, so make that call
+        outside a capture).  Asynchronous; returns the device tensors (stats float64 [K,3,8], info int32 [4]: status, took part, skipped
+        by flag, skipped as not finite; per_record or None).  ``evaluation()`` reads them."""
+        self._learns("evaluate_log")
+        take, drag, per_record = eval_request(self.log_steps, self.log_count, getattr(self, "_has_factor", False), include_pruned, drag,
+                                              getattr(self, "_has_rdrv", False), per_record)
+        out = None
+        if per_record:
+            if self.eval_per_record is None:
+                self.eval_per_record = torch.zeros((self.log_steps * self.B, QUAD_GP_MAX, 2), dtype=torch.float64, device=self.device)
+            out = self.eval_per_record[:self.log_count * self.B]
+        _lib.check(self.lib.admpc_quad_ensemble_evaluate(self._ens, self.log_count * self.B, _ptr(self.log), take, _ptr(self.factor),
+                                                         _ptr(self.rdrv) if drag else None, _ptr(out), _ptr(self._eval_partial),
+                                                         _ptr(self.eval_stats), _ptr(self.eval_info), self._stream()))
+        self._evaluated = True
+        return self.eval_stats, self.eval_info, out
+
+    def evaluation(self, units="rate"):
+        """The last ``evaluate_log`` as a ``QuadEvaluation`` (synchronises): per [K, n] count, nominal_mae and augmented_mae (what the
+        reference prints as "RMSE" is a mean absolute error), nominal_rms, augmented_rms, mean_std, within_3std (the share of the records
+        with |r| <= 3 std) and clipped (variances below 0, taken as 0), and in ``total`` the same over all clusters per regressor.
+        units="rate" leaves the residual as it is recorded, per second; units="velocity" multiplies by the observe dt, the reference's
+        ``* dt_test``."""
+        self._learns("evaluation")
+        if units not in ("rate", "velocity"):
+            raise ValueError("evaluation: units must be 'rate' or 'velocity'")
+        if not getattr(self, "_evaluated", False):
+            raise ValueError("evaluation: nothing evaluated yet: call evaluate_log() first")
+        torch.cuda.current_stream(self.device).synchronize()
+        return evaluation_table(self.eval_stats.cpu().numpy(), self.n_learn, self.control_period if units == "velocity" else None)
 
     def _cluster_bounds(self, bounds):
         """``bounds`` of search_gp as K entries for config.search_boxes: None, one list per regressor for every cluster, or K lists."""

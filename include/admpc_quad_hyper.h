@@ -21,6 +21,8 @@
  * with resume = 0 on the new statistics replaces the given length scales by found ones.
  *
  * NOT offered:
+ *   - the evaluation of what a search found on held-out records, and any predictive variance, by THESE entries: admpc_quad_eval.h
+ *     factors every regressor at the hyperparameters the search left in `hyper` and scores them on a log, on the same stream;
  *   - gradients, L-BFGS-B or random restarts: the search is the zooming grid of admpc_hyper.h;
  *   - a warm start of the search across new statistics (call with resume = 0 after a re-bin);
  *   - a K chosen by the search; handles in SQP mode;

@@ -20,6 +20,8 @@
  *   quad_mpc/quad_3d_optimizer.py:289-327  where the GP enters the model of the MPC            admpc_quad_gp_install (no host in between)
  *
  * NOT offered:
+ *   - the evaluation of the learned GPs on a data set (gp_fitting.py:304-348 gp_evaluate_test_set), the posterior standard deviation
+ *     among it, by THESE entries: admpc_quad_eval.h has it over a log of these records, for a clustered ensemble;
  *   - the search of the hyperparameters by THESE entries: to admpc_quad_gp_fit the length scales, sigma_f and the noise are GIVEN, as in
  *     admpc_learn.h; admpc_quad_hyper.h has the search (admpc_quad_gp_search, admpc_quad_gp_refit), routed to the kernels of
  *     admpc_hyper.h through the AdmpcGpBins that AdmpcQuadObserveParams holds as AdmpcObserveParams does;

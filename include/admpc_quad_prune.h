@@ -22,6 +22,8 @@
  *   experiments/comparative_experiment.py  the RDRv model loaded into the MPC (rdrv_d_mat)       admpc_quad_rdrv_install (no host in between)
  *
  * NOT offered:
+ *   - the evaluation of the fitted drag or of the GPs on a data set by THESE entries: admpc_quad_eval.h scores either, or the drag under
+ *     the GPs, on a log of records, pruned ones included or not;
  *   - the reference's plotting of the histograms (utils.py:476-485, 508-510, 519-530);
  *   - the second normalisation of the NORM's ratios (utils.py:507, 513: h / sum(h), then h[j] / sum(h) again): all four columns compare
  *     count / n_valid with thresh.  The two differ only where a ratio lies within rounding of thresh;
