@@ -7,7 +7,7 @@ import ctypes as C
 import os
 
 from .config import AdmpcConfig, AdmpcGpSearchParams, AdmpcLaneParams, AdmpcObserveParams, AdmpcPath, AdmpcPlantParams, AdmpcStepParams
-from .quad_config import AdmpcQuadConfig, AdmpcQuadNoiseParams, AdmpcQuadObserveParams, AdmpcQuadPlantParams, AdmpcQuadTargetParams
+from .quad_config import AdmpcQuadConfig, AdmpcQuadNoiseParams, AdmpcQuadObserveParams, AdmpcQuadPlantParams, AdmpcQuadTargetParams, AdmpcQuadTrajSpec
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libadmpc.so")
@@ -182,6 +182,17 @@ _QUAD_EVAL = {      # include/admpc_quad_eval.h: every regressor of an ensemble 
 }
 QUAD_EVAL_EXPORTS = tuple(_QUAD_EVAL)
 EVAL_TABLES = {"admpc_quad_eval.h": _QUAD_EVAL}
+# the loop and lemniscate references generated on the device, declared by load() in the same way
+tsp_ = C.POINTER(AdmpcQuadTrajSpec)
+_QUAD_TRAJ = {      # include/admpc_quad_traj.h: the phase lengths on the host, a generated bank, what it holds, a trajectory read back, the rows of a fleet's reset
+    "admpc_quad_traj_lengths": (I, [D, tsp_, fp]),
+    "admpc_quad_traj_bank_generate": (I, [I, I, tsp_, pp, D, vp, hp]),
+    "admpc_quad_traj_bank_info": (I, [vp, fp, C.POINTER(C.c_int64), fp]),
+    "admpc_quad_traj_bank_copy": (I, [vp, I, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "admpc_quad_traj_rows_batch": (I, [vp, I, ip, ip, dp, dp, vp]),
+}
+QUAD_TRAJ_EXPORTS = tuple(_QUAD_TRAJ)
+TRAJ_TABLES = {"admpc_quad_traj.h": _QUAD_TRAJ}
 
 _lib = None
 
@@ -200,7 +211,8 @@ def load():
                          "there is no CPU fallback" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
     for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()) + \
-            list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()) + list(PRUNE_TABLES.values()) + list(EVAL_TABLES.values()):
+            list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()) + list(PRUNE_TABLES.values()) + list(EVAL_TABLES.values()) + \
+            list(TRAJ_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -19,14 +19,6 @@
 #define QC_THREADS 256
 #define QC_GRID 4096           // blocks of the chunk kernel at most
 
-struct AdmpcQuadTrajBank {
-    int device, K;
-    long long rows;              // sum of M
-    void* d_mem;                 // the one allocation: desc [K], X [rows][13], U [rows][4]
-    const QuadTrajDesc* d_desc;
-    const double *d_X, *d_U;
-};
-
 __global__ __launch_bounds__(QC_THREADS) void admpc_quad_chunk_kernel(const QuadTrajDesc* __restrict__ desc, const double* __restrict__ X,
                                                                        const double* __restrict__ U, int K, int B, int N, int over,
                                                                        const int32_t* __restrict__ traj_of, const int32_t* __restrict__ idx,
@@ -109,7 +101,10 @@ int admpc_quad_traj_bank_create(int device, int K, const int32_t* M, const doubl
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     AdmpcQuadTrajBank* b = new (std::nothrow) AdmpcQuadTrajBank();
     QuadTrajDesc* desc = new (std::nothrow) QuadTrajDesc[K];
-    if (!b || !desc) { delete b; delete[] desc; return admpc_set_error(ADMPC_ENOMEM, "out of host memory"); }
+    int32_t* hM = new (std::nothrow) int32_t[K];
+    if (!b || !desc || !hM) { delete b; delete[] desc; delete[] hM; return admpc_set_error(ADMPC_ENOMEM, "out of host memory"); }
+    for (int k = 0; k < K; ++k) hM[k] = M[k];
+    b->h_M = hM;
     const size_t nd = (size_t)K * sizeof(QuadTrajDesc), nx = (size_t)rows * QX * sizeof(double), nu = (size_t)rows * QU * sizeof(double);
     b->device = device; b->K = K; b->rows = rows; b->d_mem = nullptr;
     bool ok = hipMalloc(&b->d_mem, nd + nx + nu) == hipSuccess;
@@ -128,6 +123,7 @@ int admpc_quad_traj_bank_create(int device, int K, const int32_t* M, const doubl
     delete[] desc;
     if (!ok) {
         if (b->d_mem) (void)hipFree(b->d_mem);
+        delete[] b->h_M;
         delete b;
         return admpc_set_error(ADMPC_EHIP, "admpc_quad_traj_bank_create: device allocation or copy failed");
     }
@@ -140,6 +136,7 @@ void admpc_quad_traj_bank_destroy(AdmpcQuadTrajBank* bank)
     if (!bank) return;
     DeviceGuard guard(bank->device);
     if (bank->d_mem) (void)hipFree(bank->d_mem);
+    delete[] bank->h_M;
     delete bank;
 }
 

@@ -115,6 +115,38 @@ class AdmpcQuadTargetParams(C.Structure):
 TARGET_MODES = {"preset": 0, "aggressive": 1, "uniform": 2}
 
 
+class AdmpcQuadTrajSpec(C.Structure):
+    """include/admpc_quad_traj.h: one generated reference trajectory, a loop or a lemniscate that ramps to v_max and back."""
+    _fields_ = [("kind", C.c_int32), ("clockwise", C.c_int32), ("radius", C.c_double), ("z", C.c_double), ("lin_acc", C.c_double),
+                ("v_max", C.c_double)]
+
+
+TRAJ_KINDS = {"loop": 0, "lemniscate": 1}
+QUAD_TRAJ_MAX_M = 16384     # ADMPC_QUAD_TRAJ_MAX_M
+
+
+def quad_traj_specs(kind, v_max, radius=5.0, z=1.0, lin_acc=None, clockwise=True):
+    """(AdmpcQuadTrajSpec * K) of ``QuadFleet.generate_trajectories``'s arguments, each a scalar or a length-K sequence (K: the longest;
+    a scalar goes to all).  ``lin_acc=None`` is 0.25 * v_max, the comparative experiment's choice.  A kind that is not "loop" or
+    "lemniscate" and sequences of different lengths are ValueErrors; the values themselves are the library's to refuse."""
+    cols = {"kind": kind, "v_max": v_max, "radius": radius, "z": z, "lin_acc": lin_acc, "clockwise": clockwise}
+    seq = {k: (list(v) if isinstance(v, (list, tuple, np.ndarray)) else None) for k, v in cols.items()}
+    lens = {len(v) for v in seq.values() if v is not None}
+    if len(lens) > 1 or 0 in lens:
+        raise ValueError("quad_traj_specs: the sequences among the arguments must have one length, at least 1")
+    K = lens.pop() if lens else 1
+    col = {k: (seq[k] if seq[k] is not None else [cols[k]] * K) for k in cols}
+    specs = (AdmpcQuadTrajSpec * K)()
+    for k in range(K):
+        if col["kind"][k] not in TRAJ_KINDS:
+            raise ValueError("quad_traj_specs: kind must be one of %s" % sorted(TRAJ_KINDS))
+        s = specs[k]
+        s.kind, s.clockwise = TRAJ_KINDS[col["kind"][k]], 1 if col["clockwise"][k] else 0
+        s.v_max, s.radius, s.z = float(col["v_max"][k]), float(col["radius"][k]), float(col["z"][k])
+        s.lin_acc = 0.25 * s.v_max if col["lin_acc"][k] is None else float(col["lin_acc"][k])
+    return specs
+
+
 def quad_target_params(mode="aggressive", world_radius=3.0, thresh=0.05, v_max=14.0, max_iters=100, seed=None, n_preset=0):
     """AdmpcQuadTargetParams with the reference's constants (point_tracking_and_record.py:112, :204, :255); every refusal of the header
     is a ValueError here.  ``seed`` (0 .. 2^64 - 1) is needed by the two random modes."""

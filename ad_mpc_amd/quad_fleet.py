@@ -8,7 +8,8 @@ learning.py's), and searches their hyperparameters there (include/admpc_quad_hyp
 as well).  With ``noise_seed`` and a vehicle whose ``noisy`` or ``motor_noise`` is set, the plant is the simulator under its random
 disturbances (include/admpc_quad_noise.h).  With ``set_targets`` the fleet flies the reference's other experiment,
 ``experiments/point_tracking_and_record.py``: every vehicle chases random target points, reached within a threshold that is tested after
-every simulator sub-step, and is recorded over the time it really flew (include/admpc_quad_targets.h)."""
+every simulator sub-step, and is recorded over the time it really flew (include/admpc_quad_targets.h).  ``generate_trajectories`` makes the
+reference's loop and lemniscate trajectories on the device (include/admpc_quad_traj.h); ``set_trajectories`` uploads any others."""
 import ctypes as C
 from collections import namedtuple
 
@@ -19,7 +20,7 @@ from . import _lib
 from .engine import QuadBatchSolver, _ptr
 from .learning import FleetLearning, FleetSearch, placeholder_gps
 from .quad_config import (QNX, QNU, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, default_quad_config, quad_is_noisy, quad_learn_bins,
-                          quad_noise_params, quad_plant_params, quad_target_params, set_quad_gp)
+                          quad_noise_params, quad_plant_params, quad_target_params, quad_traj_specs, set_quad_gp)
 
 QuadRollout = namedtuple("QuadRollout", ("x", "idx", "tally", "counts", "traj", "u"))
 QuadTargetRollout = namedtuple("QuadTargetRollout", ("x", "target", "target_no", "tcounts", "traj", "u", "nsub", "targets"))
@@ -184,9 +185,39 @@ class QuadFleet(FleetLearning):
             self.lib.admpc_quad_traj_bank_destroy(self._bank)
         self._bank, self._M, self._traj = h, np.array([t.shape[0] for t, _ in tr]), tr
 
+    def generate_trajectories(self, kind, v_max, radius=5.0, z=1.0, lin_acc=None, clockwise=True):
+        """K reference trajectories generated on the device (admpc_quad_traj_bank_generate of include/admpc_quad_traj.h): the
+        reference's ``loop_trajectory`` / ``lemniscate_trajectory`` (``kind`` "loop" or "lemniscate") that ramp to ``v_max`` and back,
+        one row per control period, for this fleet's vehicle.  Every argument is a scalar or a length-K sequence; ``lin_acc=None`` is
+        0.25 * v_max.  Replaces the bank as ``set_trajectories`` does; no host copy is kept (``trajectory(k)`` reads one back).  The
+        generation is enqueued on the current stream: work enqueued on it later sees the finished bank."""
+        specs = quad_traj_specs(kind, v_max, radius, z, lin_acc, clockwise)
+        K = len(specs)
+        h = C.c_void_p(0)
+        _lib.check(self.lib.admpc_quad_traj_bank_generate(self.device_index, K, specs, C.byref(self._plant), self.control_period, self._stream(),
+                                                          C.byref(h)))
+        if self._bank:
+            torch.cuda.synchronize(self.device)
+            self.lib.admpc_quad_traj_bank_destroy(self._bank)
+        M = (C.c_int32 * K)()
+        _lib.check(self.lib.admpc_quad_traj_bank_info(h, None, None, M))
+        self._bank, self._M, self._traj = h, np.array(M[:], dtype=np.int64), None
+
+    def trajectory(self, k):
+        """(traj [M,13], u [M,4]) of trajectory k of the bank as numpy arrays (admpc_quad_traj_bank_copy).  Synchronises."""
+        self._need_bank("trajectory")
+        k = int(k)
+        if not 0 <= k < len(self._M):
+            raise ValueError("trajectory: k must be in [0, K)")
+        M = int(self._M[k])
+        traj, u = np.empty((M, QNX)), np.empty((M, QNU))
+        dbl = C.POINTER(C.c_double)
+        _lib.check(self.lib.admpc_quad_traj_bank_copy(self._bank, k, traj.ctypes.data_as(dbl), u.ctypes.data_as(dbl)))
+        return traj, u
+
     def _need_bank(self, who):
         if not self._bank:
-            raise ValueError("%s: call set_trajectories first" % who)
+            raise ValueError("%s: call set_trajectories or generate_trajectories first" % who)
 
     def reset(self, traj_of, idx0=0, x0=None):
         """Vehicle b follows trajectory traj_of[b] from row idx0 (a number or [B]); it starts at x0 [B,13] or, as the reference does, at
@@ -198,13 +229,19 @@ class QuadFleet(FleetLearning):
         if x0 is None:
             if (tk < 0).any() or (tk >= len(self._M)).any() or (i0 < 0).any() or (i0 >= self._M[tk]).any():
                 raise ValueError("reset: x0 is needed for a vehicle whose traj_of or idx0 is out of range")
-            x0 = np.stack([self._traj[k][0][i] for k, i in zip(tk, i0)])
-        x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        if x0.shape != (self.B, QNX):
-            raise ValueError("reset: x0 must be [B,13]")
+            if self._traj is not None:
+                x0 = np.stack([self._traj[k][0][i] for k, i in zip(tk, i0)])
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            if x0.shape != (self.B, QNX):
+                raise ValueError("reset: x0 must be [B,13]")
         self.traj_of.copy_(torch.as_tensor(tk.astype(np.int32)))
         self.idx.copy_(torch.as_tensor(i0.astype(np.int32)))
-        self.x.copy_(torch.as_tensor(x0))
+        if x0 is not None:
+            self.x.copy_(torch.as_tensor(x0))
+        else:                                                                              # a generated bank has no host copy
+            _lib.check(self.lib.admpc_quad_traj_rows_batch(self._bank, self.B, _ptr(self.traj_of), _ptr(self.idx), _ptr(self.x), None,
+                                                           self._stream()))
         for t in (self.x_opt, self.w_opt, self.tally, self.counts, self.cost, self.status, self.iters):
             t.zero_()
 
