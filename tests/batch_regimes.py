@@ -46,6 +46,20 @@ LAUNCH_LINES = (
     ("admpc_quad.hip", "quad_solve", "const bool seg20 = s->cfg.N == 20 && !s->wide20;"),
     ("admpc_quad.hip", "quad_solve", "else if (s->cfg.N * QU > 64)"),
     ("admpc_quad.hip", "quad_solve", "else if (s->cfg.N * QU == 40 && !s->generic)"),
+    # the dispatch of admpc_create / solve_impl that car_routed_spec.car_kernel, split_mode and chunks mirror, and the routed skip of kernel R
+    ("admpc_kernels.hip", "admpc_create", 's->use_dense = (cfg->N == 20) && !(e && strcmp(e, "riccati") == 0);'),
+    ("admpc_kernels.hip", "admpc_create", 's->use_seg = admpc_seg_supports(cfg->N) && (cfg->n_gp == 0 ? !(e && strcmp(e, "riccati") == 0) : (e && strcmp(e, "seg") == 0));'),
+    ("admpc_kernels.hip", "solve_impl", "const bool dense = s->use_dense && !snap && !(nsqp > 1 && s->cfg.sqp_tol > 0.0);"),
+    ("admpc_kernels.hip", "solve_impl", "if (s->use_seg && !snap && !(nsqp > 1 && s->cfg.sqp_tol > 0.0)) {"),
+    ("admpc_kernels.hip", "rowqp_chunk", "if (s->row_chunk > 0 && (unsigned long long)s->row_chunk < m) m = (unsigned long long)s->row_chunk;"),
+    ("admpc_kernels.hip", "rowqp_chunk", "const unsigned long long per = (unsigned long long)(N + 1) * 42ull * (unsigned long long)elem;"),
+    ("admpc_kernels.hip", "admpc_create", "s->split_mode = e && e[0] == '0' ? 0 : (e && e[0] == '1' ? 1 : -1);"),
+    ("admpc_kernels.hip", "admpc_create", "s->row_chunk = c ? atoi(c) : 0;"),
+    ("admpc_seg.hip", "admpc_seg_supports", "return N == 40 || N == 60 || N == 80;"),
+    ("admpc_kernels.hip", "solve_rows", "const int first = (sq == 0 && !routed) ? 1 : 0;"),
+    ("admpc_kernels.hip", "solve_rows", "first ? (const int32_t*)nullptr : (const int32_t*)cst, (T*)s->d_GT, (T*)s->d_bl, s->d_sched);"),
+    ("admpc_rowqp.hip", "admpc_rowqp_kernel", "if (!first_pass) valid = valid && statusg[ic] == 0;"),
+    ("admpc_rowqp.hip", "admpc_rowqp_kernel", "int ic = inst < total && has_lds ? inst : total - 1;"),
 )
 
 
