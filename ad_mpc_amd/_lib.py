@@ -193,6 +193,15 @@ _QUAD_TRAJ = {      # include/admpc_quad_traj.h: the phase lengths on the host, 
 }
 QUAD_TRAJ_EXPORTS = tuple(_QUAD_TRAJ)
 TRAJ_TABLES = {"admpc_quad_traj.h": _QUAD_TRAJ}
+# references through keyframes generated on the device, declared by load() in the same way
+hd_ = C.POINTER(C.c_double)
+_QUAD_POLY_TRAJ = {  # include/admpc_quad_poly_traj.h: s and M on the host, the fit's weight matrix on the host, a bank of piecewise polynomials through keyframes
+    "admpc_quad_poly_traj_lengths": (I, [D, I, hd_, D, fp, fp]),
+    "admpc_quad_poly_traj_weights": (I, [I, hd_]),
+    "admpc_quad_poly_traj_bank_generate": (I, [I, I, I, hd_, hd_, pp, D, vp, hp]),
+}
+QUAD_POLY_TRAJ_EXPORTS = tuple(_QUAD_POLY_TRAJ)
+POLY_TRAJ_TABLES = {"admpc_quad_poly_traj.h": _QUAD_POLY_TRAJ}
 
 _lib = None
 
@@ -212,7 +221,7 @@ def load():
     L = C.CDLL(LIB_PATH)
     for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()) + \
             list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()) + list(PRUNE_TABLES.values()) + list(EVAL_TABLES.values()) + \
-            list(TRAJ_TABLES.values()):
+            list(TRAJ_TABLES.values()) + list(POLY_TRAJ_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -147,6 +147,25 @@ def quad_traj_specs(kind, v_max, radius=5.0, z=1.0, lin_acc=None, clockwise=True
     return specs
 
 
+QUAD_POLY_TRAJ_KEYS = (3, 32)     # ADMPC_QUAD_POLY_TRAJ_MIN_KEYS, ADMPC_QUAD_POLY_TRAJ_MAX_KEYS
+
+
+def quad_poly_traj_args(keyframes, speed):
+    """(keys float64 [K,n_key,3] C-contiguous, speed float64 [K]) of ``QuadFleet.generate_polynomial_trajectories``'s arguments:
+    keyframes [K,n_key,3] or [n_key,3] (K: the speed's length then, or 1), speed a scalar or a length-K sequence.  Shapes that do not fit
+    are ValueErrors; the values themselves are the library's to refuse (include/admpc_quad_poly_traj.h)."""
+    keys = np.array(keyframes, dtype=np.float64)
+    sp = np.array(speed, dtype=np.float64)
+    if sp.ndim > 1 or keys.ndim not in (2, 3) or keys.shape[-1] != 3 or keys.shape[-2] < 1:
+        raise ValueError("quad_poly_traj_args: keyframes are [K,n_key,3] or [n_key,3], speed a scalar or [K]")
+    if keys.ndim == 2:
+        keys = np.broadcast_to(keys, (sp.shape[0] if sp.ndim else 1,) + keys.shape)
+    K = keys.shape[0]
+    if K < 1 or (sp.ndim == 1 and sp.shape[0] != K):
+        raise ValueError("quad_poly_traj_args: speed must be a scalar or have one entry per trajectory, at least one")
+    return np.ascontiguousarray(keys), np.ascontiguousarray(np.broadcast_to(sp, (K,)))
+
+
 def quad_target_params(mode="aggressive", world_radius=3.0, thresh=0.05, v_max=14.0, max_iters=100, seed=None, n_preset=0):
     """AdmpcQuadTargetParams with the reference's constants (point_tracking_and_record.py:112, :204, :255); every refusal of the header
     is a ValueError here.  ``seed`` (0 .. 2^64 - 1) is needed by the two random modes."""

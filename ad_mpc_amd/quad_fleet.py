@@ -9,7 +9,9 @@ as well).  With ``noise_seed`` and a vehicle whose ``noisy`` or ``motor_noise`` 
 disturbances (include/admpc_quad_noise.h).  With ``set_targets`` the fleet flies the reference's other experiment,
 ``experiments/point_tracking_and_record.py``: every vehicle chases random target points, reached within a threshold that is tested after
 every simulator sub-step, and is recorded over the time it really flew (include/admpc_quad_targets.h).  ``generate_trajectories`` makes the
-reference's loop and lemniscate trajectories on the device (include/admpc_quad_traj.h); ``set_trajectories`` uploads any others."""
+reference's loop and lemniscate trajectories on the device (include/admpc_quad_traj.h), ``generate_random_trajectories`` and
+``generate_polynomial_trajectories`` its random and any other trajectories through keyframes (include/admpc_quad_poly_traj.h);
+``set_trajectories`` uploads any others."""
 import ctypes as C
 from collections import namedtuple
 
@@ -20,7 +22,8 @@ from . import _lib
 from .engine import QuadBatchSolver, _ptr
 from .learning import FleetLearning, FleetSearch, placeholder_gps
 from .quad_config import (QNX, QNU, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, default_quad_config, quad_is_noisy, quad_learn_bins,
-                          quad_noise_params, quad_plant_params, quad_target_params, quad_traj_specs, set_quad_gp)
+                          quad_noise_params, quad_plant_params, quad_poly_traj_args, quad_target_params, quad_traj_specs, set_quad_gp)
+from .quad_keyframes import random_keyframes
 
 QuadRollout = namedtuple("QuadRollout", ("x", "idx", "tally", "counts", "traj", "u"))
 QuadTargetRollout = namedtuple("QuadTargetRollout", ("x", "target", "target_no", "tcounts", "traj", "u", "nsub", "targets"))
@@ -196,6 +199,31 @@ class QuadFleet(FleetLearning):
         h = C.c_void_p(0)
         _lib.check(self.lib.admpc_quad_traj_bank_generate(self.device_index, K, specs, C.byref(self._plant), self.control_period, self._stream(),
                                                           C.byref(h)))
+        self._take_generated(h, K)
+
+    def generate_polynomial_trajectories(self, keyframes, speed):
+        """K reference trajectories through keyframes generated on the device (admpc_quad_poly_traj_bank_generate of
+        include/admpc_quad_poly_traj.h): the piecewise degree-7 polynomial the reference's ``random_trajectory`` and
+        ``straight_trajectory`` fit through their position keyframes, flown at the average ``speed``, one row per control period, for this
+        fleet's vehicle.  ``keyframes`` [K,n_key,3] or [n_key,3] (3 <= n_key <= 32), ``speed`` a scalar or a length-K sequence.  Replaces the
+        bank as ``generate_trajectories`` does: no host copy is kept, ``reset`` takes its start rows from the device, and the generation
+        is enqueued on the current stream."""
+        keys, sp = quad_poly_traj_args(keyframes, speed)
+        K = keys.shape[0]
+        dbl = C.POINTER(C.c_double)
+        h = C.c_void_p(0)
+        _lib.check(self.lib.admpc_quad_poly_traj_bank_generate(self.device_index, K, keys.shape[1], keys.ctypes.data_as(dbl), sp.ctypes.data_as(dbl),
+                                                               C.byref(self._plant), self.control_period, self._stream(), C.byref(h)))
+        self._take_generated(h, K)
+
+    def generate_random_trajectories(self, seeds, speed):
+        """The reference's ``random_trajectory(quad, control_period, seed, speed)`` (map_name=None) for every seed of ``seeds`` (a number or
+        a sequence): ``random_keyframes(seed)`` on the host, then ``generate_polynomial_trajectories``."""
+        seeds = np.atleast_1d(np.asarray(seeds))
+        self.generate_polynomial_trajectories(np.stack([random_keyframes(int(sd)) for sd in seeds]), speed)
+
+    def _take_generated(self, h, K):
+        """The generated bank h of K trajectories replaces the fleet's bank; its lengths are read from the library."""
         if self._bank:
             torch.cuda.synchronize(self.device)
             self.lib.admpc_quad_traj_bank_destroy(self._bank)

@@ -18,8 +18,10 @@
  *   experiments/trajectory_test.py:72-90, comparative_experiment.py  the trajectory a run flies   the generated bank
  *
  * DEVIATIONS, all deliberate: gravity is the literal 9.81 of trajectories.py:154 and NOT plant->g; `clockwise` is honoured for both
- * kinds (the reference's lemniscate ignores its flag: it is the clockwise one here); the yawing branch, random_trajectory and the map
- * limits are NOT offered.
+ * kinds (the reference's lemniscate ignores its flag: it is the clockwise one here); the yawing branch and the map limits are NOT
+ * offered.  The reference's random_trajectory and straight_trajectory, piecewise polynomials through keyframes, are
+ * admpc_quad_poly_traj.h's: their banks are this header's, and steps 4 .. 9 below and the passes B, C, D are theirs too (ONE text,
+ * csrc/quad_traj_tail_dev.h).
  *
  * THE RULE.  For one trajectory let a = lin_acc / radius, M = n[0] + .. + n[4] its rows, i the row and j the row's index within its
  * phase.  t_total = 2 * v_max / lin_acc + 2 * 2, coasting = (t_total - 4 * 2) / 2, and the phases stop at 2, coasting, 4, coasting, 2:
