@@ -202,6 +202,12 @@ _QUAD_POLY_TRAJ = {  # include/admpc_quad_poly_traj.h: s and M on the host, the 
 }
 QUAD_POLY_TRAJ_EXPORTS = tuple(_QUAD_POLY_TRAJ)
 POLY_TRAJ_TABLES = {"admpc_quad_poly_traj.h": _QUAD_POLY_TRAJ}
+# the training points of every regressor picked from the log, declared by load() in the same way
+_QUAD_SELECT = {    # include/admpc_quad_select.h: per (cluster, regressor, bin) the median record of the reference's distance_maximizing_points_1d, into the bins the fit reads
+    "admpc_quad_ensemble_select_points": (I, [vp, C.c_int64, dp, fp, ip, dp, ip, dp, ip, ip, vp]),
+}
+QUAD_SELECT_EXPORTS = tuple(_QUAD_SELECT)
+SELECT_TABLES = {"admpc_quad_select.h": _QUAD_SELECT}
 
 _lib = None
 
@@ -221,7 +227,7 @@ def load():
     L = C.CDLL(LIB_PATH)
     for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()) + \
             list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()) + list(PRUNE_TABLES.values()) + list(EVAL_TABLES.values()) + \
-            list(TRAJ_TABLES.values()) + list(POLY_TRAJ_TABLES.values()):
+            list(TRAJ_TABLES.values()) + list(POLY_TRAJ_TABLES.values()) + list(SELECT_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -208,6 +208,33 @@ def quad_learn_bins(learn):
     return learn_bins(learn, feat_range=(7, QNX + QNU - 1), out_range=(7, 9), gp_max=QUAD_GP_MAX)
 
 
+def select_request(blocks, n_points=None):
+    """``n_points`` of ``QuadEnsembleFleet.select_points`` checked as admpc_quad_ensemble_select_points checks it
+    (include/admpc_quad_select.h), for the K blocks ``blocks`` of a fleet that learns ([(AdmpcGpBins array, n_gp)] of
+    ``ensemble_layout``): a scalar, one value per regressor, or None for each regressor's nbins.  Returns QUAD_GP_MAX ints, the
+    entries past n_gp zero.  Raises ValueError; needs no GPU."""
+    n = blocks[0][1]
+    for bins, _ in blocks:
+        if any(int(bins[g].n_feat) != 1 for g in range(n)):
+            raise ValueError("select_points: a regressor with more than one feature: the selection is offered for one-feature regressors")
+    most = [min(GP_MAX_POINTS, min(int(bins[g].nb[0]) * int(bins[g].nb[1]) * int(bins[g].nb[2]) for bins, _ in blocks)) for g in range(n)]
+    if n_points is None:
+        want = list(most)
+    else:
+        want = np.atleast_1d(np.asarray(n_points)).reshape(-1)
+        if want.size == 1:
+            want = np.repeat(want, n)
+        if want.size != n:
+            raise ValueError("select_points: n_points must be a scalar or one value per regressor (%d)" % n)
+        if any(int(w) != w for w in want):
+            raise ValueError("select_points: n_points must be whole numbers")
+        want = [int(w) for w in want]
+    for g in range(n):
+        if not 1 <= want[g] <= most[g]:
+            raise ValueError("select_points: n_points of regressor %d must be in 1 .. %d (min(32, its nbins)), got %d" % (g, most[g], want[g]))
+    return want + [0] * (QUAD_GP_MAX - n)
+
+
 class SimQuad:
     """The attributes of the reference's ``Quadrotor3D`` (quad_3d.py:22-95) that the plant reads, with its values: the vehicle of
     ``quad_plant_params(None, ...)`` and of the tests."""

@@ -14,7 +14,7 @@ from .config import AdmpcGp, AdmpcGpSearchParams, GP_HYPER, GP_MAX_POINTS, GP_SE
 from .engine import QuadBatchSolver, _ptr
 from .learning import decode_gps, hyper_dicts, placeholder_gps
 from .quad_3d_optimizer import QuadGPEnsemble
-from .quad_config import QNX, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, quad_learn_bins
+from .quad_config import QNX, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, quad_learn_bins, select_request
 from .quad_fleet import QuadFleet, fleet_quad_config
 
 QuadEnsembleRollout = namedtuple("QuadEnsembleRollout", ("x", "idx", "tally", "counts", "traj", "u", "routes"))
@@ -25,6 +25,7 @@ CLUSTERS_MAX = 8
 GMM_BLOCKS_MAX, GMM_ROW, GMM_PARTIAL, GMM_ENOVALID = 256, 18, 81, -100                  # include/admpc_quad_clusters.h
 PRUNE_BINS_MAX, PRUNE_PARTIAL, RDRV_PARTIAL, PRUNE_ENOVALID, REC_PRUNED = 256, 9, 7, -100, 2.0        # include/admpc_quad_prune.h
 EVAL_FACTOR, EVAL_STATS, EVAL_ENOVALID = 672, 8, -100                                    # include/admpc_quad_eval.h
+SELECT_WORK, SELECT_ENOVALID = 201376, -100                                              # include/admpc_quad_select.h
 
 
 def ensemble_layout(centroids, feats, learn=None):
@@ -181,7 +182,12 @@ class QuadEnsembleFleet(QuadFleet):
     The chain closes with the evaluation of what was learned (include/admpc_quad_eval.h): ``fit_gp(factor=True)`` or
     ``search_gp(factor=True)`` -> ``log_reset()`` -> ``rollout(T, observe=True, log=True)`` again -> ``evaluate_log()`` -> ``evaluation()``.
     ``factor`` [K,3,672] holds every regressor factored once (alpha and W = L^-1), ``eval_stats`` [K,3,8] and ``eval_info`` [4] the sums
-    and the counts of the last evaluation, ``eval_per_record`` the mean and the standard deviation of every record once asked for."""
+    and the counts of the last evaluation, ``eval_per_record`` the mean and the standard deviation of every record once asked for.
+
+    Between the clusters and the fit, ``select_points()`` trains every GP on real records picked from the log as the reference picks
+    them, in place of the bin means (include/admpc_quad_select.h): ``rollout(T, observe=True, log=True)`` -> ``prune_log()`` ->
+    ``fit_clusters()`` -> ``select_points()`` -> ``search_gp(factor=True)`` -> ``evaluate_log()``.  ``sel`` [K,3,32] and ``select_info``
+    [K,3,4] are its results; it overwrites ``bins``, which ``rebin()`` restores."""
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
                  ensemble=None, centroids=None, feats=None, learn=None, rdrv_d_mat=None, device=0, observe_substeps=1, noise_seed=None,
@@ -261,6 +267,12 @@ class QuadEnsembleFleet(QuadFleet):
             self._eval_partial, self.eval_stats = z(GMM_BLOCKS_MAX, self.K * QUAD_GP_MAX * EVAL_STATS), z(self.K, QUAD_GP_MAX, EVAL_STATS)
             self.eval_info, self.eval_per_record = z(4, dtype=torch.int32), None
             self._has_factor = self._has_rdrv = self._evaluated = False
+            # the training points picked from the log (include/admpc_quad_select.h): the work area, the edges, results
+            self._blocks = blocks
+            self._select_code, self._select_work = z(self.log_steps * self.B, dtype=torch.int32), z(SELECT_WORK, dtype=torch.int32)
+            self.select_edges = z(self.K, QUAD_GP_MAX, GP_MAX_POINTS + 1)
+            self.sel = torch.full((self.K, QUAD_GP_MAX, GP_MAX_POINTS), -1, dtype=torch.int32, device=self.device)
+            self.select_info = z(self.K, QUAD_GP_MAX, 4, dtype=torch.int32)
 
     # -- lifetime ---------------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -369,6 +381,51 @@ class QuadEnsembleFleet(QuadFleet):
         if rebin:
             self.rebin()
         return self.prune_info
+
+    def select_points(self, n_points=None):
+        """The training points of every regressor of every cluster picked from the logged records, as the reference's
+        distance_maximizing_points_1d picks them (admpc_quad_ensemble_select_points; include/admpc_quad_select.h has the rule): a
+        histogram of ``n_points`` bins over the feature values of the cluster's records with flag 1.0, and the median record of every
+        bin that is not empty.  ``n_points``: a scalar, one value per regressor, or None for each regressor's nbins; at most
+        min(32, nbins).  Every regressor must have ONE feature.  ``bins`` is OVERWRITTEN: a row per selected record, with count 1, so
+        ``fit_gp()``, ``search_gp()``, ``factor_gp()`` and ``evaluate_log()`` follow unchanged with min_count=1.  ``rebin()``,
+        ``prune_log(rebin=True)`` and ``fit_clusters(rebin=True)`` go back to the bin means.  An observed flight after a selection adds
+        its sums to rows that hold single records: re-bin or select again before the next fit.  One chain of 22 launches on the stream,
+        asynchronous; returns the device tensors (sel int32 [K, n, 32]: the record index t * B + b per bin, -1 for an empty bin or one
+        past n_points; info int32 [K, n, 4]: the points, the cluster's records that took part, the empty bins, the status)."""
+        self._learns("select_points")
+        if not self.log_steps:
+            raise ValueError("select_points: this fleet keeps no log, create it with log_steps")
+        want = select_request(self._blocks, n_points)
+        if self.log_count < 1:
+            raise ValueError("select_points: the log is empty: fly rollout(T, observe=True, log=True) first")
+        _lib.check(self.lib.admpc_quad_ensemble_select_points(self._ens, self.log_count * self.B, _ptr(self.log), (C.c_int32 * QUAD_GP_MAX)(*want),
+                                                              _ptr(self._select_code), _ptr(self.select_edges), _ptr(self._select_work),
+                                                              _ptr(self.bins), _ptr(self.sel), _ptr(self.select_info), self._stream()))
+        self._selected = True
+        return self.sel[:, :self.n_learn], self.select_info[:, :self.n_learn]
+
+    def selected_points(self):
+        """The last ``select_points`` as numpy (synchronises): K lists of one dict per regressor with ``index`` (the record indices in
+        ascending bin order), ``z`` and ``y`` (the records' feature and target), ``bins`` (the bin of every point), ``took_part``,
+        ``empty`` and ``status``."""
+        self._learns("selected_points")
+        if not getattr(self, "_selected", False):
+            raise ValueError("selected_points: nothing selected yet: call select_points() first")
+        torch.cuda.current_stream(self.device).synchronize()
+        sel, info = self.sel.cpu().numpy(), self.select_info.cpu().numpy()
+        log = self.log.reshape(-1, QUAD_REC).cpu().numpy()
+        out = []
+        for c in range(self.K):
+            row = []
+            for g in range(self.n_learn):
+                gp = self._blocks[c][0][g]
+                at = np.flatnonzero(sel[c, g] >= 0)
+                idx = sel[c, g, at].astype(np.int64)
+                row.append({"index": idx, "z": log[idx, int(gp.feat[0]) - 7].copy(), "y": log[idx, 10 + int(gp.out) - 7].copy(), "bins": at,
+                            "took_part": int(info[c, g, 1]), "empty": int(info[c, g, 2]), "status": int(info[c, g, 3])})
+            out.append(row)
+        return out
 
     def fit_rdrv(self, axes=(7, 8, 9), install=True):
         """Faessler's diagonal linear drag from the logged records with flag 1.0 (admpc_quad_rdrv_fit: D_i = sum v_b,i y_i / sum v_b,i^2

@@ -29,7 +29,8 @@
  *     (gp.py:436-441).  Here the variance is CLIPPED at 0, std = sqrt(max(var, 0)), and every clip is counted (stats entry 7);
  *   - covariance propagation through the horizon (the reference raises NotImplementedError there with a GP, quad_3d_opt_utils.py:123);
  *   - sample_y, the plots and the dense-GP resampling of gp_visualization.py;
- *   - training-point selection (distance_maximizing_points): the points are the means of the bins, as in every fit here;
+ *   - training-point selection (distance_maximizing_points) by THESE entries: they factor whatever the bins hold, the means of a grid or
+ *     the records that admpc_quad_select.h picks from the log;
  *   - a log for QuadFleet and for flights to targets: the entries work on ANY array of records, the fleet that keeps one is the
  *     clustered ensemble's;
  *   - the car.
