@@ -43,6 +43,13 @@
 //     (same-line atomics retire at ~10 ns: 35 % slower), and compare-and-swap pops took 35 ms per step.
 //   - the expansion's LDS reads where hipcc puts them, three waits for reads of its own stage in every stage of the recursion: 40 % more
 //     wave time in phase E on a lone wave, 1.2 % per step at configs[1] (profiles/r4/f20_expand_ring.txt).
+//   - the predictor and the corrector of an interior-point iteration as two straight-line sections of one always-inline lambda instead of a
+//     loop of two trips (whose carried state hipcc moves through 18 + 18 + 13 v_mov_b64 per iteration): the copies fall to 10, but the
+//     results are no longer the parent's bits (1e-13 on u; statuses and iteration counts identical).  The loop keeps six pass-invariant
+//     products (G0 rd0 ... G6 Drd1) hoisted and rounded on their own and computes t lam of the centring step in a block of its own;
+//     straight-line, hipcc contracts them into other multiply-adds.  Pinning the six products was not enough; reproducing every
+//     contraction by hand was not attempted.  Laundering the state at the back edge moves the copies (8 + 36 + 8), it does not remove them
+//     (profiles/r4/f20_valu_diet.txt).
 //   - wave-priority classes, a reversed ticket order for the second wave of a SIMD, a trap on the never-taken side of the per-stage
 //     block test, other rungs of the priority ladder (see phase D for the measured ones).
 #include <hip/hip_runtime.h>
@@ -56,6 +63,16 @@ namespace {
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 #include "cond_common.h"      // dimensions, model_dev.h, dense40.h, LAUNDER_LANE / LAUNDER_CFG, staging, slot fetch
+
+// LDS access through a byte address held in a register plus a compile-time byte offset (the instruction's offset: field): the stage chains
+// of phases C and E form their per-lane addresses once per instance and launder them -- built from indices into lds_raw, hipcc
+// rematerialises every address from literals in every stage block (machine LICM is off for this unit, see the Makefile)
+typedef __attribute__((address_space(3))) double lds_f64;
+typedef double d2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) d2 lds_f64x2;
+__device__ __forceinline__ double lds_ld(const unsigned a, const int off) { return *reinterpret_cast<const lds_f64*>((size_t)(a + (unsigned)off)); }
+__device__ __forceinline__ double2 lds_ld2(const unsigned a, const int off) { const d2 v = *reinterpret_cast<const lds_f64x2*>((size_t)(a + (unsigned)off)); return make_double2(v.x, v.y); }
+__device__ __forceinline__ void lds_st(const unsigned a, const int off, const double v) { *reinterpret_cast<lds_f64*>((size_t)(a + (unsigned)off)) = v; }
 
 // ---- optional per-phase wave-time accounting (build with -DADMPC_PHASE_TIMERS: `make timers`): s_memtime ticks (100 MHz) summed
 //      over all waves: 0 ticket draw, 1 A1 (state RK4 + model), 2 A2 (sensitivity columns), 3 C (condensing), 4 D trial,
@@ -97,7 +114,7 @@ __device__ unsigned long long g_f20_ticks[16];
 //   A   JT [0, 1960) Jacobian tables of the RK stages (over GT, H/L, park; clear of bl and the scheduler table); GT is written when the
 //       tables are dead
 //   C   dq [860, 1008), gam [1008, 1520) in the H/L buffer (dead until the row store of H behind the last stage)
-//   E   dq -> dx [860, 1008), du [1008, 1072), dump [1072, 1276) in the H/L buffer (dead behind the interior point)
+//   E   dq -> dx [860, 1008), du [1008, 1072), dump [1072, 1276), zeros [1276, 1468) in the H/L buffer (dead behind the interior point)
 // Banks: the tables keep stride 98; GT, dq, gam keep their offsets; H/L moves by 840 doubles as a whole (16-byte aligned: the
 // LDS-DMA destination), which keeps the triangular row starts' conflict-free pattern.
 struct FusedLds {
@@ -110,10 +127,12 @@ struct FusedLds {
                                                                         // 768 B apart the 20 stages of a table access all hit one bank group
     static constexpr int oJT = 0, oDqC = 860, oGam = oDqC + 148;
     static constexpr int oDumpE = oGam + 64;                            // phase E: where lanes that hold no state store (behind du, per stage + 7)
+    static constexpr int oZeroE = oDumpE + 64 + N * NX, nZeroE = 192;   // phase E: zeros, what lanes >= 7 read for b_k and du (offsets up to (N - 1) * NX)
     static_assert(oJT + N * JTK <= oBl, "LDS aliases: phase A's tables end before bl and the scheduler table");
     static_assert(oGT + N * GTS <= oH, "LDS aliases: GT survives phases C, D, E (clear of H/L, park and the exchange buffers)");
     static_assert(oDqC >= oH && oDqC + (N + 1) * NX <= oGam && oGam + (NX + 1) * 64 <= oH + NTRI, "LDS aliases: dq, gam (phase C), dx, du (phase E) inside H/L");
     static_assert(oDumpE >= oGam + 64 && oDumpE + 64 + N * NX <= oH + NTRI, "LDS aliases: phase E's dump area behind du, inside H/L");
+    static_assert(oZeroE >= oDumpE + 64 + N * NX && oZeroE + nZeroE <= oH + NTRI && (N - 1) * NX + 1 <= nZeroE && 2 * N <= nZeroE, "LDS aliases: phase E's zeros behind the dump area, inside H/L");
     static_assert(oBl >= oCb + 4 * 64 && oBl + N * NX <= oSch && oSch + 64 <= total, "LDS aliases: bl, scheduler table");
     static_assert(oH % 2 == 0 && oCb % 2 == 0, "16-byte alignment: LDS-DMA destination, double2 exchange");
     static_assert(8 * total * 8 <= 160 * 1024, "eight instances per CU");
@@ -394,6 +413,26 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                 });
             }
             gam[7 * 64 + lane] = 0.0;                                // the zero row (gam has room for an eighth row)
+            // What a stage addresses per lane does not change during the instance, or changes from stage to stage by a compile-time
+            // constant: formed here once, as LDS byte addresses, and laundered; a stage adds offsets only and keeps one compare and one
+            // select for "is this my stage".
+            //   a_bown  the lane's own column of B_k (its stage is ki), a_zero the zero row, a_bl / a_bls base and stride of lane 40's b_k
+            //   (the zero row and 0 elsewhere), a_aq the two A_k operand reads, a_gst the gam store, a_uni the uniform reads (dq, what lane 40
+            //   published in gam), a_cr the MFMA operand reads crow * 64 + r16, h6 the lane's entry of row 6 of B
+            unsigned a_bown = lds_byte_addr(GT + ki * GTS + 5 * 6 + 6 * ji), a_zero = lds_byte_addr(gam + 7 * 64);
+            unsigned a_bl = lane == n ? lds_byte_addr(bl) : a_zero;
+            int a_bls = lane == n ? 7 * 8 : 0;
+            unsigned a_aq0 = lds_byte_addr(GT + r16), a_aq1 = lds_byte_addr(GT + 16 + (r16 < 14 ? r16 : 13));
+            unsigned a_gst = lds_byte_addr(gam + lane), a_uni = lds_byte_addr(gam + n) - 3 * 512;
+            unsigned a_cr[NSTEP];
+#pragma unroll
+            for (int st_ = 0; st_ < NSTEP; ++st_) { a_cr[st_] = lds_byte_addr(gam + crow[st_] * 64 + r16); asm volatile("" : "+v"(a_cr[st_])); }
+            double h6 = ji ? h : 0.0;
+            asm volatile("" : "+v"(a_bown), "+v"(a_zero), "+v"(a_bl), "+v"(a_bls), "+v"(a_aq0), "+v"(a_aq1), "+v"(a_gst), "+v"(a_uni), "+v"(h6));
+            // (a_uni: three rows of gam in front of gam[0][n], so that the reads of gam[c][n] are whole multiples of 512 B away from it -- what
+            // ds_read2st64_b64 encodes without an address add -- and dq stays inside the 8-bit offsets of ds_read2_b64)
+            constexpr int oUniGam = (3 * 64 - n) * 8, oUniDq = oUniGam - (FusedLds::oGam - FusedLds::oDqC) * 8;      // gam[0][0] and dq[0] seen from a_uni
+            static_assert(oUniDq >= 0 && oUniDq + ((N + 1) * NX - 1) * 8 <= 255 * 8, "phase C: dq within ds_read2_b64's offsets from a_uni");
             d4 acc[3][3];
 #pragma unroll
             for (int I = 0; I < 3; ++I)
@@ -417,16 +456,15 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                 double2 Bv[3]; double blv[NX], Aq[2];
                 const bool mine_p = ki == k;
                 if constexpr (k < N) {
-                    const double* Gk = GT + k * GTS;
-                    // (indices into the one LDS array, not selected pointers: hipcc turns a select of two LDS pointers into flat pointers and
+                    // (32-bit LDS addresses, not selected pointers: hipcc turns a select of two LDS pointers into flat pointers and
                     // converts every element address back with a null check -- five scalar instructions per load)
-                    const int bidx = mine_p ? FusedLds::oGT + k * GTS + 5 * 6 + 6 * ji : FusedLds::oGam + 7 * 64;
-                    { const int e16 = lane & 15; Aq[0] = Gk[e16]; Aq[1] = Gk[16 + (e16 < 14 ? e16 : 13)]; }
+                    const unsigned baddr = mine_p ? a_bown : a_zero;
+                    Aq[0] = lds_ld(a_aq0, k * GTS * 8); Aq[1] = lds_ld(a_aq1, k * GTS * 8);
 #pragma unroll
-                    for (int q_ = 0; q_ < 3; ++q_) Bv[q_] = *reinterpret_cast<const double2*>(lds_raw + bidx + 2 * q_);
-                    const int lidx = lane == n ? FusedLds::oBl + k * 7 : FusedLds::oGam + 7 * 64;      // b_k for the column of the free response, zeros for the others
+                    for (int q_ = 0; q_ < 3; ++q_) Bv[q_] = lds_ld2(baddr, 16 * q_);
+                    const unsigned laddr = a_bl + (unsigned)__mul24(a_bls, k);      // b_k for the column of the free response, zeros for the others
 #pragma unroll
-                    for (int r = 0; r < NX; ++r) blv[r] = lds_raw[lidx + r];
+                    for (int r = 0; r < NX; ++r) blv[r] = lds_ld(laddr, 8 * r);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if constexpr (k >= 1) {
@@ -435,19 +473,19 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                         if constexpr ((QMASK >> c) & 1) {
                             const double w = k < N ? Qd[c] : Qe[c];
                             wg[c] = w * g[c];
-                            gam[c * 64 + lane] = g[c];
+                            lds_st(a_gst, c * 512, g[c]);
                         }
                     });
-                    if constexpr (!((QMASK >> 6) & 1)) gam[6 * 64 + lane] = g[6];      // xhat_k[6] for the steering rows
+                    if constexpr (!((QMASK >> 6) & 1)) lds_st(a_gst, 6 * 512, g[6]);      // xhat_k[6] for the steering rows
                     static_for<0, NX>([&](auto cc) __attribute__((always_inline)) {
                         constexpr int c = decltype(cc)::value;
-                        if constexpr ((QMASK >> c) & 1) g0 += wg[c] * (gam[c * 64 + n] + dqC[k * 7 + c]);      // lane 40 has just published xhat_k[c]
+                        if constexpr ((QMASK >> c) & 1) g0 += wg[c] * (lds_ld(a_uni, oUniGam + (c * 64 + n) * 8) + lds_ld(a_uni, oUniDq + (k * 7 + c) * 8));      // lane 40 has just published xhat_k[c]
                     });
-                    { double x6 = gam[6 * 64 + n]; asm volatile("" : "+v"(x6)); xh6_own = lane == k ? x6 : xh6_own; }      // (an unconditional load)
+                    { double x6 = lds_ld(a_uni, oUniGam + (6 * 64 + n) * 8); asm volatile("" : "+v"(x6)); xh6_own = lane == k ? x6 : xh6_own; }      // (an unconditional load)
 #pragma unroll
                     for (int st_ = 0; st_ < NSTEP; ++st_)
 #pragma unroll
-                        for (int m = 0; m < nblk; ++m) blk[st_][m] = gam[crow[st_] * 64 + 16 * m + r16];
+                        for (int m = 0; m < nblk; ++m) blk[st_][m] = lds_ld(a_cr[st_], 16 * m * 8);
                 }
                 if constexpr (k < N) {
                     // The inputs of stage k enter with B_k: lanes 2k, 2k + 1 (whose column of Gamma is still zero) start the product from
@@ -457,7 +495,7 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
 #pragma unroll
                     for (int r = 0; r < 6; r += 2) { gn[r] = Bv[r / 2].x; gn[r + 1] = Bv[r / 2].y; }
                     gn[0] += g[0]; gn[1] += g[1];
-                    gn[6] = mine ? (ji ? h : 0.0) : g[6];
+                    gn[6] = mine ? h6 : g[6];
 #pragma unroll
                     for (int r = 0; r < NX; ++r) gn[r] += blv[r];                  // b_k in lane 40, + 0.0 elsewhere
                     static_for<0, 5>([&](auto cc) __attribute__((always_inline)) {
@@ -826,6 +864,8 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             stage_dq<N>(dqE, xbg, yrg, yrefeg + (size_t)inst * NX, lane);
             du = uact ? du : 0.0;
             dus[lane] = du;
+#pragma unroll
+            for (int q_ = 0; q_ < FusedLds::nZeroE; q_ += WAVE) lds_raw[FusedLds::oZeroE + q_ + lane] = 0.0;
             const double ubar_i = ubg[sc];
             const double uref_i = yrg[(sc >> 1) * 9 + 7 + (sc & 1)];
             double dx = lane < NX ? x0g[(size_t)inst * NX + r7] - xbg[r7] : 0.0;      // dx_0 (lanes 0..6)
@@ -848,6 +888,12 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
             struct ERing { double dq, bk, g[5], b0, b1, u0, u1; };
             ERing ring[E_RING];
             const int sidx = lane < NX ? FusedLds::oDqC + lane : FusedLds::oDumpE + lane;
+            // Lanes >= 7 read b_k and du from the zeros and hold 0.0 in h6: their row-6 value fma(0.0, 0.0, 0.0 + 0.0) is exactly 0.0 whatever the
+            // other lanes hold, so the next dx is ONE select (rows 0..5 or row 6) instead of two.  The addresses are formed once and laundered.
+            unsigned a_bk = lds_byte_addr(lane < NX ? bl + lane : lds_raw + FusedLds::oZeroE);
+            unsigned a_du = lds_byte_addr(lane < NX ? dus : lds_raw + FusedLds::oZeroE);
+            double h6 = lane == 6 ? h : 0.0;
+            asm volatile("" : "+v"(a_bk), "+v"(a_du), "+v"(h6));
             auto e_read = [&](auto kc) __attribute__((always_inline)) {
                 constexpr int k = decltype(kc)::value;
                 ERing& r = ring[k % E_RING];
@@ -856,8 +902,8 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     const double* Gk = GT + k * GTS;
                     // rows 0..5 from the packed record; every lane loads (lanes >= 6 read row 0 and drop the result): seven loads under their
                     // own EXEC masks were 18 scalar instructions per stage.  Row 6 of [A B] is [e6, 0, h]: one multiply-add in lane 6.
-                    r.u0 = dus[2 * k]; r.u1 = dus[2 * k + 1];
-                    r.bk = bl[k * 7 + r7];
+                    r.u0 = lds_ld(a_du, 16 * k); r.u1 = lds_ld(a_du, 16 * k + 8);
+                    r.bk = lds_ld(a_bk, 56 * k);
 #pragma unroll
                     for (int c = 0; c < 5; ++c) r.g[c] = Gk[c * 6 + r6];
                     r.b0 = Gk[5 * 6 + r6]; r.b1 = Gk[6 * 6 + r6];
@@ -878,11 +924,11 @@ __global__ __launch_bounds__(WAVE, 2) void admpc_fused20_kernel(const AdmpcConfi
                     const double u0 = r.u0, u1 = r.u1, bk = r.bk, b0 = r.b0, b1 = r.b1;
                     double acc = bk + (lane < 2 ? dx : 0.0);
                     acc += b0 * u0 + b1 * u1;
-                    const double acc6 = fma(h, u1, bk + dx);
+                    const double acc6 = fma(h6, u1, bk + dx);                 // lane 6; exactly 0.0 in lanes >= 7 (dx = 0.0 there, by induction)
                     // (the pad of the first multiply-add covers the write of dx; the others follow it through acc)
                     fmac_rowbc<2>(acc, dx, r.g[0]); fmac_rowbc_ld<3>(acc, dx, r.g[1]); fmac_rowbc_ld<4>(acc, dx, r.g[2]);
                     fmac_rowbc_ld<5>(acc, dx, r.g[3]); fmac_rowbc_ld<6>(acc, dx, r.g[4]);
-                    dx = lane < 6 ? acc : (lane == 6 ? acc6 : 0.0);
+                    dx = lane < 6 ? acc : acc6;
                 }
                 __builtin_amdgcn_sched_barrier(0);
             });
