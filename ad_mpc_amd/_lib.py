@@ -209,6 +209,15 @@ _QUAD_SELECT = {    # include/admpc_quad_select.h: per (cluster, regressor, bin)
 QUAD_SELECT_EXPORTS = tuple(_QUAD_SELECT)
 SELECT_TABLES = {"admpc_quad_select.h": _QUAD_SELECT}
 
+# solver_type "SQP" inside the one-wave solve kernel, declared by load() in the same way
+_QUAD_SQP = {       # include/admpc_quad_sqp.h: the mode of a handle, what it holds, the solve with the QPs per instance
+    "admpc_quad_set_sqp": (I, [vp, I, D]),
+    "admpc_quad_get_sqp": (I, [vp, fp, C.POINTER(C.c_double)]),
+    "admpc_quad_solve_batch_sqp": (I, [vp, I, dp, dp, dp, dp, dp, dp, dp, ip, ip, ip, vp]),
+}
+QUAD_SQP_EXPORTS = tuple(_QUAD_SQP)
+SQP_TABLES = {"admpc_quad_sqp.h": _QUAD_SQP}
+
 _lib = None
 
 
@@ -227,7 +236,8 @@ def load():
     L = C.CDLL(LIB_PATH)
     for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()) + \
             list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()) + list(PRUNE_TABLES.values()) + list(EVAL_TABLES.values()) + \
-            list(TRAJ_TABLES.values()) + list(POLY_TRAJ_TABLES.values()) + list(SELECT_TABLES.values()):
+            list(TRAJ_TABLES.values()) + list(POLY_TRAJ_TABLES.values()) + list(SELECT_TABLES.values()) + \
+            list(SQP_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

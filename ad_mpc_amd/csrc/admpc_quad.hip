@@ -19,6 +19,7 @@
 #include <new>
 #include <type_traits>
 #include "admpc_host.h"      // the public headers; DeviceGuard, admpc_set_error, admpc_quad_solver_config_device
+#include "../../include/admpc_quad_sqp.h"
 
 #ifdef ADMPC_QUAD_TIMERS
 // per-wave accumulators, flushed once at the end of the kernel (an atomic per stamp costs more than most phases)
@@ -137,6 +138,8 @@ __global__ __launch_bounds__(64) void admpc_quad_shoot_kernel(const Cfg* __restr
 //                             the same Cholesky with one THREAD per input; what one wave exchanges by v_readlane and DPP scans goes through
 //                             LDS slots and workgroup barriers -- about a thousand barriers per interior-point iteration: a compatibility path
 // All three keep the oracle's summation order in the factorisation and the substitutions.
+// A second parameter, SQP, adds the SQP loop of an instance around the step for the two one-wave paths (include/admpc_quad_sqp.h): the
+// blocks under `if constexpr (SQP)`; with SQP = false the kernel is the text without them.
 template <bool FAST_> struct WavePath {
     static constexpr int NT = 64;
     static constexpr bool FAST = FAST_;
@@ -192,11 +195,18 @@ struct WidePath {
     }
 };
 
-template <class P>
+// solver_type "SQP" inside the kernel (include/admpc_quad_sqp.h): what the SQP instantiations take beside the arguments of one step, and their
+// LDS region behind the regions of Lds -- the iterate xit [(N+1)*13] | uit [N*4], which stays there between the QPs of an instance, and the
+// multipliers of the last QP pk [N*13] | mk [N*4].  quad_lds_doubles sizes the launches of the other instantiations and keeps its value.
+struct QuadSqpArgs { int qp_max; double tol; int32_t* qps; };
+__host__ __device__ inline int quad_sqp_lds_doubles(int N) { return quad_lds_doubles(N) + (N + 1) * QX + N * QU + N * (QX + QU); }
+
+template <class P, bool SQP = false>
 __global__ __launch_bounds__(P::NT) void admpc_quad_solve_kernel(const Cfg* __restrict__ c, int B, const double* __restrict__ x0g, const double* __restrict__ yrefg,
                                                              const double* __restrict__ yrefeg, double* __restrict__ xbarg, double* __restrict__ ubarg,
                                                              double* __restrict__ costg, int32_t* __restrict__ statusg, int32_t* __restrict__ itersg,
-                                                             int* __restrict__ ticket, const double* __restrict__ gpsg, const int32_t* __restrict__ routeg, int which)
+                                                             int* __restrict__ ticket, const double* __restrict__ gpsg, const int32_t* __restrict__ routeg, int which,
+                                                             QuadSqpArgs sa = QuadSqpArgs())
 {
     extern __shared__ double lds_raw[];
     const int N = c->N, n = N * QU, tid = threadIdx.x;
@@ -225,12 +235,23 @@ __global__ __launch_bounds__(P::NT) void admpc_quad_solve_kernel(const Cfg* __re
         const double* ye = yrefeg + (size_t)inst * QX;
         const double* x0 = x0g + (size_t)inst * QX;
         const double* gq = gpsg ? gpsg + (size_t)inst * QX : x0;       // GP state of the first node: run_optimization's default is the initial state
+        int sq = 0;                                                    // SQP: QPs started for this instance
+        if constexpr (SQP) {
+            // the iterate of the instance lives in LDS until the instance leaves: from here on xb / ub are that copy, and every line below
+            // that reads or steps the iterate works on it
+            double* const xit = lds_raw + quad_lds_doubles(N); double* const uit = xit + (N + 1) * QX;
+            for (int i = tid; i < (N + 1) * QX; i += P::NT) xit[i] = xb[i];
+            for (int i = tid; i < n; i += P::NT) uit[i] = ub[i];
+            xb = xit; ub = uit;
+            __syncthreads();
+        }
         QSTART();
         for (int i = tid; i < (N + 1) * QX; i += P::NT) L.xbs[i] = xb[i];
         for (int i = tid; i < N * QY + QX; i += P::NT) L.yrs[i] = i < N * QY ? yr[i] : ye[i - N * QY];
         // ---- 1. shooting
         shoot_instance(c, xb, ub, gq, L, tid, nullptr, P::NT);
         QSTAMP(0);
+sqp_qp:                                                                // SQP: QP `sq` of the instance on the linearisation in LDS (the only jump here is in the SQP block below)
         // ---- 2. condensing (oracle: condense)
         if constexpr (!P::FAST) { for (int j = 0; j <= li; ++j) if (act) L.H[tri(li, j)] = 0.0; }
         double hrow[P::FAST ? 40 : 1];                                  // FAST: row li of H in registers, Gamma of the other inputs through DPP broadcasts
@@ -485,6 +506,89 @@ __global__ __launch_bounds__(P::NT) void admpc_quad_solve_kernel(const Cfg* __re
             if (itersg) itersg[inst] = it;
         }
         __syncthreads();
+        if constexpr (SQP) {
+            // ---- 5. the SQP loop of the instance (oracle/quad_oracle.c: quad_oracle_solve_batch; the host loop of admpc_quad_solve_batch_ex in one wave).
+            // Everything below is decided on values every lane holds alike: the branches are wave-uniform.
+            ++sq;
+            const double tol = sa.tol;
+            int fin = -1;                                              // the status the instance leaves with; -1: another QP
+            if (bad) fin = 4;                                          // a failed QP ends the instance at once; the iterate is the one before it
+            else if (sq >= sa.qp_max) fin = tol > 0.0 ? 2 : 0;         // the limit: ACADOS_MAXITER when a test was asked for, the iterate is valid
+            else {
+                double* const pks = lds_raw + quad_lds_doubles(N) + (N + 1) * QX + n; double* const mks = pks + N * QX;
+                const int col = tid < QX + QU ? tid : 0, cm = col >= QX ? col - QX : 0;
+                if (tol > 0.0) {
+                    // multipliers of the QP just solved, by the adjoint recursion of its stationarity on its own linearisation, which is still in
+                    // L.A / L.B (admpc_quad_sqp_test_kernel: pk, pm, mk): lanes 0..12 the state rows, lanes 13..16 the input rows of a stage
+                    if (tid < QX) pks[(N - 1) * QX + tid] = L.wts[QX + tid] * (xb[N * QX + tid] - L.yrs[N * QY + tid]);
+                    __syncthreads();
+                    for (int k = N - 1; k >= 0; --k) {
+                        if (tid < QX) {
+                            if (k >= 1) {
+                                double gr = L.wts[tid] * (xb[k * QX + tid] - L.yrs[k * QY + tid]);
+                                asm volatile("" : "+v"(gr));           // a value of its own, as in the test kernel, not a product to fuse into the sum
+                                double pm = gr;
+                                for (int i = 0; i < QX; ++i) pm += L.A[(k * QX + i) * QX + tid] * pks[k * QX + i];
+                                pks[(k - 1) * QX + tid] = pm;
+                            }
+                        } else if (tid < QX + QU) {
+                            double gr = Ts * c->W[QX + cm] * (ub[k * QU + cm] - L.yrs[k * QY + QX + cm]);
+                            asm volatile("" : "+v"(gr));
+                            double mk = gr;
+                            for (int i = 0; i < QX; ++i) mk += L.B[(k * QX + i) * QU + cm] * pks[k * QX + i];
+                            mks[k * QU + cm] = mk;
+                        }
+                        __syncthreads();
+                    }
+                }
+                // the linearisation of the new iterate: the stopping test reads it, and the next QP is built on it
+                for (int i = tid; i < (N + 1) * QX; i += P::NT) L.xbs[i] = xb[i];
+                shoot_instance(c, xb, ub, gq, L, tid, nullptr, P::NT);
+                if (tol > 0.0) {
+                    // acados' stopping test (oracle: quad_nlp_residuals): stationarity, defects, box violation, complementarity; 17 N rows over the lanes
+                    double rs = 0.0, re = 0.0, ri = 0.0, rc = 0.0;
+                    auto upn = [](double& acc, double v) { const double a = fabs(v); if (a > acc || !(a == a)) acc = a; };
+                    if (tid < QX) upn(re, xb[tid] - x0[tid]);
+                    for (int i = tid; i < N * QX; i += P::NT) upn(re, L.b[i]);
+                    for (int t = tid; t < N * (QX + QU); t += P::NT) {
+                        const int k = t / (QX + QU), cc = t - k * (QX + QU);
+                        if (cc < QX) {
+                            if (k >= 1) {
+                                double gr = L.wts[cc] * (xb[k * QX + cc] - L.yrs[k * QY + cc]);
+                                asm volatile("" : "+v"(gr));
+                                double a = gr;
+                                for (int i = 0; i < QX; ++i) a += L.A[(k * QX + i) * QX + cc] * pks[k * QX + i];
+                                upn(rs, a - pks[(k - 1) * QX + cc]);
+                            }
+                        } else {
+                            const int m = cc - QX;
+                            const double u = ub[k * QU + m], lb = c->lbu[m], ubd = c->ubu[m], mk = mks[k * QU + m];
+                            double gr = Ts * c->W[QX + m] * (u - L.yrs[k * QY + QX + m]);
+                            asm volatile("" : "+v"(gr));
+                            double a = gr;
+                            for (int i = 0; i < QX; ++i) a += L.B[(k * QX + i) * QU + m] * pks[k * QX + i];
+                            upn(rs, a - mk);
+                            const double vl = lb - u, vu = u - ubd;
+                            upn(ri, vl > 0.0 ? vl : 0.0); upn(ri, vu > 0.0 ? vu : 0.0);
+                            const double ml = mk > 0.0 ? mk : 0.0, mu_ = mk < 0.0 ? -mk : 0.0;
+                            upn(rc, ml * (u - lb)); upn(rc, mu_ * (ubd - u));
+                        }
+                    }
+                    rs = X.max(rs); re = X.max(re); ri = X.max(ri); rc = X.max(rc);      // NaN-propagating, as upn is
+                    if (rs <= tol && re <= tol && ri <= tol && rc <= tol) fin = 0;
+                }
+                if (fin < 0) goto sqp_qp;
+            }
+            // the instance leaves: its iterate back to global memory, the final status over the last QP's
+            double* const xg = xbarg + (size_t)inst * (N + 1) * QX; double* const ug = ubarg + (size_t)inst * N * QU;
+            for (int i = tid; i < (N + 1) * QX; i += P::NT) xg[i] = xb[i];
+            for (int i = tid; i < n; i += P::NT) ug[i] = ub[i];
+            if (tid == 0) {
+                if (statusg) statusg[inst] = fin;
+                if (sa.qps) sa.qps[inst] = sq;
+            }
+            __syncthreads();
+        }
         inst = X.next(inst, ticket);
     }
     QFLUSH();
@@ -1024,6 +1128,9 @@ struct AdmpcQuadSolver {
     int cap_sqp;
     double *d_A[2], *d_B[2], *d_phi;
     int32_t *d_act, *d_fst, *d_st;
+    // the SQP loop inside the kernel (admpc_quad_set_sqp): QPs per instance at the most (<= 1: off) and the tolerance of the stopping test
+    int sqp_max;
+    double sqp_tol;
 };
 
 extern "C" {
@@ -1072,6 +1179,7 @@ int admpc_quad_create(const AdmpcQuadConfig* cfg, int device, AdmpcQuadSolver** 
     if (!s) return admpc_set_error(ADMPC_ENOMEM, "out of host memory");
     s->cfg = *cfg; s->device = device; s->d_cfg = nullptr; s->d_ticket = nullptr;
     s->d_slot = nullptr;
+    s->sqp_max = 0; s->sqp_tol = 0.0;
     s->cap_sqp = 0; s->d_A[0] = s->d_A[1] = s->d_B[0] = s->d_B[1] = s->d_phi = nullptr; s->d_act = s->d_fst = s->d_st = nullptr;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) { delete s; return admpc_set_error(ADMPC_EHIP, "hipGetDeviceProperties failed"); }
@@ -1088,6 +1196,8 @@ int admpc_quad_create(const AdmpcQuadConfig* cfg, int device, AdmpcQuadSolver** 
     (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<GenericPath>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<Dense40Path>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)admpc_quad_shoot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<GenericPath, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<Dense40Path, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)admpc_quad_solve_kernel<WidePath>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)admpc_quad_seg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     *out = s;
@@ -1150,6 +1260,58 @@ static int quad_solve(AdmpcQuadSolver* s, int B, const double* x0, const double*
     return ADMPC_OK;
 }
 
+// the SQP loop inside the one-wave kernel (include/admpc_quad_sqp.h): one launch, every instance stops at its own convergence.  Instances take
+// 1 .. qp_max QPs, so whatever is past the first round of workgroups is drawn from the work counter
+static int quad_solve_sqp(AdmpcQuadSolver* s, int B, const double* x0, const double* yref, const double* yref_e, const double* gp_state,
+                          double* xbar, double* ubar, double* cost, int32_t* status, int32_t* iters, int32_t* qps, hipStream_t st)
+{
+    const int ldsb = quad_sqp_lds_doubles(s->cfg.N) * (int)sizeof(double);
+    int per_cu = (160 * 1024) / ldsb; if (per_cu > 8) per_cu = 8; if (per_cu < 1) per_cu = 1;
+    int grid = s->num_cu * per_cu; if (grid > B) grid = B;
+    int* ticket = B > grid ? s->d_ticket : nullptr;
+    if (ticket && hipMemsetAsync(ticket, 0, sizeof(int), st) != hipSuccess) return admpc_set_error(ADMPC_EHIP, "hipMemsetAsync failed");
+    const QuadSqpArgs sa = { s->sqp_max, s->sqp_tol, qps };
+    if (s->cfg.N * QU == 40 && !s->generic)
+        hipLaunchKernelGGL((admpc_quad_solve_kernel<Dense40Path, true>), dim3(grid), dim3(64), ldsb, st, s->d_cfg, B, x0, yref, yref_e, xbar, ubar, cost, status, iters, ticket, gp_state, (const int32_t*)nullptr, 0, sa);
+    else
+        hipLaunchKernelGGL((admpc_quad_solve_kernel<GenericPath, true>), dim3(grid), dim3(64), ldsb, st, s->d_cfg, B, x0, yref, yref_e, xbar, ubar, cost, status, iters, ticket, gp_state, (const int32_t*)nullptr, 0, sa);
+    if (hipGetLastError() != hipSuccess) return admpc_set_error(ADMPC_EHIP, "quad SQP solve kernel launch failed");
+    return ADMPC_OK;
+}
+
+int admpc_quad_set_sqp(AdmpcQuadSolver* s, int qp_max, double tol)
+{
+    if (!s) return admpc_set_error(ADMPC_EINVAL, "null solver");
+    if (qp_max < 0 || qp_max > 10000) return admpc_set_error(ADMPC_EINVAL, "quad: qp_max must be in [0, 10000]");
+    if (!(tol >= 0)) return admpc_set_error(ADMPC_EINVAL, "quad: the SQP tolerance must be >= 0");
+    if (s->cfg.sqp_iters > 1) return admpc_set_error(ADMPC_EINVAL, "quad: the handle was built with sqp_iters > 1 (the launch-per-QP loop); the in-kernel SQP loop needs sqp_iters <= 1");
+    if (qp_max > 1 && s->cfg.N * QU > 64) return admpc_set_error(ADMPC_EINVAL, "quad: the in-kernel SQP loop serves N <= 16 (the one-wave kernels)");
+    s->sqp_max = qp_max > 1 ? qp_max : 0;
+    s->sqp_tol = qp_max > 1 ? tol : 0.0;
+    return ADMPC_OK;
+}
+
+int admpc_quad_get_sqp(const AdmpcQuadSolver* s, int* qp_max, double* tol)
+{
+    if (!s) return admpc_set_error(ADMPC_EINVAL, "null solver");
+    if (qp_max) *qp_max = s->sqp_max;
+    if (tol) *tol = s->sqp_tol;
+    return ADMPC_OK;
+}
+
+int admpc_quad_solve_batch_sqp(AdmpcQuadSolver* s, int B, const double* x0, const double* yref, const double* yref_e, const double* gp_state,
+                               double* xbar, double* ubar, double* cost, int32_t* status, int32_t* iters, int32_t* qps, void* stream)
+{
+    if (!s) return admpc_set_error(ADMPC_EINVAL, "null solver");
+    if (s->sqp_max <= 1) return admpc_set_error(ADMPC_EINVAL, "quad: the in-kernel SQP loop is off on this handle (admpc_quad_set_sqp)");
+    if (B < 0) return admpc_set_error(ADMPC_EINVAL, "negative batch");
+    if (B == 0) return ADMPC_OK;
+    if (!x0 || !yref || !yref_e || !xbar || !ubar) return admpc_set_error(ADMPC_EINVAL, "null array argument");
+    DeviceGuard guard(s->device);
+    if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
+    return quad_solve_sqp(s, B, x0, yref, yref_e, gp_state, xbar, ubar, cost, status, iters, qps, (hipStream_t)stream);
+}
+
 int admpc_quad_solve_batch_ex(AdmpcQuadSolver* s, int B, const double* x0, const double* yref, const double* yref_e, const double* gp_state,
                               double* xbar, double* ubar, double* cost, int32_t* status, int32_t* iters, void* stream)
 {
@@ -1160,6 +1322,7 @@ int admpc_quad_solve_batch_ex(AdmpcQuadSolver* s, int B, const double* x0, const
     DeviceGuard guard(s->device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
+    if (s->sqp_max > 1) return quad_solve_sqp(s, B, x0, yref, yref_e, gp_state, xbar, ubar, cost, status, iters, nullptr, st);      // admpc_quad_set_sqp: the same solve, one launch
     const int nsqp = s->cfg.sqp_iters > 1 ? s->cfg.sqp_iters : 1;
     if (nsqp == 1) return quad_solve(s, B, x0, yref, yref_e, gp_state, xbar, ubar, cost, status, iters, nullptr, 0, st);
     // ---- solver_type "SQP": nsqp QPs, acados' stopping test in front of every one but the first when a tolerance is set
@@ -1232,6 +1395,7 @@ int admpc_quad_solve_batch_routed(AdmpcQuadSolver* const* solvers, int K, int B,
         if (!solvers[c]) return admpc_set_error(ADMPC_EINVAL, "null solver");
         if (solvers[c]->device != solvers[0]->device || solvers[c]->cfg.N != solvers[0]->cfg.N) return admpc_set_error(ADMPC_EINVAL, "the cluster solvers must share device and horizon");
         if (solvers[c]->cfg.sqp_iters > 1) return admpc_set_error(ADMPC_EINVAL, "quad: solver_type SQP (sqp_iters > 1) is not implemented for routed (clustered GP) solves");
+        if (solvers[c]->sqp_max > 1) return admpc_set_error(ADMPC_EINVAL, "quad: the in-kernel SQP loop (admpc_quad_set_sqp) is not offered for routed (clustered GP) solves");
     }
     DeviceGuard guard(solvers[0]->device);
     if (!guard.ok()) return admpc_set_error(ADMPC_EHIP, "hipSetDevice failed");

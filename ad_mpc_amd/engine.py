@@ -367,6 +367,28 @@ class QuadBatchSolver(_Handle):
         _lib.check(self.lib.admpc_quad_solve_batch_ex(self._h, B, _ptr(x0), _ptr(yref), _ptr(yref_e), _ptr(gp_state), _ptr(xbar), _ptr(ubar),
                                                       _ptr(cost), _ptr(status), _ptr(iters), self._stream()))
 
+    def set_sqp(self, qp_max=100, tol=1e-6):
+        """solver_type "SQP" inside the solve kernel (include/admpc_quad_sqp.h): from here on ``solve`` and every rollout on this handle
+        take up to ``qp_max`` QPs per instance, each instance until acados' stopping test passes at ``tol`` (0.0: no test, ``qp_max``
+        QPs).  ``qp_max <= 1`` turns the mode off.  Host state: set it before a graph capture.  The defaults are the reference's."""
+        _lib.check(self.lib.admpc_quad_set_sqp(self._h, int(qp_max), float(tol)))
+
+    @property
+    def sqp(self):
+        """(qp_max, tol) of ``set_sqp``; (0, 0.0): the mode is off."""
+        q, t = C.c_int32(0), C.c_double(0.0)
+        _lib.check(self.lib.admpc_quad_get_sqp(self._h, C.byref(q), C.byref(t)))
+        return int(q.value), float(t.value)
+
+    def solve_sqp(self, x0, yref, yref_e, xbar, ubar, cost=None, status=None, iters=None, gp_state=None, qps=None):
+        """``solve`` on a handle whose SQP mode is on (``set_sqp``), with qps [B] int32: the QPs started per instance.  status: 0 converged,
+        2 the limit of QPs reached (the iterate is valid), 4 a failed QP (the iterate is the one before it).  Asynchronous."""
+        B = x0.shape[0]
+        self._chk_solve(B, x0, yref, yref_e, xbar, ubar, cost, status, iters, gp_state)
+        if qps is not None: self._chk(qps, (B,), torch.int32)
+        _lib.check(self.lib.admpc_quad_solve_batch_sqp(self._h, B, _ptr(x0), _ptr(yref), _ptr(yref_e), _ptr(gp_state), _ptr(xbar), _ptr(ubar),
+                                                       _ptr(cost), _ptr(status), _ptr(iters), _ptr(qps), self._stream()))
+
     def shoot(self, xbar, ubar, gp_state=None):
         N, B = self.N, xbar.shape[0]
         self._chk(xbar, (B, N + 1, QNX)); self._chk(ubar, (B, N, QNU))

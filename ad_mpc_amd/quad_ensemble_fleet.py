@@ -15,7 +15,7 @@ from .engine import QuadBatchSolver, _ptr
 from .learning import decode_gps, hyper_dicts, placeholder_gps
 from .quad_3d_optimizer import QuadGPEnsemble
 from .quad_config import QNX, QNY, QUAD_GP_MAX, QUAD_REC, AdmpcQuadObserveParams, quad_learn_bins, select_request
-from .quad_fleet import QuadFleet, fleet_quad_config
+from .quad_fleet import QuadFleet, fleet_quad_config, fleet_solver_type
 
 QuadEnsembleRollout = namedtuple("QuadEnsembleRollout", ("x", "idx", "tally", "counts", "traj", "u", "routes"))
 QuadClusters = namedtuple("QuadClusters", ("weights", "means", "covariances", "n_iter", "converged", "status", "perm"))
@@ -191,9 +191,10 @@ class QuadEnsembleFleet(QuadFleet):
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
                  ensemble=None, centroids=None, feats=None, learn=None, rdrv_d_mat=None, device=0, observe_substeps=1, noise_seed=None,
-                 log_steps=0):
+                 log_steps=0, solver_type="SQP_RTI"):
         self._ens = None
         self._solvers = []
+        fleet_solver_type("QuadEnsembleFleet", solver_type, n_nodes, None, offered=("SQP_RTI",))      # "SQP": refused, routed solves do not serve it
         self._init_plant(B, quad, t_horizon, n_nodes, simulation_dt, reference_over_sampling, noise_seed)
         # every refusal that needs no GPU, before a handle exists
         if (ensemble is None) == (learn is None):

@@ -70,6 +70,22 @@ def fleet_quad_config(quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=
     return cfg
 
 
+def fleet_solver_type(who, solver_type, n_nodes, sqp, offered=("SQP_RTI", "SQP")):
+    """The checks of a fleet's ``solver_type`` and ``sqp`` that come before a handle exists; returns (qp_max, tol) for "SQP", else None."""
+    if solver_type not in ("SQP_RTI", "SQP"):
+        raise ValueError('%s: solver_type must be "SQP_RTI" or "SQP" (quad_3d_optimizer.py:203), got %r' % (who, solver_type))
+    if solver_type not in offered:
+        raise ValueError('%s: solver_type "SQP" is not served for clustered GP ensembles (include/admpc_quad_sqp.h: routed solves)' % who)
+    if solver_type == "SQP_RTI":
+        return None
+    if int(n_nodes) > 16:
+        raise ValueError('%s: solver_type "SQP" is served up to n_nodes = 16 (include/admpc_quad_sqp.h), got %d' % (who, int(n_nodes)))
+    qp_max, tol = sqp
+    if not 2 <= int(qp_max) <= 10000 or not float(tol) >= 0.0:
+        raise ValueError("%s: sqp must be (qp_max in [2, 10000], tol >= 0)" % who)
+    return int(qp_max), float(tol)
+
+
 class QuadFleet(FleetLearning):
     """B quadrotors, each on one of K reference trajectories.  State on the device: ``x`` [B,13], ``idx`` [B] int32 (the sliding index),
     ``traj_of`` [B] int32, the persistent never-shifted iterate ``x_opt`` [B,N+1,13] / ``w_opt`` [B,N,4], the window ``yref`` / ``yref_e``,
@@ -86,7 +102,13 @@ class QuadFleet(FleetLearning):
     ``noise_seed``: the key of the disturbances' generator.  With it and a quad whose ``noisy`` or ``motor_noise`` is set, ``plant_step``
     and ``rollout``, observed or not, go through the entries of include/admpc_quad_noise.h, and ``noise_step`` [B] int64 holds every
     vehicle's period counter (zeros at first; the 64 bits are the header's uint64).  A quad without disturbances ignores the seed; a quad
-    with them and no seed is refused."""
+    with them and no seed is refused.
+
+    ``solver_type``: "SQP_RTI" (one QP per period) or "SQP", the setting of the reference's point-tracking controllers: up to
+    ``sqp[0]`` QPs per period, every vehicle until acados' stopping test passes at ``sqp[1]``, inside the solve kernel
+    (include/admpc_quad_sqp.h; n_nodes <= 16).  It is set on the controller's handle, not on the nominal observer; ``counts[:, 1]`` and
+    ``tcounts[:, 3]`` then count the periods that ended at the limit of QPs (status 2) as well.  ``terminal_cost``: the terminal weights
+    are the stage weights of the state (quad_3d_optimizer.py:84), whatever the solver type."""
     _FIT, _INSTALL, _GP_CAP, _REC, _EMPTY, _NOUN = "admpc_quad_gp_fit", "admpc_quad_gp_install", QUAD_GP_MAX, QUAD_REC, 7, "fleet"
 
     def __new__(cls, *args, **kw):
@@ -96,7 +118,9 @@ class QuadFleet(FleetLearning):
         return object.__new__(QuadLearningFleet if cls is QuadFleet and learn is not None else cls)
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
-                 gp_regressors=None, rdrv_d_mat=None, device=0, learn=None, observe_substeps=1, noise_seed=None):
+                 gp_regressors=None, rdrv_d_mat=None, device=0, learn=None, observe_substeps=1, noise_seed=None, solver_type="SQP_RTI",
+                 terminal_cost=False, sqp=(100, 1e-6)):
+        sqp = fleet_solver_type("QuadFleet", solver_type, n_nodes, sqp)
         self._init_plant(B, quad, t_horizon, n_nodes, simulation_dt, reference_over_sampling, noise_seed)
         if learn is not None:                                                              # every refusal before a handle exists
             learn = [dict(d) for d in learn]
@@ -106,10 +130,16 @@ class QuadFleet(FleetLearning):
             if not 1 <= int(observe_substeps) <= 64:
                 raise ValueError("QuadFleet: observe_substeps must be in [1, 64]")
         cfg = fleet_quad_config(quad, t_horizon, n_nodes, q_cost, r_cost, gp_regressors, rdrv_d_mat)
+        if terminal_cost:
+            for i in range(QNX):
+                cfg.We[i] = cfg.W[i]
         if learn is not None:
             self._nominal = QuadBatchSolver(cfg, device=device)
             cfg = set_quad_gp(cfg.copy(), placeholder_gps(learn))
         self._eng = QuadBatchSolver(cfg, device=device)
+        self.solver_type = solver_type
+        if sqp is not None:
+            self._eng.set_sqp(*sqp)
         self._alloc_state([self._eng])
         if learn is not None:
             obs = AdmpcQuadObserveParams(dt=self.control_period, substeps=int(observe_substeps), n_gp=n_gp, gp=bins)

@@ -24,7 +24,8 @@
  *     log of the records flown, and installs them in the object's device copy;
  *   - the search of the hyperparameters by THESE entries: to admpc_quad_ensemble_fit the length scales, sigma_f and the noise of every
  *     cluster are GIVEN; admpc_quad_hyper.h searches them for all clusters in one chain of launches (admpc_quad_ensemble_search, _refit);
- *   - SQP mode (a handle with sqp_iters > 1 is refused: the rollout is the RTI loop).
+ *   - SQP mode (a handle with sqp_iters > 1 is refused: the rollout is the RTI loop).  The SQP loop inside the solve kernel of
+ *     admpc_quad_sqp.h serves one-handle rollouts; routed solves refuse a handle that has it on.
  *
  * ONE ITERATE PER VEHICLE.  xbar / ubar of vehicle b are used by whichever cluster solves it: a vehicle that changes cluster is
  * warm-started from the other cluster's solution.  The reference keeps an iterate per solver instead (each acados solver its own), so

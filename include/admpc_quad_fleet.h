@@ -110,7 +110,8 @@ int admpc_quad_ref_chunk_batch(const AdmpcQuadTrajBank* bank, int B, int N, int 
  * No host synchronisation and no allocation between the steps.  The N = 20 handle allocates its slot buffer at its FIRST solve, so the
  * chain can be captured into a graph once one solve has run on the handle.  If an enqueue fails in the middle the error is returned;
  * the steps already enqueued run.  T == 0 or B == 0 is a no-op.
- * NOT served: handles in SQP mode (the rollout is the RTI loop of trajectory_test.py).  One handle drives the whole fleet here;
+ * NOT served: handles in SQP mode (the rollout is the RTI loop of trajectory_test.py).  The SQP loop inside the solve kernel, set on an RTI
+ * handle by admpc_quad_set_sqp of admpc_quad_sqp.h, is served by this chain as it stands.  One handle drives the whole fleet here;
  * clustered GP ensembles are flown by admpc_quad_ensemble_rollout_batch of admpc_quad_ensemble.h, which is this chain with the routing
  * from the window and admpc_quad_solve_batch_routed in place of step 2.
  * ADMPC_EINVAL, in this order: a null solver; a solver with sqp_iters > 1; a null bank; a bank on another device than the solver; the

@@ -25,7 +25,7 @@
  *     factors every regressor at the hyperparameters the search left in `hyper` and scores them on a log, on the same stream;
  *   - gradients, L-BFGS-B or random restarts: the search is the zooming grid of admpc_hyper.h;
  *   - a warm start of the search across new statistics (call with resume = 0 after a re-bin);
- *   - a K chosen by the search; handles in SQP mode;
+ *   - a K chosen by the search; handles in SQP mode.  admpc_quad_sqp.h has the SQP loop that one-handle rollouts fly;
  *   - per-cluster grid, rounds or shrink in an ensemble (one chain of launches serves all clusters; the boxes are free per cluster).
  *
  * WHY THE ENSEMBLE HAS KERNELS OF ITS OWN.  The kernels behind admpc_gp_search take their regressors and search descriptors by value:

@@ -29,7 +29,8 @@
  *     has observe -> bin -> fit -> install per cluster, and the rollout that flies them;
  *   - np.random's own stream for the simulator's random disturbances: their distributions are flown by admpc_quad_rollout_noise_batch
  *     (admpc_quad_noise.h), observed or not, from a counter-based generator;
- *   - handles in SQP mode (the rollout is the RTI loop);
+ *   - handles in SQP mode (the rollout is the RTI loop).  The SQP loop inside the solve kernel, set on an RTI handle by admpc_quad_set_sqp of
+ *     admpc_quad_sqp.h, is served by the observed rollout as it stands;
  *   - pruning by a velocity cap and by the error histograms (gp_common.py:101-112) by THESE entries, beyond what the box of the bins does (a
  *     sample outside the box is dropped and counted): admpc_quad_prune.h has the reference's prune over a log of these records, which
  *     rewrites entry 13 -- a pruned record carries 2.0 there and is taken by no bin -- and the RDRv drag fit from what is left.

@@ -31,7 +31,8 @@
  *   - pruning that feeds anything but flags: no compaction of the log, no index list;
  *   - a log for QuadFleet and for flights to targets (admpc_quad_targets.h): the entries work on ANY array of records, the fleet that
  *     keeps one is the clustered ensemble's;
- *   - RDRv in covariance mode, a full (non-diagonal) drag matrix, an intercept; handles in SQP mode.
+ *   - RDRv in covariance mode, a full (non-diagonal) drag matrix, an intercept; handles in SQP mode.  admpc_quad_sqp.h has the SQP loop that
+ *     one-handle rollouts fly.
  *
  * THE RECORDS are admpc_quad_learn.h's [14]: entries 0 .. 2 the body-frame velocity v_b, 10 .. 12 the residual y, entry 13 the flag.
  * ADMPC_QUAD_REC_PRUNED (2.0) is a third value of the flag next to 0.0 (not valid) and 1.0 (valid, kept): the pack kernel of the EM and the

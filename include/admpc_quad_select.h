@@ -31,7 +31,8 @@
  *   - the route for two or more features, a randomly started k-means with random picks, which cannot be pinned; the dead PCA branch;
  *   - the reference's y_mean = the mean of ALL targets of the cluster (gp_fitting.py:242, 296): the fit keeps the mean of the selected
  *     targets (gp_ymean);
- *   - soft top-2 cluster membership (gp_common.py:253-262); handles in SQP mode;
+ *   - soft top-2 cluster membership (gp_common.py:253-262); handles in SQP mode.  admpc_quad_sqp.h has the SQP loop that one-handle
+ *     rollouts fly;
  *   - a selection for QuadFleet, which keeps no log.
  *
  * THE RULE, quirks included.  For cluster c and regressor g with ONE feature f and output o, the POINTS are the records of the log, in log

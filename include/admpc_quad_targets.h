@@ -27,7 +27,9 @@
  * NOT offered:
  *   - np.random's own stream: the DISTRIBUTIONS of sample_random_target are the reference's, the numbers come from the counter-based
  *     generator of admpc_quad_noise.h, so that this contract says which numbers every vehicle's every target takes;
- *   - SQP mode, although the reference's script asks for it: the RTI loop is what every rollout here flies;
+ *   - SQP mode, although the reference's script asks for it: the RTI loop is what every rollout here flies.  That is a handle BUILT with
+ *     sqp_iters > 1; the SQP loop inside the solve kernel, set on an RTI handle by admpc_quad_set_sqp of admpc_quad_sqp.h, is flown by
+ *     admpc_quad_rollout_targets_batch as it stands, and tcounts[b][3] then counts status 2 as well;
  *   - clustered ensembles (admpc_quad_ensemble.h) and the logged rollout of admpc_quad_clusters.h;
  *   - the CSV data set and the real-time plot;
  *   - the reference's record of a period that ended in a recovery, which pairs the state before the recovery with the one after it: here
