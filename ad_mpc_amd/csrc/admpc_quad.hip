@@ -130,6 +130,11 @@ __global__ __launch_bounds__(64) void admpc_quad_shoot_kernel(const Cfg* __restr
     }
 }
 
+// The centring parameter and the step of the box-QP interior point (oracle: box_qp), which both loops below call: pure, uniform over the block.  muaff
+// reaches them by each kernel's own sum (direct in the one-block kernel, the identity with two sums in the two-wave kernel): not the same bits.
+__device__ __forceinline__ double ipm_sigma(double muaff, double mu, double alpha_prev) { double sigma = muaff / mu; sigma = sigma * sigma * sigma; return alpha_prev < ADMPC_QUAD_IPM_BLOCKED_STEP ? 1.0 : sigma; }
+__device__ __forceinline__ double ipm_alpha(double muaff, double amax) { double tau = 1.0 - muaff; tau = fmax(tau, 0.995); tau = fmin(tau, 0.999999); return fmin(tau * amax, 1.0); }
+
 // ---- the dense solve kernel is one text; a path says how the block of an instance exchanges values, and nothing else:
 //   Dense40Path  64 threads   N nu = 40, the shipped horizon: the Newton systems go through dense40.h -- register-resident LDL' with DPP rank-1
 //                             updates and the generated substitution assembly (3.9x less time per interior-point iteration than the next)
@@ -442,16 +447,13 @@ sqp_qp:                                                                // SQP: Q
             };
             double amax = ratio();
             const double muaff = X.sum(act ? (tl + amax * dtl) * (ll + amax * dll) + (tu + amax * dtu) * (lu + amax * dlu) : 0.0) / (2.0 * n);
-            double sigma = muaff / mu; sigma = sigma * sigma * sigma;
-            if (alpha_prev < ADMPC_QUAD_IPM_BLOCKED_STEP) sigma = 1.0;
-            const double smu = sigma * mu;
+            const double smu = ipm_sigma(muaff, mu, alpha_prev) * mu;
             const double cl = act ? (smu - (cons ? 0.0 : dtl * dll)) / tl : 0.0, cu = act ? (smu - (cons ? 0.0 : dtu * dlu)) / tu : 0.0;
             const double d = solve(act ? -rs + (cl - ll - Dl * rl) - (cu - lu - Du * ru) : 0.0);
             dtl = d + rl; dtu = -d + ru;
             dll = cl - ll - Dl * dtl; dlu = cu - lu - Du * dtu;
             amax = ratio();
-            double tau = 1.0 - muaff; tau = fmax(tau, 0.995); tau = fmin(tau, 0.999999);
-            const double alpha = fmin(tau * amax, 1.0);
+            const double alpha = ipm_alpha(muaff, amax);
             if (act) {
                 du += alpha * d;
                 tl = fmax(tl + alpha * dtl, 1e-40); tu = fmax(tu + alpha * dtu, 1e-40);
@@ -932,9 +934,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             double amax = fmin(QRED(0, 1, 0), QRED(1, 1, 0));
             // sum (t + a dt)(l + a dl) = (1 - a) sum t l + a^2 sum dt dl  (the predictor's right-hand side is t l: t dl + l dt = -t l exactly)
             const double muaff = ((1.0 - amax) * mu / inv2n + amax * amax * (QRED(0, 1, 1) + QRED(1, 1, 1))) * inv2n;
-            double sigma = muaff / mu; sigma = sigma * sigma * sigma;
-            if (alpha_prev < ADMPC_QUAD_IPM_BLOCKED_STEP) sigma = 1.0;
-            const double smu = sigma * mu;
+            const double smu = ipm_sigma(muaff, mu, alpha_prev) * mu;
             const double cl = act ? (smu - (cons ? 0.0 : dtl * dll)) / tl : 0.0, cu = act ? (smu - (cons ? 0.0 : dtu * dlu)) / tu : 0.0;
             const double d = solve(-rs_loc + (cl - ll - Dl * rl) - (cu - lu - Du * ru), -gzc);
             dtl = d + rl; dtu = -d + ru;
@@ -945,8 +945,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             QSYNC();
             amax = fmin(QRED(0, 2, 0), QRED(1, 2, 0));
-            double tau = 1.0 - muaff; tau = fmax(tau, 0.995); tau = fmin(tau, 0.999999);
-            const double alpha = fmin(tau * amax, 1.0);
+            const double alpha = ipm_alpha(muaff, amax);
             if (act) {
                 du += alpha * d;
                 tl = fmax(tl + alpha * dtl, 1e-40); tu = fmax(tu + alpha * dtu, 1e-40);
