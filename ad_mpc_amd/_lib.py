@@ -218,6 +218,15 @@ _QUAD_SQP = {       # include/admpc_quad_sqp.h: the mode of a handle, what it ho
 QUAD_SQP_EXPORTS = tuple(_QUAD_SQP)
 SQP_TABLES = {"admpc_quad_sqp.h": _QUAD_SQP}
 
+# the start of the Gaussian-mixture EM found on the device, declared by load() in the same way
+_QUAD_KMEANS = {    # include/admpc_quad_kmeans.h: scikit-learn's k-means++ seeding and Lloyd k-means over the log, the n_init rule over two fits
+    "admpc_quad_kmeans_fit": (I, [vp, C.c_uint64, C.c_uint32, I, D, C.c_int64, dp, dp, dp, ip, dp, dp, ip, dp, ip, vp]),
+    "admpc_quad_clusters_keep": (I, [vp, I, dp, ip, dp, ip, ip, vp]),
+    "admpc_quad_kmeans_keep": (I, [vp, I, C.c_int64, ip, dp, ip, ip, dp, ip, dp, ip, ip, dp, ip, vp]),
+}
+QUAD_KMEANS_EXPORTS = tuple(_QUAD_KMEANS)
+KMEANS_TABLES = {"admpc_quad_kmeans.h": _QUAD_KMEANS}
+
 _lib = None
 
 
@@ -237,7 +246,7 @@ def load():
     for table in list(TABLES.values()) + list(MORE_TABLES.values()) + list(ENSEMBLE_TABLES.values()) + list(CLUSTER_TABLES.values()) + \
             list(HYPER_TABLES.values()) + list(TARGET_TABLES.values()) + list(PRUNE_TABLES.values()) + list(EVAL_TABLES.values()) + \
             list(TRAJ_TABLES.values()) + list(POLY_TRAJ_TABLES.values()) + list(SELECT_TABLES.values()) + \
-            list(SQP_TABLES.values()):
+            list(SQP_TABLES.values()) + list(KMEANS_TABLES.values()):
         for name, (restype, argtypes) in table.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -21,8 +21,11 @@ QuadEnsembleRollout = namedtuple("QuadEnsembleRollout", ("x", "idx", "tally", "c
 QuadClusters = namedtuple("QuadClusters", ("weights", "means", "covariances", "n_iter", "converged", "status", "perm"))
 QuadEvaluation = namedtuple("QuadEvaluation", ("count", "nominal_mae", "augmented_mae", "nominal_rms", "augmented_rms", "mean_std", "within_3std",
                                                "clipped", "total"))
+QuadKMeans = namedtuple("QuadKMeans", ("centers", "idx", "labels", "n_iter", "converged", "status", "n_valid", "inertia", "tol_abs", "shift",
+                                       "potential", "kept"))
 CLUSTERS_MAX = 8
 GMM_BLOCKS_MAX, GMM_ROW, GMM_PARTIAL, GMM_ENOVALID = 256, 18, 81, -100                  # include/admpc_quad_clusters.h
+KMEANS_PARTIAL, KMEANS_STATE, KMEANS_EFEW, KMEANS_N_INIT_MAX = 33, 48, -101, 64      # include/admpc_quad_kmeans.h; the last is this layer's
 PRUNE_BINS_MAX, PRUNE_PARTIAL, RDRV_PARTIAL, PRUNE_ENOVALID, REC_PRUNED = 256, 9, 7, -100, 2.0        # include/admpc_quad_prune.h
 EVAL_FACTOR, EVAL_STATS, EVAL_ENOVALID = 672, 8, -100                                    # include/admpc_quad_eval.h
 SELECT_WORK, SELECT_ENOVALID = 201376, -100                                              # include/admpc_quad_select.h
@@ -89,6 +92,30 @@ def clusters_request(K, feats, steps, max_iter=100, tol=1e-3, reg_covar=1e-6, in
     if init is not None:
         init = centroid_block("fit_clusters: init", init, K, len(feats))
     return int(max_iter), tol, reg_covar, init
+
+
+def kmeans_work(M):
+    """The doubles of admpc_quad_kmeans_fit's work area for M records (ADMPC_KMEANS_WORK)."""
+    return 2 * ((int(M) + 255) // 256) + GMM_BLOCKS_MAX * KMEANS_PARTIAL + KMEANS_STATE
+
+
+def kmeans_request(seed, n_init=1, km_max_iter=300, km_tol=1e-4, resume=False):
+    """The arguments ``fit_clusters`` takes with init="kmeans", checked as admpc_quad_kmeans_fit checks them:
+    (seed, n_init, km_max_iter, km_tol).  Raises ValueError; needs no GPU."""
+    if seed is None:
+        raise ValueError("fit_clusters: init=\"kmeans\" needs a seed")
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("fit_clusters: seed must be a whole number in 0 .. 2^64 - 1")
+    if isinstance(n_init, (bool, np.bool_)) or int(n_init) != n_init or not 1 <= int(n_init) <= KMEANS_N_INIT_MAX:
+        raise ValueError("fit_clusters: n_init must be in 1 .. %d" % KMEANS_N_INIT_MAX)
+    if int(km_max_iter) != km_max_iter or not 1 <= int(km_max_iter) <= 1000:
+        raise ValueError("fit_clusters: km_max_iter must be in 1 .. 1000")
+    km_tol = float(km_tol)
+    if not (km_tol >= 0.0 and np.isfinite(km_tol)):
+        raise ValueError("fit_clusters: km_tol must be finite and not negative")
+    if resume:
+        raise ValueError("fit_clusters: resume=True goes on from the last fit; init=\"kmeans\" starts a new one")
+    return int(seed), int(n_init), int(km_max_iter), km_tol
 
 
 def prune_request(steps, x_cap=16.0, bins=40, thresh=0.001):
@@ -187,7 +214,11 @@ class QuadEnsembleFleet(QuadFleet):
     Between the clusters and the fit, ``select_points()`` trains every GP on real records picked from the log as the reference picks
     them, in place of the bin means (include/admpc_quad_select.h): ``rollout(T, observe=True, log=True)`` -> ``prune_log()`` ->
     ``fit_clusters()`` -> ``select_points()`` -> ``search_gp(factor=True)`` -> ``evaluate_log()``.  ``sel`` [K,3,32] and ``select_info``
-    [K,3,4] are its results; it overwrites ``bins``, which ``rebin()`` restores."""
+    [K,3,4] are its results; it overwrites ``bins``, which ``rebin()`` restores.
+
+    ``fit_clusters(init="kmeans", seed=...)`` needs no centroids to start from: scikit-learn's k-means++ seeding and Lloyd k-means run on
+    the device in front of the EM (include/admpc_quad_kmeans.h), as the reference's GaussianMixture(n_clusters).fit does by default;
+    ``km_centers``, ``km_idx``, ``km_info``, ``km_stats``, ``km_labels`` and ``km_kept`` hold its results, ``learned_kmeans()`` reads them."""
 
     def __init__(self, B, quad=None, t_horizon=1.0, n_nodes=10, q_cost=None, r_cost=None, simulation_dt=5e-4, reference_over_sampling=5,
                  ensemble=None, centroids=None, feats=None, learn=None, rdrv_d_mat=None, device=0, observe_substeps=1, noise_seed=None,
@@ -461,14 +492,29 @@ class QuadEnsembleFleet(QuadFleet):
         torch.cuda.current_stream(self.device).synchronize()
         return np.diag(self.rdrv.cpu().numpy())
 
-    def fit_clusters(self, max_iter=100, tol=1e-3, reg_covar=1e-6, init=None, install=True, rebin=True, resume=False):
+    def fit_clusters(self, max_iter=100, tol=1e-3, reg_covar=1e-6, init=None, install=True, rebin=True, resume=False, seed=None, n_init=1,
+                     km_max_iter=300, km_tol=1e-4):
         """The centroids from the log: sklearn's Gaussian-mixture EM (full covariances; max_iter, tol and reg_covar are its defaults) from
         the means ``init`` [K, n_feat] (default: the present centroids; a float64 tensor on the fleet's device is taken as it is, which
         keeps the call free of copies for a graph) over the logged records (admpc_quad_clusters_fit), then
         (`install`) its means, sorted along the first feature, as the ensemble's centroids, and (`rebin`) the log binned again under
         them.  One chain of launches on the stream, asynchronous; returns the device tensors (info int32 [4]: iterations, converged,
-        status, n_valid; perm int32 [K]; installed int32 [1]), the last two None without `install`."""
+        status, n_valid; perm int32 [K]; installed int32 [1]), the last two None without `install`.
+
+        ``init="kmeans"`` is what the reference's GaussianMixture(n_clusters).fit does with nothing given: scikit-learn's k-means++
+        seeding and Lloyd k-means under ``seed`` (required; ``km_max_iter`` and ``km_tol`` are KMeans' defaults) find the means the EM
+        starts from (admpc_quad_kmeans_fit; include/admpc_quad_kmeans.h), and with ``n_init`` > 1 the chain runs under draw = 0 ..
+        n_init - 1 and the fit with the largest lower bound is kept (admpc_quad_clusters_keep), installed and returned; ``km_kept``
+        int32 [1] is its draw.  A k-means that fails hands the EM the present centroids.  ``km_centers``, ``km_idx``, ``km_info``,
+        ``km_stats`` and ``km_labels`` are allocated at the first such call (call once before capturing a graph, with the n_init that
+        will be captured) and hold the k-means of the fit that was kept (admpc_quad_kmeans_keep); ``learned_kmeans()`` returns them."""
         self._learns("fit_clusters")
+        if isinstance(init, str):
+            if init != "kmeans":
+                raise ValueError("fit_clusters: init must be None, K x len(feats) means or \"kmeans\"")
+            return self._fit_clusters_kmeans(max_iter, tol, reg_covar, install, rebin, resume, seed, n_init, km_max_iter, km_tol)
+        if seed is not None or n_init != 1:
+            raise ValueError("fit_clusters: seed and n_init go with init=\"kmeans\"")
         start = None
         if torch.is_tensor(init):
             self._eng._chk(init, (self.K, len(self.feats)))
@@ -486,6 +532,59 @@ class QuadEnsembleFleet(QuadFleet):
         if rebin:
             self.rebin()
         return (self.gmm_info, self.perm, self.centroids_installed) if install else (self.gmm_info, None, None)
+
+    def _fit_clusters_kmeans(self, max_iter, tol, reg_covar, install, rebin, resume, seed, n_init, km_max_iter, km_tol):
+        max_iter, tol, reg_covar, _ = clusters_request(self.K, self.feats, self.log_count, max_iter, tol, reg_covar, None)
+        seed, n_init, km_max_iter, km_tol = kmeans_request(seed, n_init, km_max_iter, km_tol, resume)
+        if getattr(self, "km_centers", None) is None:
+            z = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=self.device)
+            cap = self.log_steps * self.B
+            self.km_centers, self.km_idx = z(self.K, len(self.feats)), z(self.K, dtype=torch.int64)
+            self.km_info, self.km_stats, self.km_labels = z(4, dtype=torch.int32), z(4), z(cap, dtype=torch.int32)
+            self.km_kept = z(1, dtype=torch.int32)
+            self._km_dist, self._km_work = z(cap), z(kmeans_work(cap))
+            self._gmm_try, self._gmm_info_try = z(1 + self.K, GMM_ROW), z(4, dtype=torch.int32)
+            self._km_try = None                                                                # the k-means results of a try, at the first n_init > 1
+        s, M = self._stream(), self.log_count * self.B
+        many = n_init > 1
+        gmm, info = (self._gmm_try, self._gmm_info_try) if many else (self.gmm, self.gmm_info)
+        best = (self.km_centers, self.km_idx, self.km_labels, self.km_stats, self.km_info)
+        if many and self._km_try is None:
+            self._km_try = tuple(torch.zeros_like(t) for t in best)
+        centers, idx, labels, stats, kinfo = self._km_try if many else best
+        for draw in range(n_init):
+            _lib.check(self.lib.admpc_quad_kmeans_fit(self._ens, seed, draw, km_max_iter, km_tol, M, _ptr(self.log), _ptr(self._packed),
+                                                      _ptr(self._km_dist), _ptr(labels), _ptr(self._km_work), _ptr(centers), _ptr(idx), _ptr(stats),
+                                                      _ptr(kinfo), s))
+            _lib.check(self.lib.admpc_quad_clusters_fit(self._ens, max_iter, tol, reg_covar, 0, M, _ptr(self.log), _ptr(centers),
+                                                        _ptr(self._packed), _ptr(self._partial), _ptr(gmm), _ptr(info), s))
+            if many:
+                _lib.check(self.lib.admpc_quad_clusters_keep(self._ens, draw, _ptr(gmm), _ptr(info), _ptr(self.gmm), _ptr(self.gmm_info),
+                                                             _ptr(self.km_kept), s))
+                _lib.check(self.lib.admpc_quad_kmeans_keep(self._ens, draw, M, _ptr(self.km_kept), _ptr(centers), _ptr(idx), _ptr(labels), _ptr(stats),
+                                                           _ptr(kinfo), *[_ptr(t) for t in best], s))
+        self._km_many = many
+        if install:
+            _lib.check(self.lib.admpc_quad_clusters_install(self._ens, _ptr(self.gmm), _ptr(self.gmm_info), _ptr(self.perm),
+                                                            _ptr(self.centroids_installed), s))
+            self._moved = True
+        if rebin:
+            self.rebin()
+        return (self.gmm_info, self.perm, self.centroids_installed) if install else (self.gmm_info, None, None)
+
+    def learned_kmeans(self):
+        """The k-means of the last fit_clusters(init="kmeans") as numpy (synchronises): QuadKMeans(centers [K,n_feat], idx int64 [K] the
+        seeded records t * B + b, labels int32 [records logged] with -1 where a record does not count, n_iter, converged (0; 1 by
+        tolerance; 2 because no label changed), status, n_valid, inertia, tol_abs, shift, potential, kept: the draw whose fit was kept
+        with n_init > 1, else 0; everything else is that draw's k-means)."""
+        self._learns("learned_kmeans")
+        if getattr(self, "km_centers", None) is None:
+            raise ValueError("learned_kmeans: no k-means yet: call fit_clusters(init=\"kmeans\", seed=...) first")
+        torch.cuda.current_stream(self.device).synchronize()
+        info, stats = self.km_info.cpu().numpy(), self.km_stats.cpu().numpy()
+        return QuadKMeans(self.km_centers.cpu().numpy().copy(), self.km_idx.cpu().numpy().copy(),
+                          self.km_labels[:self.log_count * self.B].cpu().numpy().copy(), int(info[0]), int(info[1]), int(info[2]), int(info[3]),
+                          float(stats[0]), float(stats[1]), float(stats[2]), float(stats[3]), int(self.km_kept.cpu()[0]) if self._km_many else 0)
 
     def learned_clusters(self):
         """The mixture of the last fit_clusters as numpy (synchronises): QuadClusters(weights [K], means [K,n_feat], covariances

@@ -20,7 +20,8 @@
  *                                                                                              admpc_quad_ensemble_fit / _install
  *
  * NOT offered:
- *   - k-means++ and random initialisation, n_init restarts: the start is the given means (init, or the ensemble's present centroids);
+ *   - k-means++ and random initialisation, n_init restarts, by THESE entries: the start is the given means (init, or the ensemble's present
+ *     centroids); admpc_quad_kmeans.h has scikit-learn's k-means++ seeding, its Lloyd k-means and the n_init rule in front of this fit;
  *   - covariance types other than "full"; choosing K: K is the ensemble's;
  *   - the soft top-2 membership of gp_common.py:253-262: a record trains only its nearest cluster, as admpc_quad_ensemble.h bins it;
  *   - the PCA point selection of gp_fitting.py:237-240;
